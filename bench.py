@@ -12,8 +12,9 @@ engine's stream (`roofline` uses the events, `value` the host clock).
 N = 1 (default): BASELINE.json configs[1] -- 1M x 1024, gamma 20 nnz/row, K = 100, fp32, synthetic (own seeded generator
 restating create_matrices.py's distributions). `value` is measured CACHE-DEFEATED: the engine keeps 4 copies of the 118 MB
 packet stream and rotates them per query, so no query is served from the 256 MiB Infinity Cache and the roofline fraction
-is an honest HBM fraction. Beside the headline the line carries: `parity_checked` (the last timed query against the CPU
-oracle), `timing` (median / p95 over >= 30 repetitions, first 2 dropped: the reference's hygiene,
+is an honest HBM fraction. A plain run sets up, warms up, times the steps and prints the headline line (`--dump-outputs DIR`:
+the last timed query's top-k as .npy files). With --full, beside the headline the line carries: `parity_checked` (the last
+timed query against the CPU oracle), `timing` (median / p95 over >= 30 repetitions, first 2 dropped: the reference's hygiene,
 host_spmv_bscsr.cpp:699), `single_query` (the literal reference loop: one reset -> operator() -> read_result at a time),
 `configs` (BASELINE configs[2] and configs[4]), `cache_warm`, `multi_query`, `cpu_baseline` (fp64 and fp32).
 
@@ -22,7 +23,8 @@ seed 4) cut into N contiguous row shards balanced by nnz; every rank builds only
 everywhere), runs its engine with global row ids, and per query the ranks exchange K (row, score) pairs with ONE RCCL
 all-gather (32 queries per exchange, on a side stream) followed by a merge kernel. STRONG scaling: `value` = global queries
 per second = steps / max-over-ranks time. The exchange must be the native one (csrc/dist.hip); without it the run fails
-loudly unless TKSPMV_DIST=torch asks for the torch.distributed exchange.
+loudly unless TKSPMV_DIST=torch asks for the torch.distributed exchange. --full adds the cross-check of the two exchanges, the
+per-rank kernel and load-only figures, parity over the whole matrix and (N > 1) configs[3].
 """
 import argparse
 import json
@@ -50,13 +52,13 @@ def parse():
     ap.add_argument("--nnz", type=int, default=20)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--config3-rows", type=int, default=10000000,
-                    help="--gpus N > 1: rows of the BASELINE configs[3] matrix sharded over the same GPUs beside the headline (0 = skip)")
+                    help="--gpus N > 1 --full: rows of the BASELINE configs[3] matrix sharded over the same GPUs beside the headline (0 = skip)")
     ap.add_argument("--total-rows", type=int, default=0,
                     help="rows of the ONE matrix cut across the ranks (default: --rows, the matrix of the --gpus 1 line); given at "
                          "--gpus 1 it runs the sharded code path with one shard")
     ap.add_argument("--replicas", type=int, default=4, help="packet-stream copies rotated per query (cache defeat)")
-    ap.add_argument("--reps", type=int, default=32, help="repetitions of the timed batch for median / p95 (first 2 dropped)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--reps", type=int, default=32, help="--full: repetitions of the timed batch for median / p95 (first 2 dropped)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline leg (0 = skip)")
     ap.add_argument("--queries", type=int, default=64, help="distinct query vectors resident in HBM")
     ap.add_argument("--nnz-per-lane", type=int, default=0, help="entries per lane and packet (0 = the engine's default)")
     ap.add_argument("--waves-per-cu", type=int, default=0, help="streaming waves per CU (0 = the engine's default)")
@@ -65,19 +67,37 @@ def parse():
                     help="profiler runs: nothing but the headline's queries (warm-up, timed region, repetitions) -- no side leg, no nonstationary "
                          "stream, no CPU baseline, no traffic pass; the kernel trace of such a run holds the headline kernel alone")
     ap.add_argument("--skip-warm", action="store_true",
-                    help="profiler runs: nothing but the headline queries (no side legs, homogeneous launches for rocprofv3)")
+                    help="--full without the side legs: nothing but headline queries (homogeneous launches for rocprofv3)")
     ap.add_argument("--multi-q", type=int, nargs="*", default=[4, 8],
-                    help="queries per matrix pass of the multi-query leg (reported beside the headline; empty = skip)")
+                    help="--full: queries per matrix pass of the multi-query leg (reported beside the headline; empty = skip)")
     ap.add_argument("--multi-only", type=int, default=0,
                     help="profiler runs: launch nothing but the multi-query path with this many queries per pass")
     ap.add_argument("--traffic", choices=["auto", "live", "static", "off"], default="auto",
-                    help="roofline.traffic: a live rocprofv3 --pmc pass over a child run (auto: when rocprofv3 is on PATH), "
+                    help="--full: roofline.traffic from a live rocprofv3 --pmc pass over a child run (auto: when rocprofv3 is on PATH), "
                          "or the figure committed under profiles/ (labelled static)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the child of the live traffic pass
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: parity against the oracle, repetitions, the load-only floor, the side legs, "
+                         "the CPU baseline and the traffic pass (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path delivered for its last query (top-k row ids and scores) "
+                         "as DIR/<name>.npy")
     a = ap.parse_args()
     if a.headline_only:
         a.skip_warm = True
+        a.full = True  # (its short line carries the repetitions and the load-only floor)
+    if a.dump_outputs and a.multi_only:
+        ap.error("--dump-outputs: --multi-only times a path whose results stay on the device")
     return a
+
+
+def dump_outputs(out_dir, idx, val):
+    """--dump-outputs: the last timed query's top-k as its caller receives it (row ids and scores, descending score), row ids as
+    float64 (exact below 2**53), scores as float32: two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "topk_row_ids.npy"), np.asarray(idx).astype(np.float64))
+    np.save(os.path.join(out_dir, "topk_scores.npy"), np.asarray(val, dtype=np.float32))
 
 
 def workload_name(rows, cols, nnz_per_row, nnz, k, replicas):
@@ -441,6 +461,32 @@ def _finish_headline_only(a, info, alg_bytes, kernel_ns, elapsed, reps, read_us,
 
 
 # ---- N = 1: BASELINE configs[1] ---------------------------------------------------------------------------------------------
+def single_line(a, info, elapsed, kernel_ns):
+    """The headline line: the host clock over the timed steps (`value`, `ms_per_step`) and the event pair inside the same call
+    (`roofline`). --full adds to it."""
+    alg_bytes = info["algorithmic_bytes"]
+    return {
+        "metric": "queries_per_sec", "value": a.steps / elapsed, "unit": "queries/s", "n_gpus": 1,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
+        # (strong: --gpus N cuts THIS matrix into N row shards -- bench_sharded -- so the total work is fixed as N grows)
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload_name(a.rows, a.cols, a.nnz, int(info["nnz"]), a.k, a.replicas),
+                   "rows": a.rows, "cols": a.cols, "nnz": int(info["nnz"]), "k": a.k, "parallelism": "single GPU",
+                   "launch": {"grid": info["grid"], "block": info["block"] + 64,
+                              "wave_partitions": info["n_wave_partitions"], "packet_entries": info["packet_entries"],
+                              # (tkspmv_info.batch_mode: how the engine runs back-to-back queries on this matrix, DESIGN.md 3.0b)
+                              "selector_workgroups": info.get("batch_mode", 0) & 0xFF,
+                              "thresholds": {0: "device-wide exchange", 1: "workgroup-local (best packet maximum per wave), checked by the selection; an exact launch repeats what failed",
+                                             2: "workgroup-local (second best packet maximum per wave), checked by the selection; an exact launch repeats what failed"}[(info.get("batch_mode", 0) >> 8) & 0xFF]}},
+        "roofline": {"bound": "hbm", "achieved": alg_bytes / kernel_ns, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": alg_bytes / kernel_ns / HBM_PEAK_GBS,
+                     "kernel": "tkspmv::batch_kernel<4,1024,7,false,true> (fp32, 12-bit column words, workgroup-local thresholds; up to 32 "
+                               "queries per launch; figures are per query; a failed check is repaired by an exact launch -- in the stream while "
+                               "the host has not seen clean verdicts, from the host's next wait otherwise: `late_repairs`)",
+                     "algorithmic_bytes": int(alg_bytes), "kernel_us": kernel_ns / 1e3},
+    }
+
+
 def bench_single(a, mod, torch, np, dev, local_rank):
     m = mod.generate_matrix(a.rows, a.cols, a.nnz, "gamma", 2)
     xs = np.stack([mod.create_sample_vector(a.cols, True, False, True, 1000 + i) for i in range(a.queries)])
@@ -474,8 +520,17 @@ def bench_single(a, mod, torch, np, dev, local_rank):
     host_side = {"timed_call_us": 1e6 * (t1 - t0), "device_us_by_events": kernel_ns * a.steps / 1e3,
                  "synchronisation_after_us": 1e6 * (elapsed - (t1 - t0)),
                  "note": "value uses the host clock over call + synchronisations; roofline the event pair inside the call"}
+    # ---- what the timed path delivered for its last query (engine-owned result buffers: the last query wins)
+    if a.full or a.dump_outputs:
+        val, idx = eng.read_result()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, idx, val)
+    line = single_line(a, info, elapsed, kernel_ns)
+    if not a.full:
+        eng.close()
+        print(json.dumps(line))
+        return
     # ---- parity of the last timed query against the oracle
-    val, idx = eng.read_result()
     parity_ok, parity = check_parity(mod, m, xs[(a.steps - 1) % a.queries], a.k, idx, val, eng)
     # ---- repetitions (reference hygiene: >= 30 runs, first 2 dropped, host_spmv_bscsr.cpp:699). All repetitions are enqueued
     # before the first wait (tkspmv_time_query_batches: one hipEvent between consecutive ones), so the GPU never idles between
@@ -633,26 +688,8 @@ def bench_single(a, mod, torch, np, dev, local_rank):
             detail = {"live_pass": detail}
     if traffic is None and a.traffic != "off":
         traffic, source = static_traffic(), "static"
-    line = {
-        "metric": "queries_per_sec", "value": a.steps / elapsed, "unit": "queries/s", "n_gpus": 1,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
-        # (strong: --gpus N cuts THIS matrix into N row shards -- bench_sharded -- so the total work is fixed as N grows)
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload_name(a.rows, a.cols, a.nnz, int(info["nnz"]), a.k, a.replicas),
-                   "rows": a.rows, "cols": a.cols, "nnz": int(info["nnz"]), "k": a.k, "parallelism": "single GPU",
-                   "launch": {"grid": info["grid"], "block": info["block"] + 64,
-                              "wave_partitions": info["n_wave_partitions"], "packet_entries": info["packet_entries"],
-                              # (tkspmv_info.batch_mode: how the engine runs back-to-back queries on this matrix)
-                              "selector_workgroups": info.get("batch_mode", 0) & 0xFF,
-                              "thresholds": {0: "device-wide exchange", 1: "workgroup-local (best packet maximum per wave), checked by the selection; an exact launch repeats what failed",
-                                             2: "workgroup-local (second best packet maximum per wave), checked by the selection; an exact launch repeats what failed"}[(info.get("batch_mode", 0) >> 8) & 0xFF]}},
-        "roofline": {"bound": "hbm", "achieved": alg_bytes / kernel_ns, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": alg_bytes / kernel_ns / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": source,
-                     "traffic_detail": detail,
-                     "kernel": "tkspmv::batch_kernel<4,1024,7,false,true> (fp32, 12-bit column words, workgroup-local thresholds; up to 32 "
-                               "queries per launch; figures are per query; a failed check is repaired by an exact launch -- in the stream while "
-                               "the host has not seen clean verdicts, from the host's next wait otherwise: `late_repairs`)",
-                     "algorithmic_bytes": int(alg_bytes), "kernel_us": kernel_ns / 1e3,
+    line["roofline"].update({
+                     "traffic": traffic, "traffic_source": source, "traffic_detail": detail,
                      # scalar keys (nested objects do not survive into the driver's record): the load-only floor of this
                      # box, the kernel against it, the kernel under sustained load, the checks of the timed region and its warm-up
                      "read_only_us": read_us, "kernel_vs_read_only": read_us / (kernel_ns / 1e3),
@@ -677,8 +714,7 @@ def bench_single(a, mod, torch, np, dev, local_rank):
                                "duration = event time / steps. A launch of the batch kernel streams the matrix once per "
                                "query for up to 32 queries (one continuous prefetch pipeline per wave) and selects each "
                                "query's top-k in its selector workgroup; rocprofv3's average launch duration / queries per "
-                               "launch agrees (profiles/README.md). `timing` repeats the measurement (median, p95)."},
-    }
+                               "launch agrees (profiles/README.md). `timing` repeats the measurement (median, p95)."})
     line.update(extra)
     if a.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(mod, m, xs, a.k, a.cpu_seconds)
@@ -690,8 +726,8 @@ def bench_sharded(a, mod, torch, np, dev, local_rank, rank, world):
     """--gpus N strong-scales THE workload of the --gpus 1 line: the same 1M x 1024 matrix (seed 2; every row has its own PRNG
     streams, so a rank generates exactly its rows of it), cut into N contiguous row shards balanced by nnz. BASELINE configs[3]
     -- the 10M-row matrix over the same N GPUs -- rides along as the line's `config3` key (--config3-rows 0 skips it)."""
-    line = sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, a.total_rows or a.rows, 2, a.steps, a.warmup)
-    if a.config3_rows > 0 and (world > 1 or a.total_rows == 0):
+    line = sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, a.total_rows or a.rows, 2, a.steps, a.warmup, a.dump_outputs)
+    if a.full and a.config3_rows > 0 and (world > 1 or a.total_rows == 0):
         c3 = sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, a.config3_rows, 4, min(a.steps, 256), min(a.warmup, 32))
         if rank == 0:
             line["config3"] = {k: c3[k] for k in ("value", "unit", "ms_per_step", "steps", "config", "roofline", "per_rank", "parity_checked")}
@@ -699,7 +735,7 @@ def bench_sharded(a, mod, torch, np, dev, local_rank, rank, world):
         print(json.dumps(line))
 
 
-def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, seed, steps, warmup):
+def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, seed, steps, warmup, dump=None):
     from importlib import import_module
     dist = import_module("torch.distributed")
     dmod = import_module("approximate_spmv_topk_amd.distributed")
@@ -730,7 +766,7 @@ def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, see
                   f"          (set TKSPMV_DIST=torch to measure the torch.distributed exchange instead)", file=sys.stderr)
             sys.exit(3)
     cross = None
-    if native is not None and (multi or os.environ.get("TKSPMV_BENCH_CROSS")):  # (the variable: rehearsal on one GPU)
+    if native is not None and a.full and (multi or os.environ.get("TKSPMV_BENCH_CROSS")):  # (the variable: rehearsal on one GPU)
         # The native exchange has to prove itself before it is timed (it cannot be rehearsed on a one-GPU box: RCCL refuses two
         # ranks on one device): a few queries through it, the last one's merged list against the same query through the
         # torch.distributed exchange. A mismatch, an error or no answer within 3 minutes ends the run with a message and a
@@ -776,10 +812,10 @@ def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, see
         sync_all()
         elapsed = time.perf_counter() - t0
         val, idx = native.read()  # merged (global) top-k of the last timed query
-        exchange_ns = native.time_exchange(20)
+        exchange_ns = native.time_exchange(20) if a.full else None
         exchange = {"kind": "native: RCCL ncclAllGather of 2*K int32 per rank and query + merge kernel, 32 queries per exchange, on a "
                             "side stream overlapping the next batch's local kernels (csrc/dist.hip)",
-                    "us_per_exchange_batch": exchange_ns / 1e3, "queries_per_exchange": 32,
+                    "us_per_exchange_batch": exchange_ns / 1e3 if exchange_ns is not None else None, "queries_per_exchange": 32,
                     "note": "the exchange alone, back to back (all-gather + merge launch); inside the step it overlaps the local kernels",
                     "cross_check": cross}
         native.close()
@@ -806,29 +842,14 @@ def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, see
         idx, val = ei.cpu().numpy().astype(np.uint32), ev.cpu().numpy()
         exchange = {"kind": "torch.distributed all_gather_into_tensor of 2*K int32 per rank + on-device merge, every step "
                             "(TKSPMV_DIST=torch)"}
-    kernel_ns = eng.time_queries(dxs.data_ptr(), a.queries, min(max(steps, 64), 512))  # this rank's local kernel alone
-    read_ns = sorted(eng.time_stream_read(64) for _ in range(3))[1]  # this shard's load-only floor on this rank's GPU
-    per_rank = [{"rank": rank, "rows": r1 - r0, "first_row": r0, "nnz": int(info["nnz"]), "kernel_us": kernel_ns / 1e3,
-                 "algorithmic_bytes": int(info["algorithmic_bytes"]),
-                 "frac": info["algorithmic_bytes"] / kernel_ns / HBM_PEAK_GBS,
-                 "read_only_us": read_ns / 1e3, "batch_mode": {"selector_workgroups": info.get("batch_mode", 0) & 0xFF,
-                                                              "local_thresholds": (info.get("batch_mode", 0) >> 8) & 0xFF}}]
+    if rank == 0 and dump:
+        dump_outputs(dump, idx, val)
     if multi:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        gathered = [None] * world
-        dist.all_gather_object(gathered, per_rank[0])
-        per_rank = gathered
-    parity_ok, parity, line = None, None, None
+    line = None
     if rank == 0:
-        # the merged result of the last timed query against the gold over the WHOLE matrix (built here, outside the timed
-        # region, on rank 0 only)
-        whole = mod.generate_matrix(total_rows, a.cols, a.nnz, "gamma", seed)
-        assert whole.nnz == total_nnz
-        parity_ok, parity = check_parity(mod, whole, xs[(steps - 1) % a.queries], a.k, idx, val, None, bit_exact=False)
-        del whole
-        slowest = max(per_rank, key=lambda r: r["kernel_us"])
         line = {
             "metric": "queries_per_sec", "value": steps / elapsed, "unit": "queries/s", "n_gpus": world,
             "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
@@ -837,15 +858,39 @@ def sharded_leg(a, mod, torch, np, dev, local_rank, rank, world, total_rows, see
                        "rows": total_rows, "cols": a.cols, "nnz": total_nnz, "k": a.k, "n_shards": world,
                        "parallelism": f"row-shard x{world}: ONE matrix cut into {world} contiguous row shards balanced by nnz; per "
                                       f"query one RCCL all-gather of K (row, score) pairs per rank + merge"},
+        }
+    if not a.full:
+        eng.close()
+        return line
+    kernel_ns = eng.time_queries(dxs.data_ptr(), a.queries, min(max(steps, 64), 512))  # this rank's local kernel alone
+    read_ns = sorted(eng.time_stream_read(64) for _ in range(3))[1]  # this shard's load-only floor on this rank's GPU
+    per_rank = [{"rank": rank, "rows": r1 - r0, "first_row": r0, "nnz": int(info["nnz"]), "kernel_us": kernel_ns / 1e3,
+                 "algorithmic_bytes": int(info["algorithmic_bytes"]),
+                 "frac": info["algorithmic_bytes"] / kernel_ns / HBM_PEAK_GBS,
+                 "read_only_us": read_ns / 1e3, "batch_mode": {"selector_workgroups": info.get("batch_mode", 0) & 0xFF,
+                                                              "local_thresholds": (info.get("batch_mode", 0) >> 8) & 0xFF}}]
+    if multi:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, per_rank[0])
+        per_rank = gathered
+    if rank == 0:
+        # the merged result of the last timed query against the gold over the WHOLE matrix (built here, outside the timed
+        # region, on rank 0 only)
+        whole = mod.generate_matrix(total_rows, a.cols, a.nnz, "gamma", seed)
+        assert whole.nnz == total_nnz
+        parity_ok, parity = check_parity(mod, whole, xs[(steps - 1) % a.queries], a.k, idx, val, None, bit_exact=False)
+        del whole
+        slowest = max(per_rank, key=lambda r: r["kernel_us"])
+        line.update({
             "roofline": {"bound": "hbm", "achieved": slowest["algorithmic_bytes"] / (slowest["kernel_us"] * 1e3), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": slowest["frac"], "traffic": None,
                          "kernel": "tkspmv::batch_kernel<4,1024,7> on the slowest rank's shard (per query)",
                          "algorithmic_bytes": slowest["algorithmic_bytes"], "kernel_us": slowest["kernel_us"],
                          "method": "per rank: one hipEvent pair around a batch of back-to-back local launches, no exchange"},
             "per_rank": per_rank, "exchange": exchange, "parity_checked": parity_ok, "parity": parity,
-        }
+        })
     eng.close()
-    return line if rank == 0 else None
+    return line
 
 
 def main():

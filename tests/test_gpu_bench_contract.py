@@ -1,7 +1,7 @@
 """bench.py's output contract, as the round driver consumes it: ONE JSON line with the named keys, the headline config, a
 roofline object computed from the timed region's own events and a parity verdict -- on the driver's own command line
-(`--gpus 1 --steps 20 --warmup 5`) and on the row-sharded workload of `--gpus N` rehearsed with one rank. Also the
-load-only probe behind `roofline.read_only` (tkspmv_time_stream_read)."""
+(`--gpus 1 --steps 20 --warmup 5`, with --full) and on the row-sharded workload of `--gpus N` rehearsed with one rank; the plain
+line and what `--dump-outputs` writes. Also the load-only probe behind `roofline.read_only` (tkspmv_time_stream_read)."""
 import json
 import os
 import subprocess
@@ -25,7 +25,7 @@ def _bench(*args, env=None):
 
 
 def test_headline_line_on_the_drivers_command_line():
-    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--skip-warm", "--cpu-seconds", "0", "--traffic", "off")
+    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--skip-warm", "--cpu-seconds", "0", "--traffic", "off")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "parity_checked", "timing"):
         assert key in d, key
@@ -48,10 +48,28 @@ def test_headline_line_on_the_drivers_command_line():
 
 
 def test_sharded_line_rehearsed_with_one_rank():
-    d = _bench("--total-rows", "600000", "--steps", "40", "--warmup", "8", env={"TKSPMV_BENCH_CROSS": "1"})
+    d = _bench("--total-rows", "600000", "--steps", "40", "--warmup", "8", "--full", env={"TKSPMV_BENCH_CROSS": "1"})
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["config"]["rows"] == 600000 and d["config"]["n_shards"] == 1
     assert d["parity_checked"] is True and d["exchange"]["cross_check"]["native_vs_torch_exchange_same_list"] is True
     assert len(d["per_rank"]) == 1 and d["per_rank"][0]["rows"] == 600000 and d["roofline"]["bound"] == "hbm"
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run: the headline keys, exactly `steps` timed queries, and the last timed query's top-k on disk -- the same list as
+    the gold's for that query (bench.py's matrix and vectors: seed 2, vector seeds 1000 + i over 64 resident vectors)."""
+    d = _bench("--gpus", "1", "--steps", "37", "--warmup", "5", "--dump-outputs", str(tmp_path))
+    assert d["metric"] == "queries_per_sec" and d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 37 and d["warmup"] == 5 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["ms_per_step"] * 1e3 >= d["roofline"]["kernel_us"] > 0
+    ids, scores = np.load(tmp_path / "topk_row_ids.npy"), np.load(tmp_path / "topk_scores.npy")
+    assert ids.dtype == np.float64 and scores.dtype == np.float32 and ids.shape == scores.shape == (100,)
+    import _pkg
+    import bench
+    mod = _pkg.load()
+    m = mod.generate_matrix(1000000, 1024, 20, "gamma", 2)
+    x = mod.create_sample_vector(1024, True, False, True, 1000 + 36 % 64)
+    ok, parity = bench.check_parity(mod, m, x, 100, ids.astype(np.uint32), scores)  # (the bar of the line's parity_checked)
+    assert ok, parity
 
 
 def test_load_only_probe_brackets_the_kernel(pkg):

@@ -19,9 +19,9 @@ mkdir -p "$OUT"
 ALIVE=$!
 trap "kill $ALIVE 2>/dev/null" EXIT
 if [ "$PART" != B ]; then
-python3 bench.py --steps 3000 --warmup 300 > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
+python3 bench.py --steps 3000 --warmup 300 --full > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
 # (the driver's own command line: ONE launch of 20 queries, start-up and tail included)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --skip-warm --cpu-seconds 0 --traffic off > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --skip-warm --cpu-seconds 0 --traffic off > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
 cd /tmp && export TMPDIR=/tmp
 # (--headline-only: the trace holds nothing but headline queries -- VERDICT r4 --, plus the 100 launches tkspmv_create measures its pacing
 #  with, which tools/summarize_profile.py leaves out of <tag>_headline_launches.json)
@@ -53,13 +53,13 @@ unset TKSPMV_MULTI_CHAINS
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/q17f2" -- python3 "$REPO/tools/q17f_probe.py" --only > "$OUT/q17f2.log" 2> "$OUT/q17f2.err"
 # 7. one shard of a strong-scaled run (1/8 of the 1M-row matrix) through bench.py's sharded code path: the batch kernel with its
 #    small-matrix settings (4 selector workgroups, workgroup-local thresholds, the repair launch behind every batch launch)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/shard125k" -- python3 "$REPO/bench.py" --total-rows 125000 --config3-rows 0 --steps 2048 --warmup 256 > "$OUT/shard125k.json" 2> "$OUT/shard125k.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/shard125k" -- python3 "$REPO/bench.py" --total-rows 125000 --config3-rows 0 --steps 2048 --warmup 256 --full > "$OUT/shard125k.json" 2> "$OUT/shard125k.err"
 # 8. BASELINE configs[3] on ONE GPU (10M rows) in the mode the bench reports it: back-to-back batch launches, two stream copies
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/config3" -- python3 "$REPO/bench.py" --rows 10000000 --replicas 2 --steps 128 --warmup 32 --cpu-seconds 0 --skip-warm --traffic off --reps 4 --multi-q > "$OUT/config3.json" 2> "$OUT/config3.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/config3" -- python3 "$REPO/bench.py" --rows 10000000 --replicas 2 --steps 128 --warmup 32 --full --cpu-seconds 0 --skip-warm --traffic off --reps 4 --multi-q > "$OUT/config3.json" 2> "$OUT/config3.err"
 cd "$REPO"
 # 9. the shards of a strong-scaled 1M-row run through bench.py's sharded code path on ONE GPU, and the size sweep
 for rows in 125000 250000 500000; do
-  timeout -k 10 300 python3 bench.py --total-rows $rows --config3-rows 0 --steps 2048 --warmup 256 > "$OUT/shard_rehearsal_$rows.json" 2> "$OUT/shard_rehearsal_$rows.err"
+  timeout -k 10 300 python3 bench.py --total-rows $rows --config3-rows 0 --steps 2048 --warmup 256 --full > "$OUT/shard_rehearsal_$rows.json" 2> "$OUT/shard_rehearsal_$rows.err"
 done
 { echo "# us per query of back-to-back queries (batch kernel), median of 5 timed batches of 256; tools/size_sweep.py"
   echo "## SWEEP=small (the shard sizes of a strong-scaled 1M-row matrix), defaults"; SWEEP=small timeout -k 10 300 python3 tools/size_sweep.py 2>/dev/null | grep F32
