@@ -25,7 +25,7 @@ static const OptionDef k_options[] = {
     {"OVF_LISTS", "tuning", "1 | 2 | 4 (default 4; 2 for engines that stream with local thresholds; at least 2 wherever the deferred scheme can run)", "overflow lists of the exact kernel (8 bytes per row each), shared round robin by the queries of a launch under flow control"},
     {"PACE", "tuning", "0..32 (default by size)", "pacing quantum of the batch kernel's workgroups by rank (s_sleep units); 0 = none"},
     {"PACE_LEVELS", "tuning", "1..8", "number of distinct pacing ranks"},
-    {"AUTOTUNE", "behaviour", "0 | 1 (default 1)", "1: tkspmv_create measures a handful of pacing settings on the matrix it has just packed (engines of checked local thresholds that pace at all; ~10 ms) and keeps the fastest; PACE / PACE_LEVELS / PACE_BASE switch it off"},
+    {"AUTOTUNE", "behaviour", "0 | 1 (default 1)", "1: tkspmv_create measures a handful of pacing settings on the matrix it has just packed -- pauses by rank, then the period of a timetable unless PACE_PERIOD gives one -- (engines of checked local thresholds that pace at all; ~140 ms at 1M rows) and keeps the fastest; PACE / PACE_LEVELS / PACE_BASE switch it off"},
     {"PACE_CARRY", "tuning", "0 | 1 (default 1)", "1: a workgroup starts a launch with the pause it ended the previous launch with; 0: every launch starts unpaced"},
     {"HOST_TIMES", "diagnostic", "set = on", "tkspmv_time_queries prints to stderr where the host's microseconds around the timed region go"},
     {"EXT_EVENTS", "diagnostic", "0 | 1 | 2 (default 1; 2 = the pair recorded right in front of the first and right behind the last launch: 7 us more per region than 1, and the device-wide wait behind the call 11 us cheaper)", "tkspmv_time_queries: 1 = the event pair travels with the region's first and last kernel (hipExtLaunchKernelGGL: the dispatches' own start and end stamps, what rocprofv3 reports); 0 = hipEventRecord before and after (the start stamp then precedes the host's writing of the first dispatch packet: +1.6 us)"},
@@ -37,7 +37,7 @@ static const OptionDef k_options[] = {
      "who looks at the verdict of a launch of checked local thresholds: host = the launch goes out alone once the verdicts the host has seen are clean, "
      "and tkspmv_synchronize / tkspmv_read (any engine call that waits for the engine's stream) repair a flagged query with an exact launch; "
      "stream = the exact launch follows every local launch in the stream (always so on a caller's stream and for 64 launches after an observed failure)"},
-    {"OVERLAP", "behaviour", "0 | 1 (default 1)", "1: consecutive launches of one sequence of checked local thresholds alternate between two streams while they go out trusted (REPAIR=host): the next launch's ramp fills the previous one's tail; 0: one launch at a time"},
+    {"OVERLAP", "behaviour", "0 | 1 (default 0)", "1: consecutive launches of one sequence of checked local thresholds alternate between two streams while they go out trusted (REPAIR=host): the next launch's ramp fills the previous one's tail -- the second stream is created only then; 0: one launch at a time"},
     {"FUSED", "behaviour", "0 | 1 (default 1 where the selection fits one workgroup)", "0: stream and selection as two launches"},
     {"RADIX", "behaviour", "0 | 1 (default: k above 3/8 of the publishing groups)", "1: scores + radix select instead of thresholded streaming"},
     {"MULTI_Q", "behaviour", "0 | 1 | 3 | 5 | 8 (default by size; desc.multi_q wins)", "queries per pass of the small-matrix kernel (multi_kernel); 0 = off"},
