@@ -79,6 +79,11 @@ int tkspmv_enqueue_many(tkspmv_t *h, const float *dev_xs, int32_t n_x, int32_t c
 int tkspmv_enqueue_batch(tkspmv_t *h, const float *dev_xs, int32_t count, uint32_t *dev_idx, float *dev_val, void *stream) {
     ENGINE_CALL(enqueue_batch(dev_xs, count, dev_idx, dev_val, stream, err))
 }
+int tkspmv_enqueue_filtered(tkspmv_t *h, const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words,
+                            uint32_t *dev_idx, float *dev_val, void *stream) {
+    ENGINE_CALL(enqueue_filtered(dev_xs, count, dev_mask, mask_stride_words, dev_idx, dev_val, stream, err))
+}
+int tkspmv_set_filter(tkspmv_t *h, const uint32_t *host_mask) { ENGINE_CALL(set_filter(host_mask, err)) }
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
 int tkspmv_result_device(tkspmv_t *h, const uint32_t **dev_idx, const float **dev_val) {

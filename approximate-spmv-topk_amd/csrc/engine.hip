@@ -290,6 +290,11 @@ struct EngineImpl {
     uint32_t *d_lready = nullptr;            // [grid] the streaming workgroups' flags (LocalParams::ready; NULL: the last workgroup selects)
     mutable uint64_t single_launches = 0, single_repairs = 0;
     uint32_t uni_ppp = 0, uni_last = 0;  // uniform partition table (StreamParams::uni_ppp): partition q = packets [q * uni_ppp, ...)
+    // Filtered queries (tkspmv_enqueue_filtered, stream_filter_kernel): the allow-mask tkspmv_set_filter installed, ceil(rows / 32)
+    // words (allocated on the first call), and whether one is installed now
+    uint32_t *d_filter = nullptr;
+    bool have_filter = false;
+    uint32_t mask_words() const { return std::max<uint32_t>(1u, (desc.rows + 31u) / 32u); }
 
     StreamParams stream_params(const float *x, int set = 0) const {
         StreamParams P{};
@@ -653,7 +658,7 @@ struct EngineImpl {
         }
     }
     // One query of a back-to-back sequence: its selection runs inside the NEXT deferred launch (or in drain()).
-    void launch_deferred(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s) const {
+    void launch_deferred(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) const {
         if (!can_defer) {
             launch_query(x, out_idx, out_val, s);
             return;
@@ -667,7 +672,7 @@ struct EngineImpl {
             S.unit_inv_in = st[pending_set].unit_inv;
         }
         ++launch_counter;
-        hipLaunchKernelGGL(kernel_for(false), dim3(grid), dim3(block + 64), 0, s, P, S);
+        launch_stream_kernel(false, F, s, P, S);
         pending = true;
         pending_set = cur_set;
         pending_idx = out_idx;
@@ -716,7 +721,49 @@ struct EngineImpl {
         if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096> : &stream_kernel<4, false, 4096>;
         return scores ? &stream_kernel<4, true, 16384> : &stream_kernel<4, false, 16384>;
     }
-    void launch_stream(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host = false) const {
+    // The filtered twin of kernel_for: fp32 engines only (12-bit column words, plain fp32 up to 16384 columns, 8 entries per lane).
+    typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
+    filter_fn filter_kernel_for(bool scores) const {
+        if (info.packet_entries == 512) return scores ? &stream_filter_kernel<8, true, 1024, 0, 2> : &stream_filter_kernel<8, false, 1024, 0, 2>;
+        if (pm.precision == Precision::F32C12) return scores ? &stream_filter_kernel<4, true, 1024, 7> : &stream_filter_kernel<4, false, 1024, 7>;
+        if (xcols <= 1024) return scores ? &stream_filter_kernel<4, true, 1024> : &stream_filter_kernel<4, false, 1024>;
+        if (xcols <= 4096) return scores ? &stream_filter_kernel<4, true, 4096> : &stream_filter_kernel<4, false, 4096>;
+        return scores ? &stream_filter_kernel<4, true, 16384> : &stream_filter_kernel<4, false, 16384>;
+    }
+    // One launch of the streaming kernel: stream_kernel, or stream_filter_kernel with the allow-mask F.
+    void launch_stream_kernel(bool scores, const FilterParams *F, hipStream_t s, const StreamParams &P, const SelectParams &S) const {
+        if (F) hipLaunchKernelGGL(filter_kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S, *F);
+        else hipLaunchKernelGGL(kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S);
+    }
+    // Why filtered queries are not served by this engine (nullptr: they are).
+    const char *filter_unsupported() const {
+        if (desc.precision != TKSPMV_F32) return "filtered queries need fp32 values (TKSPMV_F32)";
+        if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12) return "filtered queries need an fp32 packet stream";
+        if (approx_parts) return "filtered queries are exact only: partitions > 1 with k > k_per_partition is the approximate per-partition path";
+        if (!d_packets || !d_pkt_row) return "filtered queries stream the wave-BSCSR packets: this engine does not hold them";
+        return nullptr;
+    }
+    // A sequence of filtered queries (query i: x = xs[i], mask = mask + i * stride words), complete in stream order when this
+    // returns. The launch scheme is the one of a single exact query: deferred selections where the engine has them, else stream +
+    // select, scores + radix select where the engine takes that path. Never the batch, single or multi-query kernels: their carried
+    // thresholds assume the score distribution of the query before, which a per-query filter breaks.
+    void launch_filtered(const float *const *xs, const uint32_t *mask, size_t stride, uint32_t *const *out_idx, float *const *out_val, int n,
+                         hipStream_t s) const {
+        drain(s);  // (a deferred selection still owed uses the same exchange-state sets)
+        for (int i = 0; i < n; ++i) {
+            const FilterParams F{mask + (size_t)i * stride, mask_words()};
+            if (use_radix) {
+                launch_query_radix(xs[i], out_idx[i], out_val[i], s, &F);
+            } else if (can_defer) {
+                launch_deferred(xs[i], out_idx[i], out_val[i], s, &F);
+            } else {
+                launch_stream(xs[i], out_idx[i], out_val[i], s, false, &F);
+                if (!fused) launch_select(out_idx[i], out_val[i], s);
+            }
+        }
+        drain(s);
+    }
+    void launch_stream(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host = false, const FilterParams *F = nullptr) const {
         StreamParams P = stream_params(x);
         SelectParams S = select_params(out_idx, out_val);
         if (to_host) {
@@ -725,7 +772,7 @@ struct EngineImpl {
             S.t_start = d_tstart;
         }
         ++launch_counter;
-        hipLaunchKernelGGL(kernel_for(false), dim3(grid), dim3(block + 64), 0, s, P, S);
+        launch_stream_kernel(false, F, s, P, S);
     }
     // One query through single_kernel (local thresholds, checked): the result is exact iff the status word / host flag says the
     // check passed; otherwise the caller runs launch_stream, whose result is exact on its own.
@@ -753,8 +800,8 @@ struct EngineImpl {
         if (pm.precision == Precision::F32C12) hipLaunchKernelGGL((single_kernel<7>), dim3(grid), dim3(512), 0, s, P, S, G);
         else hipLaunchKernelGGL((single_kernel<0>), dim3(grid), dim3(512), 0, s, P, S, G);
     }
-    void launch_query_radix(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s) const {
-        launch_scores(x, s, d_rscores);
+    void launch_query_radix(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) const {
+        launch_scores(x, s, d_rscores, F);
         RadixParams R{};
         R.scores = d_rscores;
         R.rows = desc.rows;
@@ -790,12 +837,12 @@ struct EngineImpl {
         S.out_scale = 1.0f;  // the scores kernel already wrote final scores
         hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
     }
-    void launch_scores(const float *x, hipStream_t s, float *dst = nullptr) const {
+    void launch_scores(const float *x, hipStream_t s, float *dst = nullptr, const FilterParams *F = nullptr) const {
         StreamParams P = stream_params(x);
         if (dst) P.scores = dst;
         SelectParams S = select_params(d_out_idx, d_out_val);
         ++launch_counter;  // the stream copies rotate per query here too (cache-defeat mode)
-        hipLaunchKernelGGL(kernel_for(true), dim3(grid), dim3(block + 64), 0, s, P, S);
+        launch_stream_kernel(true, F, s, P, S);
     }
     void launch_select(uint32_t *out_idx, float *out_val, hipStream_t s, int set = 0) const {
         SelectParams S = select_params(out_idx, out_val, set);
@@ -1887,6 +1934,65 @@ int Engine::enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_
     hipStream_t s = stream ? (hipStream_t)stream : m.stream;
     HIP_TRY(hipSetDevice(m.device));
     m.launch_multi_sequence(dev_xs, dev_idx, dev_val, count, s);
+    HIP_TRY(hipGetLastError());
+    m.ran = true;
+    m.last_on_host = false;
+    return TKSPMV_OK;
+}
+
+int Engine::set_filter(const uint32_t *host_mask, std::string &err) {
+    EngineImpl &m = *impl_;
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(hipStreamSynchronize(m.stream));  // (a filtered query enqueued earlier may still read the installed mask)
+    if (!host_mask) {
+        m.have_filter = false;
+        return TKSPMV_OK;
+    }
+    if (!m.d_filter) HIP_TRY(m.alloc(m.d_filter, (size_t)m.mask_words() * 4));
+    HIP_TRY(hipMemcpy(m.d_filter, host_mask, (size_t)m.mask_words() * 4, hipMemcpyHostToDevice));
+    m.have_filter = true;
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
+                             float *dev_val, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (const char *why = m.filter_unsupported()) {
+        err = why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) {
+        err = "bad arguments to enqueue_filtered (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (!dev_mask && !m.have_filter) {
+        err = "no allow-mask given and none installed (tkspmv_set_filter)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (!dev_xs && count != 1) {
+        err = "dev_xs = NULL takes the installed query vector: count must be 1";
+        return TKSPMV_ERR_INVALID;
+    }
+    const float *x = dev_xs ? dev_xs : m.d_x_cur;
+    if (!x) {
+        err = "no query vector installed (call tkspmv_set_query first)";
+        return TKSPMV_ERR_STATE;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
+    HIP_TRY(hipSetDevice(m.device));
+    // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
+    // after the filtered queries did. Settle them now (the host waits for the engine's stream once).
+    if (!m.pending_checks.empty()) {
+        HIP_TRY(hipStreamSynchronize(m.stream));
+        HIP_TRY(m.settle());
+    }
+    HIP_TRY(m.order_x(x, s));
+    std::vector<const float *> xs;
+    std::vector<uint32_t *> oi;
+    std::vector<float *> ov;
+    sequence_lists(m, x, count, count, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, dev_idx ? (size_t)m.desc.k : 0, xs, oi,
+                   ov);
+    m.launch_filtered(xs.data(), dev_mask ? dev_mask : m.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, oi.data(), ov.data(), count, s);
     HIP_TRY(hipGetLastError());
     m.ran = true;
     m.last_on_host = false;

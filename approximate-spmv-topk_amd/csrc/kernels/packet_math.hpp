@@ -463,6 +463,54 @@ __device__ __forceinline__ uint32_t ends_below(const RowSums<C> &R) {
     return below;
 }
 
+// Allow-mask of a filtered query (stream_filter_kernel). A kernel argument of its own, not fields of StreamParams: every other
+// kernel keeps its argument layout. Bit r & 31 of word r >> 5 set: local row r may be returned.
+struct FilterParams {
+    const uint32_t *mask;  // this query's words
+    uint32_t words;        // ceil(rows / 32), at least 1
+};
+// Mask words w and w + 1 (clamped to the last word: the loads never leave the mask; a clamped word only ever stands for rows
+// that do not exist). Scalar loads: they retire through lgkmcnt, so neither issuing them in the packet loop nor waiting for
+// them holds back the packet prefetch (vmcnt).
+__device__ __forceinline__ uint2 mask_pair(const FilterParams &F, uint32_t rb) {
+    const uint32_t w = rb >> 5, last = F.words - 1u;
+    return make_uint2(scalar_load(F.mask + (w < last ? w : last)), scalar_load(F.mask + (w + 1u < last ? w + 1u : last)));
+}
+// Marks the row ends of R whose rows the mask excludes the way a placeholder of an empty row is marked (bit 8 + j of fl), so
+// valid(j) is false for them. rb: the packet's first row; mw: mask_pair(F, rb), prefetched. The lane's row ends are the
+// consecutive rows r0, r0 + 1, ... (at most C of them), so two words picked in registers cover them; the words past rb's
+// second are loaded here, only for packets that end more rows than those 33..64 (scalar, uniform, usually none).
+template <int C>
+__device__ __forceinline__ void mask_rows(RowSums<C> &R, uint32_t rb, uint2 mw, const FilterParams &F) {
+    uint32_t below = 0, n_ends = 0;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const uint64_t b = __ballot(R.end(j));
+        below += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        n_ends += (uint32_t)__popcll(b);
+    }
+    const uint32_t r0 = rb + below;  // the lane's first row end
+    const uint32_t wb = rb >> 5;
+    const uint32_t lw = (r0 >> 5) - wb;  // the lane's first word, relative to wb
+    uint32_t lo = lw == 0u ? mw.x : (lw == 1u ? mw.y : 0u);
+    uint32_t hi = lw == 0u ? mw.y : 0u;
+    const uint32_t we = n_ends != 0u ? (rb + n_ends - 1u) >> 5 : wb;  // last word the packet's rows reach (uniform)
+    for (uint32_t w = wb + 2u; w <= we; ++w) {
+        const uint32_t s = scalar_load(F.mask + (w < F.words - 1u ? w : F.words - 1u));
+        lo = (lw == w - wb) ? s : lo;
+        hi = (lw + 1u == w - wb) ? s : hi;
+    }
+    uint32_t bits = __builtin_amdgcn_alignbit(hi, lo, r0 & 31u);  // bit t: row r0 + t
+    uint32_t kill = 0u;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const uint32_t e = (R.fl >> j) & 1u;
+        kill |= (e & ~bits & 1u) << (8 + j);
+        bits >>= e;
+    }
+    R.fl |= kill;
+}
+
 // Filter a wave's private candidate list against the threshold: lane l holds entries l, l+64, ... (EPL per lane);
 // keep[] / pos[] tell which survive and where they go in the compacted order. Returns the number kept.
 template <uint32_t EPL>

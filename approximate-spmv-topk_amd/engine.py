@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .host import row_mask
 
 
 class SpMV:
@@ -144,6 +145,39 @@ class SpMV:
                                                    C.c_void_p(int(dev_val)) if dev_val else None,
                                                    C.c_void_p(int(stream))))
 
+    def enqueue_filtered(self, dev_xs, count, dev_mask, mask_stride=0, dev_idx=0, dev_val=0, stream=0):
+        """Filtered top-k of `count` queries: query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset())
+        restricted to the rows set in the allow-mask dev_mask + i*mask_stride words (mask_stride = 0: one mask for every query;
+        dev_mask = 0: the mask installed by set_filter). Masks are uint32 words as row_mask() builds them. Results as in
+        enqueue_batch. No host sync."""
+        _lib.check(_lib.lib().tkspmv_enqueue_filtered(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
+                                                      C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
+                                                      C.c_void_p(int(dev_idx)) if dev_idx else None,
+                                                      C.c_void_p(int(dev_val)) if dev_val else None,
+                                                      C.c_void_p(int(stream))))
+
+    def set_filter(self, mask_words):
+        """Installs an allow-mask (row_mask() words, ceil(rows/32) of them) for enqueue_filtered(dev_mask=0); None removes it."""
+        if mask_words is None:
+            _lib.check(_lib.lib().tkspmv_set_filter(self._h, None))
+            return
+        w = np.ascontiguousarray(mask_words, dtype=np.uint32)
+        if w.shape != ((self.num_rows + 31) // 32,):
+            raise ValueError(f"allow-mask has {w.size} words, expected {(self.num_rows + 31) // 32} for {self.num_rows} rows")
+        _lib.check(_lib.lib().tkspmv_set_filter(self._h, w.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def run_filtered(self, vec=None, allow=None):
+        """One filtered query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
+        row_mask() words), then the query restricted to the installed mask. Returns (values, indices) like read_result."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self.enqueue_filtered(0, 1, 0)
+        self.synchronize()
+        return self.read_result()
+
     def enqueue_multi(self, dev_xs, count, dev_idx=0, dev_val=0, stream=0):
         """enqueue_batch with several queries per pass over the matrix (info()["multi_q"] of them share every chunk that
         is loaded; engine created with multi_q > 0). Same arguments; dev_xs = 0 with count = 1: the vector installed by
@@ -218,10 +252,13 @@ class SpMV:
             pass
 
 
-def topk_spmv(m, vec, k=100, **kw):
-    """One-shot helper: build the engine for CooMatrix m, run one query, return (values, indices)."""
+def topk_spmv(m, vec, k=100, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, run one query, return (values, indices). allow: a bool array of
+    length m.rows (or row_mask() words): the top-k among those rows only (filtered query)."""
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
     try:
+        if allow is not None:
+            return e.run_filtered(allow=allow)
         e()
         return e.read_result()
     finally:

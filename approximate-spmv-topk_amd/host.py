@@ -71,6 +71,33 @@ def create_sample_vector(size, random=False, sum_to_one=True, norm_one=False, se
     return vec
 
 
+def row_mask(rows, allow=None, exclude=None):
+    """Allow-mask of a filtered query (SpMV.enqueue_filtered / set_filter): ceil(rows/32) uint32 words, bit r & 31 of word
+    r >> 5 set when local row r may be returned (LSB first: numpy's packbits(..., bitorder="little") viewed as <u4).
+    allow: bool array of length rows (None: every row); exclude: row ids to clear afterwards."""
+    rows = int(rows)
+    if rows < 0:
+        raise ValueError("rows must be non-negative")
+    if allow is None:
+        bits = np.ones(rows, dtype=bool)
+    else:
+        bits = np.asarray(allow)
+        if bits.dtype != np.bool_:
+            raise ValueError("allow must be a bool array")
+        if bits.shape != (rows,):
+            raise ValueError(f"allow has shape {bits.shape}, expected ({rows},)")
+        bits = bits.copy()
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).ravel()
+        if ex.size and (ex.min() < 0 or ex.max() >= rows):
+            raise ValueError("exclude holds a row id outside [0, rows)")
+        bits[ex] = False
+    words = max(1, (rows + 31) // 32)
+    padded = np.zeros(words * 32, dtype=bool)
+    padded[:rows] = bits
+    return np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()

@@ -200,6 +200,23 @@ int tkspmv_enqueue_many(tkspmv_t *e, const float *dev_xs, int32_t n_x, int32_t c
  * dev_val + i * k (both NULL => engine-owned buffers, last query wins). Same launch scheme as enqueue_many. */
 int tkspmv_enqueue_batch(tkspmv_t *e, const float *dev_xs, int32_t count, uint32_t *dev_idx, float *dev_val,
                          void *stream);
+/* Filtered top-k: query i = dev_xs + i * cols, restricted to the rows set in dev_mask + i * mask_stride_words
+ * (mask_stride_words = 0: one mask for every query). dev_xs = NULL with count = 1: the vector installed by
+ * tkspmv_set_query. dev_mask = NULL: the engine-owned mask installed by tkspmv_set_filter.
+ * dev_idx/dev_val: [count][k] or NULL (engine-owned buffers, last query wins). Exact; same stream contract as tkspmv_enqueue_batch.
+ * The allow-mask: one bit per local row (before desc.first_row is added), bit r & 31 of word r >> 5 set = row r may be
+ * returned; ceil(rows / 32) words per mask, bits at and beyond rows are ignored. The result is exactly the top-k of the
+ * allowed rows that have entries and score >= min_score, in the usual order (score descending, then row descending), with
+ * scores bit-identical to the unfiltered query's; fewer than k such rows: padded with (0, 0.0f) as tkspmv_read documents.
+ * Launch scheme: one exact launch per query (deferred selection, or stream + select, or scores + radix select as the engine
+ * would run a single query), never the batch, single-query or multi-query kernels. Errors: TKSPMV_ERR_INVALID for a NULL mask
+ * with no filter installed, count < 1 or a negative stride; TKSPMV_ERR_STATE for a NULL dev_xs with no query installed;
+ * TKSPMV_ERR_UNSUPPORTED on engines without this path (values other than TKSPMV_F32, the approximate per-partition path). */
+int tkspmv_enqueue_filtered(tkspmv_t *e, const float *dev_xs, int32_t count, const uint32_t *dev_mask,
+                            int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, void *stream);
+/* Host allow-mask (ceil(rows/32) words) copied into an engine-owned device buffer; NULL removes it. Waits for the engine's
+ * stream first (a filtered query enqueued there may still read the mask it replaces). */
+int tkspmv_set_filter(tkspmv_t *e, const uint32_t *host_mask);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
