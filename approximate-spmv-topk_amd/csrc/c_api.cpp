@@ -84,6 +84,13 @@ int tkspmv_enqueue_filtered(tkspmv_t *h, const float *dev_xs, int32_t count, con
     ENGINE_CALL(enqueue_filtered(dev_xs, count, dev_mask, mask_stride_words, dev_idx, dev_val, stream, err))
 }
 int tkspmv_set_filter(tkspmv_t *h, const uint32_t *host_mask) { ENGINE_CALL(set_filter(host_mask, err)) }
+int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask,
+                         int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream) {
+    ENGINE_CALL(enqueue_range(dev_xs, count, dev_thresholds, dev_mask, mask_stride_words, dev_idx, dev_val, capacity, dev_counts, stream, err))
+}
+int tkspmv_run_range(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count) {
+    ENGINE_CALL(run_range(threshold, use_filter, idx, val, capacity, count, err))
+}
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
 int tkspmv_result_device(tkspmv_t *h, const uint32_t **dev_idx, const float **dev_val) {

@@ -33,6 +33,7 @@
 
 #include "device_pack.hpp"
 #include "engine.hpp"
+#include "host_utils.hpp"
 #include "options.hpp"
 #include "wsell.hpp"
 
@@ -45,6 +46,7 @@
 #include "kernels/multi_kernel.hpp"
 #include "kernels/radix_select.hpp"
 #include "kernels/read_probe.hpp"
+#include "kernels/range_kernel.hpp"
 
 namespace tkspmv {
 
@@ -295,6 +297,16 @@ struct EngineImpl {
     uint32_t *d_filter = nullptr;
     bool have_filter = false;
     uint32_t mask_words() const { return std::max<uint32_t>(1u, (desc.rows + 31u) / 32u); }
+    // Range queries (tkspmv_enqueue_range, range_kernel). They touch none of the state above: what is kept here is the timetable's
+    // period (option RANGE_PERIOD, ns per query; unset: the engine's own pace_period_ns when tkspmv_create kept one) and the
+    // scratch of tkspmv_run_range (allocated on its first call, grown to the largest capacity asked for).
+    static constexpr int RANGE_MAX = 32;  // queries per launch
+    bool range_period_set = false;
+    uint32_t range_period_ns = 0;
+    uint32_t *d_range_idx = nullptr;
+    float *d_range_val = nullptr;
+    uint32_t range_cap = 0;
+    uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count
 
     StreamParams stream_params(const float *x, int set = 0) const {
         StreamParams P{};
@@ -734,6 +746,48 @@ struct EngineImpl {
     void launch_stream_kernel(bool scores, const FilterParams *F, hipStream_t s, const StreamParams &P, const SelectParams &S) const {
         if (F) hipLaunchKernelGGL(filter_kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S, *F);
         else hipLaunchKernelGGL(kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S);
+    }
+    // The range twin of filter_kernel_for: the same fp32 packet streams, with and without an allow-mask.
+    typedef void (*range_fn)(const StreamParams, const RangeParams);
+    template <bool FILT>
+    range_fn range_kernel_of() const {
+        if (info.packet_entries == 512) return &range_kernel<8, 1024, 0, FILT, 2>;
+        if (pm.precision == Precision::F32C12) return &range_kernel<4, 1024, 7, FILT, 3>;
+        if (xcols <= 1024) return &range_kernel<4, 1024, 0, FILT, 3>;
+        if (xcols <= 4096) return &range_kernel<4, 4096, 0, FILT, 3>;
+        return &range_kernel<4, 16384, 0, FILT, 3>;
+    }
+    // n range queries (query i: x = xs + i * cols, threshold thresholds[i], mask = mask + i * stride words or none), complete in
+    // stream order when this returns: the counters are zeroed in front, then launches of up to RANGE_MAX queries. No engine state is
+    // read or written besides the matrix: the stream copies rotate with the query's number in THIS call.
+    void launch_range(const float *xs, int n, const float *thresholds, const uint32_t *mask, size_t stride, uint32_t *idx, float *val,
+                      uint32_t capacity, uint32_t *counts, hipStream_t s) const {
+        (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
+        StreamParams P = stream_params(xs);
+        RangeParams R{};
+        R.n_replicas = d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(d_replicas.size(), 16);
+        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = d_replicas.empty() ? d_packets : d_replicas[r];
+        R.mask_stride = (uint32_t)stride;
+        R.mask_words = mask_words();
+        R.capacity = capacity;
+        R.first_row = desc.first_row;
+        const uint32_t period_ns = range_period_set ? range_period_ns : pace_period_ns;
+        const range_fn fn = mask ? range_kernel_of<true>() : range_kernel_of<false>();
+        for (int i = 0; i < n; i += RANGE_MAX) {
+            const int c = std::min(RANGE_MAX, n - i);
+            R.q0 = (uint32_t)i;
+            R.n_q = (uint32_t)c;
+            R.xs = xs + (size_t)i * desc.cols;
+            R.thresholds = thresholds + i;
+            R.mask = mask ? mask + (size_t)i * stride : nullptr;
+            R.counts = counts + i;
+            R.idx = idx ? idx + (size_t)i * capacity : nullptr;
+            R.val = val ? val + (size_t)i * capacity : nullptr;
+            // (the waves keep the timetable in 32 bits of ticks << 8, as in launch_batch; one partition per wave, or no timetable)
+            R.period = (uint32_t)std::min<uint64_t>(0xFFFFFF00ull, (uint64_t)period_ns * 256u / 10u);
+            if ((uint64_t)period_ns * (uint64_t)c > 40000000ull || (uint64_t)P.n_parts > (uint64_t)grid * 8u) R.period = 0u;
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
+        }
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -1419,6 +1473,10 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     if (const char *f = opt("PACE_CARRY")) m.pace_carry = atoi(f) != 0;
     if (const char *f = opt("PACE_ADAPT")) m.pace_adapt_on = atoi(f) != 0;
     if (const char *f = opt("PACE_PERIOD")) m.pace_period_ns = (uint32_t)std::max(0, std::min(10000000, atoi(f)));
+    if (const char *f = opt("RANGE_PERIOD")) {
+        m.range_period_set = true;
+        m.range_period_ns = (uint32_t)std::max(0, std::min(10000000, atoi(f)));
+    }
     if (m.use_local && m.pace_quads != 0u) {
         HIP_TRY(m.alloc(m.d_wg_pace, (size_t)m.grid * 4, Mem::Device, 0));
         HIP_TRY(m.alloc(m.d_pace_adapt, 128, Mem::Exchange, 0));
@@ -1996,6 +2054,86 @@ int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t 
     HIP_TRY(hipGetLastError());
     m.ran = true;
     m.last_on_host = false;
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                          uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (const char *why = m.filter_unsupported()) {
+        err = std::string("range queries share the filtered path's scope: ") + why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    if (count < 1 || !dev_thresholds || !dev_counts || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) ||
+        (capacity > 0u && !dev_idx) || (capacity == 0u && dev_idx)) {
+        err = "bad arguments to enqueue_range (count >= 1, thresholds and counts given, mask_stride_words >= 0, dev_idx and dev_val both given with "
+              "capacity > 0 or both NULL with capacity = 0)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (!dev_xs && count != 1) {
+        err = "dev_xs = NULL takes the installed query vector: count must be 1";
+        return TKSPMV_ERR_INVALID;
+    }
+    const float *x = dev_xs ? dev_xs : m.d_x_cur;
+    if (!x) {
+        err = "no query vector installed (call tkspmv_set_query first)";
+        return TKSPMV_ERR_STATE;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(m.order_x(x, s));
+    m.launch_range(x, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_idx, dev_val, capacity, dev_counts, s);
+    HIP_TRY(hipGetLastError());
+    return TKSPMV_OK;
+}
+
+int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (const char *why = m.filter_unsupported()) {
+        err = std::string("range queries share the filtered path's scope: ") + why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx)) {
+        err = "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (use_filter && !m.have_filter) {
+        err = "use_filter without an installed allow-mask (tkspmv_set_filter)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (!m.d_x_cur) {
+        err = "no query vector installed (call tkspmv_set_query first)";
+        return TKSPMV_ERR_STATE;
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    if (!m.d_range_word) HIP_TRY(m.alloc(m.d_range_word, 128, Mem::Device, 0));
+    if (capacity > m.range_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's launch is long complete: run_range waits itself)
+        m.release(m.d_range_idx);
+        m.release(m.d_range_val);
+        m.d_range_idx = nullptr;
+        m.d_range_val = nullptr;
+        m.range_cap = 0u;
+        HIP_TRY(m.alloc(m.d_range_idx, (size_t)capacity * 4));
+        HIP_TRY(m.alloc(m.d_range_val, (size_t)capacity * 4));
+        m.range_cap = capacity;
+    }
+    HIP_TRY(hipMemcpy(m.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
+    const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.d_range_word), use_filter ? m.d_filter : nullptr, 0,
+                                 capacity ? m.d_range_idx : nullptr, capacity ? m.d_range_val : nullptr, capacity, m.d_range_word + 1, nullptr, err);
+    if (st != TKSPMV_OK) return st;
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(m.settle());  // (the host has just waited for the engine's stream)
+    m.x_pending = false;
+    uint32_t found = 0u;
+    HIP_TRY(hipMemcpy(&found, m.d_range_word + 1, 4, hipMemcpyDeviceToHost));
+    *count = found;
+    const size_t kept = std::min<size_t>(found, capacity);
+    if (kept) {
+        HIP_TRY(hipMemcpy(idx, m.d_range_idx, kept * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(val, m.d_range_val, kept * 4, hipMemcpyDeviceToHost));
+        sort_tuples(kept, idx, val);
+    }
     return TKSPMV_OK;
 }
 

@@ -34,6 +34,11 @@ class Engine {
     int enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
                          float *dev_val, void *stream, std::string &err);
     int set_filter(const uint32_t *host_mask, std::string &err);
+    // Range queries (range_kernel): every allowed row with entries that scores >= the query's threshold, unordered; run_range is
+    // the host-side counterpart (installed vector, host threshold, waits, sorts).
+    int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                      uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err);
+    int run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err);
     // enqueue_list through the multi-query path when the engine has one (desc.multi_q), else the ordinary sequence
     int enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                            void *stream, std::string &err);

@@ -178,6 +178,45 @@ class SpMV:
         self.synchronize()
         return self.read_result()
 
+    def enqueue_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_idx=0, dev_val=0, capacity=0, dev_mask=0, mask_stride=0, stream=0):
+        """Range queries: for query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()) every row that
+        has entries, is allowed by dev_mask + i*mask_stride words (0: unfiltered) and scores >= dev_thresholds[i]. dev_counts[i]
+        receives the number of matches; dev_idx / dev_val + i*capacity the first min(count, capacity) of them, in no particular
+        order (capacity = 0 with no outputs: count only). No host sync, no engine state touched."""
+        _lib.check(_lib.lib().tkspmv_enqueue_range(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
+                                                   C.c_void_p(int(dev_thresholds)) if dev_thresholds else None,
+                                                   C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
+                                                   C.c_void_p(int(dev_idx)) if dev_idx else None,
+                                                   C.c_void_p(int(dev_val)) if dev_val else None, int(capacity),
+                                                   C.c_void_p(int(dev_counts)) if dev_counts else None,
+                                                   C.c_void_p(int(stream))))
+
+    def _run_range(self, threshold, use_filter, capacity):
+        idx = np.zeros(max(capacity, 1), dtype=np.uint32)
+        val = np.zeros(max(capacity, 1), dtype=np.float32)
+        count = C.c_uint64(0)
+        _lib.check(_lib.lib().tkspmv_run_range(self._h, float(threshold), int(use_filter),
+                                               idx.ctypes.data_as(C.POINTER(C.c_uint32)) if capacity else None,
+                                               val.ctypes.data_as(C.POINTER(C.c_float)) if capacity else None, int(capacity), C.byref(count)))
+        n = min(int(count.value), capacity)
+        return val[:n], idx[:n], int(count.value)
+
+    def run_range(self, threshold, vec=None, allow=None, capacity=None):
+        """One range query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
+        row_mask() words; the query is then restricted to it), then every row scoring >= threshold. Returns (values, indices)
+        sorted like read_result. capacity=None: the count is asked for first, then exactly that many (the set is deterministic);
+        else at most `capacity` matches are returned and last_range_count holds the true number."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        use_filter = allow is not None
+        if capacity is None:
+            _, _, capacity = self._run_range(threshold, use_filter, 0)
+        val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity))
+        return val, idx
+
     def enqueue_multi(self, dev_xs, count, dev_idx=0, dev_val=0, stream=0):
         """enqueue_batch with several queries per pass over the matrix (info()["multi_q"] of them share every chunk that
         is loaded; engine created with multi_q > 0). Same arguments; dev_xs = 0 with count = 1: the vector installed by
@@ -261,5 +300,16 @@ def topk_spmv(m, vec, k=100, allow=None, **kw):
             return e.run_filtered(allow=allow)
         e()
         return e.read_result()
+    finally:
+        e.close()
+
+
+def range_spmv(m, vec, threshold, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices) of every row scoring >= threshold (among the
+    rows of `allow`, if given), sorted like topk_spmv's result."""
+    kw.setdefault("k", 8)
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
+    try:
+        return e.run_range(threshold, allow=allow)
     finally:
         e.close()

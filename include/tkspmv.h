@@ -217,6 +217,29 @@ int tkspmv_enqueue_filtered(tkspmv_t *e, const float *dev_xs, int32_t count, con
 /* Host allow-mask (ceil(rows/32) words) copied into an engine-owned device buffer; NULL removes it. Waits for the engine's
  * stream first (a filtered query enqueued there may still read the mask it replaces). */
 int tkspmv_set_filter(tkspmv_t *e, const uint32_t *host_mask);
+/* Range queries: every row scoring at least a per-query threshold (radius search), where tkspmv_enqueue_filtered answers
+ * "the k best". Range query i = dev_xs + i * cols (NULL with count = 1: the vector installed by tkspmv_set_query), threshold
+ * dev_thresholds[i] (device array of count floats). dev_mask: optional allow-mask as in tkspmv_enqueue_filtered
+ * (NULL: unfiltered; mask_stride_words = 0: one mask for every query). Every row that has entries, is allowed, and
+ * scores >= the threshold is a match. dev_counts[i] (required) = number of matches, also when it exceeds capacity;
+ * dev_idx / dev_val + i * capacity (both NULL with capacity = 0: count only) receive min(count, capacity) distinct
+ * matches -- row id + desc.first_row, and the score, bit-identical to the score every other path reports for that
+ * row -- in NO particular order; which matches are kept when count > capacity is unspecified. Entries beyond
+ * min(count, capacity) are not written. Any float is a threshold: -inf returns every row that has entries, NaN matches
+ * nothing; desc.min_score plays no part. Complete in stream order on any stream; reads and writes no engine state (no result
+ * buffer, no carried threshold), so it may be mixed freely with the other calls. Errors: TKSPMV_ERR_UNSUPPORTED where
+ * tkspmv_enqueue_filtered reports it; TKSPMV_ERR_INVALID for count < 1, NULL thresholds or counts, a negative stride, one of
+ * dev_idx / dev_val NULL and not the other, capacity > 0 with NULL outputs or capacity = 0 with outputs, NULL dev_xs with
+ * count != 1; TKSPMV_ERR_STATE for a NULL dev_xs with no query installed. */
+int tkspmv_enqueue_range(tkspmv_t *e, const float *dev_xs, int32_t count, const float *dev_thresholds,
+                         const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                         uint32_t capacity, uint32_t *dev_counts, void *stream);
+/* The host-side counterpart (reset -> run -> read in one call): the installed query vector, a host threshold, the
+ * mask installed by tkspmv_set_filter when use_filter != 0; waits; idx/val (host, capacity entries) receive the
+ * matches SORTED like tkspmv_read (score descending, row descending); *count = number of matches (also beyond capacity;
+ * min(*count, capacity) entries are written). TKSPMV_ERR_INVALID for use_filter with no filter installed. */
+int tkspmv_run_range(tkspmv_t *e, float threshold, int32_t use_filter, uint32_t *idx, float *val,
+                     uint32_t capacity, uint64_t *count);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
