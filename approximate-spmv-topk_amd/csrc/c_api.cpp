@@ -10,6 +10,7 @@
 #include "engine.hpp"
 #include "host_utils.hpp"
 #include "options.hpp"
+#include "row_lookup.hpp"
 #include "wbscsr.hpp"
 #include "wsell.hpp"
 
@@ -90,6 +91,15 @@ int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const 
 }
 int tkspmv_run_range(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count) {
     ENGINE_CALL(run_range(threshold, use_filter, idx, val, capacity, count, err))
+}
+int tkspmv_enqueue_row_vectors(tkspmv_t *h, const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream) {
+    ENGINE_CALL(enqueue_row_vectors(dev_rows, count, dev_xs, dev_len, stream, err))
+}
+int tkspmv_row_vectors(tkspmv_t *h, const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len) {
+    ENGINE_CALL(row_vectors(host_rows, count, host_xs, host_len, err))
+}
+int tkspmv_run_similar(tkspmv_t *h, const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val) {
+    ENGINE_CALL(run_similar(host_rows, count, exclude_self, idx, val, err))
 }
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
@@ -333,6 +343,32 @@ int tkspmv_packed_raw(const tkspmv_packed *p, const void **packets, uint64_t *pa
     if (part_first) *part_first = p->pm.part_first.data();
     if (part_count) *part_count = p->pm.part_count.data();
     if (n_parts) *n_parts = (uint32_t)p->pm.part_first.size();
+    return TKSPMV_OK;
+}
+
+int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, float *val, uint32_t capacity, uint32_t *n) {
+    if (!p || !n || (capacity > 0u && (!col || !val))) return fail(TKSPMV_ERR_INVALID, "NULL argument");
+    const PackedMatrix &pm = p->pm;
+    if (row >= pm.rows) return fail(TKSPMV_ERR_INVALID, "row out of range (>= rows)");
+    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
+        return fail(TKSPMV_ERR_UNSUPPORTED, "rows are looked up in fp32 packet streams only (TKSPMV_F32)");
+    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
+    const uint32_t PE = pm.packet_entries;
+    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
+                        pm.precision == Precision::F32C12};
+    RowRun run{0u, 0u, 0u, 0u};
+    *n = 0u;
+    if (!locate_row(V, row, pm.n_packets, (uint32_t)pm.part_first.size(), PE, run)) return TKSPMV_OK;  // beyond the last stored row
+    *n = row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot));
+    if (*n == 0u) return TKSPMV_OK;
+    uint32_t out = 0u;
+    for (uint32_t pk = run.first_pkt; pk <= run.last_pkt && out < capacity; ++pk) {
+        const uint32_t s0 = pk == run.first_pkt ? run.first_slot : 0u, s1 = pk == run.last_pkt ? run.last_slot : PE - 1u;
+        for (uint32_t ss = s0; ss <= s1 && out < capacity; ++ss, ++out) {
+            col[out] = (uint32_t)(V.word(pk, ss) >> COLW_COL_SHIFT);
+            val[out] = V.value(pk, ss);
+        }
+    }
     return TKSPMV_OK;
 }
 

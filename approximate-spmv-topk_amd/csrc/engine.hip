@@ -47,6 +47,7 @@
 #include "kernels/radix_select.hpp"
 #include "kernels/read_probe.hpp"
 #include "kernels/range_kernel.hpp"
+#include "kernels/row_vectors.hpp"
 
 namespace tkspmv {
 
@@ -307,6 +308,14 @@ struct EngineImpl {
     float *d_range_val = nullptr;
     uint32_t range_cap = 0;
     uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count
+    // Queries by stored row (tkspmv_enqueue_row_vectors, row_vectors_kernel) touch none of the state above either. Kept here: the
+    // scratch of tkspmv_run_similar -- a chunk's row ids, its vectors and its [chunk][k] results --, allocated on its first call and
+    // grown to the largest chunk asked for (at most SIMILAR_MAX_ROWS rows and SIMILAR_MAX_BYTES of vectors).
+    static constexpr uint32_t SIMILAR_MAX_ROWS = 1024;
+    static constexpr size_t SIMILAR_MAX_BYTES = (size_t)64 << 20;
+    uint32_t *d_sim_rows = nullptr, *d_sim_idx = nullptr;
+    float *d_sim_xs = nullptr, *d_sim_val = nullptr;
+    uint32_t sim_cap = 0;  // rows the scratch holds
 
     StreamParams stream_params(const float *x, int set = 0) const {
         StreamParams P{};
@@ -788,6 +797,37 @@ struct EngineImpl {
             if ((uint64_t)period_ns * (uint64_t)c > 40000000ull || (uint64_t)P.n_parts > (uint64_t)grid * 8u) R.period = 0u;
             hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
         }
+    }
+    // Why stored rows cannot be expanded by this engine (nullptr: they can). Unlike filtered queries, the approximate per-partition
+    // engines are served: extraction does not depend on how rows are selected.
+    const char *row_vectors_unsupported() const {
+        if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12) return "row vectors need an fp32 packet stream (TKSPMV_F32)";
+        if (pm.n_packets != 0u && (!d_packets || !d_pkt_row || !d_part_first)) return "row vectors are read from the wave-BSCSR packets: this engine does not hold them";
+        return nullptr;
+    }
+    // Rows ids[0 .. n) as dense vectors xs[n][cols] (len[n]: their entries, optional), complete in stream order when this returns:
+    // one wave per row. Stream copy 0 is read whatever stream_replicas says.
+    void launch_row_vectors(const uint32_t *ids, int n, float *xs, uint32_t *len, hipStream_t s) const {
+        RowVecParams R{};
+        R.packets = d_packets;
+        R.pkt_row = d_pkt_row;
+        R.part_first = d_part_first;
+        R.part_count = d_part_count;
+        R.n_packets = pm.n_packets;
+        R.n_parts = (uint32_t)pm.part_first.size();
+        R.packet_bytes = pm.packet_bytes;
+        R.cols = desc.cols;
+        R.rows = desc.rows;
+        R.first_row = desc.first_row;
+        R.ids = ids;
+        R.xs = xs;
+        R.len = len;
+        void (*fn)(const RowVecParams) = info.packet_entries == 512 ? &row_vectors_kernel<8, 1024, false>
+                                         : pm.precision == Precision::F32C12 ? &row_vectors_kernel<4, 1024, true>
+                                         : xcols <= 1024 ? &row_vectors_kernel<4, 1024, false>
+                                         : xcols <= 4096 ? &row_vectors_kernel<4, 4096, false>
+                                                         : &row_vectors_kernel<4, 16384, false>;
+        hipLaunchKernelGGL(fn, dim3((uint32_t)n), dim3(64), 0, s, R);
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -2133,6 +2173,115 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
         HIP_TRY(hipMemcpy(idx, m.d_range_idx, kept * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(val, m.d_range_val, kept * 4, hipMemcpyDeviceToHost));
         sort_tuples(kept, idx, val);
+    }
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_rows || !dev_xs || count < 1) {
+        err = "bad arguments to enqueue_row_vectors (row ids and vectors given, count >= 1)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (const char *why = m.row_vectors_unsupported()) {
+        err = why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
+    HIP_TRY(hipSetDevice(m.device));
+    m.launch_row_vectors(dev_rows, count, dev_xs, dev_len, s);
+    HIP_TRY(hipGetLastError());
+    return TKSPMV_OK;
+}
+
+int Engine::row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_rows || !host_xs || count < 1) {
+        err = "bad arguments to row_vectors (row ids and vectors given, count >= 1)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (const char *why = m.row_vectors_unsupported()) {
+        err = why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    // (buffers of this call alone: the caller asks for `count` whole vectors at once, whatever their size)
+    uint32_t *d_rows = nullptr, *d_len = nullptr;
+    float *d_xs = nullptr;
+    const size_t xs_bytes = (size_t)count * m.desc.cols * 4;
+    hipError_t e = hipMalloc((void **)&d_rows, (size_t)count * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_len, (size_t)count * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_xs, xs_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_rows, host_rows, (size_t)count * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        m.launch_row_vectors(d_rows, count, d_xs, d_len, m.stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(m.stream);
+    if (e == hipSuccess) e = m.settle();  // (the host has just waited for the engine's stream)
+    if (e == hipSuccess) e = hipMemcpy(host_xs, d_xs, xs_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && host_len) e = hipMemcpy(host_len, d_len, (size_t)count * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_rows);
+    (void)hipFree(d_len);
+    (void)hipFree(d_xs);
+    HIP_TRY(e);
+    return TKSPMV_OK;
+}
+
+int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_rows || !idx || !val || count < 1) {
+        err = "bad arguments to run_similar (row ids and [count][k] outputs given, count >= 1)";
+        return TKSPMV_ERR_INVALID;
+    }
+    if (const char *why = m.row_vectors_unsupported()) {
+        err = why;
+        return TKSPMV_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    const size_t k = (size_t)m.desc.k, cols = m.desc.cols;
+    const uint32_t chunk_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(EngineImpl::SIMILAR_MAX_ROWS, EngineImpl::SIMILAR_MAX_BYTES / (cols * 4)));
+    const uint32_t want = std::min<uint32_t>((uint32_t)count, chunk_max);
+    if (want > m.sim_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: run_similar waits itself)
+        HIP_TRY(m.settle());
+        for (const void *p : {(const void *)m.d_sim_rows, (const void *)m.d_sim_idx, (const void *)m.d_sim_xs, (const void *)m.d_sim_val}) m.release(p);
+        m.d_sim_rows = m.d_sim_idx = nullptr;
+        m.d_sim_xs = m.d_sim_val = nullptr;
+        m.sim_cap = 0u;
+        HIP_TRY(m.alloc(m.d_sim_rows, (size_t)want * 4));
+        HIP_TRY(m.alloc(m.d_sim_xs, (size_t)want * cols * 4));
+        HIP_TRY(m.alloc(m.d_sim_idx, (size_t)want * k * 4));
+        HIP_TRY(m.alloc(m.d_sim_val, (size_t)want * k * 4));
+        m.sim_cap = want;
+    }
+    for (int32_t i0 = 0; i0 < count; i0 += (int32_t)m.sim_cap) {
+        const int32_t c = std::min<int32_t>((int32_t)m.sim_cap, count - i0);
+        // upload ids, row vectors, the batch sequence, then WAIT: under REPAIR=host a trusted batch launch may be repaired from the
+        // host's next wait (settle()); the repair reads the query vectors again and writes the results again, so the scratch vectors
+        // must not be overwritten and the results not be read before the engine has settled.
+        HIP_TRY(hipMemcpy(m.d_sim_rows, host_rows + i0, (size_t)c * 4, hipMemcpyHostToDevice));
+        m.launch_row_vectors(m.d_sim_rows, c, m.d_sim_xs, nullptr, m.stream);
+        HIP_TRY(hipGetLastError());
+        int st = enqueue_batch(m.d_sim_xs, c, m.d_sim_idx, m.d_sim_val, nullptr, err);
+        if (st == TKSPMV_OK) st = synchronize(err);
+        if (st != TKSPMV_OK) return st;
+        HIP_TRY(hipMemcpy(idx + (size_t)i0 * k, m.d_sim_idx, (size_t)c * k * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(val + (size_t)i0 * k, m.d_sim_val, (size_t)c * k * 4, hipMemcpyDeviceToHost));
+    }
+    if (exclude_self) {
+        // the query's own row leaves its list: the rest moves up, the last slot becomes the pad (0, 0.0f)
+        for (int32_t i = 0; i < count; ++i) {
+            uint32_t *li = idx + (size_t)i * k;
+            float *lv = val + (size_t)i * k;
+            const uint32_t *hit = std::find(li, li + k, host_rows[i]);
+            if (hit == li + k) continue;
+            const size_t j = (size_t)(hit - li);
+            std::copy(li + j + 1, li + k, li + j);
+            std::copy(lv + j + 1, lv + k, lv + j);
+            li[k - 1] = 0u;
+            lv[k - 1] = 0.0f;
+        }
     }
     return TKSPMV_OK;
 }

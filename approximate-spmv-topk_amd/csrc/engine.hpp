@@ -39,6 +39,12 @@ class Engine {
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
                       uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err);
     int run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err);
+    // Queries by stored row (row_vectors_kernel): rows of the matrix, given by the global ids queries return, expanded into the dense
+    // vectors every enqueue_* call takes; run_similar = the engine's top-k with each given row as the query (chunks on engine-owned
+    // scratch: ids up, row vectors, the batch sequence, wait, results down), the row itself removed from its list on request.
+    int enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream, std::string &err);
+    int row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len, std::string &err);
+    int run_similar(const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val, std::string &err);
     // enqueue_list through the multi-query path when the engine has one (desc.multi_q), else the ordinary sequence
     int enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                            void *stream, std::string &err);

@@ -133,13 +133,13 @@ inline void colw12s_store(uint8_t *planes, uint32_t slot, uint16_t cw) {  // int
     std::memcpy(pl + colw12s_a_offset(lane), &A, 4);
     std::memcpy(pl + colw12s_b_offset(lane), &Bv, 2);
 }
-inline uint16_t colw12s_load(const uint8_t *planes, uint32_t slot) {
+TKSPMV_HD inline uint16_t colw12s_load(const uint8_t *planes, uint32_t slot) {  // (also the row lookup's, on the device: row_lookup.hpp)
     const uint32_t t = slot & 255u, lane = t >> 2, j = t & 3u;
     const uint8_t *pl = planes + (size_t)(slot >> 8) * 384u;
     uint32_t A;
     uint16_t Bv;
-    std::memcpy(&A, pl + colw12s_a_offset(lane), 4);
-    std::memcpy(&Bv, pl + colw12s_b_offset(lane), 2);
+    __builtin_memcpy(&A, pl + colw12s_a_offset(lane), 4);
+    __builtin_memcpy(&Bv, pl + colw12s_b_offset(lane), 2);
     const uint32_t col = j == 0u ? (A >> 2) & 1023u : (j == 1u ? (A >> 12) & 1023u : (j == 2u ? (A >> 22) & 1023u : ((uint32_t)Bv >> 2) & 1023u));
     const uint32_t skip = j == 0u ? (A & 1u) : (j == 1u ? ((A >> 1) & 1u) : (j == 2u ? (Bv & 1u) : ((Bv >> 1) & 1u)));
     const uint32_t end = ((uint32_t)Bv >> (12u + j)) & 1u;

@@ -217,6 +217,38 @@ class SpMV:
         val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity))
         return val, idx
 
+    def enqueue_row_vectors(self, dev_rows, count, dev_xs, dev_len=0, stream=0):
+        """Stored rows as dense query vectors: dev_rows[i] (uint32, a GLOBAL row id as queries return them) is expanded into
+        dev_xs + i*cols (float32: zeros, and the row's values at their columns; a repeated column holds the fp32 sum of its entries
+        in order). dev_len[i] (optional) receives the row's number of entries, 0xFFFFFFFF for an id outside the engine's rows (a
+        zero vector). The output feeds enqueue_batch / enqueue_filtered / enqueue_range / enqueue_multi unchanged. No host sync, no
+        engine state touched."""
+        _lib.check(_lib.lib().tkspmv_enqueue_row_vectors(self._h, C.c_void_p(int(dev_rows)) if dev_rows else None, int(count),
+                                                         C.c_void_p(int(dev_xs)) if dev_xs else None,
+                                                         C.c_void_p(int(dev_len)) if dev_len else None, C.c_void_p(int(stream))))
+
+    def row_vectors(self, rows):
+        """enqueue_row_vectors with host arrays: (xs[n, cols] float32, lengths[n] uint32) of the given global row ids. Waits."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        xs = np.empty((ids.size, self.num_cols), dtype=np.float32)
+        ln = np.empty(ids.size, dtype=np.uint32)
+        if ids.size:
+            _lib.check(_lib.lib().tkspmv_row_vectors(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size),
+                                                     xs.ctypes.data_as(C.POINTER(C.c_float)), ln.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return xs, ln
+
+    def similar(self, rows, exclude_self=False):
+        """More-like-this: for every given global row id the engine's top-k with that row as the query, (values[n, k], indices[n, k]),
+        each list ordered like read_result. exclude_self: the row itself leaves its list (the rest moves up, the last slot becomes
+        the pad (0, 0.0)); to get k others create the engine with k + 1. Waits."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        idx = np.zeros((ids.size, self.k), dtype=np.uint32)
+        val = np.zeros((ids.size, self.k), dtype=np.float32)
+        if ids.size:
+            _lib.check(_lib.lib().tkspmv_run_similar(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size), int(bool(exclude_self)),
+                                                     idx.ctypes.data_as(C.POINTER(C.c_uint32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+        return val, idx
+
     def enqueue_multi(self, dev_xs, count, dev_idx=0, dev_val=0, stream=0):
         """enqueue_batch with several queries per pass over the matrix (info()["multi_q"] of them share every chunk that
         is loaded; engine created with multi_q > 0). Same arguments; dev_xs = 0 with count = 1: the vector installed by
@@ -311,5 +343,22 @@ def range_spmv(m, vec, threshold, allow=None, **kw):
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
     try:
         return e.run_range(threshold, allow=allow)
+    finally:
+        e.close()
+
+
+def knn_graph(m, k, rows=None, **kw):
+    """The k-NN self-join (A.A^T top-n, what sparse_dot_topn computes on the CPU): for every row of CooMatrix m (or the given
+    row ids) its k most similar OTHER rows, (values[n, k], indices[n, k]). The engine is built with k + 1 and the row itself
+    is removed from its list."""
+    k = int(k)
+    if k < 1 or k + 1 > _lib.MAX_K:
+        raise ValueError(f"k + 1 must be in [2, {_lib.MAX_K}]")
+    first_row = int(kw.get("first_row", 0))
+    ids = np.arange(first_row, first_row + m.rows, dtype=np.uint32) if rows is None else np.asarray(rows, dtype=np.uint32)
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k + 1, **kw)
+    try:
+        val, idx = e.similar(ids, exclude_self=True)
+        return val[:, :k].copy(), idx[:, :k].copy()
     finally:
         e.close()

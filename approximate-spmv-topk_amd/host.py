@@ -261,6 +261,19 @@ class Packed:
         n = int(n.value)
         return row[:n], col[:n], val[:n]
 
+    def get_row(self, row):
+        """(cols, vals) of one row, in stream order (= the order of the COO): found by bisecting the packets' row table, the lookup
+        the engine's row_vectors_kernel runs on the device. fp32 values only (TkspmvError ERR_UNSUPPORTED otherwise)."""
+        n = C.c_uint32()
+        L = _lib.lib()
+        _lib.check(L.tkspmv_packed_get_row(self._h, int(row), None, None, 0, C.byref(n)))
+        col = np.empty(max(n.value, 1), dtype=np.uint32)
+        val = np.empty(max(n.value, 1), dtype=np.float32)
+        if n.value:
+            _lib.check(L.tkspmv_packed_get_row(self._h, int(row), col.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               val.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+        return col[:n.value], val[:n.value]
+
     def raw(self):
         """(packets bytes, packet_bytes, pkt_row, part_first, part_count) as numpy views/copies."""
         pk = C.c_void_p()

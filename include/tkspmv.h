@@ -240,6 +240,29 @@ int tkspmv_enqueue_range(tkspmv_t *e, const float *dev_xs, int32_t count, const 
  * min(*count, capacity) entries are written). TKSPMV_ERR_INVALID for use_filter with no filter installed. */
 int tkspmv_run_range(tkspmv_t *e, float threshold, int32_t use_filter, uint32_t *idx, float *val,
                      uint32_t capacity, uint64_t *count);
+/* Queries by stored row ("which rows are closest to row r?": more-like-this, de-duplication, the k-NN self-join A.A^T top-n --
+ * the product the reference's CPU comparator sparse_dot_topn exists for). dev_rows[i] is a GLOBAL row id (desc.first_row + local
+ * row): exactly what queries return, so results can be fed back. dev_xs + i * cols receives row i as the dense vector of cols
+ * floats that every tkspmv_enqueue_* call takes: zeros, and at each column of the row the fp32 sum of the row's entries with that
+ * column, added in stream order starting from +0.0f (a column may occur several times in a row) -- the vector for which A.x means
+ * "similarity to row r". dev_len[i] (dev_len may be NULL) receives the row's number of entries: 0 for a row without entries (a zero
+ * vector), 0xFFFFFFFF for an id outside [first_row, first_row + rows) (a zero vector as well). The same id may occur any number of
+ * times. Asynchronous, complete in stream order on any stream (NULL: the engine's); reads and writes no engine state, so it may be
+ * mixed freely with the other calls, as tkspmv_enqueue_range may; stream copy 0 of the matrix is read (desc.stream_replicas plays no
+ * part). One wave per row (row_vectors_kernel): the row is found by bisecting the packets' row table.
+ * Errors: TKSPMV_ERR_INVALID for a NULL engine, dev_rows or dev_xs or count < 1 (checked before any device call);
+ * TKSPMV_ERR_UNSUPPORTED when the engine's packet stream is not fp32 (reduced-precision and fixed-point values) or the engine does
+ * not hold the packets. The approximate per-partition engines ARE served: extraction does not depend on how rows are selected. */
+int tkspmv_enqueue_row_vectors(tkspmv_t *e, const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream);
+/* The same with host arrays (host_xs: [count][cols], host_len: [count] or NULL); waits. */
+int tkspmv_row_vectors(tkspmv_t *e, const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len);
+/* For every given row (global ids, host array) the engine's top-k with that row as the query: idx / val are [count][k] host
+ * arrays, each list ordered as tkspmv_read orders it and final when the call returns. Works in chunks of at most 1024 rows and
+ * 64 MiB of vectors on engine-owned scratch: ids up, row vectors, the launch path of tkspmv_enqueue_batch, tkspmv_synchronize,
+ * results down. exclude_self != 0: the entry whose id is the query's own row is removed from its list on the host -- the rest
+ * moves up, the last slot becomes the pad (0, 0.0f); a list without the row is unchanged. To get k others, create the engine
+ * with k + 1. Errors as above (idx and val must be given). */
+int tkspmv_run_similar(tkspmv_t *e, const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
@@ -424,6 +447,11 @@ int tkspmv_packed_decode(const tkspmv_packed *p, uint32_t *row, uint32_t *col, f
 /* Raw views (host memory owned by p). */
 int tkspmv_packed_raw(const tkspmv_packed *p, const void **packets, uint64_t *packet_bytes, const uint32_t **pkt_row,
                       const uint32_t **part_first, const uint32_t **part_count, uint32_t *n_parts);
+/* One row of a packed matrix: its entries in stream order (= the order of the COO). *n = the row's length, also beyond
+ * capacity; min(*n, capacity) entries are written (col / val may be NULL with capacity = 0). Found by bisecting the packets' row
+ * table (csrc/row_lookup.hpp, the lookup the engine's row_vectors_kernel runs), not by decoding the stream. No GPU needed.
+ * TKSPMV_ERR_INVALID for row >= rows, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32. */
+int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, float *val, uint32_t capacity, uint32_t *n);
 void tkspmv_packed_free(tkspmv_packed *p);
 /* The DEVICE packer (what tkspmv_create uses by default): packs desc's COO with HIP kernels on desc->device
  * and copies the result back into a tkspmv_packed, so that it can be compared byte for byte with tkspmv_pack's
