@@ -35,6 +35,7 @@
 #include "engine.hpp"
 #include "host_utils.hpp"
 #include "options.hpp"
+#include "stream_format.hpp"
 #include "wsell.hpp"
 
 #include "kernels/common.hpp"
@@ -77,6 +78,9 @@ __global__ void bar_check_kernel(const uint32_t *x, uint32_t last, uint32_t *out
         }                                                                                               \
     } while (0)
 
+// The failure return of the creation stages and of the entry points' argument checks.
+static int fail(std::string &err, int status, std::string msg) { err = std::move(msg); return status; }
+
 // Exchange words that other XCDs poll (published maxima, threshold word, tickets) live in fine-grained device memory:
 // it is not cached in the per-XCD L2s, so a poll never hits a stale copy (with ordinary memory an agent-scope load can
 // keep returning the old value until the line happens to be evicted: milliseconds on an idle L2).
@@ -87,6 +91,59 @@ static hipError_t malloc_exchange(void **p, size_t bytes) {
     return hipMalloc(p, bytes);
 }
 enum class Mem { Device, Exchange, Pinned };  // EngineImpl::alloc: hipMalloc, malloc_exchange, hipHostMalloc (mapped)
+
+// The kernels of one engine, chosen once (choose_kernels, at creation) by the format of its packet stream. NULL: the family has no
+// kernel for this format. multi_kernel and read_probe_kernel are keyed on other things and keep their own tables.
+typedef void (*stream_fn)(const StreamParams, const SelectParams);
+typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
+typedef void (*range_fn)(const StreamParams, const RangeParams);
+typedef void (*row_vectors_fn)(const RowVecParams);
+typedef void (*batch_fn)(const BatchArgs);
+typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
+struct Kernels {
+    stream_fn stream[2] = {};  // [SCORES]; [0] is the tracing twin on an engine that traces
+    filter_fn filter[2] = {};  // [SCORES]
+    range_fn range[2] = {};    // [FILT]
+    row_vectors_fn row_vectors = nullptr;
+    batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
+    single_fn single = nullptr;
+};
+// The instantiations of ONE format, every family restricted to the formats it is built for (the predicates of stream_format.hpp).
+template <int C, int XCOLS, int QM>
+static Kernels kernels_of(bool dbg) {
+    constexpr StreamFormat F{C, XCOLS, QM};
+    constexpr int NBUF = C == 8 ? 2 : TKSPMV_NBUF;  // (8 entries per lane: two packet buffers, 3 KB packets)
+    Kernels K;
+    K.stream[0] = &stream_kernel<C, false, XCOLS, QM, NBUF>;
+    K.stream[1] = &stream_kernel<C, true, XCOLS, QM, NBUF>;
+    if constexpr (is_fp32(F)) {
+        K.filter[0] = &stream_filter_kernel<C, false, XCOLS, QM, NBUF>;
+        K.filter[1] = &stream_filter_kernel<C, true, XCOLS, QM, NBUF>;
+        K.range[0] = &range_kernel<C, XCOLS, QM, false, C == 8 ? 2 : 3>;
+        K.range[1] = &range_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
+        K.row_vectors = &row_vectors_kernel<C, XCOLS, QM == QM_F32C12>;
+    }
+    if constexpr (is_batchable(F)) {
+        K.batch[0] = &batch_kernel<C, XCOLS, QM, false, false>;
+        K.batch[1] = &batch_kernel<C, XCOLS, QM, false, true>;
+    }
+    if constexpr (has_tracing_twins(F)) {
+        if (dbg) {
+            K.stream[0] = &stream_kernel<C, false, XCOLS, QM, NBUF, true>;
+            K.batch[0] = &batch_kernel<C, XCOLS, QM, true, false>;
+            K.batch[1] = &batch_kernel<C, XCOLS, QM, true, true>;
+        }
+    }
+    if constexpr (has_single_kernel(F)) K.single = &single_kernel<QM>;
+    return K;
+}
+static Kernels kernels_for(StreamFormat f, bool dbg) {
+#define X(C, XCOLS, QM) \
+    if (f.c == C && f.xcols == XCOLS && f.qm == QM) return kernels_of<C, XCOLS, QM>(dbg);
+    TKSPMV_STREAM_FORMATS(X)
+#undef X
+    return Kernels{};
+}
 
 struct EngineImpl {
     tkspmv_desc desc{};
@@ -178,7 +235,7 @@ struct EngineImpl {
     uint32_t *d_done = nullptr;
     bool fused = true;
     bool can_defer = false;
-    bool can_batch = false;         // batch kernel usable (exchange on, x double-buffered in LDS, 4 entries per lane)
+    bool can_batch = false;         // batch kernel usable (exchange on, x double-buffered in LDS: is_batchable)
     // Queries per launch of the batch kernel = exchange-state sets allocated. Every set carries an overflow list that must be
     // able to hold EVERY row (a degenerate query -- x = 0, all scores equal -- makes every row a candidate, and the result
     // must still be exact), 8 B per row: 256 MB at 1M rows, 2.6 GB at 10M rows -- under 1 % of this GPU's 288 GB either way;
@@ -273,11 +330,12 @@ struct EngineImpl {
     uint32_t groups_with_rows = 0;  // publishing groups that own at least one wave partition
     float *d_out_val = nullptr, *d_scores = nullptr;
     unsigned long long *d_stats = nullptr;
-    uint32_t grid = 0, block = 0, gpw = 1, n_sets = 0, n_groups_pub = 0, cand_cap = 0, ovf_cap = 0, lds_bytes = 0,
-             xcols = 1024;
+    uint32_t grid = 0, block = 0, gpw = 1, n_sets = 0, n_groups_pub = 0, cand_cap = 0, ovf_cap = 0, lds_bytes = 0;
+    StreamFormat fmt{};  // what the kernels of this engine's packet stream are instantiated with (exchange_geometry)
+    Kernels kern;        // ... and those kernels (choose_kernels)
     bool collect_stats = false;
     // TKSPMV_TRACE / TKSPMV_STATS / TKSPMV_STAMPS / TKSPMV_DBG_FLAGS / TKSPMV_DBG_REPEAT: launch the instantiations that
-    // carry the tracing and ablation hooks (fp32 values, 4 entries per lane, <= 1024 columns; elsewhere the hooks do not exist)
+    // carry the tracing and ablation hooks (has_tracing_twins; elsewhere the hooks do not exist)
     bool dbg_kernels = false;
     bool collect_stamps = false;
     unsigned long long *d_trace = nullptr;  // TKSPMV_TRACE=1: 4 launches x [grid+1][9][8] stamps
@@ -451,9 +509,9 @@ struct EngineImpl {
         const dim3 mblock(multi_stream_waves * 64u + 64u);
         typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
         const int qi = multi_q <= 1 ? 0 : (multi_q <= 2 ? 1 : (multi_q <= 4 ? 2 : 3));
-        static const multi_fn fns[3][4] = {{&multi_kernel<1, 0>, &multi_kernel<2, 0>, &multi_kernel<4, 0>, &multi_kernel<8, 0>},
-                                           {&multi_kernel<1, 1>, &multi_kernel<2, 1>, &multi_kernel<4, 1>, &multi_kernel<8, 1>},
-                                           {&multi_kernel<1, 5>, &multi_kernel<2, 5>, &multi_kernel<4, 5>, &multi_kernel<8, 5>}};
+        static const multi_fn fns[3][4] = {{&multi_kernel<1, VT_F32>, &multi_kernel<2, VT_F32>, &multi_kernel<4, VT_F32>, &multi_kernel<8, VT_F32>},
+                                           {&multi_kernel<1, VT_Q17>, &multi_kernel<2, VT_Q17>, &multi_kernel<4, VT_Q17>, &multi_kernel<8, VT_Q17>},
+                                           {&multi_kernel<1, VT_Q17C12>, &multi_kernel<2, VT_Q17C12>, &multi_kernel<4, VT_Q17C12>, &multi_kernel<8, VT_Q17C12>}};
         hipLaunchKernelGGL(fns[sell_byte_values ? (sell_c12 ? 2 : 1) : 0][qi], dim3(grid), mblock, 0, s, P, S, M);
         pending_group[chain] = M.cur;
         multi_parity[chain] ^= 1;
@@ -494,22 +552,6 @@ struct EngineImpl {
         launch_stream(x, out_idx, out_val, s);
         if (!fused) launch_select(out_idx, out_val, s);
     }
-    typedef void (*batch_fn)(const BatchArgs);
-    // can_batch: x of at most 1024 columns (it is held twice in LDS). local: the kernel of the checked local thresholds.
-    template <bool LOCAL>
-    batch_fn batch_kernel_of() const {
-        if (desc.precision == TKSPMV_Q1_7) return &batch_kernel<4, 1024, 1, false, LOCAL>;
-        if (desc.precision == TKSPMV_Q1_7_WIDE) return &batch_kernel<4, 1024, 2, false, LOCAL>;
-        if (desc.precision == TKSPMV_F16) return &batch_kernel<4, 1024, 3, false, LOCAL>;
-        if (desc.precision == TKSPMV_FIXED)
-            return pm.precision == Precision::FIXED20 ? &batch_kernel<4, 1024, 6, false, LOCAL>
-                                                      : (pm.precision == Precision::FIXED26 ? &batch_kernel<4, 1024, 8, false, LOCAL> : &batch_kernel<4, 1024, 4, false, LOCAL>);
-        if (desc.precision == TKSPMV_Q1_7_F32) return &batch_kernel<4, 1024, 5, false, LOCAL>;
-        if (info.packet_entries == 512) return &batch_kernel<8, 1024, 0, false, LOCAL>;
-        if (pm.precision == Precision::F32C12) return dbg_kernels ? &batch_kernel<4, 1024, 7, true, LOCAL> : &batch_kernel<4, 1024, 7, false, LOCAL>;
-        return dbg_kernels ? &batch_kernel<4, 1024, 0, true, LOCAL> : &batch_kernel<4, 1024, 0, false, LOCAL>;
-    }
-    batch_fn batch_kernel_for(bool local = false) const { return local ? batch_kernel_of<true>() : batch_kernel_of<false>(); }
     // n <= BATCH_MAX queries in one launch of the batch kernel; results complete in stream order after the launch.
     void launch_batch(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s, uint32_t parity = 0u,
                       bool final_launch = true) const {
@@ -589,11 +631,11 @@ struct EngineImpl {
             B.verdict_host = h_verdict_dev + slot;
             const bool trusted = repair_by_host && clean_seen != 0u && distrust_left == 0u;
             BatchArgs A{P, S, B};
-            go(batch_kernel_for(true), A, trusted);
+            go(kern.batch[1], A, trusted);
             if (!trusted) {
                 BatchArgs R = A;
                 R.B.repair = 1u;
-                go(batch_kernel_for(false), R, true);
+                go(kern.batch[0], R, true);
                 if (distrust_left != 0u) --distrust_left;
             } else {
                 ++trusted_launches;
@@ -605,10 +647,10 @@ struct EngineImpl {
         if (use_local) {
             // the kernel of the checked local thresholds, then the exact kernel for whatever failed its check (the launch is
             // empty -- every workgroup reads the verdict word and leaves -- unless a query was unlike the ones before it)
-            go(batch_kernel_for(true), A, false);
+            go(kern.batch[1], A, false);
             A.B.repair = 1u;
         }
-        go(batch_kernel_for(false), A, true);
+        go(kern.batch[0], A, true);
     }
     // The host has just waited for the engine's stream: look at the verdicts of the launches enqueued since it last did. A flagged
     // query of a TRUSTED launch (no repair launch behind it) is repaired now -- exact launch of the flagged queries, one more wait --;
@@ -642,7 +684,7 @@ struct EngineImpl {
                         R.B.io[q].out_idx = d_alias_idx + (size_t)q * desc.k;
                         R.B.io[q].out_val = d_alias_val + (size_t)q * desc.k;
                     }
-            hipLaunchKernelGGL(batch_kernel_for(false), dim3(grid), dim3(block + 64), 0, stream, R);
+            hipLaunchKernelGGL(kern.batch[0], dim3(grid), dim3(block + 64), 0, stream, R);
             ++late_repairs;
             late = true;
         }
@@ -700,71 +742,10 @@ struct EngineImpl {
         pending_val = out_val;
         cur_set ^= 1;
     }
-    typedef void (*stream_fn)(const StreamParams, const SelectParams);
-    stream_fn kernel_for(bool scores) const {
-        const bool c8 = info.packet_entries == 512;
-        if (desc.precision == TKSPMV_Q1_7) {
-            if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024, 1> : &stream_kernel<4, false, 1024, 1>;
-            if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096, 1> : &stream_kernel<4, false, 4096, 1>;
-            return scores ? &stream_kernel<4, true, 16384, 1> : &stream_kernel<4, false, 16384, 1>;
-        }
-        if (desc.precision == TKSPMV_F16) {
-            if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024, 3> : &stream_kernel<4, false, 1024, 3>;
-            if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096, 3> : &stream_kernel<4, false, 4096, 3>;
-            return scores ? &stream_kernel<4, true, 16384, 3> : &stream_kernel<4, false, 16384, 3>;
-        }
-        if (desc.precision == TKSPMV_FIXED && pm.precision == Precision::FIXED20)  // bit-packed: at most 1024 columns
-            return scores ? &stream_kernel<4, true, 1024, 6> : &stream_kernel<4, false, 1024, 6>;
-        if (desc.precision == TKSPMV_FIXED && pm.precision == Precision::FIXED26)  // five bytes per entry: at most 1024 columns
-            return scores ? &stream_kernel<4, true, 1024, 8> : &stream_kernel<4, false, 1024, 8>;
-        if (desc.precision == TKSPMV_FIXED) {
-            if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024, 4> : &stream_kernel<4, false, 1024, 4>;
-            if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096, 4> : &stream_kernel<4, false, 4096, 4>;
-            return scores ? &stream_kernel<4, true, 16384, 4> : &stream_kernel<4, false, 16384, 4>;
-        }
-        if (desc.precision == TKSPMV_Q1_7_F32) {
-            if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024, 5> : &stream_kernel<4, false, 1024, 5>;
-            if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096, 5> : &stream_kernel<4, false, 4096, 5>;
-            return scores ? &stream_kernel<4, true, 16384, 5> : &stream_kernel<4, false, 16384, 5>;
-        }
-        if (desc.precision == TKSPMV_Q1_7_WIDE) {
-            if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024, 2> : &stream_kernel<4, false, 1024, 2>;
-            if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096, 2> : &stream_kernel<4, false, 4096, 2>;
-            return scores ? &stream_kernel<4, true, 16384, 2> : &stream_kernel<4, false, 16384, 2>;
-        }
-        if (c8) return scores ? &stream_kernel<8, true, 1024, 0, 2> : &stream_kernel<8, false, 1024, 0, 2>;  // (two packet buffers: 3 KB packets)
-        if (pm.precision == Precision::F32C12) {  // 12-bit column words: at most 1024 columns, 4 entries per lane
-            if (dbg_kernels && !scores) return &stream_kernel<4, false, 1024, 7, TKSPMV_NBUF, true>;
-            return scores ? &stream_kernel<4, true, 1024, 7> : &stream_kernel<4, false, 1024, 7>;
-        }
-        if (xcols <= 1024 && dbg_kernels && !scores) return &stream_kernel<4, false, 1024, 0, TKSPMV_NBUF, true>;
-        if (xcols <= 1024) return scores ? &stream_kernel<4, true, 1024> : &stream_kernel<4, false, 1024>;
-        if (xcols <= 4096) return scores ? &stream_kernel<4, true, 4096> : &stream_kernel<4, false, 4096>;
-        return scores ? &stream_kernel<4, true, 16384> : &stream_kernel<4, false, 16384>;
-    }
-    // The filtered twin of kernel_for: fp32 engines only (12-bit column words, plain fp32 up to 16384 columns, 8 entries per lane).
-    typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
-    filter_fn filter_kernel_for(bool scores) const {
-        if (info.packet_entries == 512) return scores ? &stream_filter_kernel<8, true, 1024, 0, 2> : &stream_filter_kernel<8, false, 1024, 0, 2>;
-        if (pm.precision == Precision::F32C12) return scores ? &stream_filter_kernel<4, true, 1024, 7> : &stream_filter_kernel<4, false, 1024, 7>;
-        if (xcols <= 1024) return scores ? &stream_filter_kernel<4, true, 1024> : &stream_filter_kernel<4, false, 1024>;
-        if (xcols <= 4096) return scores ? &stream_filter_kernel<4, true, 4096> : &stream_filter_kernel<4, false, 4096>;
-        return scores ? &stream_filter_kernel<4, true, 16384> : &stream_filter_kernel<4, false, 16384>;
-    }
     // One launch of the streaming kernel: stream_kernel, or stream_filter_kernel with the allow-mask F.
     void launch_stream_kernel(bool scores, const FilterParams *F, hipStream_t s, const StreamParams &P, const SelectParams &S) const {
-        if (F) hipLaunchKernelGGL(filter_kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S, *F);
-        else hipLaunchKernelGGL(kernel_for(scores), dim3(grid), dim3(block + 64), 0, s, P, S);
-    }
-    // The range twin of filter_kernel_for: the same fp32 packet streams, with and without an allow-mask.
-    typedef void (*range_fn)(const StreamParams, const RangeParams);
-    template <bool FILT>
-    range_fn range_kernel_of() const {
-        if (info.packet_entries == 512) return &range_kernel<8, 1024, 0, FILT, 2>;
-        if (pm.precision == Precision::F32C12) return &range_kernel<4, 1024, 7, FILT, 3>;
-        if (xcols <= 1024) return &range_kernel<4, 1024, 0, FILT, 3>;
-        if (xcols <= 4096) return &range_kernel<4, 4096, 0, FILT, 3>;
-        return &range_kernel<4, 16384, 0, FILT, 3>;
+        if (F) hipLaunchKernelGGL(kern.filter[scores], dim3(grid), dim3(block + 64), 0, s, P, S, *F);
+        else hipLaunchKernelGGL(kern.stream[scores], dim3(grid), dim3(block + 64), 0, s, P, S);
     }
     // n range queries (query i: x = xs + i * cols, threshold thresholds[i], mask = mask + i * stride words or none), complete in
     // stream order when this returns: the counters are zeroed in front, then launches of up to RANGE_MAX queries. No engine state is
@@ -781,7 +762,7 @@ struct EngineImpl {
         R.capacity = capacity;
         R.first_row = desc.first_row;
         const uint32_t period_ns = range_period_set ? range_period_ns : pace_period_ns;
-        const range_fn fn = mask ? range_kernel_of<true>() : range_kernel_of<false>();
+        const range_fn fn = kern.range[mask != nullptr];
         for (int i = 0; i < n; i += RANGE_MAX) {
             const int c = std::min(RANGE_MAX, n - i);
             R.q0 = (uint32_t)i;
@@ -801,7 +782,7 @@ struct EngineImpl {
     // Why stored rows cannot be expanded by this engine (nullptr: they can). Unlike filtered queries, the approximate per-partition
     // engines are served: extraction does not depend on how rows are selected.
     const char *row_vectors_unsupported() const {
-        if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12) return "row vectors need an fp32 packet stream (TKSPMV_F32)";
+        if (!kern.row_vectors) return "row vectors need an fp32 packet stream (TKSPMV_F32)";
         if (pm.n_packets != 0u && (!d_packets || !d_pkt_row || !d_part_first)) return "row vectors are read from the wave-BSCSR packets: this engine does not hold them";
         return nullptr;
     }
@@ -822,20 +803,20 @@ struct EngineImpl {
         R.ids = ids;
         R.xs = xs;
         R.len = len;
-        void (*fn)(const RowVecParams) = info.packet_entries == 512 ? &row_vectors_kernel<8, 1024, false>
-                                         : pm.precision == Precision::F32C12 ? &row_vectors_kernel<4, 1024, true>
-                                         : xcols <= 1024 ? &row_vectors_kernel<4, 1024, false>
-                                         : xcols <= 4096 ? &row_vectors_kernel<4, 4096, false>
-                                                         : &row_vectors_kernel<4, 16384, false>;
-        hipLaunchKernelGGL(fn, dim3((uint32_t)n), dim3(64), 0, s, R);
+        hipLaunchKernelGGL(kern.row_vectors, dim3((uint32_t)n), dim3(64), 0, s, R);
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
-        if (desc.precision != TKSPMV_F32) return "filtered queries need fp32 values (TKSPMV_F32)";
-        if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12) return "filtered queries need an fp32 packet stream";
+        if (!is_fp32(fmt)) return "filtered queries need fp32 values (TKSPMV_F32)";
+        if (!kern.filter[0]) return "filtered queries need an fp32 packet stream";
         if (approx_parts) return "filtered queries are exact only: partitions > 1 with k > k_per_partition is the approximate per-partition path";
         if (!d_packets || !d_pkt_row) return "filtered queries stream the wave-BSCSR packets: this engine does not hold them";
         return nullptr;
+    }
+    bool range_unsupported(std::string &err) const {  // (fills err)
+        const char *why = filter_unsupported();
+        if (why) err = std::string("range queries share the filtered path's scope: ") + why;
+        return why != nullptr;
     }
     // A sequence of filtered queries (query i: x = xs[i], mask = mask + i * stride words), complete in stream order when this
     // returns. The launch scheme is the one of a single exact query: deferred selections where the engine has them, else stream +
@@ -891,8 +872,7 @@ struct EngineImpl {
         G.trace = d_trace ? d_trace + (launch_counter % 4) * trace_words : nullptr;
         ++launch_counter;
         ++single_launches;
-        if (pm.precision == Precision::F32C12) hipLaunchKernelGGL((single_kernel<7>), dim3(grid), dim3(512), 0, s, P, S, G);
-        else hipLaunchKernelGGL((single_kernel<0>), dim3(grid), dim3(512), 0, s, P, S, G);
+        hipLaunchKernelGGL(kern.single, dim3(grid), dim3(512), 0, s, P, S, G);
     }
     void launch_query_radix(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) const {
         launch_scores(x, s, d_rscores, F);
@@ -962,6 +942,31 @@ struct EngineImpl {
     hipError_t order_x(const float *x, hipStream_t s) const {
         if (x != d_x || !x_pending || s == stream || bar_x) return hipSuccess;  // (bar_x: the host wrote x itself, nothing is enqueued)
         return hipStreamWaitEvent(s, ev2, 0);
+    }
+    // dev_xs = NULL names the vector tkspmv_set_query / set_query_device installed: the call is then for that one query.
+    int resolve_query(const float *&dev_xs, int32_t count, std::string &err) const {
+        if (dev_xs) return TKSPMV_OK;
+        if (count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+        if (!d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
+        dev_xs = d_x_cur;
+        return TKSPMV_OK;
+    }
+    // Replaces the buffers of a scratch set that grows on demand (run_range, run_similar) by larger ones: all released, then all
+    // allocated; `cap` is 0 while the set is incomplete. The caller has waited for whatever used the old ones.
+    struct ScratchSlot { void **p; size_t bytes; };
+    hipError_t grow_scratch(uint32_t &cap, uint32_t want, std::initializer_list<ScratchSlot> slots) {
+        for (const ScratchSlot &b : slots) {
+            release(*b.p);
+            *b.p = nullptr;
+        }
+        cap = 0u;
+        for (const ScratchSlot &b : slots) {
+            uint8_t *q = nullptr;
+            if (const hipError_t e = alloc(q, b.bytes)) return e;
+            *b.p = q;
+        }
+        cap = want;
+        return hipSuccess;
     }
 };
 
@@ -1042,6 +1047,12 @@ template <class T> struct ScratchBuffer {
     T *p = nullptr;
     ~ScratchBuffer() { if (p) (void)hipFree(p); }
 };
+// The events of one host function (a measurement's brackets), likewise.
+struct ScratchEvents {
+    std::vector<hipEvent_t> e;
+    explicit ScratchEvents(size_t n) : e(n, nullptr) {}
+    ~ScratchEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
 
 // tkspmv_create: create_impl runs the stages below in order. Each returns a TKSPMV_* status; what the engine keeps goes into
 // EngineImpl, what only a later stage needs into Setup. Buffers go through EngineImpl::alloc: ~Engine frees them on every path.
@@ -1062,9 +1073,6 @@ struct Setup {
     uint32_t sell_pack_us = 0;      // packing of the wave-sliced ELL copy (multi-query engines)
     uint64_t sell_bytes = 0;
 };
-
-// The failure return of the creation stages.
-static int fail(std::string &err, int status, std::string msg) { err = std::move(msg); return status; }
 
 // The descriptor alone: no device call before these checks (tests/test_capi.py::test_argument_validation_before_device).
 static int check_desc(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
@@ -1210,8 +1218,9 @@ static int exchange_geometry(const tkspmv_desc &d, Setup &S, EngineImpl &m, std:
     m.n_sets = (std::min<uint32_t>(n_pub_wg * m.gpw, MAX_GM * 64) >= (uint32_t)d.k) ? 1u : 0u;  // 0: exchange disabled, every row >= min_score is a candidate
     if (!m.n_sets) m.n_groups_pub = 1;
     m.ovf_cap = std::max<uint32_t>(d.rows, 1u);
-    m.xcols = d.cols <= 1024 ? 1024u : (d.cols <= 4096 ? 4096u : 16384u);
-    m.cand_cap = m.xcols <= 1024 ? 2048u : 1024u;  // ListGeom<XCOLS>::CAND_CAP
+    m.fmt = stream_format_of(d.precision, m.pm.precision, m.info.packet_entries, d.cols);
+    if (m.fmt.c == 0) return fail(err, TKSPMV_ERR_UNSUPPORTED, "no kernel is built for this descriptor's packet stream");  // (the packers accept none)
+    m.cand_cap = m.fmt.xcols <= 1024 ? 2048u : 1024u;  // ListGeom<XCOLS>::CAND_CAP
     // groups (workgroup, local group) whose first wave owns a partition: wave w of streaming workgroup b streams
     // partition w * n_pub_wg + b (n_pub_wg: the streaming workgroups of a sequence launch)
     const uint32_t n_parts = (uint32_t)m.pm.part_first.size();
@@ -1222,7 +1231,7 @@ static int exchange_geometry(const tkspmv_desc &d, Setup &S, EngineImpl &m, std:
             if ((uint64_t)w0 * n_pub_wg + b < n_parts && (uint64_t)b * m.gpw + g < m.n_groups_pub) ++m.groups_with_rows;
         }
     if (S.C == 8 && d.cols > 1024) return fail(err, TKSPMV_ERR_UNSUPPORTED, "nnz_per_lane = 8 is only built for cols <= 1024");
-    m.lds_bytes = (uint32_t)std::max<size_t>(sizeof(SelectShared), (size_t)m.xcols * 4 + (size_t)m.cand_cap * 8) +
+    m.lds_bytes = (uint32_t)std::max<size_t>(sizeof(SelectShared), (size_t)m.fmt.xcols * 4 + (size_t)m.cand_cap * 8) +
                   MISC_WORDS * 4;  // all static
     return TKSPMV_OK;
 }
@@ -1335,7 +1344,7 @@ static int choose_path(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
     m.fused = (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.block + 64);
     m.can_defer = S.defer_capable;
     if (const char *f = opt("FUSED")) m.fused = m.fused && atoi(f) != 0;
-    m.can_batch = m.can_defer && m.n_sets != 0u && m.xcols <= 1024u && (S.C == 4u || (S.C == 8u && d.precision == TKSPMV_F32));  // larger x: two workgroups no longer fit a CU
+    m.can_batch = m.can_defer && m.n_sets != 0u && is_batchable(m.fmt);
     if (const char *f = opt("BATCH")) m.can_batch = m.can_batch && atoi(f) != 0;
     // Large k: the scores + radix-select path wherever the threshold exchange is off or next to useless (k above
     // 3/8 of the publishing groups: measured cross-over on the BASELINE matrix, tools/k_probe.py). TKSPMV_RADIX=0/1 forces.
@@ -1524,10 +1533,10 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     return TKSPMV_OK;
 }
 
-// single_kernel serves tkspmv_run where the engine streams with local thresholds: fp32 values, 4 entries per lane, x of at most
-// 1024 columns, at most 512 workgroups (select_local's first cut), one partition per wave of ITS launch (8 waves x grid).
+// single_kernel serves tkspmv_run where the engine streams with local thresholds: a format it is built for (has_single_kernel),
+// at most 512 workgroups (select_local's first cut), one partition per wave of ITS launch (8 waves x grid).
 static int setup_single(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    m.can_single = m.single_mode != 0u && d.precision == TKSPMV_F32 && S.C == 4u && m.xcols <= 1024u && m.grid <= 512u && m.block == 512u &&
+    m.can_single = m.single_mode != 0u && has_single_kernel(m.fmt) && m.grid <= 512u && m.block == 512u &&
                    d.impl == TKSPMV_IMPL_STREAM && !m.use_radix && m.fused && m.host_path && m.h_res != nullptr &&
                    m.pm.part_first.size() <= (size_t)m.grid * 8u;
     if (const char *f = opt("SINGLE")) m.can_single = m.can_single && atoi(f) != 0;
@@ -1616,14 +1625,21 @@ static int setup_diagnostics(const tkspmv_desc &d, Setup &S, EngineImpl &m, std:
         HIP_TRY(m.alloc(m.d_trace, m.trace_words * 4 * 8, Mem::Device, 0));
     }
     m.dbg_kernels = m.collect_stats || m.collect_stamps || m.d_trace != nullptr;
-    if (m.dbg_kernels && (d.precision != TKSPMV_F32 || S.C != 4u || m.xcols > 1024u))
+    if (m.dbg_kernels && !has_tracing_twins(m.fmt))
         fprintf(stderr, "[tkspmv] tracing / statistics hooks exist in the fp32, 4-entries-per-lane, <= 1024-column kernels only: "
                         "this engine runs without them\n");
+    return TKSPMV_OK;
+}
+
+// The kernels of this engine's format (behind setup_diagnostics: an engine that traces takes the tracing twins), and the DEBUG_OCC
+// occupancy report about them.
+static int choose_kernels(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
+    m.kern = kernels_for(m.fmt, m.dbg_kernels);
     if (opt("DEBUG_OCC")) {
         int n1 = -1, n2 = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, reinterpret_cast<const void *>(m.kernel_for(false)), (int)m.block + 64, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, reinterpret_cast<const void *>(m.kern.stream[0]), (int)m.block + 64, 0);
         if (m.can_batch)
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, reinterpret_cast<const void *>(m.batch_kernel_for()), (int)m.block + 64, 0);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, reinterpret_cast<const void *>(m.kern.batch[0]), (int)m.block + 64, 0);
         fprintf(stderr, "[tkspmv] workgroups per CU by the runtime's occupancy calculator: stream kernel %d, batch kernel %d; LDS per CU %zu\n",
                 n1, n2, S.lds_per_cu);
     }
@@ -1819,7 +1835,8 @@ static int create_impl(const tkspmv_desc &d, EngineImpl &m, std::string &err, co
     // (in this order: the descriptor is checked before any device call, and the HIP calls keep one sequence)
     static int (*const stages[])(const tkspmv_desc &, Setup &, EngineImpl &, std::string &) = {
         check_desc,  setup_geometry, pack_matrix,    exchange_geometry,   upload_matrix,     setup_host_boundary, choose_path,
-        setup_multi, setup_verdicts, setup_single, setup_exchange_sets, setup_diagnostics, fill_engine_info,    autotune_pacing};
+        setup_multi, setup_verdicts, setup_single, setup_exchange_sets, setup_diagnostics, choose_kernels,      fill_engine_info,
+        autotune_pacing};
     Setup S{prepacked};
     for (auto stage : stages)
         if (const int st = stage(d, S, m, err)) return st;
@@ -1858,10 +1875,7 @@ int wave_partitions_for(const tkspmv_desc &d, uint32_t *out, std::string &err) {
 
 int Engine::set_query(const float *host_x, double *elapsed_ns, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_x) {
-        err = "query vector is NULL";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!host_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
     auto t0 = std::chrono::high_resolution_clock::now();
     HIP_TRY(hipSetDevice(m.device));
     if (m.bar_x) {
@@ -1904,138 +1918,105 @@ int Engine::set_query(const float *host_x, double *elapsed_ns, std::string &err)
 }
 
 int Engine::set_query_device(const float *dev_x, std::string &err) {
-    if (!dev_x) {
-        err = "query vector is NULL";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!dev_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
     impl_->d_x_cur = dev_x;
     impl_->have_query = true;
     return TKSPMV_OK;
 }
 
-int Engine::enqueue(const float *dev_x, uint32_t *dev_idx, float *dev_val, void *stream, std::string &err) {
-    EngineImpl &m = *impl_;
-    const float *x = dev_x ? dev_x : m.d_x_cur;
-    if (!x) {
-        err = "no query vector installed (call tkspmv_set_query first)";
-        return TKSPMV_ERR_STATE;
-    }
+// What every enqueue_* entry and drain do around their launches. In front: the stream (the caller's, or the engine's own) and the
+// device. Behind: the launches' error and, for the entries that write a result pair, the marks tkspmv_read goes by.
+template <class Launch>
+static int enqueue_on(EngineImpl &m, void *stream, bool writes_result, std::string &err, Launch launch) {
     hipStream_t s = stream ? (hipStream_t)stream : m.stream;
     HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(m.order_x(x, s));
-    m.launch_query(x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
+    if (const int st = launch(s)) return st;
     HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
+    if (writes_result) {
+        m.ran = true;
+        m.last_on_host = false;
+    }
     return TKSPMV_OK;
 }
 
-// Pointer lists of a back-to-back sequence (query i = dev_xs + (i % n_x) * cols; results to out + i * stride).
-static void sequence_lists(const EngineImpl &m, const float *dev_xs, int32_t n_x, int32_t count, uint32_t *idx, float *val,
-                           size_t stride, std::vector<const float *> &xs, std::vector<uint32_t *> &oi,
-                           std::vector<float *> &ov) {
-    xs.resize(count);
-    oi.resize(count);
-    ov.resize(count);
-    for (int i = 0; i < count; ++i) {
-        xs[i] = dev_xs + (size_t)(i % n_x) * m.desc.cols;
-        oi[i] = idx + (size_t)i * stride;
-        ov[i] = val + (size_t)i * stride;
+// Pointer lists of a back-to-back sequence: query i = dev_xs + (i % n_x) * cols; its result goes to dev_idx / dev_val + i * k, or,
+// where none are given, into the engine's own pair (every query: the last one wins).
+struct SequenceLists {
+    std::vector<const float *> xs;
+    std::vector<uint32_t *> oi;
+    std::vector<float *> ov;
+    SequenceLists(const EngineImpl &m, const float *dev_xs, int32_t n_x, int32_t count, uint32_t *dev_idx = nullptr, float *dev_val = nullptr)
+        : xs(count), oi(count), ov(count) {
+        const size_t stride = dev_idx ? (size_t)m.desc.k : 0;
+        for (int i = 0; i < count; ++i) {
+            xs[i] = dev_xs + (size_t)(i % n_x) * m.desc.cols;
+            oi[i] = (dev_idx ? dev_idx : m.d_out_idx) + (size_t)i * stride;
+            ov[i] = (dev_val ? dev_val : m.d_out_val) + (size_t)i * stride;
+        }
     }
+};
+
+int Engine::enqueue(const float *dev_x, uint32_t *dev_idx, float *dev_val, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (const int st = m.resolve_query(dev_x, 1, err)) return st;
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        HIP_TRY(m.order_x(dev_x, s));
+        m.launch_query(dev_x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_many(const float *dev_xs, int32_t n_x, int32_t count, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || n_x < 1 || count < 0) {
-        err = "bad arguments to enqueue_many";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    sequence_lists(m, dev_xs, n_x, count, m.d_out_idx, m.d_out_val, 0, xs, oi, ov);
-    m.launch_sequence(xs.data(), oi.data(), ov.data(), count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_xs || n_x < 1 || count < 0) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_many");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        const SequenceLists L(m, dev_xs, n_x, count);
+        m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_batch(const float *dev_xs, int32_t count, uint32_t *dev_idx, float *dev_val, void *stream,
                           std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || count < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) {
-        err = "bad arguments to enqueue_batch";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    sequence_lists(m, dev_xs, count > 0 ? count : 1, count, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val,
-                   dev_idx ? (size_t)m.desc.k : 0, xs, oi, ov);
-    m.launch_sequence(xs.data(), oi.data(), ov.data(), count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_xs || count < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_batch");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        const SequenceLists L(m, dev_xs, count > 0 ? count : 1, count, dev_idx, dev_val);
+        m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                          void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || !dev_idx || !dev_val || count < 0) {
-        err = "bad arguments to enqueue_list";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    m.launch_sequence(dev_xs, dev_idx, dev_val, count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_xs || !dev_idx || !dev_val || count < 0) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_list");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        m.launch_sequence(dev_xs, dev_idx, dev_val, count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_multi(const float *dev_xs, int32_t count, uint32_t *dev_idx, float *dev_val, void *stream,
                           std::string &err) {
     EngineImpl &m = *impl_;
     if (!dev_xs && count == 1) dev_xs = m.d_x_cur;  // the vector installed by tkspmv_set_query / set_query_device
-    if (!dev_xs || count < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) {
-        err = "bad arguments to enqueue_multi";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    sequence_lists(m, dev_xs, count > 0 ? count : 1, count, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val,
-                   dev_idx ? (size_t)m.desc.k : 0, xs, oi, ov);
-    m.launch_multi_sequence(xs.data(), oi.data(), ov.data(), count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_xs || count < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_multi");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        const SequenceLists L(m, dev_xs, count > 0 ? count : 1, count, dev_idx, dev_val);
+        m.launch_multi_sequence(L.xs.data(), L.oi.data(), L.ov.data(), count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                                void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || !dev_idx || !dev_val || count < 0) {
-        err = "bad arguments to enqueue_multi_list";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    m.launch_multi_sequence(dev_xs, dev_idx, dev_val, count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_xs || !dev_idx || !dev_val || count < 0) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_multi_list");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        m.launch_multi_sequence(dev_xs, dev_idx, dev_val, count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::set_filter(const uint32_t *host_mask, std::string &err) {
@@ -2055,108 +2036,54 @@ int Engine::set_filter(const uint32_t *host_mask, std::string &err) {
 int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
                              float *dev_val, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (const char *why = m.filter_unsupported()) {
-        err = why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
-    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) {
-        err = "bad arguments to enqueue_filtered (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (!dev_mask && !m.have_filter) {
-        err = "no allow-mask given and none installed (tkspmv_set_filter)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (!dev_xs && count != 1) {
-        err = "dev_xs = NULL takes the installed query vector: count must be 1";
-        return TKSPMV_ERR_INVALID;
-    }
-    const float *x = dev_xs ? dev_xs : m.d_x_cur;
-    if (!x) {
-        err = "no query vector installed (call tkspmv_set_query first)";
-        return TKSPMV_ERR_STATE;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
-    // after the filtered queries did. Settle them now (the host waits for the engine's stream once).
-    if (!m.pending_checks.empty()) {
-        HIP_TRY(hipStreamSynchronize(m.stream));
-        HIP_TRY(m.settle());
-    }
-    HIP_TRY(m.order_x(x, s));
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    sequence_lists(m, x, count, count, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, dev_idx ? (size_t)m.desc.k : 0, xs, oi,
-                   ov);
-    m.launch_filtered(xs.data(), dev_mask ? dev_mask : m.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, oi.data(), ov.data(), count, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (const char *why = m.filter_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_filtered (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)");
+    if (!dev_mask && !m.have_filter) return fail(err, TKSPMV_ERR_INVALID, "no allow-mask given and none installed (tkspmv_set_filter)");
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
+        // after the filtered queries did. Settle them now (the host waits for the engine's stream once).
+        if (!m.pending_checks.empty()) {
+            HIP_TRY(hipStreamSynchronize(m.stream));
+            HIP_TRY(m.settle());
+        }
+        HIP_TRY(m.order_x(dev_xs, s));
+        const SequenceLists L(m, dev_xs, count, count, dev_idx, dev_val);
+        m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, L.oi.data(), L.ov.data(), count, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
                           uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (const char *why = m.filter_unsupported()) {
-        err = std::string("range queries share the filtered path's scope: ") + why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
+    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
     if (count < 1 || !dev_thresholds || !dev_counts || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) ||
-        (capacity > 0u && !dev_idx) || (capacity == 0u && dev_idx)) {
-        err = "bad arguments to enqueue_range (count >= 1, thresholds and counts given, mask_stride_words >= 0, dev_idx and dev_val both given with "
-              "capacity > 0 or both NULL with capacity = 0)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (!dev_xs && count != 1) {
-        err = "dev_xs = NULL takes the installed query vector: count must be 1";
-        return TKSPMV_ERR_INVALID;
-    }
-    const float *x = dev_xs ? dev_xs : m.d_x_cur;
-    if (!x) {
-        err = "no query vector installed (call tkspmv_set_query first)";
-        return TKSPMV_ERR_STATE;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(m.order_x(x, s));
-    m.launch_range(x, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_idx, dev_val, capacity, dev_counts, s);
-    HIP_TRY(hipGetLastError());
-    return TKSPMV_OK;
+        (capacity > 0u && !dev_idx) || (capacity == 0u && dev_idx))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_range (count >= 1, thresholds and counts given, mask_stride_words >= 0, dev_idx and "
+                                             "dev_val both given with capacity > 0 or both NULL with capacity = 0)");
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_range(dev_xs, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_idx, dev_val, capacity, dev_counts, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err) {
     EngineImpl &m = *impl_;
-    if (const char *why = m.filter_unsupported()) {
-        err = std::string("range queries share the filtered path's scope: ") + why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
-    if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx)) {
-        err = "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (use_filter && !m.have_filter) {
-        err = "use_filter without an installed allow-mask (tkspmv_set_filter)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (!m.d_x_cur) {
-        err = "no query vector installed (call tkspmv_set_query first)";
-        return TKSPMV_ERR_STATE;
-    }
+    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
+    if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)");
+    if (use_filter && !m.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const float *installed = nullptr;
+    if (const int st = m.resolve_query(installed, 1, err)) return st;
     HIP_TRY(hipSetDevice(m.device));
     if (!m.d_range_word) HIP_TRY(m.alloc(m.d_range_word, 128, Mem::Device, 0));
     if (capacity > m.range_cap) {
         HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's launch is long complete: run_range waits itself)
-        m.release(m.d_range_idx);
-        m.release(m.d_range_val);
-        m.d_range_idx = nullptr;
-        m.d_range_val = nullptr;
-        m.range_cap = 0u;
-        HIP_TRY(m.alloc(m.d_range_idx, (size_t)capacity * 4));
-        HIP_TRY(m.alloc(m.d_range_val, (size_t)capacity * 4));
-        m.range_cap = capacity;
+        HIP_TRY(m.grow_scratch(m.range_cap, capacity, {{(void **)&m.d_range_idx, (size_t)capacity * 4}, {(void **)&m.d_range_val, (size_t)capacity * 4}}));
     }
     HIP_TRY(hipMemcpy(m.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
     const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.d_range_word), use_filter ? m.d_filter : nullptr, 0,
@@ -2179,65 +2106,40 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
 
 int Engine::enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_rows || !dev_xs || count < 1) {
-        err = "bad arguments to enqueue_row_vectors (row ids and vectors given, count >= 1)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (const char *why = m.row_vectors_unsupported()) {
-        err = why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    m.launch_row_vectors(dev_rows, count, dev_xs, dev_len, s);
-    HIP_TRY(hipGetLastError());
-    return TKSPMV_OK;
+    if (!dev_rows || !dev_xs || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_row_vectors (row ids and vectors given, count >= 1)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_row_vectors(dev_rows, count, dev_xs, dev_len, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_rows || !host_xs || count < 1) {
-        err = "bad arguments to row_vectors (row ids and vectors given, count >= 1)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (const char *why = m.row_vectors_unsupported()) {
-        err = why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
+    if (!host_rows || !host_xs || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to row_vectors (row ids and vectors given, count >= 1)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     HIP_TRY(hipSetDevice(m.device));
     // (buffers of this call alone: the caller asks for `count` whole vectors at once, whatever their size)
-    uint32_t *d_rows = nullptr, *d_len = nullptr;
-    float *d_xs = nullptr;
+    ScratchBuffer<uint32_t> d_rows, d_len;
+    ScratchBuffer<float> d_xs;
     const size_t xs_bytes = (size_t)count * m.desc.cols * 4;
-    hipError_t e = hipMalloc((void **)&d_rows, (size_t)count * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_len, (size_t)count * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_xs, xs_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_rows, host_rows, (size_t)count * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        m.launch_row_vectors(d_rows, count, d_xs, d_len, m.stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(m.stream);
-    if (e == hipSuccess) e = m.settle();  // (the host has just waited for the engine's stream)
-    if (e == hipSuccess) e = hipMemcpy(host_xs, d_xs, xs_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && host_len) e = hipMemcpy(host_len, d_len, (size_t)count * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rows);
-    (void)hipFree(d_len);
-    (void)hipFree(d_xs);
-    HIP_TRY(e);
+    HIP_TRY(hipMalloc((void **)&d_rows.p, (size_t)count * 4));
+    HIP_TRY(hipMalloc((void **)&d_len.p, (size_t)count * 4));
+    HIP_TRY(hipMalloc((void **)&d_xs.p, xs_bytes));
+    HIP_TRY(hipMemcpy(d_rows.p, host_rows, (size_t)count * 4, hipMemcpyHostToDevice));
+    m.launch_row_vectors(d_rows.p, count, d_xs.p, d_len.p, m.stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(m.settle());  // (the host has just waited for the engine's stream)
+    HIP_TRY(hipMemcpy(host_xs, d_xs.p, xs_bytes, hipMemcpyDeviceToHost));
+    if (host_len) HIP_TRY(hipMemcpy(host_len, d_len.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 
 int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_rows || !idx || !val || count < 1) {
-        err = "bad arguments to run_similar (row ids and [count][k] outputs given, count >= 1)";
-        return TKSPMV_ERR_INVALID;
-    }
-    if (const char *why = m.row_vectors_unsupported()) {
-        err = why;
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
+    if (!host_rows || !idx || !val || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_similar (row ids and [count][k] outputs given, count >= 1)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     HIP_TRY(hipSetDevice(m.device));
     const size_t k = (size_t)m.desc.k, cols = m.desc.cols;
     const uint32_t chunk_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(EngineImpl::SIMILAR_MAX_ROWS, EngineImpl::SIMILAR_MAX_BYTES / (cols * 4)));
@@ -2245,15 +2147,8 @@ int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclud
     if (want > m.sim_cap) {
         HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: run_similar waits itself)
         HIP_TRY(m.settle());
-        for (const void *p : {(const void *)m.d_sim_rows, (const void *)m.d_sim_idx, (const void *)m.d_sim_xs, (const void *)m.d_sim_val}) m.release(p);
-        m.d_sim_rows = m.d_sim_idx = nullptr;
-        m.d_sim_xs = m.d_sim_val = nullptr;
-        m.sim_cap = 0u;
-        HIP_TRY(m.alloc(m.d_sim_rows, (size_t)want * 4));
-        HIP_TRY(m.alloc(m.d_sim_xs, (size_t)want * cols * 4));
-        HIP_TRY(m.alloc(m.d_sim_idx, (size_t)want * k * 4));
-        HIP_TRY(m.alloc(m.d_sim_val, (size_t)want * k * 4));
-        m.sim_cap = want;
+        HIP_TRY(m.grow_scratch(m.sim_cap, want, {{(void **)&m.d_sim_rows, (size_t)want * 4}, {(void **)&m.d_sim_xs, (size_t)want * cols * 4},
+                                                 {(void **)&m.d_sim_idx, (size_t)want * k * 4}, {(void **)&m.d_sim_val, (size_t)want * k * 4}}));
     }
     for (int32_t i0 = 0; i0 < count; i0 += (int32_t)m.sim_cap) {
         const int32_t c = std::min<int32_t>((int32_t)m.sim_cap, count - i0);
@@ -2288,27 +2183,21 @@ int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclud
 
 int Engine::time_multi(const float *dev_xs, int32_t n_x, int32_t iters, double *ns_per_query, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || n_x < 1 || iters < 1 || !ns_per_query) {
-        err = "bad arguments to time_multi";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!dev_xs || n_x < 1 || iters < 1 || !ns_per_query) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_multi");
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(m.settle());
     HIP_TRY(hipEventRecord(m.ev0, m.stream));
     {
-        std::vector<const float *> xs;
-        std::vector<uint32_t *> oi;
-        std::vector<float *> ov;
-        sequence_lists(m, dev_xs, n_x, iters, m.d_out_idx, m.d_out_val, 0, xs, oi, ov);
+        SequenceLists L(m, dev_xs, n_x, iters);
         if (m.d_multi_out_idx) {  // a result buffer per query in flight (two groups): the two chains may run
             for (int i = 0; i < iters; ++i) {
                 const size_t slot = (size_t)(i % (2 * MULTI_Q_MAX)) * (size_t)m.desc.k;
-                oi[i] = m.d_multi_out_idx + slot;
-                ov[i] = m.d_multi_out_val + slot;
+                L.oi[i] = m.d_multi_out_idx + slot;
+                L.ov[i] = m.d_multi_out_val + slot;
             }
         }
-        m.launch_multi_sequence(xs.data(), oi.data(), ov.data(), iters, m.stream);
+        m.launch_multi_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
     }
     HIP_TRY(hipEventRecord(m.ev1, m.stream));
     HIP_TRY(hipEventSynchronize(m.ev1));
@@ -2339,34 +2228,24 @@ int Engine::time_multi(const float *dev_xs, int32_t n_x, int32_t iters, double *
 
 int Engine::enqueue_deferred(const float *dev_x, uint32_t *dev_idx, float *dev_val, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_x) {
-        err = "query vector is NULL";
-        return TKSPMV_ERR_INVALID;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    m.launch_deferred(dev_x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
-    HIP_TRY(hipGetLastError());
-    m.ran = true;
-    m.last_on_host = false;
-    return TKSPMV_OK;
+    if (!dev_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
+    return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
+        m.launch_deferred(dev_x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::drain(void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    hipStream_t s = stream ? (hipStream_t)stream : m.stream;
-    HIP_TRY(hipSetDevice(m.device));
-    m.drain(s);
-    HIP_TRY(hipGetLastError());
-    return TKSPMV_OK;
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {
+        m.drain(s);
+        return TKSPMV_OK;
+    });
 }
 
 int Engine::run(double *kernel_ns, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.have_query) {
-        err = "no query vector installed (call tkspmv_set_query first)";
-        return TKSPMV_ERR_STATE;
-    }
+    if (!m.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
     HIP_TRY(hipSetDevice(m.device));
     // The fused single launch can hand its result to the host itself (see h_res); the other launch schemes (radix select,
     // row per lane, unfused selection) complete in stream order and are waited for with the event.
@@ -2421,10 +2300,7 @@ int Engine::run(double *kernel_ns, std::string &err) {
         if (seen) {  // the kernel is in its last instructions: the end event follows within a microsecond or two
             hipError_t q;
             while ((q = hipEventQuery(m.ev1)) == hipErrorNotReady) __builtin_ia32_pause();
-            if (q != hipSuccess) {
-                err = std::string("hipEventQuery failed: ") + hipGetErrorString(q);
-                return TKSPMV_ERR_DEVICE;
-            }
+            if (q != hipSuccess) return fail(err, TKSPMV_ERR_DEVICE, std::string("hipEventQuery failed: ") + hipGetErrorString(q));
         }
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
@@ -2445,10 +2321,7 @@ int Engine::synchronize(std::string &err) {
 
 int Engine::read(uint32_t *idx, float *val, int32_t *n, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.ran) {
-        err = "no query has been run";
-        return TKSPMV_ERR_STATE;
-    }
+    if (!m.ran) return fail(err, TKSPMV_ERR_STATE, "no query has been run");
     if (m.last_on_host) {  // tkspmv_run left the result in pinned host memory
         if (idx) std::memcpy(idx, m.h_res, (size_t)m.desc.k * 4);
         if (val) std::memcpy(val, m.h_res + m.desc.k, (size_t)m.desc.k * 4);
@@ -2470,10 +2343,7 @@ int Engine::read(uint32_t *idx, float *val, int32_t *n, std::string &err) {
 // out[4] = launches the local thresholds as a whole stay switched off for, out[5] = the length of that closure.
 int Engine::debug_counters(unsigned long long *out, int n, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!out || n < 6) {
-        err = "debug_counters needs room for 6 values";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!out || n < 6) return fail(err, TKSPMV_ERR_INVALID, "debug_counters needs room for 6 values");
     HIP_TRY(hipSetDevice(m.device));
     if (m.stream) HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(m.settle());
@@ -2521,10 +2391,7 @@ int Engine::read_trace(unsigned long long *host, size_t max_words, size_t *words
         if (words) *words = n;
         return TKSPMV_OK;
     }
-    if (!m.d_trace) {
-        err = "tracing is off (set TKSPMV_TRACE=1 before tkspmv_create)";
-        return TKSPMV_ERR_STATE;
-    }
+    if (!m.d_trace) return fail(err, TKSPMV_ERR_STATE, "tracing is off (set TKSPMV_TRACE=1 before tkspmv_create)");
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = std::min(max_words, m.trace_words * 4);
@@ -2541,10 +2408,7 @@ int Engine::result_device(const uint32_t **dev_idx, const float **dev_val) {
 
 int Engine::scores(float *host_y, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.have_query) {
-        err = "no query vector installed";
-        return TKSPMV_ERR_STATE;
-    }
+    if (!m.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed");
     HIP_TRY(hipSetDevice(m.device));
     if (!m.d_scores) HIP_TRY(m.alloc(m.d_scores, std::max<size_t>(m.desc.rows, 1) * 4));
     HIP_TRY(hipMemsetAsync(m.d_scores, 0, std::max<size_t>(m.desc.rows, 1) * 4, m.stream));
@@ -2558,10 +2422,7 @@ int Engine::scores(float *host_y, std::string &err) {
 
 int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double *ns_per_query, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || n_x < 1 || iters < 1 || !ns_per_query) {
-        err = "bad arguments to time_queries";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!dev_xs || n_x < 1 || iters < 1 || !ns_per_query) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_queries");
     const bool host_times = opt("HOST_TIMES") != nullptr;  // (diagnostic: where the host's microseconds around the region go, to stderr)
     auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double h0 = host_times ? now_us() : 0.0;
@@ -2579,11 +2440,8 @@ int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double
         HIP_TRY(hipEventRecord(m.ev0, m.stream));
     }
     {
-        std::vector<const float *> xs;
-        std::vector<uint32_t *> oi;
-        std::vector<float *> ov;
-        sequence_lists(m, dev_xs, n_x, iters, m.d_out_idx, m.d_out_val, 0, xs, oi, ov);
-        m.launch_sequence(xs.data(), oi.data(), ov.data(), iters, m.stream);
+        const SequenceLists L(m, dev_xs, n_x, iters);
+        m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
     }
     if (!ext) HIP_TRY(hipEventRecord(m.ev1, m.stream));
     const double h2 = host_times ? now_us() : 0.0;
@@ -2622,22 +2480,17 @@ int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double
 // after a host-side gap, 10-25 % slower for about a millisecond (power management: DESIGN.md).
 int Engine::time_query_batches(const float *dev_xs, int32_t n_x, int32_t iters, int32_t reps, double *ns_per_query, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || n_x < 1 || iters < 1 || reps < 1 || reps > 4096 || !ns_per_query) {
-        err = "bad arguments to time_query_batches";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!dev_xs || n_x < 1 || iters < 1 || reps < 1 || reps > 4096 || !ns_per_query) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_query_batches");
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(m.settle());
-    std::vector<hipEvent_t> evs((size_t)reps + 1);
+    ScratchEvents scratch_events((size_t)reps + 1);
+    std::vector<hipEvent_t> &evs = scratch_events.e;
     for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    sequence_lists(m, dev_xs, n_x, iters, m.d_out_idx, m.d_out_val, 0, xs, oi, ov);
+    const SequenceLists L(m, dev_xs, n_x, iters);
     HIP_TRY(hipEventRecord(evs[0], m.stream));
     for (int r = 0; r < reps; ++r) {
-        m.launch_sequence(xs.data(), oi.data(), ov.data(), iters, m.stream);
+        m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
         HIP_TRY(hipEventRecord(evs[(size_t)r + 1], m.stream));
     }
     HIP_TRY(hipGetLastError());
@@ -2648,7 +2501,6 @@ int Engine::time_query_batches(const float *dev_xs, int32_t n_x, int32_t iters, 
         HIP_TRY(hipEventElapsedTime(&ms, evs[(size_t)r], evs[(size_t)r + 1]));
         ns_per_query[r] = (double)ms * 1e6 / iters;
     }
-    for (auto &e : evs) (void)hipEventDestroy(e);
     m.ran = true;
     m.last_on_host = false;
     return TKSPMV_OK;
@@ -2656,10 +2508,7 @@ int Engine::time_query_batches(const float *dev_xs, int32_t n_x, int32_t iters, 
 
 int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &err) {
     EngineImpl &m = *impl_;
-    if (passes < 1 || !ns_per_pass) {
-        err = "bad arguments to time_stream_read";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (passes < 1 || !ns_per_pass) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_stream_read");
     if (m.pm.n_packets == 0) {
         *ns_per_pass = 0.0;
         return TKSPMV_OK;
@@ -2703,10 +2552,7 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
 #undef RP
         }
     }
-    if (!fn) {
-        err = "no read probe for this packet size";
-        return TKSPMV_ERR_UNSUPPORTED;
-    }
+    if (!fn) return fail(err, TKSPMV_ERR_UNSUPPORTED, "no read probe for this packet size");
     HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(m.settle());
     R.n_pass = 2;  // (warm-up: code object, clocks)
@@ -2761,10 +2607,7 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
 
 int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timing *out, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || n_x < 1 || iters < 1 || !out) {
-        err = "bad arguments to profile";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!dev_xs || n_x < 1 || iters < 1 || !out) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to profile");
     std::memset(out, 0, sizeof(*out));
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipStreamSynchronize(m.stream));
@@ -2775,11 +2618,8 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
     // (1) whole queries back-to-back
     HIP_TRY(hipEventRecord(m.ev0, m.stream));
     {
-        std::vector<const float *> xs;
-        std::vector<uint32_t *> oi;
-        std::vector<float *> ov;
-        sequence_lists(m, dev_xs, n_x, iters, m.d_out_idx, m.d_out_val, 0, xs, oi, ov);
-        m.launch_sequence(xs.data(), oi.data(), ov.data(), iters, m.stream);
+        const SequenceLists L(m, dev_xs, n_x, iters);
+        m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
     }
     HIP_TRY(hipEventRecord(m.ev1, m.stream));
     HIP_TRY(hipEventSynchronize(m.ev1));
@@ -2882,10 +2722,7 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
 // kernel_ns[i] = what tkspmv_run returned for it. What a C++ host of the reference sees per iteration; a Python caller adds a
 // ctypes transition per call to it.
 int Engine::time_host_loop(const float *host_xs, int32_t n_x, int32_t iters, double *loop_ns, double *kernel_ns, std::string &err) {
-    if (!host_xs || n_x < 1 || iters < 1 || !loop_ns) {
-        err = "time_host_loop: NULL or empty arguments";
-        return TKSPMV_ERR_INVALID;
-    }
+    if (!host_xs || n_x < 1 || iters < 1 || !loop_ns) return fail(err, TKSPMV_ERR_INVALID, "time_host_loop: NULL or empty arguments");
     EngineImpl &m = *impl_;
     std::vector<uint32_t> idx((size_t)m.desc.k);
     std::vector<float> val((size_t)m.desc.k);

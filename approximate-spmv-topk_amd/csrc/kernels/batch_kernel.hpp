@@ -266,7 +266,7 @@ __device__ __forceinline__ void gate_update(const BatchParams &B, uint32_t faile
 template <int C, int XCOLS, int QM, bool DBG, bool LOCAL>
 __device__ __forceinline__ void batch_phase(const StreamParams &P0, const SelectParams &SP0, const BatchParams &B, const bool repair,
                                             BatchLds<XCOLS, C> &L) {
-    constexpr bool Q8 = QM == 1 || QM == 2;  // x staged as Q1.7 integers
+    constexpr bool Q8 = QM == QM_Q17 || QM == QM_Q17_WIDE;  // x staged as Q1.7 integers
     constexpr int VT = value_type_of(QM);
     constexpr int NBUF = C == 8 ? 2 : 3;  // packets of 8 entries per lane are twice as large: one ahead is as many bytes
     constexpr uint32_t WAVE_CAP = ListGeom<XCOLS>::WAVE_CAP;
@@ -434,7 +434,7 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
         // the two remembered priors with their signatures (slot 0: wg_prior, the most recently used), and per query in flight: its
         // signature and the slot it started from (2: none)
         // (signatures are formed from the fp32 copy of x in LDS: the integer-staged value types keep round 4's behaviour)
-        const bool sigs = carry_local && B.wg_sig != nullptr && !Q8 && QM != 4 && QM != 6 && QM != 8;
+        const bool sigs = carry_local && B.wg_sig != nullptr && !Q8 && QM != QM_FIXED && QM != QM_FIXED20 && QM != QM_FIXED26;
         float p_rho[2] = {0.0f, 0.0f}, p_pr[2] = {0.0f, 0.0f}, prior1 = 0.0f;
         // (wave-uniform values: kept in scalar registers -- as vector registers they cost the kernel 60 spilled registers)
         auto uni = [](float v) __attribute__((always_inline)) -> float { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
@@ -471,7 +471,7 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
                     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xres, i * 4u, 0, 0));
                 };
                 float x_scale = 1.0f, unit_scale = 1.0f;
-                if (QM == 2) {
+                if (QM == QM_Q17_WIDE) {
                     float lm = 0.0f;
 #pragma unroll 1
                     for (uint32_t b0 = 0; b0 < (uint32_t)XCOLS; b0 += 1024u) {  // 16 loads in flight per lane
@@ -493,9 +493,9 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
                     }
                     x_scale = (float)(1u << sh);
                     unit_scale = 128.0f * x_scale;
-                } else if (QM == 1) {
+                } else if (QM == QM_Q17) {
                     unit_scale = 128.0f;
-                } else if (QM == 4 || QM == 6 || QM == 8) {
+                } else if (QM == QM_FIXED || QM == QM_FIXED20 || QM == QM_FIXED26) {
                     unit_scale = 2147483648.0f;
                 }
                 inv_unit_q[par] = 1.0f / unit_scale;
@@ -522,12 +522,12 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
                         const uint32_t i = b0 + lane + 64u * (uint32_t)u;
                         if (Q8)
                             reinterpret_cast<uint32_t *>(xl)[i] = to_q1_7_dev(r[u] * x_scale);
-                        else if (QM == 6)
+                        else if (QM == QM_FIXED20)
                             reinterpret_cast<uint32_t *>(xl)[i] = to_fixed_dev(r[u], P0.fixed_width) >> 12;
-                        else if (QM == 4 || QM == 8)
+                        else if (QM == QM_FIXED || QM == QM_FIXED26)
                             reinterpret_cast<uint32_t *>(xl)[i] = to_fixed_dev(r[u], P0.fixed_width) >> (P0.fixed_width <= 24u ? 8 : 0);
                         else
-                            xl[i] = QM == 5 ? r[u] * Q17_UNIT : r[u];
+                            xl[i] = QM == QM_Q17_F32 ? r[u] * Q17_UNIT : r[u];
                     }
                 }
                 uint32_t *mp = L.misc[par];
@@ -786,7 +786,7 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
     // again (step 0: a fixed number of younger loads lets the compiler wait with a counted vmcnt). fp32 streams are fetched with
     // buffer loads (load_packet_buf): resource = this wave's partition in the query's stream copy. The row base of a packet is
     // looked up on the candidate path only (pkt_row[p0 + jc], a scalar load where round 4 carried one per packet).
-    constexpr bool BUF = C == 4 && (VT == 0 || VT == 4);
+    constexpr bool BUF = C == 4 && (VT == VT_F32 || VT == VT_F32C12);
     auto stream_of = [&](uint32_t q) __attribute__((always_inline)) -> const uint8_t * {
         return B.io[qx(q)].packets;
     };

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "../stream_format.hpp"
+
 namespace tkspmv {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -88,23 +90,22 @@ struct ListGeom {
 constexpr uint32_t WG_SLOTS = 8;              // fixed result slots every workgroup writes (no count round trip)
 constexpr uint32_t SLOT_INVALID = 0xFFFFFFFFu;  // row id of an unused slot
 
-// One lane's share of a packet. VT = value type of the stream: 0 = C fp32 values; 1 = C Q1.7 values packed four to a
-// dword; 2 = C fp16 values packed two to a dword.
-// QM (kernel template parameter): 0 = fp32, 1 = Q1.7 strict (8-bit wrapping sums, the FPGA's real_type), 2 = Q1.7 values
-// with x block-scaled by a power of two per query and exact wide accumulation, 3 = fp16 values, fp32 x, fp32 arithmetic
-// (the CUDA comparator's half mode, -a: host_spmv_topk_csr_gpu.cu:132-136,152-160), 4 = fixed point of W bits (the
-// FPGA's real_type for any FIXED_WIDTH): values and x as left-aligned Q1.31 words, integer products and sums.
+// The arithmetic of the kernels' modes (QM, a template parameter; the names, and VT -- a lane's share of a packet --: stream_format.hpp):
+// QM_F32      fp32 values, fp32 x, fp32 products and sums.
+// QM_Q17      Q1.7 strict: 8-bit wrapping sums, the FPGA's real_type.
+// QM_Q17_WIDE Q1.7 values with x block-scaled by a power of two per query and exact wide accumulation.
+// QM_F16      fp16 values, fp32 x, fp32 arithmetic (the CUDA comparator's half mode, -a: host_spmv_topk_csr_gpu.cu:132-136,152-160).
+// QM_FIXED    fixed point of W bits (the FPGA's real_type for any FIXED_WIDTH): values and x as left-aligned Q1.31 words, integer products
+//             and sums.
+// QM_Q17_F32  Q1.7 values (rounded to nearest) dequantised to fp32 (v_cvt_f32_ubyteN: one VALU per entry), fp32 x held in LDS pre-scaled
+//             by 2^-7 (exact), fp32 products and sums: the Q1.7 modes' byte stream, the fp32 path's arithmetic (BASELINE configs[4]).
+// QM_FIXED20  fixed point of at most 20 bits, one dword per entry carrying value, column and flags; QM_FIXED's arithmetic with both
+//             factors as 20-bit integers.
+// QM_F32C12   fp32 exactly like QM_F32, the column words travelling as 12 bits each in a split plane.
+// QM_FIXED26  fixed point of 21..26 bits in five bytes per entry; the arithmetic is QM_FIXED's.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));  // a dwordx2 at a 4-byte boundary
-// QM 5 = Q1.7 values (rounded to nearest) dequantised to fp32 (v_cvt_f32_ubyteN: one VALU per entry), fp32 x held in LDS
-// pre-scaled by 2^-7 (exact), fp32 products and sums: the byte stream of the Q1.7 modes with the arithmetic of the fp32
-// path (TKSPMV_Q1_7_F32, BASELINE configs[4]).
-// QM 6 = fixed point of at most 20 bits, bit-packed (wbscsr.hpp FIXED20): one dword per entry carrying value, column and
-// flags; the arithmetic is QM 4's with both factors as 20-bit integers.
-// QM 7 = fp32 exactly like QM 0, the column words travelling as 12 bits each in a split plane (wbscsr.hpp F32C12): value type 4.
-// QM 8 = fixed point of 21..26 bits in five bytes per entry (wbscsr.hpp FIXED26): value type 6; the arithmetic is QM 4's.
-constexpr int value_type_of(int QM) { return QM == 8 ? 6 : (QM == 7 ? 4 : (QM == 6 ? 3 : (QM == 3 ? 2 : ((QM == 1 || QM == 2 || QM == 5) ? 1 : 0)))); }  // QM 4: one u32 per value, loaded like fp32
 // Byte b (0..3) of a dword as a float: v_cvt_f32_ubyte0..3.
 template <int B>
 __device__ __forceinline__ float ubyte_to_float(uint32_t w) {
@@ -134,42 +135,42 @@ __device__ __forceinline__ uint32_t scalar_load(const uint32_t *uniform_ptr) {
 // from them when the stream comes from HBM, tools/stream_probe.hip).
 template <int C, int VT>
 struct Pkt {
-    float v[(VT == 0 || VT == 3 || VT == 4 || VT == 6) ? C : 1];  // VT 3, 6: the packed dwords (value | column bits | flags); VT 6: cw[0] = E (column bits 9..4)
-    uint32_t vq[(VT == 1 || VT == 5) ? C / 4 : (VT == 2 ? C / 2 : 1)];  // VT 5: byte values with 12-bit column words (row-per-lane chunks)
-    uint32_t cw[C / 2];  // VT 4: the two dwords of the pair's 12-byte block that hold the lane's A and the pair's B (split_ab below)
+    float v[(VT == VT_F32 || VT == VT_FIXED20 || VT == VT_F32C12 || VT == VT_FIXED26) ? C : 1];  // VT_FIXED20, VT_FIXED26: the packed dwords (value | column bits | flags); VT_FIXED26: cw[0] = E (column bits 9..4)
+    uint32_t vq[(VT == VT_Q17 || VT == VT_Q17C12) ? C / 4 : (VT == VT_F16 ? C / 2 : 1)];  // VT_Q17C12: byte values with 12-bit column words (row-per-lane chunks)
+    uint32_t cw[C / 2];  // VT_F32C12: the two dwords of the pair's 12-byte block that hold the lane's A and the pair's B (split_ab below)
 };
 
 template <int C, int VT>
 __device__ __forceinline__ void load_packet(const uint8_t *__restrict__ pk, uint32_t lane, Pkt<C, VT> &o) {
 #pragma unroll
     for (int q = 0; q < C / 4; ++q) {
-        if (VT == 3) {
+        if (VT == VT_FIXED20) {
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + q * 1024 + lane * 16));
-            o.v[VT == 3 ? 4 * q + 0 : 0] = f.x;
-            o.v[VT == 3 ? 4 * q + 1 : 0] = f.y;
-            o.v[VT == 3 ? 4 * q + 2 : 0] = f.z;
-            o.v[VT == 3 ? 4 * q + 3 : 0] = f.w;
-        } else if (VT == 6) {  // FIXED26: the lane's four dwords D_j and its dword E
+            o.v[VT == VT_FIXED20 ? 4 * q + 0 : 0] = f.x;
+            o.v[VT == VT_FIXED20 ? 4 * q + 1 : 0] = f.y;
+            o.v[VT == VT_FIXED20 ? 4 * q + 2 : 0] = f.z;
+            o.v[VT == VT_FIXED20 ? 4 * q + 3 : 0] = f.w;
+        } else if (VT == VT_FIXED26) {  // FIXED26: the lane's four dwords D_j and its dword E
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + lane * 16));
-            o.v[VT == 6 ? 0 : 0] = f.x;
-            o.v[VT == 6 ? 1 : 0] = f.y;
-            o.v[VT == 6 ? 2 : 0] = f.z;
-            o.v[VT == 6 ? 3 : 0] = f.w;
+            o.v[VT == VT_FIXED26 ? 0 : 0] = f.x;
+            o.v[VT == VT_FIXED26 ? 1 : 0] = f.y;
+            o.v[VT == VT_FIXED26 ? 2 : 0] = f.z;
+            o.v[VT == VT_FIXED26 ? 3 : 0] = f.w;
             o.cw[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + 1024 + lane * 4));
-        } else if (VT == 4) {
+        } else if (VT == VT_F32C12) {
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + q * 1024 + lane * 16));
-            o.v[VT == 4 ? 4 * q + 0 : 0] = f.x;
-            o.v[VT == 4 ? 4 * q + 1 : 0] = f.y;
-            o.v[VT == 4 ? 4 * q + 2 : 0] = f.z;
-            o.v[VT == 4 ? 4 * q + 3 : 0] = f.w;
+            o.v[VT == VT_F32C12 ? 4 * q + 0 : 0] = f.x;
+            o.v[VT == VT_F32C12 ? 4 * q + 1 : 0] = f.y;
+            o.v[VT == VT_F32C12 ? 4 * q + 2 : 0] = f.z;
+            o.v[VT == VT_F32C12 ? 4 * q + 3 : 0] = f.w;
             // split 12-bit plane (wbscsr.hpp colw12s_*), 12 bytes per pair of lanes [A_even][B_even | B_odd << 16][A_odd]: ONE
             // dwordx2 at a 4-byte boundary per lane -- dwords 0-1 on the even lane, 1-2 on the odd one. cw[0] / cw[1] hold the
             // two dwords as loaded: reduce_packet picks A and B out of them by the lane's parity.
             const u32x2_a4 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2_a4 *>(pk + C * 256 + q * 384 + (lane >> 1) * 12 + (lane & 1u) * 4));
             o.cw[2 * q + 0] = c.x;
             o.cw[2 * q + 1] = c.y;
-        } else if (VT == 5) {
-            o.vq[VT == 5 ? q : 0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + q * 256 + lane * 4));
+        } else if (VT == VT_Q17C12) {
+            o.vq[VT == VT_Q17C12 ? q : 0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + q * 256 + lane * 4));
             // Back-to-back 12-bit words, two lanes sharing three dwords: one dwordx2 at a 4-byte boundary per lane. Two other
             // arrangements were measured on BASELINE configs[4] (19.6 us per query as it stands): the split plane of the
             // wave-BSCSR packets (one dword + one halfword per lane: three loads per chunk, 9 of 29 vector instructions fewer)
@@ -179,24 +180,24 @@ __device__ __forceinline__ void load_packet(const uint8_t *__restrict__ pk, uint
             const u32x2_a4 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2_a4 *>(pk + C * 64 + q * 384 + (lane >> 1) * 12 + (lane & 1u) * 4));
             o.cw[2 * q + 0] = c.x;
             o.cw[2 * q + 1] = c.y;
-        } else if (VT == 1) {
-            o.vq[VT == 1 ? q : 0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + q * 256 + lane * 4));
+        } else if (VT == VT_Q17) {
+            o.vq[VT == VT_Q17 ? q : 0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + q * 256 + lane * 4));
             const u32x2 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(pk + C * 64 + q * 512 + lane * 8));
             o.cw[2 * q + 0] = c.x;
             o.cw[2 * q + 1] = c.y;
-        } else if (VT == 2) {
+        } else if (VT == VT_F16) {
             const u32x2 hv = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(pk + q * 512 + lane * 8));
-            o.vq[VT == 2 ? 2 * q + 0 : 0] = hv.x;
-            o.vq[VT == 2 ? 2 * q + 1 : 0] = hv.y;
+            o.vq[VT == VT_F16 ? 2 * q + 0 : 0] = hv.x;
+            o.vq[VT == VT_F16 ? 2 * q + 1 : 0] = hv.y;
             const u32x2 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(pk + C * 128 + q * 512 + lane * 8));
             o.cw[2 * q + 0] = c.x;
             o.cw[2 * q + 1] = c.y;
         } else {
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + q * 1024 + lane * 16));
-            o.v[VT == 0 ? 4 * q + 0 : 0] = f.x;
-            o.v[VT == 0 ? 4 * q + 1 : 0] = f.y;
-            o.v[VT == 0 ? 4 * q + 2 : 0] = f.z;
-            o.v[VT == 0 ? 4 * q + 3 : 0] = f.w;
+            o.v[VT == VT_F32 ? 4 * q + 0 : 0] = f.x;
+            o.v[VT == VT_F32 ? 4 * q + 1 : 0] = f.y;
+            o.v[VT == VT_F32 ? 4 * q + 2 : 0] = f.z;
+            o.v[VT == VT_F32 ? 4 * q + 3 : 0] = f.w;
             const u32x2 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(pk + C * 256 + q * 512 + lane * 8));
             o.cw[2 * q + 0] = c.x;
             o.cw[2 * q + 1] = c.y;
@@ -204,7 +205,7 @@ __device__ __forceinline__ void load_packet(const uint8_t *__restrict__ pk, uint
     }
 }
 
-// The same packet through BUFFER loads (round 5; fp32 streams of 4 entries per lane: value types 0 and 4). A buffer load takes its
+// The same packet through BUFFER loads (round 5; fp32 streams of 4 entries per lane: VT_F32 and VT_F32C12). A buffer load takes its
 // address as resource (4 SGPRs: the partition's first byte in the stream copy of the query, its length) + SGPR byte offset (the
 // packet) + VGPR byte offset (the lane's share, the same for every packet): nothing is added per packet on the vector unit -- the
 // flat form spent three 64-bit vector adds per packet on the two addresses --, and the packet pointer is ONE scalar add. Loads
@@ -214,10 +215,10 @@ struct LaneOffsets {
 };
 template <int C, int VT>
 __device__ __forceinline__ LaneOffsets lane_offsets(uint32_t lane) {
-    static_assert(C == 4 && (VT == 0 || VT == 4), "buffer-load packets: fp32 values, 4 entries per lane");
+    static_assert(C == 4 && (VT == VT_F32 || VT == VT_F32C12), "buffer-load packets: fp32 values, 4 entries per lane");
     LaneOffsets o;
     o.v = lane * 16u;
-    o.c = VT == 4 ? (uint32_t)C * 256u + (lane >> 1) * 12u + (lane & 1u) * 4u : (uint32_t)C * 256u + lane * 8u;
+    o.c = VT == VT_F32C12 ? (uint32_t)C * 256u + (lane >> 1) * 12u + (lane & 1u) * 4u : (uint32_t)C * 256u + lane * 8u;
     return o;
 }
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -228,9 +229,9 @@ template <int C, int VT>
 __device__ __forceinline__ void load_packet_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t packet_off, const LaneOffsets &lo, Pkt<C, VT> &o) {
     const u32x4 f = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lo.v, packet_off, 2);  // (aux 2: non-temporal, like the flat form)
     o.v[0] = __uint_as_float(f.x);
-    o.v[VT == 0 || VT == 4 ? 1 : 0] = __uint_as_float(f.y);
-    o.v[VT == 0 || VT == 4 ? 2 : 0] = __uint_as_float(f.z);
-    o.v[VT == 0 || VT == 4 ? 3 : 0] = __uint_as_float(f.w);
+    o.v[VT == VT_F32 || VT == VT_F32C12 ? 1 : 0] = __uint_as_float(f.y);
+    o.v[VT == VT_F32 || VT == VT_F32C12 ? 2 : 0] = __uint_as_float(f.z);
+    o.v[VT == VT_F32 || VT == VT_F32C12 ? 3 : 0] = __uint_as_float(f.w);
     const u32x2 c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lo.c, packet_off, 2);
     o.cw[0] = c.x;
     o.cw[1] = c.y;

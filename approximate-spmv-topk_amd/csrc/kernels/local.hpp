@@ -462,7 +462,7 @@ struct SingleLds {
 constexpr uint32_t SINGLE_REC_STRIDE = 16;  // 64-bit words between the records of consecutive workgroups when workgroup 0 selects (LocalParams::ready)
 template <int QM>
 __global__ void __launch_bounds__(512, 4) single_kernel(const StreamParams P, const SelectParams SP, const LocalParams G) {
-    static_assert(QM == 0 || QM == 7, "single_kernel: fp32 values, 4 entries per lane, at most 1024 columns");
+    static_assert(QM == QM_F32 || QM == QM_F32C12, "single_kernel: fp32 values, 4 entries per lane, at most 1024 columns");
     constexpr int C = 4, NBUF = 3;
     constexpr int VT = value_type_of(QM);
     constexpr uint32_t WAVE_CAP = ListGeom<1024>::WAVE_CAP;

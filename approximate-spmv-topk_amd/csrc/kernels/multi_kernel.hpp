@@ -140,18 +140,18 @@ __device__ __forceinline__ void offer_rows(const SetAddr &A, uint32_t set, uint3
 // fp32 number as (byte / 128) * x.
 template <int VT>
 __device__ __forceinline__ float chunk_value(const Pkt<4, VT> &p, int j) {
-    if (VT == 1 || VT == 5) return ubyte_to_float(p.vq[0], j);
-    return p.v[VT == 0 ? j : 0];
+    if (VT == VT_Q17 || VT == VT_Q17C12) return ubyte_to_float(p.vq[0], j);
+    return p.v[VT == VT_F32 ? j : 0];
 }
 
 // VT: 0 = fp32 chunks (1536 B), 1 = byte chunks (768 B; four of them in flight behind the one being reduced instead of two).
-template <int Q, int VT = 0>
+template <int Q, int VT = VT_F32>
 __global__ void __launch_bounds__(576, Q >= 8 ? 4 : 6) multi_kernel(const StreamParams P0, const SelectParams SP0, const MultiParams M) {
     // (byte chunks: four in flight behind the one being reduced; one query per pass -- BASELINE configs[4] -- seven: 19.0 against 19.6 us
     //  per query, while 4 queries per pass lose 1 % by it and ten or more chunks spill: 89 us)
-    constexpr int C = 4, NBUF = (VT == 1 || VT == 5) ? (Q == 1 ? 8 : TKSPMV_SELL_BYTE_NBUF) : 3, DEFER_S = MultiGeom<Q>::HOLD;
-    constexpr bool BYTES = VT == 1 || VT == 5;  // VT 5: byte values with 12-bit column words (640-byte chunks, padding slots 1022 / 1023)
-    constexpr uint32_t PAD_NEUTRAL = VT == 5 ? 1022u : SELL_PAD_NEUTRAL, PAD_ONE = VT == 5 ? 1023u : SELL_PAD_ONE;
+    constexpr int C = 4, NBUF = (VT == VT_Q17 || VT == VT_Q17C12) ? (Q == 1 ? 8 : TKSPMV_SELL_BYTE_NBUF) : 3, DEFER_S = MultiGeom<Q>::HOLD;
+    constexpr bool BYTES = VT == VT_Q17 || VT == VT_Q17C12;  // VT_Q17C12: byte values with 12-bit column words (640-byte chunks, padding slots 1022 / 1023)
+    constexpr uint32_t PAD_NEUTRAL = VT == VT_Q17C12 ? 1022u : SELL_PAD_NEUTRAL, PAD_ONE = VT == VT_Q17C12 ? 1023u : SELL_PAD_ONE;
     constexpr uint32_t MULTI_WAVE_CAP = MultiGeom<Q>::WAVE_CAP;
     __shared__ MultiLds<Q> L;
     const uint32_t tid0 = threadIdx.x;
@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(576, Q >= 8 ? 4 : 6) multi_kernel(const Stream
             // bits. 16-bit words: two dwords of two. 12-bit words: 48 bits of the two dwords loaded, from bit 0 on even lanes and from
             // bit 16 on odd ones -- taken apart straight into offsets (9 instructions; via an intermediate pair of 16-bit words: 15).
             uint32_t off[C], fw[C];
-            if (VT == 5) {
+            if (VT == VT_Q17C12) {
                 const uint32_t odd16 = (threadIdx.x & 1u) << 4;
                 const uint32_t lo = __builtin_amdgcn_alignbit(cur.cw[1], cur.cw[0], odd16), hi = cur.cw[1] >> odd16;
                 const uint32_t mid = __builtin_amdgcn_alignbit(hi, lo, 24);

@@ -301,7 +301,7 @@ __device__ __forceinline__ void split_ab(const uint32_t d0, const uint32_t d1, u
 template <int C, int QM>
 __device__ __forceinline__ uint32_t packet_flags(const Pkt<C, value_type_of(QM)> &cur) {
     constexpr int VT = value_type_of(QM);
-    if (VT == 4) {  // split 12-bit plane: ROW_END 0-3 at bits 12-15 of the halfword, SKIP 0, 1 in the dword, 2, 3 in the halfword
+    if (VT == VT_F32C12) {  // split 12-bit plane: ROW_END 0-3 at bits 12-15 of the halfword, SKIP 0, 1 in the dword, 2, 3 in the halfword
         uint32_t A, B;
         split_ab(cur.cw[0], cur.cw[1], A, B);
         return (B >> 12) | ((A & 3u) << 8) | ((B & 3u) << 10);
@@ -309,7 +309,7 @@ __device__ __forceinline__ uint32_t packet_flags(const Pkt<C, value_type_of(QM)>
     uint32_t fl = 0u;
 #pragma unroll
     for (int j = 0; j < C; ++j) {
-        const uint32_t w = (VT == 3 || VT == 6) ? __float_as_uint(cur.v[(VT == 3 || VT == 6) ? j : 0]) : (cur.cw[j >> 1] >> (16 * (j & 1)));
+        const uint32_t w = (VT == VT_FIXED20 || VT == VT_FIXED26) ? __float_as_uint(cur.v[(VT == VT_FIXED20 || VT == VT_FIXED26) ? j : 0]) : (cur.cw[j >> 1] >> (16 * (j & 1)));
         fl |= ((w & 1u) << j) | (((w >> 1) & 1u) << (8 + j));
     }
     return fl;
@@ -322,14 +322,14 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
     constexpr int VT = value_type_of(QM);
     float p[C];
     uint32_t m[C];
-    if (QM == 6) {
+    if (QM == QM_FIXED20) {
         // Bit-packed fixed point: word = value (bits 31..12, the top 20 bits of its Q1.31 word) | column << 2 | flags. x is
         // staged as a 20-bit integer (Q1.19); both factors fit the full-rate 24-bit multipliers; the 40-bit product is
         // Q2.38, of which bits 38..7 are the product in Q1.31 (integer part wrapped to one bit), masked to the width.
         uint32_t any = 0u;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
-            const uint32_t w = __float_as_uint(cur.v[VT == 3 ? j : 0]);
+            const uint32_t w = __float_as_uint(cur.v[VT == VT_FIXED20 ? j : 0]);
             const uint32_t xq = lds_u32(xbase + (w & 0xFFCu));
             uint32_t v20, hi;
             asm("v_bfe_u32 %0, %1, 12, 20" : "=v"(v20) : "v"(w));
@@ -340,16 +340,16 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
         }
         return reduce_core<C, true>(p, m, (any & 1u) != 0u, carry);
     }
-    if (QM == 8) {
+    if (QM == QM_FIXED26) {
         // Five bytes per entry (wbscsr.hpp FIXED26): D_j = value (bits 31..6) | column bits 3..0 << 2 | flags, E = column bits 9..4
-        // of entry j at bits 6 j. The arithmetic is QM 4's: Q1.31 words, 24-bit multipliers up to 24 bits (x staged shifted down
+        // of entry j at bits 6 j. The arithmetic is QM_FIXED's: Q1.31 words, 24-bit multipliers up to 24 bits (x staged shifted down
         // by 8), quarter-rate 32-bit multiplies for 25 and 26.
-        static_assert(QM != 8 || C == 4, "FIXED26 is built for 4 entries per lane");
+        static_assert(QM != QM_FIXED26 || C == 4, "FIXED26 is built for 4 entries per lane");
         uint32_t any = 0u;
         const uint32_t E = cur.cw[0];
 #pragma unroll
         for (int j = 0; j < C; ++j) {
-            const uint32_t w = __float_as_uint(cur.v[VT == 6 ? j : 0]);
+            const uint32_t w = __float_as_uint(cur.v[VT == VT_FIXED26 ? j : 0]);
             uint32_t hi6;
             asm("v_bfe_u32 %0, %1, %2, 6" : "=v"(hi6) : "v"(E), "n"(6 * j));
             const uint32_t xq = lds_u32(xbase + ((w & 0x3Cu) | (hi6 << 6)));
@@ -367,22 +367,22 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
         }
         return reduce_core<C, true>(p, m, (any & 1u) != 0u, carry);
     }
-    if (QM == 7) {
+    if (QM == QM_F32C12) {
         // fp32 values, split 12-bit plane: A = col0 << 2 | col1 << 12 | col2 << 22 | SKIP0 | SKIP1 << 1,
         // B = col3 << 2 | SKIP2 | SKIP3 << 1 | ROW_END0..3 << 12. One instruction per LDS address where the field sits at
         // bit 2 (mask + base of the x copy), two where it has to be shifted down first; the row-end masks are single bit
         // extractions of B, and "this lane holds a row end" is one compare.
-        static_assert(QM != 7 || C == 4, "the split 12-bit plane is built for 4 entries per lane");
+        static_assert(QM != QM_F32C12 || C == 4, "the split 12-bit plane is built for 4 entries per lane");
         uint32_t mask = 0xFFCu;
         asm("" : "+v"(mask));  // (kept in a register: v_and_or_b32 takes no literal)
         uint32_t A, B;
-        split_ab(cur.cw[0], cur.cw[VT == 4 ? 1 : 0], A, B);
+        split_ab(cur.cw[0], cur.cw[VT == VT_F32C12 ? 1 : 0], A, B);
         const uint32_t a0 = and_or(A, mask, xbase), a1 = and_or(A >> 10, mask, xbase), a2 = and_or(A >> 20, mask, xbase),
                        a3 = and_or(B, mask, xbase);
-        p[0] = __fmul_rn(cur.v[VT == 4 ? 0 : 0], lds_f32(a0));
-        p[C > 1 ? 1 : 0] = __fmul_rn(cur.v[VT == 4 ? 1 : 0], lds_f32(a1));
-        p[C > 2 ? 2 : 0] = __fmul_rn(cur.v[VT == 4 ? 2 : 0], lds_f32(a2));
-        p[C > 3 ? 3 : 0] = __fmul_rn(cur.v[VT == 4 ? 3 : 0], lds_f32(a3));
+        p[0] = __fmul_rn(cur.v[VT == VT_F32C12 ? 0 : 0], lds_f32(a0));
+        p[C > 1 ? 1 : 0] = __fmul_rn(cur.v[VT == VT_F32C12 ? 1 : 0], lds_f32(a1));
+        p[C > 2 ? 2 : 0] = __fmul_rn(cur.v[VT == VT_F32C12 ? 2 : 0], lds_f32(a2));
+        p[C > 3 ? 3 : 0] = __fmul_rn(cur.v[VT == VT_F32C12 ? 3 : 0], lds_f32(a3));
         m[0] = bit_mask<12>(B);
         m[C > 1 ? 1 : 0] = bit_mask<13>(B);
         m[C > 2 ? 2 : 0] = bit_mask<14>(B);
@@ -396,25 +396,25 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
         const uint32_t off = xbase + ((j & 1) ? ((word >> 16) & 0xFFFCu) : (word & 0xFFFCu));  // LDS byte address of x[col]
         m[j] = (j & 1) ? bit_mask<16>(word) : bit_mask<0>(word);
         if ((j & 1) == 0) any |= word;
-        if (QM == 5) {
+        if (QM == QM_Q17_F32) {
             // x is staged as fp32 scaled by 2^-7: byte * (x / 128), one conversion and one multiply per entry
-            p[j] = __fmul_rn(ubyte_to_float(cur.vq[VT == 1 ? (j >> 2) : 0], j & 3), lds_f32(off));
-        } else if (VT == 1) {
+            p[j] = __fmul_rn(ubyte_to_float(cur.vq[VT == VT_Q17 ? (j >> 2) : 0], j & 3), lds_f32(off));
+        } else if (VT == VT_Q17) {
             // x is staged as Q1.7 integers; product truncated to Q1.7 and wrapped to 8 bits, exact in fp32
             const uint32_t xq = lds_u32(off);
-            const uint32_t vq = (cur.vq[VT == 1 ? (j >> 2) : 0] >> (8 * (j & 3))) & 255u;
+            const uint32_t vq = (cur.vq[VT == VT_Q17 ? (j >> 2) : 0] >> (8 * (j & 3))) & 255u;
             // both factors are below 2^8: the 24-bit multiply is exact (and full rate; v_mul_lo_u32 is quarter rate)
             const uint32_t t = __umul24(vq, xq);
-            p[j] = (float)(QM == 2 ? (t >> 7) : ((t >> 7) & 255u));  // wide mode: no wrap
-        } else if (VT == 2) {
-            const uint32_t hw = cur.vq[VT == 2 ? (j >> 1) : 0];
+            p[j] = (float)(QM == QM_Q17_WIDE ? (t >> 7) : ((t >> 7) & 255u));  // wide mode: no wrap
+        } else if (VT == VT_F16) {
+            const uint32_t hw = cur.vq[VT == VT_F16 ? (j >> 1) : 0];
             const _Float16 hv = __builtin_bit_cast(_Float16, (uint16_t)((j & 1) ? (hw >> 16) : (hw & 0xFFFFu)));
             p[j] = __fmul_rn((float)hv, lds_f32(off));  // the conversion is exact
-        } else if (QM == 4) {
+        } else if (QM == QM_FIXED) {
             // both factors are Q1.31 words: the 64-bit product is Q2.62; bits 31..62 are the product in Q1.31 (its integer
             // part wrapped to one bit, like an assignment to real_type), masked down to the W-1 fraction bits kept
             const uint32_t xq = lds_u32(off);
-            const uint32_t vq = __float_as_uint(cur.v[VT == 0 ? j : 0]);
+            const uint32_t vq = __float_as_uint(cur.v[VT == VT_F32 ? j : 0]);
             if (fixed_mask & 0xFFu) {
                 p[j] = __uint_as_float(__builtin_amdgcn_alignbit(__umulhi(vq, xq), vq * xq, 31) & fixed_mask);
             } else {
@@ -427,18 +427,18 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
                 p[j] = __uint_as_float(__builtin_amdgcn_alignbit(hi, __umul24(v24, xq), 15) & fixed_mask);
             }
         } else {
-            p[j] = __fmul_rn(cur.v[VT == 0 ? j : 0], lds_f32(off));
+            p[j] = __fmul_rn(cur.v[VT == VT_F32 ? j : 0], lds_f32(off));
         }
     }
     // (`any` holds every column word of the lane: the odd entries' flags sit at bit 16 of the same words)
-    return reduce_core<C, QM == 4>(p, m, (any & 0x00010001u) != 0u, carry);  // (QM 6 returned above)
+    return reduce_core<C, QM == QM_FIXED>(p, m, (any & 0x00010001u) != 0u, carry);  // (QM_FIXED20 returned above)
 }
 template <int QM>
-constexpr bool int_sums() { return QM == 4 || QM == 6 || QM == 8; }
+constexpr bool int_sums() { return QM == QM_FIXED || QM == QM_FIXED20 || QM == QM_FIXED26; }
 
 template <int C, int QM>
 __device__ __forceinline__ float row_score(const RowSums<C> &R, int j) {  // strict Q1.7: the 8-bit wrap of the row sum
-    return QM == 1 ? q17_wrap(R.rs[j]) : R.rs[j];
+    return QM == QM_Q17 ? q17_wrap(R.rs[j]) : R.rs[j];
 }
 template <int C, int QM>
 __device__ __forceinline__ float lane_best(const RowSums<C> &R) {  // placeholders excluded

@@ -45,7 +45,7 @@ struct RangeLds {
 
 template <int C, int XCOLS, int QM, bool FILT, int NBUF>
 __global__ void __launch_bounds__(512, 4) range_kernel(const StreamParams P, const RangeParams R) {
-    static_assert((QM == 0 || QM == 7) && (C == 4 || C == 8), "range_kernel: fp32 packet streams of 4 or 8 entries per lane");
+    static_assert((QM == QM_F32 || QM == QM_F32C12) && (C == 4 || C == 8), "range_kernel: fp32 packet streams of 4 or 8 entries per lane");
     constexpr int VT = value_type_of(QM);
     constexpr bool BUF = C == 4;  // buffer loads (load_packet_buf) where they exist
     constexpr uint32_t WAVE_CAP = ListGeom<XCOLS>::WAVE_CAP;

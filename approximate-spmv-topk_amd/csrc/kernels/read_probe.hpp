@@ -124,17 +124,17 @@ __global__ void __launch_bounds__(1024) read_probe_kernel(const ReadProbeParams 
             const uint8_t *pk = base + (size_t)first * PB;
             if (WORK < 0) {  // the engine's own per-packet arithmetic (x gathers from LDS, products, segmented scan) on a ring of DEPTH
                 if constexpr (BPL == 24) {
-                    Pkt<4, 0> buf[DEPTH];
+                    Pkt<4, VT_F32> buf[DEPTH];
 #pragma unroll
-                    for (int j = 0; j < DEPTH - 1; ++j) load_packet<4, 0>(pk + (size_t)((uint32_t)j < count ? j : count - 1u) * PB, lane, buf[j]);
+                    for (int j = 0; j < DEPTH - 1; ++j) load_packet<4, VT_F32>(pk + (size_t)((uint32_t)j < count ? j : count - 1u) * PB, lane, buf[j]);
                     float carry = 0.0f, best = 0.0f;
                     for (uint32_t i = 0; i < count; i += DEPTH) {
 #pragma unroll
                         for (int j = 0; j < DEPTH; ++j) {
                             const uint32_t nxt = i + j + DEPTH - 1;
-                            load_packet<4, 0>(pk + (size_t)(nxt < count ? nxt : count - 1u) * PB, lane, buf[(j + DEPTH - 1) % DEPTH]);
+                            load_packet<4, VT_F32>(pk + (size_t)(nxt < count ? nxt : count - 1u) * PB, lane, buf[(j + DEPTH - 1) % DEPTH]);
                             if (i + j < count) {
-                                const Reduced<4> S = reduce_packet<4, 0>(buf[j], carry, lds_addr_of(xl), 0u);
+                                const Reduced<4> S = reduce_packet<4, QM_F32>(buf[j], carry, lds_addr_of(xl), 0u);
                                 const float trig = trigger_of<4, false>(S);
                                 if (WORK == -1) best = fmaxf(best, trig);
                                 else if (__any(trig >= 1e30f)) best += S.S;  // WORK == -2: the hot-path trigger as the engine has it

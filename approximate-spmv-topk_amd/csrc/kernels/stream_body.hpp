@@ -8,14 +8,14 @@
     unsigned long long *const dbg_trace = DBG ? P.trace : nullptr;
     unsigned long long *const dbg_stamps = DBG ? P.stamps : nullptr;
     unsigned long long *const dbg_counters = DBG ? P.dbg : nullptr;
-    constexpr bool Q8 = QM == 1 || QM == 2;  // x staged as Q1.7 integers
+    constexpr bool Q8 = QM == QM_Q17 || QM == QM_Q17_WIDE;  // x staged as Q1.7 integers
     constexpr int VT = value_type_of(QM);
     constexpr bool INT = int_sums<QM>();
     // Deferred packets live in registers (C row sums + C / 2 flag words each): with 8 entries per lane one packet is held,
     // not three -- the same number of rows as two 4-entry packets, and the kernel stays at 80 registers (two workgroups
     // per CU; with three it needed 96 and a single query took 57 us instead of 36).
     // (at most 1024 columns: two -- the third would push the 16-bit layouts past 80 registers; the 12-bit layout keeps one)
-    constexpr int DEFER_C = (C == 8 || QM == 7) ? 1 : (XCOLS <= 1024 ? DEFER : DEFER + 1);
+    constexpr int DEFER_C = (C == 8 || QM == QM_F32C12) ? 1 : (XCOLS <= 1024 ? DEFER : DEFER + 1);
     __shared__ StreamLds<XCOLS> L;
     // (reduce_packet forms LDS addresses of x as (word & 0xFFC) | base: x must sit on a 4 KiB boundary -- this object is the
     //  kernel's ONLY __shared__ block, so it starts at LDS address 0, and x is its first member)
@@ -102,7 +102,7 @@
     if (tid < MISC_WORDS) misc[tid] = 0u;
     float x_scale = 1.0f;    // applied to x before quantisation (2^s)
     float unit_scale = 1.0f; // units per 1.0 of score
-    if (QM == 2) {
+    if (QM == QM_Q17_WIDE) {
         __syncthreads();
         float lm = 0.0f;
         for (uint32_t i = tid; i < P.cols; i += blockDim.x) lm = fmaxf(lm, P.x[i]);
@@ -118,9 +118,9 @@
         }
         x_scale = (float)(1u << sh);
         unit_scale = 128.0f * x_scale;
-    } else if (QM == 1) {
+    } else if (QM == QM_Q17) {
         unit_scale = 128.0f;
-    } else if (QM == 4 || QM == 6 || QM == 8) {
+    } else if (QM == QM_FIXED || QM == QM_FIXED20 || QM == QM_FIXED26) {
         unit_scale = 2147483648.0f;  // scores are Q1.31 words converted to fp32
     }
     const float inv_unit = 1.0f / unit_scale;             // exact: unit_scale is a power of two
@@ -130,12 +130,12 @@
         const float xv = (i < P.cols) ? xw : 0.0f;
         if (Q8)
             reinterpret_cast<uint32_t *>(x_lds)[i] = to_q1_7_dev(xv * x_scale);  // x quantised like the matrix values
-        else if (QM == 6)  // bit-packed narrow fixed point: x as a 20-bit integer
+        else if (QM == QM_FIXED20)  // bit-packed narrow fixed point: x as a 20-bit integer
             reinterpret_cast<uint32_t *>(x_lds)[i] = to_fixed_dev(xv, P.fixed_width) >> 12;
-        else if (QM == 4 || QM == 8)  // W <= 24: as a 24-bit integer (see reduce_packet)
+        else if (QM == QM_FIXED || QM == QM_FIXED26)  // W <= 24: as a 24-bit integer (see reduce_packet)
             reinterpret_cast<uint32_t *>(x_lds)[i] = to_fixed_dev(xv, P.fixed_width) >> (P.fixed_width <= 24u ? 8 : 0);
         else
-            x_lds[i] = QM == 5 ? xv * Q17_UNIT : xv;
+            x_lds[i] = QM == QM_Q17_F32 ? xv * Q17_UNIT : xv;
     }
     if (tid == 0) misc[MISC_TAU] = __float_as_uint(min_units);
     __syncthreads();

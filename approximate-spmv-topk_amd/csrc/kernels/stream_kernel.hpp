@@ -41,8 +41,8 @@ struct StreamLds {
 #define TKSPMV_NBUF 3
 #endif
 // DBG = false (production): tracing / statistics / ablation hooks compiled out (see batch_kernel).
-template <int C, bool SCORES, int XCOLS, int QM = 0, int NBUF = TKSPMV_NBUF, bool DBG = false>
-__global__ void __launch_bounds__(576, ((C == 8 && !SCORES) || QM == 7) ? 6 : 5) stream_kernel(const StreamParams P, const SelectParams SP) {
+template <int C, bool SCORES, int XCOLS, int QM = QM_F32, int NBUF = TKSPMV_NBUF, bool DBG = false>
+__global__ void __launch_bounds__(576, ((C == 8 && !SCORES) || QM == QM_F32C12) ? 6 : 5) stream_kernel(const StreamParams P, const SelectParams SP) {
     constexpr bool FILT = false;  // (every use of F below is compiled out)
     const FilterParams F{};
 #include "stream_body.hpp"
@@ -52,8 +52,8 @@ __global__ void __launch_bounds__(576, ((C == 8 && !SCORES) || QM == 7) ? 6 : 5)
 // right after expand(), like placeholders of empty rows, so neither a candidate list nor a published group maximum ever holds
 // one (the threshold stays a lower bound of the k-th ELIGIBLE score); the SpMV-only variant writes -inf for them. The mask words
 // of a packet's first rows are scalar loads issued one packet ahead (mask_pair): lgkmcnt, never the packet loads' vmcnt.
-template <int C, bool SCORES, int XCOLS, int QM = 0, int NBUF = TKSPMV_NBUF>
-__global__ void __launch_bounds__(576, ((C == 8 && !SCORES) || QM == 7) ? 6 : 5)
+template <int C, bool SCORES, int XCOLS, int QM = QM_F32, int NBUF = TKSPMV_NBUF>
+__global__ void __launch_bounds__(576, ((C == 8 && !SCORES) || QM == QM_F32C12) ? 6 : 5)
     stream_filter_kernel(const StreamParams P, const SelectParams SP, const FilterParams F) {
     constexpr bool FILT = true;
     constexpr bool DBG = false;

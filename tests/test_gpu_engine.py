@@ -366,7 +366,7 @@ def test_reference_side_host_program(pkg):
 
 # ---- BASELINE configs[4]: Q1.7 fixed-point values ("FIXED_WIDTH-style" reduced precision) ----------------------------
 @pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (60000, 512, 40, 100, 2),
-                                                  (20000, 1024, 20, 8, 3), (5000, 3000, 30, 50, 4)])
+                                                  (20000, 1024, 20, 8, 3), (5000, 3000, 30, 50, 4), (5000, 6000, 30, 50, 5)])
 def test_q1_7_bit_exact_against_integer_model(pkg, oracle, rows, cols, nnz, k, seed):
     m = pkg.generate_matrix(rows, cols, nnz, "gamma", seed)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, precision=pkg.Q1_7)
@@ -426,7 +426,8 @@ def test_q1_7_full_size_config(pkg, oracle):
 
 # ---- TKSPMV_FIXED: the FPGA's real_type for any FIXED_WIDTH (reference builds: 20/21/25/26/32 bits) --------------------
 @pytest.mark.parametrize("width", [8, 20, 21, 25, 26, 32])
-@pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (60000, 1024, 20, 100, 2), (5000, 3000, 30, 50, 4)])
+@pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (60000, 1024, 20, 100, 2), (5000, 3000, 30, 50, 4),
+                                                  (5000, 6000, 30, 50, 5)])
 def test_fixed_point_bit_exact_against_integer_model(pkg, oracle, width, rows, cols, nnz, k, seed):
     """Scores of every row and the top-k, bit for bit against the W-bit integer model (oracle_fixed_scores: plain
     right-aligned integers and 64-bit products; the kernel works on left-aligned Q1.31 words)."""
@@ -584,7 +585,7 @@ def test_fixed_point_batch_equals_single_queries(pkg):
 
 
 @pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (60000, 512, 40, 100, 2),
-                                                  (20000, 1024, 20, 8, 3), (5000, 3000, 30, 50, 4)])
+                                                  (20000, 1024, 20, 8, 3), (5000, 3000, 30, 50, 4), (5000, 6000, 30, 50, 5)])
 def test_q1_7_wide_bit_exact_against_integer_model(pkg, oracle, rows, cols, nnz, k, seed):
     m = pkg.generate_matrix(rows, cols, nnz, "gamma", seed)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, precision=pkg.Q1_7_WIDE)
@@ -1228,7 +1229,8 @@ def test_three_million_rows(pkg, oracle):
 
 
 # ---- TKSPMV_F16: fp16 values, fp32 x and arithmetic (the CUDA comparator's -a mode) -----------------------------------
-@pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (120000, 1024, 20, 100, 2), (20000, 3000, 30, 8, 3)])
+@pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (120000, 1024, 20, 100, 2), (20000, 3000, 30, 8, 3),
+                                                  (5000, 6000, 30, 50, 5)])
 def test_f16_values_bit_exact_against_the_half_model(pkg, oracle, rows, cols, nnz, k, seed):
     """Bit-exact against the order-matched oracle reading the same 2-byte value stream; and, against the fp32 gold,
     the ranking quality the reference reports for its half mode: high precision@K, scores within fp16 rounding."""

@@ -27,7 +27,7 @@ def _packed_expect(pkg, oracle, m, x, k, eng, min_score=0.0):
 
 
 @pytest.mark.parametrize("rows,cols,nnz,k,seed", [(3000, 512, 40, 100, 1), (60000, 512, 40, 100, 2), (20000, 1024, 20, 8, 3),
-                                                  (5000, 3000, 30, 50, 4)])
+                                                  (5000, 3000, 30, 50, 4), (5000, 6000, 30, 50, 5)])
 def test_bit_exact_against_the_order_matched_oracle(pkg, oracle, rows, cols, nnz, k, seed):
     import torch
     m = pkg.generate_matrix(rows, cols, nnz, "gamma", seed)
