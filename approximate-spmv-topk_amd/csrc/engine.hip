@@ -93,13 +93,15 @@ static hipError_t malloc_exchange(void **p, size_t bytes) {
 enum class Mem { Device, Exchange, Pinned };  // EngineImpl::alloc: hipMalloc, malloc_exchange, hipHostMalloc (mapped)
 
 // The kernels of one engine, chosen once (choose_kernels, at creation) by the format of its packet stream. NULL: the family has no
-// kernel for this format. multi_kernel and read_probe_kernel are keyed on other things and keep their own tables.
+// kernel for this format. multi_kernel is keyed on the ELL copy's value type and the queries per pass (choose_kernels too);
+// read_probe_kernel keeps its own table: its option is read per call.
 typedef void (*stream_fn)(const StreamParams, const SelectParams);
 typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
 typedef void (*range_fn)(const StreamParams, const RangeParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
+typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
 struct Kernels {
     stream_fn stream[2] = {};  // [SCORES]; [0] is the tracing twin on an engine that traces
     filter_fn filter[2] = {};  // [SCORES]
@@ -107,6 +109,7 @@ struct Kernels {
     row_vectors_fn row_vectors = nullptr;
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
+    multi_fn multi = nullptr;  // multi-query engines only
 };
 // The instantiations of ONE format, every family restricted to the formats it is built for (the predicates of stream_format.hpp).
 template <int C, int XCOLS, int QM>
@@ -145,6 +148,16 @@ static Kernels kernels_for(StreamFormat f, bool dbg) {
     return Kernels{};
 }
 
+// The waves keep a timetable in 32 bits of ticks (10 ns) << 8, 168 ms to the wrap: a period of ns per query in those units ...
+static uint32_t period_units(uint64_t ns) { return (uint32_t)std::min<uint64_t>(0xFFFFFF00ull, ns * 256u / 10u); }
+// ... and whether a launch of n queries could last a quarter of the wrap (32 queries of 1.3 ms: 80M rows). Such a launch keeps no
+// timetable (the batch kernel paces by rank instead).
+static bool outlasts_timetable(uint32_t period_ns, int n) { return (uint64_t)period_ns * (uint64_t)n > 40000000ull; }
+
+// One engine. What the whole engine shares comes first: the descriptor, the packed matrix's host-side tables, the device, the
+// record of its buffers, its stream and events, the launch geometry, the stream format and its kernels. Everything else belongs to
+// ONE launch path and sits in that path's group below; each group says which creation stage (create_impl) fills it and who changes
+// it afterwards. The launch methods follow the groups: a method that is const changes nothing.
 struct EngineImpl {
     tkspmv_desc desc{};
     PackedMatrix pm;  // host copy is dropped after upload (only the small tables are kept)
@@ -177,250 +190,304 @@ struct EngineImpl {
         owned.erase(it);
     }
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    // device buffers
-    uint8_t *d_packets = nullptr;
-    std::vector<uint8_t *> d_replicas;  // extra copies of the packet stream (cache-defeat mode)
-    mutable uint64_t launch_counter = 0;
-    uint32_t *d_pkt_row = nullptr, *d_part_first = nullptr, *d_part_count = nullptr;
-    float *d_x = nullptr;
-    const float *d_x_cur = nullptr;
-    // Low-latency host boundary of the reference loop (reset -> operator() -> read_result, host_spmv_bscsr.cpp:602-632):
-    // set_query copies x into pinned host memory and enqueues the 4 KiB upload without waiting for it; run() launches the
-    // fused kernel, whose selection tail also writes the k results and an epoch flag to pinned host memory, and polls that
-    // flag; read() copies from the pinned block. No stream synchronisation, no device-to-host copy on the critical path.
-    float *h_x = nullptr;            // pinned staging copy of x
-    uint32_t *h_res = nullptr;       // pinned: [k] row ids, [k] score bits, [2k] epoch flag
-    uint32_t *h_res_dev = nullptr;   // the same block as the device sees it
-    mutable uint32_t host_epoch = 0;
-    mutable bool last_on_host = false;  // the most recent result is complete in h_res
-    bool x_pending = false;             // an upload from h_x may still be in flight
-    // Large BAR (every MI355X server has it; checked at create): tkspmv_set_query writes x into device memory with plain CPU stores
-    // through the PCIe aperture -- 0.5 us for 4 KiB, no copy kernel ahead of the query's launch (that copy, 3-10 us of device time
-    // plus a dispatch, stood between set_query and every tkspmv_run). Posted writes stay ordered with the launch's doorbell.
-    bool bar_x = false;
-    // CPU stores through the BAR pass the host data path (HDP) on their way to memory: the documented protocol ends them with a
-    // write to the device's HDP_MEM_COHERENCY_FLUSH_CNTL register and a read back of it (what ROCclr does behind its own large-BAR
-    // copies); the register's address comes from hipDeviceAttributeHdpMemFlushCntl. No address, no BAR path.
-    volatile uint32_t *hdp_flush = nullptr;
-    void flush_hdp() const {
-        __builtin_ia32_sfence();
-        *hdp_flush = 1u;
-        (void)*hdp_flush;  // (the read completes only behind the posted writes before it)
-    }
-    int host_path = 1;                  // TKSPMV_HOST_PATH=0: the plain path (stream synchronisation + copies)
-    float *h_x_dev = nullptr;           // h_x as the device sees it (TKSPMV_HOST_X=direct: kernels read x from host memory)
-    bool host_x_direct = false;
-    bool run_events = false;            // TKSPMV_RUN_EVENTS=1: tkspmv_run brackets the fused launch with a hipEvent pair instead of taking the kernel's own duration
-    unsigned long long *d_tstart = nullptr;  // the fused launch's start stamp (SelectParams::t_start)
-    // Exchange state of one query in flight (published maxima, threshold word, survivor slots, overflow list).
-    // Two sets: with deferred selection, launch q+1 streams into one set while its workgroup 0 selects query q from
-    // the other. Everything else uses set 0.
-    struct ExState {
-        uint32_t *tau_g = nullptr, *gmax = nullptr, *ovf_count = nullptr;
-        unsigned long long *wg_cand = nullptr, *ovf = nullptr;
-        float *unit_inv = nullptr;
-    };
-    static constexpr int N_STATE = BATCH_MAX;  // deferred selection uses sets 0/1, the batch kernel one per query
-    static constexpr uint32_t GMAX_WORDS = MAX_GM * 64, STATE_WORD_STRIDE = 64;  // set-to-set distances (elements)
-    ExState st[N_STATE];
-    mutable int cur_set = 0;                  // set the next deferred launch streams into
-    mutable bool pending = false;             // a deferred selection is owed for ...
-    mutable int pending_set = 0;              // ... this set, into ...
-    mutable uint32_t *pending_idx = nullptr;  // ... these result buffers
-    mutable float *pending_val = nullptr;
-    uint32_t *d_out_idx = nullptr;
-    uint32_t *d_alias_idx = nullptr;  // [BATCH_MAX][k] where the earlier queries of a launch write when they share the last one's buffer
-    float *d_alias_val = nullptr;
-    uint32_t *d_done = nullptr;
-    bool fused = true;
-    bool can_defer = false;
-    bool can_batch = false;         // batch kernel usable (exchange on, x double-buffered in LDS: is_batchable)
-    // Queries per launch of the batch kernel = exchange-state sets allocated. Every set carries an overflow list that must be
-    // able to hold EVERY row (a degenerate query -- x = 0, all scores equal -- makes every row a candidate, and the result
-    // must still be exact), 8 B per row: 256 MB at 1M rows, 2.6 GB at 10M rows -- under 1 % of this GPU's 288 GB either way;
-    // 32 sets up to 64M rows, fewer beyond (the lists stay within 16 GiB).
-    int batch_max = BATCH_MAX;
-    // Multi-query passes (multi_kernel, desc.multi_q): fp32 values, <= 1024 columns, exchange on. multi_q queries share one
-    // pass over the wave-sliced ELL copy of the matrix (wsell.hpp); a group's selection is owed to the next launch (or to
-    // drain()). Groups alternate between the exchange-state sets [0, MULTI_Q_MAX) and [MULTI_Q_MAX, 2 * MULTI_Q_MAX).
-    bool can_multi = false;
-    int multi_q = 0;
-    // queries per multi-query LAUNCH (= its selector workgroups): multi_q, or with one query per pass up to MULTI_Q_MAX passes
-    int multi_group = 0;
-    // Large k (see radix_hist_kernel): every query = scores kernel + radix select + the selection kernel
-    bool use_radix = false;
-    bool approx_parts = false;    // partitions > 1 with k > k_per_partition: the reference's lossy per-partition lists
-    float *d_rscores = nullptr;   // [rows], -inf where a row has no entry (never written by the scores kernel)
-    uint32_t *d_rhist = nullptr;  // [4][256]
-    uint8_t *d_sell_packets = nullptr;
-    std::vector<uint8_t *> d_sell_replicas;
-    uint32_t *d_sell_rows = nullptr, *d_sell_part_first = nullptr, *d_sell_part_count = nullptr, *d_sell_part_slice0 = nullptr;
-    uint32_t sell_parts = 0, multi_stream_waves = 8, sell_packet_bytes = 1536;
-    bool sell_byte_values = false;  // TKSPMV_Q1_7_F32: 768-byte chunks of Q1.7 bytes
-    bool sell_c12 = false;          // ... with 12-bit column words: 640-byte chunks (at most 1022 columns)
-    uint32_t *d_multi_out_idx = nullptr;  // [2 * MULTI_Q_MAX][k] results of tkspmv_time_multi
-    uint64_t multi_stat_queries = 0, multi_waits = 0, multi_wait_ticks = 0, multi_rows_offered = 0, multi_rows_overflowed = 0;  // option STATS, summed over tkspmv_time_multi calls
-    float *d_multi_out_val = nullptr;
-    // Two independent chains of multi-query launches (TKSPMV_MULTI_CHAINS=1 switches the second off): chain c runs on its own
-    // stream with its own exchange-state sets [16c, 16c + 16), so the start-up of one chain's launch fills the tail of the
-    // other's (a launch still selects the previous group of ITS chain). Measured: 6.26 against 7.84 us per query at 4
-    // queries per pass, 5.31 against 5.98 at 8.
-    mutable MultiGroup pending_group[2]{};
-    mutable int multi_parity[2] = {0, 0};
-    int multi_chains = 2;
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    uint32_t *d_tickets = nullptr;  // [BATCH_MAX] x 32 words
-    // checked local thresholds of the batch kernel (BatchParams): the launches' verdict words (two, by launch parity), the workgroups'
-    // records per exchange-state set, the epoch words of the overflow lists' flow control
-    unsigned long long *d_verdict = nullptr;
-    // The host's side of the verdicts (round 5; BatchParams::verdict_host): a ring of host-visible words, one per batch launch on
-    // the engine's own stream, and the launches whose word has not been looked at yet. While the verdicts the host has SEEN are
-    // clean, a local launch goes out alone and settle() -- called wherever the host has just waited for the engine's stream --
-    // repairs what a check flagged after all (an exact launch of the flagged queries, then one more wait). An observed failure
-    // puts the in-stream repair launch back behind the next DISTRUST_LAUNCHES launches (it also keeps the gate's books).
-    // Launches on a caller's stream are never trusted: nobody tells the engine when the caller has waited.
-    static constexpr uint32_t VERDICT_RING = 8192, DISTRUST_LAUNCHES = 64;  // (launches the host may enqueue between two waits and still look at every verdict)
-    unsigned long long *h_verdict = nullptr, *h_verdict_dev = nullptr;
-    struct PendingCheck {
-        BatchArgs A;
-        uint32_t slot;
-        bool trusted;  // no repair launch went out behind it
-    };
-    mutable std::deque<PendingCheck> pending_checks;
-    mutable uint64_t verdict_seq = 0, late_repairs = 0, trusted_launches = 0;
-    mutable uint32_t clean_seen = 0, distrust_left = 0;
-    // Two launches in flight (round 5): a launch of 32 queries pays ~35 us beyond its queries -- 5 us before the first packet is
-    // reduced, the wait for its last workgroup, the last selection, the gap to the next launch -- and an in-order stream pays them
-    // once per launch. Consecutive launches of ONE sequence alternate between the engine's stream and `bside`: the workgroups of the
-    // next launch are dispatched as the CUs of the previous one fall free, its ramp fills the other's tail. Only while launches are
-    // trusted (no exact launch behind them: two of those would share the exchange state); per-launch state (records, tickets,
-    // scale words, scratch results, verdict words) exists once per parity.
-    hipStream_t bside = nullptr;
-    hipEvent_t ev_bfork = nullptr, ev_bjoin = nullptr;
-    bool overlap_launches = false;  // option OVERLAP=1 (measured slower with rank pacing as it is: DESIGN.md section 9)
-    bool repair_by_host = true;  // option REPAIR=stream: the exact launch always follows in the stream (round 4's behaviour)
-    unsigned long long *d_rec_slots = nullptr;  // [batch_max][grid][WG_SLOTS]
-    uint32_t *d_rec_used = nullptr;             // [batch_max][grid]
-    uint32_t *d_ovf_epoch = nullptr;            // [ovf_lists] x 32 words
-    uint32_t ovf_lists = 1;                     // overflow lists allocated (batch engines: 4, or 2 with local thresholds; shared by the queries of a launch under flow control)
-    uint32_t use_local = 0;  // workgroup-local thresholds (BatchParams::local: 0 off, 1 / 2: a wave's best / second best packet maximum)
-    uint32_t single_mode = 0;  // the same choice for ONE query per launch (single_kernel): by the failure estimate alone, whatever the size
-    float *d_wg_prior = nullptr;  // [grid] + the countdown word (BatchParams::wg_prior / prior_block)
-    float *d_wg_sig = nullptr;    // [grid][8] the signatures of the remembered priors and the second prior (BatchParams::wg_sig; option SIGNATURES=0: none)
-    float local_beta = 1.0f;
-    uint32_t pace_tuned_us = 0;  // 0: the pacing is the static default (or an option); else what tkspmv_create's measurement took
-    uint32_t pace_tune_launches = 0;  // ... and the batch launches it made (synthetic queries: a kernel trace of a run holds them)
-    uint32_t pace_quads = 0, pace_levels = 3, pace_base = 0; // pacing by rank (BatchParams::pace_quads, pace_levels, pace_base)
-    unsigned long long *d_wg_times = nullptr;  // option WG_TIMES: BatchParams::wg_times of the LAST batch launch (read through tkspmv_debug_trace)
-    bool pace_carry = true;  // option PACE_CARRY=0: every launch starts unpaced
-    uint32_t *d_wg_pace = nullptr;  // [grid] the pause every workgroup ended its last launch with (BatchParams::wg_pace)
-    // time_queries: the events of its bracket ride on the region's first and last kernel (hipExtLaunchKernelGGL: the dispatch's own
-    // start and end stamps -- what rocprofv3 reports) instead of being recorded around them: a start event recorded on an idle stream
-    // is stamped before the host has written the dispatch packet (1.6 us of host time inside a 350 us bracket, tools/probes/event_probe.cpp)
-    mutable hipEvent_t ext_start = nullptr, ext_stop = nullptr;
-    mutable bool ext_last = false;  // (launch_sequence: the launch_batch being made is the region's last)
-    mutable bool ext_record = false;  // the same two events RECORDED right in front of the first and right behind the last launch (EXT_EVENTS=2)
-    uint32_t *d_pace_adapt = nullptr;  // [0] what launches add to the period, [1] late waves of the launch in flight (BatchParams::pace_adapt)
-    bool pace_adapt_on = true;         // option PACE_ADAPT=0: the period stays what tkspmv_create measured
-    uint32_t pace_period_ns = 0;  // pacing by the clock (BatchParams::pace_period): ns per query of every wave's timetable; 0: pacing by rank
-    mutable uint64_t batch_launches = 0;
-    uint32_t n_sel_wg = 1;   // selector workgroups of a batch launch (BatchParams::n_selectors): 4 on small matrices
-    uint32_t groups_with_rows = 0;  // publishing groups that own at least one wave partition
-    float *d_out_val = nullptr, *d_scores = nullptr;
-    unsigned long long *d_stats = nullptr;
-    uint32_t grid = 0, block = 0, gpw = 1, n_sets = 0, n_groups_pub = 0, cand_cap = 0, ovf_cap = 0, lds_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;  // (ev0, ev1: the brackets of the measurements; ev2: behind the upload of x)
+    uint32_t grid = 0, block = 0;
     StreamFormat fmt{};  // what the kernels of this engine's packet stream are instantiated with (exchange_geometry)
     Kernels kern;        // ... and those kernels (choose_kernels)
-    bool collect_stats = false;
-    // TKSPMV_TRACE / TKSPMV_STATS / TKSPMV_STAMPS / TKSPMV_DBG_FLAGS / TKSPMV_DBG_REPEAT: launch the instantiations that
-    // carry the tracing and ablation hooks (has_tracing_twins; elsewhere the hooks do not exist)
-    bool dbg_kernels = false;
-    bool collect_stamps = false;
-    unsigned long long *d_trace = nullptr;  // TKSPMV_TRACE=1: 4 launches x [grid+1][9][8] stamps
-    size_t trace_words = 0;
-    bool have_query = false;
-    bool ran = false;
-    // single_kernel (kernels/local.hpp): the launch of tkspmv_run on engines that stream with workgroup-local thresholds
-    bool can_single = false;
-    unsigned long long *d_lslots = nullptr;  // [grid][WG_SLOTS] the workgroups' records
-    uint32_t *d_lused = nullptr;             // [grid]
-    float *d_lprior = nullptr;               // [grid] carried thresholds | 32 words: the suspension counters (LocalParams::prior_block)
-    uint32_t *d_lstatus = nullptr;           // [0] 1: the last single launch failed its check
-    uint32_t *d_lready = nullptr;            // [grid] the streaming workgroups' flags (LocalParams::ready; NULL: the last workgroup selects)
-    mutable uint64_t single_launches = 0, single_repairs = 0;
-    uint32_t uni_ppp = 0, uni_last = 0;  // uniform partition table (StreamParams::uni_ppp): partition q = packets [q * uni_ppp, ...)
+
+    // The matrix in HBM: the wave-BSCSR packet stream, its row and partition tables, the stream's extra copies. Filled by
+    // pack_matrix (the device packer's buffers, the uniform table) and upload_matrix; afterwards only launch_counter moves: every
+    // launch method that streams advances it by its queries, so that consecutive queries read consecutive copies.
+    struct Matrix {
+        uint8_t *d_packets = nullptr;
+        std::vector<uint8_t *> d_replicas;  // extra copies of the packet stream (cache-defeat mode)
+        uint64_t launch_counter = 0;
+        uint32_t *d_pkt_row = nullptr, *d_part_first = nullptr, *d_part_count = nullptr;
+        uint32_t uni_ppp = 0, uni_last = 0;  // uniform partition table (StreamParams::uni_ppp): partition q = packets [q * uni_ppp, ...)
+        const uint8_t *packets(uint64_t n) const { return d_replicas.empty() ? d_packets : d_replicas[n % d_replicas.size()]; }  // the copy query n streams
+    } mat;
+
+    // The host boundary of the reference loop (reset -> operator() -> read_result, host_spmv_bscsr.cpp:602-632) and the engine's own
+    // result pair. set_query copies x into pinned host memory and enqueues the 4 KiB upload without waiting for it -- or, with a
+    // large BAR (bar_x; every MI355X server has it, checked at create), writes x into device memory with plain CPU stores through
+    // the PCIe aperture: 0.5 us, no copy kernel ahead of the query's launch --; run() launches the fused kernel, whose selection
+    // tail also writes the k results and an epoch flag to pinned host memory, and polls that flag; read() copies from the pinned
+    // block. No stream synchronisation, no device-to-host copy on the critical path. Filled by setup_host_boundary; changed by
+    // the entry points: set_query* (the installed vector), run (epoch, x_pending) and whatever writes a result pair (ran,
+    // last_on_host).
+    struct HostBoundary {
+        float *d_x = nullptr;
+        const float *d_x_cur = nullptr;
+        float *h_x = nullptr;            // pinned staging copy of x
+        float *h_x_dev = nullptr;        // h_x as the device sees it (TKSPMV_HOST_X=direct: kernels read x from host memory)
+        bool host_x_direct = false;
+        uint32_t *h_res = nullptr;       // pinned: [k] row ids, [k] score bits, [2k] epoch flag
+        uint32_t *h_res_dev = nullptr;   // the same block as the device sees it
+        uint32_t host_epoch = 0;
+        bool last_on_host = false;       // the most recent result is complete in h_res
+        bool x_pending = false;          // an upload from h_x may still be in flight
+        bool bar_x = false;
+        // CPU stores through the BAR pass the host data path (HDP) on their way to memory: the documented protocol ends them with a
+        // write to the device's HDP_MEM_COHERENCY_FLUSH_CNTL register and a read back of it (what ROCclr does behind its own large-BAR
+        // copies); the register's address comes from hipDeviceAttributeHdpMemFlushCntl. No address, no BAR path.
+        volatile uint32_t *hdp_flush = nullptr;
+        void flush_hdp() const {
+            __builtin_ia32_sfence();
+            *hdp_flush = 1u;
+            (void)*hdp_flush;  // (the read completes only behind the posted writes before it)
+        }
+        int host_path = 1;                  // TKSPMV_HOST_PATH=0: the plain path (stream synchronisation + copies)
+        bool run_events = false;            // TKSPMV_RUN_EVENTS=1: tkspmv_run brackets the fused launch with a hipEvent pair instead of taking the kernel's own duration
+        unsigned long long *d_tstart = nullptr;  // the fused launch's start stamp (SelectParams::t_start)
+        bool have_query = false;
+        bool ran = false;
+        uint32_t *d_out_idx = nullptr;      // the engine-owned result pair ("engine buffers, the last query wins")
+        float *d_out_val = nullptr;
+        void result_on_device() {  // an entry point has enqueued queries that write a result pair: tkspmv_read goes to the device
+            ran = true;
+            last_on_host = false;
+        }
+    } host;
+
+    // Exchange state of the queries in flight (published maxima, threshold word, survivor slots, overflow list), one set per
+    // query: with deferred selection, launch q+1 streams into one set while its workgroup 0 selects query q from the other; the
+    // batch kernel runs one set per query of a launch; everything else uses set 0. The geometry comes from exchange_geometry, the
+    // buffers from setup_exchange_sets (d_done: setup_host_boundary); nothing here changes after creation.
+    struct ExchangeSets {
+        struct ExState {
+            uint32_t *tau_g = nullptr, *gmax = nullptr, *ovf_count = nullptr;
+            unsigned long long *wg_cand = nullptr, *ovf = nullptr;
+            float *unit_inv = nullptr;
+        };
+        static constexpr int N_STATE = BATCH_MAX;  // deferred selection uses sets 0/1, the batch kernel one per query
+        static constexpr uint32_t GMAX_WORDS = MAX_GM * 64, STATE_WORD_STRIDE = 64;  // set-to-set distances (elements)
+        ExState st[N_STATE];
+        uint32_t n_sets = 0, gpw = 1, n_groups_pub = 0, cand_cap = 0, lds_bytes = 0;
+        uint32_t groups_with_rows = 0;  // publishing groups that own at least one wave partition
+        uint32_t ovf_cap = 0;
+        uint32_t ovf_lists = 1;         // overflow lists allocated (batch engines: 4, or 2 with local thresholds; shared by the queries of a launch under flow control)
+        uint32_t *d_ovf_epoch = nullptr;  // [ovf_lists] x 32 words: the epoch words of the overflow lists' flow control
+        uint32_t *d_done = nullptr;
+    } ex;
+
+    // One query per launch: the selection fused into the stream kernel's tail, or deferred -- the selection of a back-to-back
+    // query runs inside the NEXT deferred launch (or in drain()). fused / can_defer: choose_path. The rest is the selection still
+    // owed, moved by launch_deferred and settled by drain, launch_multi and whoever launches next.
+    struct Deferred {
+        bool fused = true;
+        bool can_defer = false;
+        int cur_set = 0;                  // set the next deferred launch streams into
+        bool pending = false;             // a deferred selection is owed for ...
+        int pending_set = 0;              // ... this set, into ...
+        uint32_t *pending_idx = nullptr;  // ... these result buffers
+        float *pending_val = nullptr;
+    } defer;
+
+    // Large k (see radix_hist_kernel): every query = scores kernel + radix select + the selection kernel; with partitions > 1 and
+    // k > k_per_partition the reference's lossy per-partition lists instead of the radix select. approx_parts: check_desc; the
+    // rest: choose_path. Unchanged afterwards.
+    struct Radix {
+        bool use_radix = false;
+        bool approx_parts = false;
+        float *d_rscores = nullptr;   // [rows], -inf where a row has no entry (never written by the scores kernel)
+        uint32_t *d_rhist = nullptr;  // [4][256]
+    } radix;
+
+    // Multi-query passes (multi_kernel, desc.multi_q): fp32 values, <= 1024 columns, exchange on. multi_q queries share one pass
+    // over the wave-sliced ELL copy of the matrix (wsell.hpp); a group's selection is owed to the next launch of its chain (or to
+    // drain()). Two independent chains of launches (TKSPMV_MULTI_CHAINS=1 switches the second off): chain c runs on its own
+    // stream with its own exchange-state sets [16c, 16c + 16), its groups alternating between the halves of those, so the start-up
+    // of one chain's launch fills the tail of the other's. Filled by setup_multi; launch_multi moves the owed groups and the
+    // halves, tkspmv_time_multi sums the STATS figures.
+    struct Multi {
+        bool can_multi = false;
+        int multi_q = 0;
+        int multi_group = 0;  // queries per multi-query LAUNCH (= its selector workgroups): multi_q, or with one query per pass up to MULTI_Q_MAX passes
+        uint8_t *d_sell_packets = nullptr;
+        std::vector<uint8_t *> d_sell_replicas;
+        uint32_t *d_sell_rows = nullptr, *d_sell_part_first = nullptr, *d_sell_part_count = nullptr, *d_sell_part_slice0 = nullptr;
+        uint32_t sell_parts = 0, multi_stream_waves = 8, sell_packet_bytes = 1536;
+        MultiGroup pending_group[2]{};  // per chain: the group whose selection is owed
+        int half[2] = {0, 0};           // per chain: the half of its sets the next launch streams into
+        int multi_chains = 2;
+        hipStream_t side = nullptr;     // the second chain's stream
+        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+        uint32_t *d_multi_out_idx = nullptr;  // [2 * MULTI_Q_MAX][k] results of tkspmv_time_multi
+        float *d_multi_out_val = nullptr;
+        uint64_t multi_stat_queries = 0, multi_waits = 0, multi_wait_ticks = 0, multi_rows_offered = 0, multi_rows_overflowed = 0;  // option STATS, summed over tkspmv_time_multi calls
+        const uint8_t *packets(uint64_t n) const { return d_sell_replicas.empty() ? d_sell_packets : d_sell_replicas[n % d_sell_replicas.size()]; }  // the copy pass n streams
+    } multi;
+
+    // Launches of the batch kernel: up to batch_max queries each, one exchange-state set per query. can_batch: choose_path;
+    // n_sel_wg: setup_geometry; tickets: setup_verdicts; batch_max, the workgroups' records and the alias pair:
+    // setup_exchange_sets. batch_args counts the launches. The ext_* words are tkspmv_time_queries' hand-over of its bracket: the
+    // events ride on the region's first and last kernel (hipExtLaunchKernelGGL: the dispatch's own start and end stamps -- what
+    // rocprofv3 reports) instead of being recorded around them; time_queries sets them, launch_sequence marks the last launch,
+    // launch_batch takes them.
+    struct Batch {
+        bool can_batch = false;         // batch kernel usable (exchange on, x double-buffered in LDS: is_batchable)
+        int batch_max = BATCH_MAX;      // queries per launch = exchange-state sets allocated (option BATCH_MAX)
+        uint32_t n_sel_wg = 1;          // selector workgroups of a batch launch (BatchParams::n_selectors): 4 on small matrices
+        uint32_t *d_tickets = nullptr;  // [BATCH_MAX] x 32 words
+        unsigned long long *d_rec_slots = nullptr;  // [BATCH_MAX][grid][WG_SLOTS] the workgroups' records of local mode
+        uint32_t *d_rec_used = nullptr;             // [BATCH_MAX][grid]
+        uint32_t *d_alias_idx = nullptr;  // [BATCH_MAX][k] where the earlier queries of a launch write when they share the last one's buffer
+        float *d_alias_val = nullptr;
+        uint64_t batch_launches = 0;
+        hipEvent_t ext_start = nullptr, ext_stop = nullptr;
+        bool ext_last = false;    // (launch_sequence: the launch_batch being made is the region's last)
+        bool ext_record = false;  // the same two events RECORDED right in front of the first and right behind the last launch (EXT_EVENTS=2)
+    } batch;
+
+    // Who looks at the verdict of a launch of checked local thresholds. The kernel's verdict words, and the host's side of them
+    // (BatchParams::verdict_host): a ring of host-visible words, one per batch launch on the engine's own stream, and the launches
+    // whose word has not been looked at yet. While the verdicts the host has SEEN are clean, a local launch goes out alone and
+    // settle() -- called wherever the host has just waited for the engine's stream -- repairs what a check flagged after all (an
+    // exact launch of the flagged queries, then one more wait). An observed failure puts the in-stream repair launch back behind
+    // the next DISTRUST_LAUNCHES launches (it also keeps the gate's books). Launches on a caller's stream are never trusted: nobody
+    // tells the engine when the caller has waited. Filled by setup_verdicts; launch_batch queues the checks and counts,
+    // settle() looks at them and moves the trust, autotune_pacing resets both.
+    struct Trust {
+        static constexpr uint32_t VERDICT_RING = 8192, DISTRUST_LAUNCHES = 64;  // (launches the host may enqueue between two waits and still look at every verdict)
+        unsigned long long *d_verdict = nullptr;  // four words of 128 bytes: a launch zeroes the word of the launch after the next
+        unsigned long long *h_verdict = nullptr, *h_verdict_dev = nullptr;
+        struct PendingCheck {
+            BatchArgs A;
+            uint32_t slot;
+            bool trusted;  // no repair launch went out behind it
+        };
+        std::deque<PendingCheck> pending_checks;
+        uint64_t verdict_seq = 0, late_repairs = 0, trusted_launches = 0;
+        uint32_t clean_seen = 0, distrust_left = 0;
+        bool repair_by_host = true;  // option REPAIR=stream: the exact launch always follows in the stream
+        bool has_room() const { return h_verdict && pending_checks.size() + 1u < VERDICT_RING; }  // the host can watch one more launch
+        bool trusts() const { return repair_by_host && clean_seen != 0u && distrust_left == 0u; }  // a watched launch goes out alone
+    } trust;
+
+    // Workgroup-local thresholds (checked) and the pacing of the launches that stream with them: the modes, the carried priors
+    // and their signatures, the pauses by rank and the timetable. Filled by setup_verdicts; autotune_pacing measures the pacing on
+    // this box (pace_quads, pace_levels, pace_period_ns, pace_tuned_*) and clears what its launches carried. Unchanged afterwards
+    // (the kernels move the device words).
+    struct LocalThresholds {
+        uint32_t use_local = 0;    // BatchParams::local: 0 off, 1 / 2: a wave's best / second best packet maximum
+        uint32_t single_mode = 0;  // the same choice for ONE query per launch (single_kernel): by the failure estimate alone, whatever the size
+        float *d_wg_prior = nullptr;  // [grid] + the countdown word (BatchParams::wg_prior / prior_block)
+        float *d_wg_sig = nullptr;    // [grid][8] the signatures of the remembered priors and the second prior (BatchParams::wg_sig; option SIGNATURES=0: none)
+        float local_beta = 1.0f;
+        uint32_t pace_quads = 0, pace_levels = 3, pace_base = 0;  // pacing by rank (BatchParams::pace_quads, pace_levels, pace_base)
+        bool pace_carry = true;            // option PACE_CARRY=0: every launch starts unpaced
+        uint32_t *d_wg_pace = nullptr;     // [grid] the pause every workgroup ended its last launch with (BatchParams::wg_pace)
+        uint32_t *d_pace_adapt = nullptr;  // [0] what launches add to the period, [1] late waves of the launch in flight (BatchParams::pace_adapt)
+        bool pace_adapt_on = true;         // option PACE_ADAPT=0: the period stays what tkspmv_create measured
+        uint32_t pace_period_ns = 0;       // pacing by the clock (BatchParams::pace_period): ns per query of every wave's timetable; 0: pacing by rank
+        uint32_t pace_tuned_us = 0;        // 0: the pacing is the static default (or an option); else what tkspmv_create's measurement took
+        uint32_t pace_tune_launches = 0;   // ... and the batch launches it made (synthetic queries: a kernel trace of a run holds them)
+    } local;
+
+    // single_kernel (kernels/local.hpp): the launch of tkspmv_run on engines that stream with workgroup-local thresholds. Filled
+    // by setup_single; launch_single counts the launches, tkspmv_run the repairs.
+    struct Single {
+        bool can_single = false;
+        unsigned long long *d_lslots = nullptr;  // [grid][WG_SLOTS] the workgroups' records
+        uint32_t *d_lused = nullptr;             // [grid]
+        float *d_lprior = nullptr;               // [grid] carried thresholds | 32 words: the suspension counters (LocalParams::prior_block)
+        uint32_t *d_lstatus = nullptr;           // [0] 1: the last single launch failed its check
+        uint32_t *d_lready = nullptr;            // [grid] the streaming workgroups' flags (LocalParams::ready; NULL: the last workgroup selects)
+        uint64_t single_launches = 0, single_repairs = 0;
+    } single;
+
     // Filtered queries (tkspmv_enqueue_filtered, stream_filter_kernel): the allow-mask tkspmv_set_filter installed, ceil(rows / 32)
-    // words (allocated on the first call), and whether one is installed now
-    uint32_t *d_filter = nullptr;
-    bool have_filter = false;
+    // words, and whether one is installed now. No creation stage: tkspmv_set_filter allocates on its first call and is the only writer.
+    struct Filter {
+        uint32_t *d_filter = nullptr;
+        bool have_filter = false;
+    } filter;
     uint32_t mask_words() const { return std::max<uint32_t>(1u, (desc.rows + 31u) / 32u); }
-    // Range queries (tkspmv_enqueue_range, range_kernel). They touch none of the state above: what is kept here is the timetable's
-    // period (option RANGE_PERIOD, ns per query; unset: the engine's own pace_period_ns when tkspmv_create kept one) and the
-    // scratch of tkspmv_run_range (allocated on its first call, grown to the largest capacity asked for).
-    static constexpr int RANGE_MAX = 32;  // queries per launch
-    bool range_period_set = false;
-    uint32_t range_period_ns = 0;
-    uint32_t *d_range_idx = nullptr;
-    float *d_range_val = nullptr;
-    uint32_t range_cap = 0;
-    uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count
-    // Queries by stored row (tkspmv_enqueue_row_vectors, row_vectors_kernel) touch none of the state above either. Kept here: the
-    // scratch of tkspmv_run_similar -- a chunk's row ids, its vectors and its [chunk][k] results --, allocated on its first call and
-    // grown to the largest chunk asked for (at most SIMILAR_MAX_ROWS rows and SIMILAR_MAX_BYTES of vectors).
-    static constexpr uint32_t SIMILAR_MAX_ROWS = 1024;
-    static constexpr size_t SIMILAR_MAX_BYTES = (size_t)64 << 20;
-    uint32_t *d_sim_rows = nullptr, *d_sim_idx = nullptr;
-    float *d_sim_xs = nullptr, *d_sim_val = nullptr;
-    uint32_t sim_cap = 0;  // rows the scratch holds
+
+    // Range queries (tkspmv_enqueue_range, range_kernel) touch no other group but the matrix. The timetable's period (option
+    // RANGE_PERIOD, ns per query, read by setup_verdicts; unset: the engine's own pace_period_ns) and the scratch of
+    // tkspmv_run_range, which allocates it on its first call and grows it to the largest capacity asked for.
+    struct Range {
+        static constexpr int RANGE_MAX = 32;  // queries per launch
+        bool range_period_set = false;
+        uint32_t range_period_ns = 0;
+        uint32_t *d_range_idx = nullptr;
+        float *d_range_val = nullptr;
+        uint32_t range_cap = 0;
+        uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count
+    } range;
+
+    // Queries by stored row (tkspmv_enqueue_row_vectors, row_vectors_kernel) touch no other group but the matrix either. The
+    // scratch of tkspmv_run_similar -- a chunk's row ids, its vectors and its [chunk][k] results --, which allocates it on its
+    // first call and grows it to the largest chunk asked for (at most SIMILAR_MAX_ROWS rows and SIMILAR_MAX_BYTES of vectors).
+    struct Similar {
+        static constexpr uint32_t SIMILAR_MAX_ROWS = 1024;
+        static constexpr size_t SIMILAR_MAX_BYTES = (size_t)64 << 20;
+        uint32_t *d_sim_rows = nullptr, *d_sim_idx = nullptr;
+        float *d_sim_xs = nullptr, *d_sim_val = nullptr;
+        uint32_t sim_cap = 0;  // rows the scratch holds
+    } similar;
+
+    // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
+    // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
+    // hooks (dbg_kernels; has_tracing_twins, elsewhere the hooks do not exist), and the full score vector of tkspmv_scores /
+    // tkspmv_profile, allocated by whichever is called first.
+    struct Diagnostics {
+        unsigned long long *d_stats = nullptr;
+        bool collect_stats = false, collect_stamps = false, dbg_kernels = false;
+        unsigned long long *d_trace = nullptr;  // TKSPMV_TRACE=1: 4 launches x [grid+1][9][8] stamps
+        size_t trace_words = 0;
+        unsigned long long *d_wg_times = nullptr;  // option WG_TIMES: BatchParams::wg_times of the LAST batch launch (read through tkspmv_debug_trace)
+        float *d_scores = nullptr;
+        unsigned long long *trace_slot(uint64_t launch) const { return d_trace ? d_trace + (launch % 4) * trace_words : nullptr; }
+    } diag;
 
     StreamParams stream_params(const float *x, int set = 0) const {
         StreamParams P{};
-        const ExState &E = st[set];
-        P.packets = d_replicas.empty() ? d_packets : d_replicas[launch_counter % d_replicas.size()];
-        P.pkt_row = d_pkt_row;
-        P.part_first = d_part_first;
-        P.part_count = d_part_count;
+        const ExchangeSets::ExState &E = ex.st[set];
+        P.packets = mat.packets(mat.launch_counter);
+        P.pkt_row = mat.d_pkt_row;
+        P.part_first = mat.d_part_first;
+        P.part_count = mat.d_part_count;
         P.x = x;
         P.n_parts = (uint32_t)info.n_wave_partitions;
-        P.uni_ppp = uni_ppp;
-        P.uni_last = uni_last;
+        P.uni_ppp = mat.uni_ppp;
+        P.uni_last = mat.uni_last;
         P.cols = desc.cols;
         P.packet_bytes = pm.packet_bytes;
-        P.n_sets = n_sets;
+        P.n_sets = ex.n_sets;
         P.k = (uint32_t)desc.k;
-        P.n_groups_pub = n_groups_pub;
-        P.gpw = gpw;
+        P.n_groups_pub = ex.n_groups_pub;
+        P.gpw = ex.gpw;
         P.min_score = desc.min_score;  // converted to score units inside the kernel
         P.fixed_width = pm.fixed_width;
         P.fixed_mask = pm.fixed_width ? fixed_mask(pm.fixed_width) : 0u;
         P.gmax = E.gmax;
         P.tau_g = E.tau_g;
         P.n_reducers = grid < 8u ? grid : 8u;
-        P.tau_possible = groups_with_rows >= (uint32_t)desc.k ? 1u : 0u;
+        P.tau_possible = ex.groups_with_rows >= (uint32_t)desc.k ? 1u : 0u;
 
         P.wg_cand = E.wg_cand;
         P.ovf_cand = E.ovf;
         P.ovf_count = E.ovf_count;
-        P.ovf_cap = ovf_cap;
-        P.scores = d_scores;
-        P.fused = fused ? 1u : 0u;
+        P.ovf_cap = ex.ovf_cap;
+        P.scores = diag.d_scores;
+        P.fused = defer.fused ? 1u : 0u;
         P.deferred = 0u;
         P.unit_inv_out = E.unit_inv;
-        P.dbg = collect_stats ? d_stats + 4 : nullptr;
-        P.stamps = collect_stamps ? d_stats + 16 : nullptr;
-        P.trace = d_trace ? d_trace + (launch_counter % 4) * trace_words : nullptr;
+        P.dbg = diag.collect_stats ? diag.d_stats + 4 : nullptr;
+        P.stamps = diag.collect_stamps ? diag.d_stats + 16 : nullptr;
+        P.trace = diag.trace_slot(mat.launch_counter);
         return P;
     }
     SelectParams select_params(uint32_t *out_idx, float *out_val, int set = 0) const {
         SelectParams S{};
-        const ExState &E = st[set];
+        const ExchangeSets::ExState &E = ex.st[set];
         S.wg_cand = E.wg_cand;
         S.n_wg = grid;
         S.ovf_cand = E.ovf;
         S.ovf_count = E.ovf_count;
-        S.ovf_cap = ovf_cap;
+        S.ovf_cap = ex.ovf_cap;
         S.k = (uint32_t)desc.k;
         S.first_row = desc.first_row;
         S.out_scale = desc.precision == TKSPMV_Q1_7 ? (1.0f / 128.0f)
@@ -430,137 +497,188 @@ struct EngineImpl {
         S.out_val = out_val;
         S.gmax = E.gmax;
         S.tau_g = E.tau_g;
-        S.done_count = d_done;
-        S.n_groups_pub = n_groups_pub;
-        S.use_gmax = (n_sets != 0u && n_groups_pub >= (uint32_t)desc.k) ? 1u : 0u;
-        S.stats = collect_stats ? d_stats : nullptr;
+        S.done_count = ex.d_done;
+        S.n_groups_pub = ex.n_groups_pub;
+        S.use_gmax = (ex.n_sets != 0u && ex.n_groups_pub >= (uint32_t)desc.k) ? 1u : 0u;
+        S.stats = diag.collect_stats ? diag.d_stats : nullptr;
         S.host_out = nullptr;
         S.host_epoch = 0u;
         return S;
     }
-    // The selection still owed to the last deferred launch, as its own small kernel.
-    void drain(hipStream_t s) const {
-        if (pending) {
-            launch_select(pending_idx, pending_val, s, pending_set);
-            pending = false;
-        }
+    // The deferred single-query selection still owed, as its own small kernel.
+    void settle_deferred(hipStream_t s) {
+        if (!defer.pending) return;
+        launch_select(defer.pending_idx, defer.pending_val, s, defer.pending_set);
+        defer.pending = false;
+    }
+    // Every selection still owed -- to the last deferred launch, to the multi-query chains --, each as its own small kernel.
+    void drain(hipStream_t s) {
+        settle_deferred(s);
         drain_chain(0, s);
-        if (pending_group[1].n_q != 0u) {  // (only between the fork and the join of launch_multi_sequence)
-            drain_chain(1, side);
-            (void)hipEventRecord(ev_join, side);
-            (void)hipStreamWaitEvent(s, ev_join, 0);
+        if (multi.pending_group[1].n_q != 0u) {  // (only between the fork and the join of launch_multi_sequence)
+            drain_chain(1, multi.side);
+            (void)hipEventRecord(multi.ev_join, multi.side);
+            (void)hipStreamWaitEvent(s, multi.ev_join, 0);
         }
     }
-    void drain_chain(int c, hipStream_t s) const {
-        if (pending_group[c].n_q == 0u) return;
+    void drain_chain(int c, hipStream_t s) {
+        if (multi.pending_group[c].n_q == 0u) return;
         SelectParams S = select_params(nullptr, nullptr, 0);
-        S.pos_to_row = d_sell_rows;
-        const MultiGroup &G = pending_group[c];
+        S.pos_to_row = multi.d_sell_rows;
+        const MultiGroup &G = multi.pending_group[c];
         const bool serial = G.n_q > 1u && G.io[0].out_idx == G.io[1].out_idx;
         hipLaunchKernelGGL(select_group_kernel, dim3(serial ? 1u : G.n_q), dim3(SEL_THREADS), 0, s, S, set_addr(0), G, serial ? 1u : 0u);
-        pending_group[c].n_q = 0u;
+        multi.pending_group[c].n_q = 0u;
     }
     SetAddr set_addr(int s0) const {
         SetAddr A{};
-        A.gmax0 = st[s0].gmax;
-        A.tau_g0 = st[s0].tau_g;
-        A.ovf_count0 = st[s0].ovf_count;
-        A.wg_cand0 = st[s0].wg_cand;
-        A.ovf_cand0 = st[s0].ovf;
-        A.unit_inv0 = st[s0].unit_inv;
-        A.gmax_stride = GMAX_WORDS;
-        A.word_stride = STATE_WORD_STRIDE;
+        A.gmax0 = ex.st[s0].gmax;
+        A.tau_g0 = ex.st[s0].tau_g;
+        A.ovf_count0 = ex.st[s0].ovf_count;
+        A.wg_cand0 = ex.st[s0].wg_cand;
+        A.ovf_cand0 = ex.st[s0].ovf;
+        A.unit_inv0 = ex.st[s0].unit_inv;
+        A.gmax_stride = ExchangeSets::GMAX_WORDS;
+        A.word_stride = ExchangeSets::STATE_WORD_STRIDE;
         A.cand_stride = grid * WG_SLOTS;
-        A.ovf_stride = ovf_cap;
+        A.ovf_stride = ex.ovf_cap;
         return A;
     }
     // n <= multi_group queries in ONE launch (multi_q per pass over the matrix); their selection is owed (pending_group) to the next multi launch
     // or to drain().
-    void launch_multi(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s, int chain = 0) const {
-        if (pending) {  // a deferred single-query selection uses sets 0/1: settle it first
-            launch_select(pending_idx, pending_val, s, pending_set);
-            pending = false;
-        }
+    void launch_multi(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s, int chain = 0) {
+        settle_deferred(s);  // (a deferred single-query selection uses sets 0/1)
         StreamParams P = stream_params(xs[0], 0);
         P.fused = 0u;
-        P.part_first = d_sell_part_first;
-        P.part_count = d_sell_part_count;
-        P.n_parts = sell_parts;
+        P.part_first = multi.d_sell_part_first;
+        P.part_count = multi.d_sell_part_count;
+        P.n_parts = multi.sell_parts;
         P.uni_ppp = 0u;  // (the row-per-lane stream has its own partition tables)
-        P.packet_bytes = sell_packet_bytes;
+        P.packet_bytes = multi.sell_packet_bytes;
         P.pkt_row = nullptr;
         MultiParams M{};
         M.A = set_addr(0);
-        M.part_slice0 = d_sell_part_slice0;
-        M.n_sel = (uint32_t)multi_group;
-        M.prev = pending_group[chain];
+        M.part_slice0 = multi.d_sell_part_slice0;
+        M.n_sel = (uint32_t)multi.multi_group;
+        M.prev = multi.pending_group[chain];
         M.cur.n_q = (uint32_t)n;
-        M.cur.set0 = (uint32_t)((2 * chain + multi_parity[chain]) * MULTI_Q_MAX);
+        M.cur.set0 = (uint32_t)((2 * chain + multi.half[chain]) * MULTI_Q_MAX);
         for (int q = 0; q < n; ++q) {  // (one copy of the stream per PASS: the queries of a pass share it)
             BatchIO &Q = M.cur.io[q];
             Q.x = xs[q];
-            Q.packets = d_sell_replicas.empty() ? d_sell_packets : d_sell_replicas[(launch_counter + (uint64_t)(q / multi_q)) % d_sell_replicas.size()];
+            Q.packets = multi.packets(mat.launch_counter + (uint64_t)(q / multi.multi_q));
             Q.out_idx = out_idx[q];
             Q.out_val = out_val[q];
         }
-        launch_counter += (uint64_t)((n + multi_q - 1) / multi_q);
+        mat.launch_counter += (uint64_t)((n + multi.multi_q - 1) / multi.multi_q);
         SelectParams S = select_params(nullptr, nullptr, 0);
-        S.pos_to_row = d_sell_rows;
-        const dim3 mblock(multi_stream_waves * 64u + 64u);
-        typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
-        const int qi = multi_q <= 1 ? 0 : (multi_q <= 2 ? 1 : (multi_q <= 4 ? 2 : 3));
-        static const multi_fn fns[3][4] = {{&multi_kernel<1, VT_F32>, &multi_kernel<2, VT_F32>, &multi_kernel<4, VT_F32>, &multi_kernel<8, VT_F32>},
-                                           {&multi_kernel<1, VT_Q17>, &multi_kernel<2, VT_Q17>, &multi_kernel<4, VT_Q17>, &multi_kernel<8, VT_Q17>},
-                                           {&multi_kernel<1, VT_Q17C12>, &multi_kernel<2, VT_Q17C12>, &multi_kernel<4, VT_Q17C12>, &multi_kernel<8, VT_Q17C12>}};
-        hipLaunchKernelGGL(fns[sell_byte_values ? (sell_c12 ? 2 : 1) : 0][qi], dim3(grid), mblock, 0, s, P, S, M);
-        pending_group[chain] = M.cur;
-        multi_parity[chain] ^= 1;
+        S.pos_to_row = multi.d_sell_rows;
+        hipLaunchKernelGGL(kern.multi, dim3(grid), dim3(multi.multi_stream_waves * 64u + 64u), 0, s, P, S, M);
+        multi.pending_group[chain] = M.cur;
+        multi.half[chain] ^= 1;
     }
     // A sequence of queries in passes of multi_q; complete in stream order when this returns. Engines without the
     // multi-query kernel run the ordinary back-to-back sequence.
-    void launch_multi_sequence(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s) const {
-        if (!can_multi) {
+    void launch_multi_sequence(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s) {
+        if (!multi.can_multi) {
             launch_sequence(xs, out_idx, out_val, n, s);
             return;
         }
         // (two chains only with per-query result buffers: with the engine-owned pair "the last query wins" must hold)
-        if (multi_chains < 2 || n <= 2 * multi_group || out_idx[0] == out_idx[1]) {
-            for (int i = 0; i < n; i += multi_group) launch_multi(xs + i, out_idx + i, out_val + i, std::min(multi_group, n - i), s);
+        if (multi.multi_chains < 2 || n <= 2 * multi.multi_group || out_idx[0] == out_idx[1]) {
+            for (int i = 0; i < n; i += multi.multi_group) launch_multi(xs + i, out_idx + i, out_val + i, std::min(multi.multi_group, n - i), s);
             drain(s);
             return;
         }
         drain(s);
-        (void)hipEventRecord(ev_fork, s);
-        (void)hipStreamWaitEvent(side, ev_fork, 0);
+        (void)hipEventRecord(multi.ev_fork, s);
+        (void)hipStreamWaitEvent(multi.side, multi.ev_fork, 0);
         int g = 0;
-        for (int i = 0; i < n; i += multi_group, ++g)
-            launch_multi(xs + i, out_idx + i, out_val + i, std::min(multi_group, n - i), (g & 1) ? side : s, g & 1);
+        for (int i = 0; i < n; i += multi.multi_group, ++g)
+            launch_multi(xs + i, out_idx + i, out_val + i, std::min(multi.multi_group, n - i), (g & 1) ? multi.side : s, g & 1);
         drain(s);  // both chains' last selections, then the caller's stream waits for the side stream
     }
     // One query, its result complete in stream order right after these launches: the stream kernel and, unless
     // fused into its tail, the select kernel.
-    void launch_query(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s) const {
-        if (desc.impl == TKSPMV_IMPL_ROW_PER_LANE && can_multi) {  // the row-per-lane variant, one query per pass
+    void launch_query(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s) {
+        if (desc.impl == TKSPMV_IMPL_ROW_PER_LANE && multi.can_multi) {  // the row-per-lane variant, one query per pass
             launch_multi_sequence(&x, &out_idx, &out_val, 1, s);
             return;
         }
         drain(s);
-        if (use_radix) {
+        if (radix.use_radix) {
             launch_query_radix(x, out_idx, out_val, s);
             return;
         }
         launch_stream(x, out_idx, out_val, s);
-        if (!fused) launch_select(out_idx, out_val, s);
+        if (!defer.fused) launch_select(out_idx, out_val, s);
     }
-    // n <= BATCH_MAX queries in one launch of the batch kernel; results complete in stream order after the launch.
-    void launch_batch(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s, uint32_t parity = 0u,
-                      bool final_launch = true) const {
+    // Result buffers shared by several queries (the engine-owned pair: "the last query wins"): selections run concurrently and a
+    // repair writes after the fact, so only the LAST query enqueued may keep such a buffer -- query q of a launch that must not
+    // write there goes to a scratch block nobody reads.
+    void redirect_to_alias(BatchIO &Q, size_t q) const {
+        Q.out_idx = batch.d_alias_idx + q * desc.k;
+        Q.out_val = batch.d_alias_val + q * desc.k;
+    }
+    // The arguments of one launch of n <= BATCH_MAX queries as the engine's state stands. Changes what it must: the stream copies
+    // move on by n queries (launch_counter), and the launch is counted (batch_launches: the gate's and the verdict words' turn).
+    BatchArgs batch_args(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n) {
+        StreamParams P = stream_params(xs[0], 0);
+        P.fused = 0u;
+        SelectParams S = select_params(out_idx[0], out_val[0], 0);
+        BatchParams B{};
+        B.n_q = (uint32_t)n;
+        B.tickets = batch.d_tickets;
+        static_cast<SetAddr &>(B) = set_addr(0);
+        for (int q = 0; q < n; ++q) {
+            BatchIO &Q = B.io[q];
+            Q.x = xs[q];
+            Q.packets = mat.packets(mat.launch_counter + (uint64_t)q);
+            Q.out_idx = out_idx[q];
+            Q.out_val = out_val[q];
+            if (q + 1 < n && out_idx[q] == out_idx[n - 1]) redirect_to_alias(Q, (size_t)q);
+        }
+        mat.launch_counter += (uint64_t)n;
+        B.n_selectors = batch.n_sel_wg;
+        B.local = local.use_local;
+        B.pace_quads = local.pace_quads;
+        B.pace_levels = local.pace_levels;
+        B.pace_base = local.pace_base;
+        B.pace_period = outlasts_timetable(local.pace_period_ns, n) ? 0u : period_units(local.pace_period_ns);
+        B.pace_adapt = local.pace_adapt_on ? local.d_pace_adapt : nullptr;
+        B.wg_pace = local.pace_carry ? local.d_wg_pace : nullptr;
+        B.wg_times = diag.d_wg_times;
+        B.prior_block = reinterpret_cast<uint32_t *>(local.d_wg_prior + grid);
+        B.gate_parity = (uint32_t)(batch.batch_launches & 1u);
+        // (four words: a launch zeroes the word of the launch after the next)
+        B.verdict = trust.d_verdict + 16 * (batch.batch_launches & 3u);
+        B.verdict_next = trust.d_verdict + 16 * ((batch.batch_launches + 2u) & 3u);
+        ++batch.batch_launches;
+        if (local.use_local) {
+            B.wg_prior = local.d_wg_prior;
+            B.wg_sig = local.d_wg_sig;
+            B.local_beta = local.local_beta;
+        }
+        B.lslots = batch.d_rec_slots;
+        B.lused = batch.d_rec_used;
+        B.lslots_stride = grid * WG_SLOTS;
+        B.lused_stride = grid;
+        B.ovf_epoch = ex.d_ovf_epoch;
+        B.ovf_lists = std::min(ex.ovf_lists, 4u);  // (engines with one list per set -- the multi-query ones -- lend the batch kernel their first four)
+        return BatchArgs{P, S, B};
+    }
+    // n <= BATCH_MAX queries in one launch of the batch kernel; results complete in stream order after the launch(es). With
+    // local thresholds: the kernel of the checked local thresholds, then the exact kernel for whatever failed its check (that
+    // launch is empty -- every workgroup reads the verdict word and leaves -- unless a query was unlike the ones before it). A
+    // launch the host can watch (trust.has_room, the engine's own stream) leaves its verdict in the host's ring too, and while the
+    // host trusts, the exact kernel stays away: settle() repairs.
+    void launch_batch(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s) {
         // (first: the region's start event goes with this kernel, if one is waiting; last: the stop event, if this is the region's final launch)
-        auto go = [&](void (*fn)(BatchArgs), const BatchArgs &args, bool last) {
-            hipEvent_t a = ext_start, b = (last && ext_last) ? ext_stop : nullptr;
-            ext_start = nullptr;
-            if (b) ext_stop = nullptr;
-            if (ext_record) {
+        auto go = [&](batch_fn fn, const BatchArgs &args, bool last) {
+            hipEvent_t a = batch.ext_start, b = (last && batch.ext_last) ? batch.ext_stop : nullptr;
+            batch.ext_start = nullptr;
+            if (b) batch.ext_stop = nullptr;
+            if (batch.ext_record) {
                 if (a) (void)hipEventRecord(a, s);
                 hipLaunchKernelGGL(fn, dim3(grid), dim3(block + 64), 0, s, args);
                 if (b) (void)hipEventRecord(b, s);
@@ -570,177 +688,112 @@ struct EngineImpl {
                 hipLaunchKernelGGL(fn, dim3(grid), dim3(block + 64), 0, s, args);
             }
         };
-        if (!bside || s != bside) drain(s);
-        StreamParams P = stream_params(xs[0], 0);
-        P.fused = 0u;
-        SelectParams S = select_params(out_idx[0], out_val[0], 0);
-        BatchParams B{};
-        B.n_q = (uint32_t)n;
-        B.tickets = d_tickets + (size_t)parity * BATCH_MAX * 32;
-        static_cast<SetAddr &>(B) = set_addr(0);
-        B.unit_inv0 += (size_t)parity * BATCH_MAX * STATE_WORD_STRIDE;
-        for (int q = 0; q < n; ++q) {
-            BatchIO &Q = B.io[q];
-            Q.x = xs[q];
-            Q.packets = d_replicas.empty() ? d_packets : d_replicas[(launch_counter + q) % d_replicas.size()];
-            Q.out_idx = out_idx[q];
-            Q.out_val = out_val[q];
-            // Result buffers shared by several queries of the launch (the engine-owned pair: "the last query wins"): selections run
-            // concurrently and a repair phase writes after the fact, so only the LAST query may keep such a buffer -- the earlier
-            // ones write to a scratch block nobody reads.
-            // (a launch that overlaps with its successor: its last query too, if it names the engine's own pair)
-            if ((q + 1 < n && out_idx[q] == out_idx[n - 1]) || (!final_launch && out_idx[q] == d_out_idx)) {
-                Q.out_idx = d_alias_idx + ((size_t)parity * BATCH_MAX + q) * desc.k;
-                Q.out_val = d_alias_val + ((size_t)parity * BATCH_MAX + q) * desc.k;
-            }
+        drain(s);
+        BatchArgs A = batch_args(xs, out_idx, out_val, n);
+        const bool watched = local.use_local && s == stream && trust.has_room();
+        const bool trusted = watched && trust.trusts();
+        uint32_t slot = 0u;
+        if (watched) {
+            slot = (uint32_t)(trust.verdict_seq++ % Trust::VERDICT_RING);
+            trust.h_verdict[slot] = 0ull;
+            A.B.verdict_host = trust.h_verdict_dev + slot;
         }
-        launch_counter += (uint64_t)n;
-        B.n_selectors = n_sel_wg;
-        B.local = use_local;
-        B.pace_quads = pace_quads;
-        B.pace_levels = pace_levels;
-        B.pace_base = pace_base;
-        B.pace_period = (uint32_t)std::min<uint64_t>(0xFFFFFF00ull, (uint64_t)pace_period_ns * 256u / 10u);
-        // (the waves keep the timetable in 32 bits of ticks << 8: 168 ms to the wrap. A launch that could last a quarter of that -- 32
-        //  queries of 1.3 ms: 80M rows -- paces by rank instead)
-        if ((uint64_t)pace_period_ns * (uint64_t)n > 40000000ull) B.pace_period = 0u;
-        B.pace_adapt = pace_adapt_on ? d_pace_adapt : nullptr;
-        B.wg_pace = pace_carry ? d_wg_pace : nullptr;
-        B.wg_times = d_wg_times;
-        B.prior_block = reinterpret_cast<uint32_t *>(d_wg_prior + grid);
-        B.gate_parity = (uint32_t)(batch_launches & 1u);
-        // (four words: a launch zeroes the word of the launch after the next -- its successor on the same stream --, so the scheme
-        //  holds with one launch at a time and with two in flight)
-        B.verdict = d_verdict + 16 * (batch_launches & 3u);
-        B.verdict_next = d_verdict + 16 * ((batch_launches + 2u) & 3u);
-        ++batch_launches;
-        if (use_local) {
-            B.wg_prior = d_wg_prior;
-            B.wg_sig = d_wg_sig;
-            B.local_beta = local_beta;
+        if (local.use_local) go(kern.batch[1], A, trusted);
+        if (!trusted) {
+            BatchArgs R = A;
+            R.B.repair = local.use_local ? 1u : 0u;
+            go(kern.batch[0], R, true);
         }
-        B.lslots = d_rec_slots + (size_t)parity * BATCH_MAX * grid * WG_SLOTS;
-        B.lused = d_rec_used + (size_t)parity * BATCH_MAX * grid;
-        B.lslots_stride = grid * WG_SLOTS;
-        B.lused_stride = grid;
-        B.ovf_epoch = d_ovf_epoch;
-        B.ovf_lists = std::min(ovf_lists, 4u);  // (engines with one list per set -- the multi-query ones -- lend the batch kernel their first four)
-        if (use_local && (s == stream || (bside && s == bside)) && h_verdict && pending_checks.size() + 1u < VERDICT_RING) {
-            const uint32_t slot = (uint32_t)(verdict_seq++ % VERDICT_RING);
-            h_verdict[slot] = 0ull;
-            B.verdict_host = h_verdict_dev + slot;
-            const bool trusted = repair_by_host && clean_seen != 0u && distrust_left == 0u;
-            BatchArgs A{P, S, B};
-            go(kern.batch[1], A, trusted);
-            if (!trusted) {
-                BatchArgs R = A;
-                R.B.repair = 1u;
-                go(kern.batch[0], R, true);
-                if (distrust_left != 0u) --distrust_left;
-            } else {
-                ++trusted_launches;
-            }
-            pending_checks.push_back(PendingCheck{A, slot, trusted});
-            return;
-        }
-        BatchArgs A{P, S, B};
-        if (use_local) {
-            // the kernel of the checked local thresholds, then the exact kernel for whatever failed its check (the launch is
-            // empty -- every workgroup reads the verdict word and leaves -- unless a query was unlike the ones before it)
-            go(kern.batch[1], A, false);
-            A.B.repair = 1u;
-        }
-        go(kern.batch[0], A, true);
+        if (!watched) return;
+        if (trusted) ++trust.trusted_launches;
+        else if (trust.distrust_left != 0u) --trust.distrust_left;
+        trust.pending_checks.push_back(Trust::PendingCheck{A, slot, trusted});
     }
     // The host has just waited for the engine's stream: look at the verdicts of the launches enqueued since it last did. A flagged
     // query of a TRUSTED launch (no repair launch behind it) is repaired now -- exact launch of the flagged queries, one more wait --;
     // any failure brings the in-stream repair launch back for a while. Returns hipSuccess, or the error of the repair's wait.
-    hipError_t settle() const {
+    hipError_t settle() {
         bool late = false;
-        const size_t n_pending = pending_checks.size();
+        const size_t n_pending = trust.pending_checks.size();
         for (size_t i = 0; i < n_pending; ++i) {
-            PendingCheck &pc = pending_checks[i];
-            const unsigned long long v = const_cast<volatile unsigned long long *>(h_verdict)[pc.slot];
+            Trust::PendingCheck &pc = trust.pending_checks[i];
+            const unsigned long long v = const_cast<volatile unsigned long long *>(trust.h_verdict)[pc.slot];
             const uint32_t mask = (uint32_t)(v >> 32);
             // (a word that is not complete: the launch was not waited for after all -- a caller polling an event of its own; such a
             //  launch counts as a failure of trust, not of a check: everything of it is run again below if nobody repaired it)
             const bool complete = (uint32_t)v == pc.A.B.n_q;
             if (complete && mask == 0u) {
-                if (clean_seen != 0xFFFFFFFFu) ++clean_seen;
+                if (trust.clean_seen != 0xFFFFFFFFu) ++trust.clean_seen;
                 continue;
             }
-            clean_seen = 0u;
-            distrust_left = DISTRUST_LAUNCHES;
+            trust.clean_seen = 0u;
+            trust.distrust_left = Trust::DISTRUST_LAUNCHES;
             if (!pc.trusted) continue;  // (its in-stream repair launch has dealt with it)
             BatchArgs R = pc.A;
             R.B.repair = 2u;
             R.B.repair_mask = complete ? mask : (R.B.n_q >= 32u ? 0xFFFFFFFFu : ((1u << R.B.n_q) - 1u));
             R.B.verdict_host = nullptr;
-            // "the last query wins" for the engine-owned result pair: a launch that was not the last one enqueued must not write
-            // there again after the fact
+            // (a launch that was not the last one enqueued must not write the engine-owned pair again after the fact)
             if (i + 1u < n_pending)
                 for (uint32_t q = 0; q < R.B.n_q; ++q)
-                    if (R.B.io[q].out_idx == d_out_idx) {
-                        R.B.io[q].out_idx = d_alias_idx + (size_t)q * desc.k;
-                        R.B.io[q].out_val = d_alias_val + (size_t)q * desc.k;
-                    }
+                    if (R.B.io[q].out_idx == host.d_out_idx) redirect_to_alias(R.B.io[q], q);
             hipLaunchKernelGGL(kern.batch[0], dim3(grid), dim3(block + 64), 0, stream, R);
-            ++late_repairs;
+            ++trust.late_repairs;
             late = true;
         }
-        pending_checks.clear();
+        trust.pending_checks.clear();
         return late ? hipStreamSynchronize(stream) : hipSuccess;
     }
-    // A back-to-back sequence of queries given as pointer lists: batch kernel launches of up to BATCH_MAX queries
+    // The host waits for the engine's stream, then looks at the verdicts (settle).
+    int wait_idle(std::string &err) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(settle());
+        return TKSPMV_OK;
+    }
+    // The time of `region` -- launches on the engine's stream -- by the events ev0 and ev1 recorded around it; the host waits for ev1.
+    template <class Region>
+    int bracket_ms(float &ms, std::string &err, Region region) {
+        HIP_TRY(hipEventRecord(ev0, stream));
+        region();
+        HIP_TRY(hipEventRecord(ev1, stream));
+        HIP_TRY(hipEventSynchronize(ev1));
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        return TKSPMV_OK;
+    }
+    // A back-to-back sequence of queries given as pointer lists: batch kernel launches of up to batch_max queries
     // when it is available, else deferred selection.
-    void launch_sequence(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s) const {
-        if (!can_batch) {
+    void launch_sequence(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n, hipStream_t s) {
+        if (!batch.can_batch) {
             for (int i = 0; i < n; ++i) launch_deferred(xs[i], out_idx[i], out_val[i], s);
             drain(s);
             return;
         }
-        // Two launches in flight where every launch of the sequence goes out trusted (see bside): fork, alternate, join -- the
-        // caller's view of the engine's stream is unchanged (everything enqueued here is complete when the stream is).
-        const int n_launches = (n + batch_max - 1) / batch_max;
-        const bool overlap = overlap_launches && bside && use_local && s == stream && n_launches >= 2 && repair_by_host && h_verdict &&
-                             clean_seen != 0u && distrust_left == 0u && pending_checks.size() + (size_t)n_launches + 1u < VERDICT_RING;
-        if (overlap) {
-            drain(s);
-            (void)hipEventRecord(ev_bfork, s);
-            (void)hipStreamWaitEvent(bside, ev_bfork, 0);
-        }
-        int l = 0;
-        for (int i = 0; i < n; i += batch_max, ++l) {
-            const bool odd = overlap && (l & 1);
-            ext_last = i + batch_max >= n;
-            launch_batch(xs + i, out_idx + i, out_val + i, std::min(batch_max, n - i), odd ? bside : s, odd ? 1u : 0u, !overlap || i + batch_max >= n);
-        }
-        if (overlap) {
-            (void)hipEventRecord(ev_bjoin, bside);
-            (void)hipStreamWaitEvent(s, ev_bjoin, 0);
+        for (int i = 0; i < n; i += batch.batch_max) {
+            batch.ext_last = i + batch.batch_max >= n;
+            launch_batch(xs + i, out_idx + i, out_val + i, std::min(batch.batch_max, n - i), s);
         }
     }
     // One query of a back-to-back sequence: its selection runs inside the NEXT deferred launch (or in drain()).
-    void launch_deferred(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) const {
-        if (!can_defer) {
+    void launch_deferred(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) {
+        if (!defer.can_defer) {
             launch_query(x, out_idx, out_val, s);
             return;
         }
-        StreamParams P = stream_params(x, cur_set);
+        StreamParams P = stream_params(x, defer.cur_set);
         P.fused = 0u;
         P.deferred = 1u;
         SelectParams S{};  // n_wg = 0: nothing owed
-        if (pending) {
-            S = select_params(pending_idx, pending_val, pending_set);
-            S.unit_inv_in = st[pending_set].unit_inv;
+        if (defer.pending) {
+            S = select_params(defer.pending_idx, defer.pending_val, defer.pending_set);
+            S.unit_inv_in = ex.st[defer.pending_set].unit_inv;
         }
-        ++launch_counter;
+        ++mat.launch_counter;
         launch_stream_kernel(false, F, s, P, S);
-        pending = true;
-        pending_set = cur_set;
-        pending_idx = out_idx;
-        pending_val = out_val;
-        cur_set ^= 1;
+        defer.pending = true;
+        defer.pending_set = defer.cur_set;
+        defer.pending_idx = out_idx;
+        defer.pending_val = out_val;
+        defer.cur_set ^= 1;
     }
     // One launch of the streaming kernel: stream_kernel, or stream_filter_kernel with the allow-mask F.
     void launch_stream_kernel(bool scores, const FilterParams *F, hipStream_t s, const StreamParams &P, const SelectParams &S) const {
@@ -755,16 +808,16 @@ struct EngineImpl {
         (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
         StreamParams P = stream_params(xs);
         RangeParams R{};
-        R.n_replicas = d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(d_replicas.size(), 16);
-        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = d_replicas.empty() ? d_packets : d_replicas[r];
+        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
+        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
         R.mask_stride = (uint32_t)stride;
         R.mask_words = mask_words();
         R.capacity = capacity;
         R.first_row = desc.first_row;
-        const uint32_t period_ns = range_period_set ? range_period_ns : pace_period_ns;
+        const uint32_t period_ns = range.range_period_set ? range.range_period_ns : local.pace_period_ns;
         const range_fn fn = kern.range[mask != nullptr];
-        for (int i = 0; i < n; i += RANGE_MAX) {
-            const int c = std::min(RANGE_MAX, n - i);
+        for (int i = 0; i < n; i += Range::RANGE_MAX) {
+            const int c = std::min(Range::RANGE_MAX, n - i);
             R.q0 = (uint32_t)i;
             R.n_q = (uint32_t)c;
             R.xs = xs + (size_t)i * desc.cols;
@@ -773,9 +826,8 @@ struct EngineImpl {
             R.counts = counts + i;
             R.idx = idx ? idx + (size_t)i * capacity : nullptr;
             R.val = val ? val + (size_t)i * capacity : nullptr;
-            // (the waves keep the timetable in 32 bits of ticks << 8, as in launch_batch; one partition per wave, or no timetable)
-            R.period = (uint32_t)std::min<uint64_t>(0xFFFFFF00ull, (uint64_t)period_ns * 256u / 10u);
-            if ((uint64_t)period_ns * (uint64_t)c > 40000000ull || (uint64_t)P.n_parts > (uint64_t)grid * 8u) R.period = 0u;
+            // (the timetable of launch_batch; one partition per wave, or no timetable)
+            R.period = (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
             hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
         }
     }
@@ -783,17 +835,17 @@ struct EngineImpl {
     // engines are served: extraction does not depend on how rows are selected.
     const char *row_vectors_unsupported() const {
         if (!kern.row_vectors) return "row vectors need an fp32 packet stream (TKSPMV_F32)";
-        if (pm.n_packets != 0u && (!d_packets || !d_pkt_row || !d_part_first)) return "row vectors are read from the wave-BSCSR packets: this engine does not hold them";
+        if (pm.n_packets != 0u && (!mat.d_packets || !mat.d_pkt_row || !mat.d_part_first)) return "row vectors are read from the wave-BSCSR packets: this engine does not hold them";
         return nullptr;
     }
     // Rows ids[0 .. n) as dense vectors xs[n][cols] (len[n]: their entries, optional), complete in stream order when this returns:
     // one wave per row. Stream copy 0 is read whatever stream_replicas says.
     void launch_row_vectors(const uint32_t *ids, int n, float *xs, uint32_t *len, hipStream_t s) const {
         RowVecParams R{};
-        R.packets = d_packets;
-        R.pkt_row = d_pkt_row;
-        R.part_first = d_part_first;
-        R.part_count = d_part_count;
+        R.packets = mat.d_packets;
+        R.pkt_row = mat.d_pkt_row;
+        R.part_first = mat.d_part_first;
+        R.part_count = mat.d_part_count;
         R.n_packets = pm.n_packets;
         R.n_parts = (uint32_t)pm.part_first.size();
         R.packet_bytes = pm.packet_bytes;
@@ -809,8 +861,8 @@ struct EngineImpl {
     const char *filter_unsupported() const {
         if (!is_fp32(fmt)) return "filtered queries need fp32 values (TKSPMV_F32)";
         if (!kern.filter[0]) return "filtered queries need an fp32 packet stream";
-        if (approx_parts) return "filtered queries are exact only: partitions > 1 with k > k_per_partition is the approximate per-partition path";
-        if (!d_packets || !d_pkt_row) return "filtered queries stream the wave-BSCSR packets: this engine does not hold them";
+        if (radix.approx_parts) return "filtered queries are exact only: partitions > 1 with k > k_per_partition is the approximate per-partition path";
+        if (!mat.d_packets || !mat.d_pkt_row) return "filtered queries stream the wave-BSCSR packets: this engine does not hold them";
         return nullptr;
     }
     bool range_unsupported(std::string &err) const {  // (fills err)
@@ -823,61 +875,59 @@ struct EngineImpl {
     // select, scores + radix select where the engine takes that path. Never the batch, single or multi-query kernels: their carried
     // thresholds assume the score distribution of the query before, which a per-query filter breaks.
     void launch_filtered(const float *const *xs, const uint32_t *mask, size_t stride, uint32_t *const *out_idx, float *const *out_val, int n,
-                         hipStream_t s) const {
+                         hipStream_t s) {
         drain(s);  // (a deferred selection still owed uses the same exchange-state sets)
         for (int i = 0; i < n; ++i) {
             const FilterParams F{mask + (size_t)i * stride, mask_words()};
-            if (use_radix) {
+            if (radix.use_radix) {
                 launch_query_radix(xs[i], out_idx[i], out_val[i], s, &F);
-            } else if (can_defer) {
+            } else if (defer.can_defer) {
                 launch_deferred(xs[i], out_idx[i], out_val[i], s, &F);
             } else {
                 launch_stream(xs[i], out_idx[i], out_val[i], s, false, &F);
-                if (!fused) launch_select(out_idx[i], out_val[i], s);
+                if (!defer.fused) launch_select(out_idx[i], out_val[i], s);
             }
         }
         drain(s);
     }
-    void launch_stream(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host = false, const FilterParams *F = nullptr) const {
+    // The fused launch hands its result to the host itself: the pinned block, a new epoch, the start stamp (tkspmv_run).
+    void hand_to_host(SelectParams &S) {
+        S.host_out = host.h_res_dev;
+        S.host_epoch = ++host.host_epoch;
+        S.t_start = host.d_tstart;
+    }
+    void launch_stream(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host = false, const FilterParams *F = nullptr) {
         StreamParams P = stream_params(x);
         SelectParams S = select_params(out_idx, out_val);
-        if (to_host) {
-            S.host_out = h_res_dev;
-            S.host_epoch = ++host_epoch;
-            S.t_start = d_tstart;
-        }
-        ++launch_counter;
+        if (to_host) hand_to_host(S);
+        ++mat.launch_counter;
         launch_stream_kernel(false, F, s, P, S);
     }
     // One query through single_kernel (local thresholds, checked): the result is exact iff the status word / host flag says the
     // check passed; otherwise the caller runs launch_stream, whose result is exact on its own.
-    void launch_single(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host) const {
+    void launch_single(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, bool to_host) {
         StreamParams P = stream_params(x);
         SelectParams S = select_params(out_idx, out_val);
-        if (to_host) {
-            S.host_out = h_res_dev;
-            S.host_epoch = ++host_epoch;
-            S.t_start = d_tstart;
-        }
+        if (to_host) hand_to_host(S);
         LocalParams G{};
-        G.slots = d_lslots;
-        G.used = d_lused;
-        G.wg_prior = d_lprior;
-        G.prior_block = reinterpret_cast<uint32_t *>(d_lprior + grid);
-        G.status = d_lstatus;
-        G.ready = d_lready;
-        G.epoch = (uint32_t)(single_launches + 1u) | 0x80000000u;  // (never 0, never the previous launch's)
-        G.mode = single_mode;
-        G.beta = local_beta;
-        G.trace = d_trace ? d_trace + (launch_counter % 4) * trace_words : nullptr;
-        ++launch_counter;
-        ++single_launches;
+        G.slots = single.d_lslots;
+        G.used = single.d_lused;
+        G.wg_prior = single.d_lprior;
+        G.prior_block = reinterpret_cast<uint32_t *>(single.d_lprior + grid);
+        G.status = single.d_lstatus;
+        G.ready = single.d_lready;
+        G.epoch = (uint32_t)(single.single_launches + 1u) | 0x80000000u;  // (never 0, never the previous launch's)
+        G.mode = local.single_mode;
+        G.beta = local.local_beta;
+        G.trace = diag.trace_slot(mat.launch_counter);
+        ++mat.launch_counter;
+        ++single.single_launches;
         hipLaunchKernelGGL(kern.single, dim3(grid), dim3(512), 0, s, P, S, G);
     }
-    void launch_query_radix(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) const {
-        launch_scores(x, s, d_rscores, F);
+    void launch_query_radix(const float *x, uint32_t *out_idx, float *out_val, hipStream_t s, const FilterParams *F = nullptr) {
+        launch_scores(x, s, radix.d_rscores, F);
         RadixParams R{};
-        R.scores = d_rscores;
+        R.scores = radix.d_rscores;
         R.rows = desc.rows;
         R.k = (uint32_t)desc.k;
         {  // order key of min_score (the device function's host twin)
@@ -885,23 +935,23 @@ struct EngineImpl {
             std::memcpy(&u, &desc.min_score, 4);
             R.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
         }
-        R.hist = d_rhist;
-        R.ovf_cand = st[0].ovf;
-        R.ovf_count = st[0].ovf_count;
-        R.ovf_cap = ovf_cap;
-        if (approx_parts) {
+        R.hist = radix.d_rhist;
+        R.ovf_cand = ex.st[0].ovf;
+        R.ovf_count = ex.st[0].ovf_count;
+        R.ovf_cap = ex.ovf_cap;
+        if (radix.approx_parts) {
             PartitionParams Q{};
-            Q.scores = d_rscores;
+            Q.scores = radix.d_rscores;
             Q.rows = desc.rows;
             Q.per = (desc.rows + (uint32_t)desc.partitions - 1u) / (uint32_t)desc.partitions;  // ceil(N / P): host_spmv_bscsr.cpp:136
             Q.k_part = (uint32_t)(desc.k_per_partition > 0 ? desc.k_per_partition : desc.k);
             Q.kmin = R.kmin;
             Q.ovf_cand = R.ovf_cand;
             Q.ovf_count = R.ovf_count;
-            Q.ovf_cap = ovf_cap;
+            Q.ovf_cap = ex.ovf_cap;
             hipLaunchKernelGGL(partition_topk_kernel, dim3((uint32_t)desc.partitions), dim3(RADIX_THREADS), 0, s, Q);
         } else {
-            (void)hipMemsetAsync(d_rhist, 0, 4 * 256 * 4, s);
+            (void)hipMemsetAsync(radix.d_rhist, 0, 4 * 256 * 4, s);
             const uint32_t rgrid = std::max(1u, std::min(256u, (desc.rows + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
             for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
             hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
@@ -911,26 +961,26 @@ struct EngineImpl {
         S.out_scale = 1.0f;  // the scores kernel already wrote final scores
         hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
     }
-    void launch_scores(const float *x, hipStream_t s, float *dst = nullptr, const FilterParams *F = nullptr) const {
+    void launch_scores(const float *x, hipStream_t s, float *dst = nullptr, const FilterParams *F = nullptr) {
         StreamParams P = stream_params(x);
         if (dst) P.scores = dst;
-        SelectParams S = select_params(d_out_idx, d_out_val);
-        ++launch_counter;  // the stream copies rotate per query here too (cache-defeat mode)
+        SelectParams S = select_params(host.d_out_idx, host.d_out_val);
+        ++mat.launch_counter;  // the stream copies rotate per query here too (cache-defeat mode)
         launch_stream_kernel(true, F, s, P, S);
     }
     void launch_select(uint32_t *out_idx, float *out_val, hipStream_t s, int set = 0) const {
         SelectParams S = select_params(out_idx, out_val, set);
-        S.unit_inv_in = st[set].unit_inv;  // written by the (unfused) stream kernel of that query
+        S.unit_inv_in = ex.st[set].unit_inv;  // written by the (unfused) stream kernel of that query
         hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
     }
     // Does the host-visible result block add up to the checksum its writer left behind the flag (result_checksum_term)? The block
     // is written with relaxed system-scope stores; the flag alone proves nothing by the memory model.
     bool result_block_complete(uint32_t epoch) const {
         const size_t k = (size_t)desc.k;
-        const volatile uint32_t *r = h_res;
+        const volatile uint32_t *r = host.h_res;
         // (word 2k + 5: the status of single_kernel's check. A FAILED check writes no payload -- the block still holds the previous
-        //  query's list -- and its checksum covers the epoch and the status alone: summing the stale payload here never matched,
-        //  and every failed check cost tkspmv_run its 2 s flag timeout before the repair)
+        //  query's list -- and its checksum covers the epoch and the status alone: summing the stale payload here would never match,
+        //  and every failed check would cost tkspmv_run its 2 s flag timeout before the repair)
         if (r[2 * k + 5] != 0u) return r[2 * k + 4] == epoch * 0x9E3779B1u + 0xBADC0DE5u;
         uint32_t sum = epoch * 0x9E3779B1u;
         for (size_t i = 0; i < k; ++i) sum += result_checksum_term(r[i], r[k + i], (uint32_t)i);
@@ -940,15 +990,15 @@ struct EngineImpl {
     // ANOTHER stream (tkspmv_enqueue with a caller's stream and dev_x = NULL) has no ordering against that copy -- the
     // engine's stream is non-blocking -- so it waits for the event recorded behind the copy.
     hipError_t order_x(const float *x, hipStream_t s) const {
-        if (x != d_x || !x_pending || s == stream || bar_x) return hipSuccess;  // (bar_x: the host wrote x itself, nothing is enqueued)
+        if (x != host.d_x || !host.x_pending || s == stream || host.bar_x) return hipSuccess;  // (bar_x: the host wrote x itself, nothing is enqueued)
         return hipStreamWaitEvent(s, ev2, 0);
     }
     // dev_xs = NULL names the vector tkspmv_set_query / set_query_device installed: the call is then for that one query.
     int resolve_query(const float *&dev_xs, int32_t count, std::string &err) const {
         if (dev_xs) return TKSPMV_OK;
         if (count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
-        if (!d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
-        dev_xs = d_x_cur;
+        if (!host.d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
+        dev_xs = host.d_x_cur;
         return TKSPMV_OK;
     }
     // Replaces the buffers of a scratch set that grows on demand (run_range, run_similar) by larger ones: all released, then all
@@ -1009,10 +1059,10 @@ Engine::~Engine() {
     if (!impl_) return;
     EngineImpl &m = *impl_;
     (void)hipSetDevice(m.device);
-    for (hipStream_t s : {m.stream, m.bside, m.side}) if (s) (void)hipStreamSynchronize(s);
+    for (hipStream_t s : {m.stream, m.multi.side}) if (s) (void)hipStreamSynchronize(s);
     for (const EngineImpl::Owned &b : m.owned) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
-    for (hipEvent_t e : {m.ev0, m.ev1, m.ev2, m.ev_fork, m.ev_join, m.ev_bfork, m.ev_bjoin}) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t s : {m.bside, m.side, m.stream}) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {m.ev0, m.ev1, m.ev2, m.multi.ev_fork, m.multi.ev_join}) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {m.multi.side, m.stream}) if (s) (void)hipStreamDestroy(s);
     delete impl_;
 }
 
@@ -1025,7 +1075,7 @@ Engine::~Engine() {
 // (fp32 and fp16 values: every size, wbscsr.hpp; byte and fixed-point values keep round 4's limit -- their kernels are bound by
 //  arithmetic, and there the local thresholds lose beyond it: Q1.7 bytes at 1M x 512 x 40, 154k packets: 33.0 against 24.7 us)
 static uint64_t local_matrix_packets(int32_t precision) {
-    if (const char *f = opt("SMALL_PACKETS")) return (uint64_t)atoll(f);
+    if (opt_set("SMALL_PACKETS")) return (uint64_t)opt_int("SMALL_PACKETS", 0);
     return (precision == TKSPMV_F32 || precision == TKSPMV_F16) ? LOCAL_MATRIX_PACKETS : 100000ull;
 }
 static uint32_t small_matrix_settings(const tkspmv_desc &d, uint32_t grid, bool defer_capable, uint32_t C, bool *small_out) {
@@ -1036,8 +1086,7 @@ static uint32_t small_matrix_settings(const tkspmv_desc &d, uint32_t grid, bool 
     const bool small = defer_capable && grid >= 64u && d.nnz != 0 && d.cols <= 1024u && d.impl == TKSPMV_IMPL_STREAM && d.multi_q == 0 &&
                        plain_topk && packets_lb <= local_matrix_packets(d.precision) && !opt("MULTI_Q");
     if (small_out) *small_out = small;
-    uint32_t n = small ? 4u : 1u;
-    if (const char *f = opt("SELECTORS")) n = (uint32_t)std::max(1, std::min(8, atoi(f)));
+    uint32_t n = (uint32_t)opt_int("SELECTORS", small ? 4 : 1, 1, 8);
     if (!defer_capable || grid < 2u * n) n = 1u;
     return n;
 }
@@ -1072,6 +1121,7 @@ struct Setup {
     uint32_t pack_us = 0;           // time of the packing step (upload of the COO included when on the device)
     uint32_t sell_pack_us = 0;      // packing of the wave-sliced ELL copy (multi-query engines)
     uint64_t sell_bytes = 0;
+    int sell_values = 0;            // values of that copy: 0 fp32; 1 Q1.7 bytes (TKSPMV_Q1_7_F32: 768-byte chunks); 2 ... with 12-bit column words (640-byte chunks, at most 1022 columns)
 };
 
 // The descriptor alone: no device call before these checks (tests/test_capi.py::test_argument_validation_before_device).
@@ -1097,7 +1147,7 @@ static int check_desc(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string
         // reproduces the reference's approximate union: partition_topk_kernel.
         const int kpp = d.k_per_partition > 0 ? d.k_per_partition : d.k;
         if (kpp > TKSPMV_MAX_K || d.partitions > 65535) return fail(err, TKSPMV_ERR_INVALID, "partitions must be <= 65535 and k_per_partition <= 1024");
-        m.approx_parts = d.k > kpp;
+        m.radix.approx_parts = d.k > kpp;
     }
     return TKSPMV_OK;
 }
@@ -1133,11 +1183,11 @@ static int setup_geometry(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     S.defer_capable = m.grid >= 2 && (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.block + 64);
     // Small matrices (the shards of a strong-scaled run) get 4 selector workgroups, shorter partitions and -- decided in
     // setup_verdicts, once the partitions are known -- workgroup-local thresholds: small_matrix_settings().
-    m.n_sel_wg = small_matrix_settings(d, m.grid, S.defer_capable, S.C, &S.small_matrix);
-    if (S.prepacked && S.prepacked->part_first.size() > (size_t)(m.grid - m.n_sel_wg) * S.waves_per_wg) m.n_sel_wg = 1u;
-    S.n_stream_waves = (m.grid - (S.defer_capable ? m.n_sel_wg : 0u)) * S.waves_per_wg;
+    m.batch.n_sel_wg = small_matrix_settings(d, m.grid, S.defer_capable, S.C, &S.small_matrix);
+    if (S.prepacked && S.prepacked->part_first.size() > (size_t)(m.grid - m.batch.n_sel_wg) * S.waves_per_wg) m.batch.n_sel_wg = 1u;
+    S.n_stream_waves = (m.grid - (S.defer_capable ? m.batch.n_sel_wg : 0u)) * S.waves_per_wg;
     // (TKSPMV_PARTITIONS_HINT: measurement aid of the load-only probe -- more partitions than waves; such an engine runs no queries)
-    S.n_parts_hint = opt("PARTITIONS_HINT") ? (uint32_t)atoi(opt("PARTITIONS_HINT")) : S.n_stream_waves;
+    S.n_parts_hint = (uint32_t)opt_int("PARTITIONS_HINT", S.n_stream_waves);
     return TKSPMV_OK;
 }
 
@@ -1162,8 +1212,7 @@ static int pack_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
     } else {
         // The packer runs on the device by default (device_pack.hip: same bytes as the host packer, which stays available
         // with TKSPMV_DEVICE_PACK=0 and serves tkspmv_pack / the .tkspmv files).
-        bool on_device = d.nnz > 0;
-        if (const char *f = opt("DEVICE_PACK")) on_device = on_device && atoi(f) != 0;
+        const bool on_device = d.nnz > 0 && opt_int("DEVICE_PACK", 1) != 0;
         const uint32_t min_packets = min_packets_per_partition_for(d.nnz, S.C, d.cols);
         const auto t_pack = std::chrono::steady_clock::now();
         std::string perr;
@@ -1176,8 +1225,8 @@ static int pack_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
                                       S.n_parts_hint, min_packets, fixed_width_of(d), dp, kind);
             if (perr.empty()) {
                 m.pm = std::move(dp.meta);
-                m.d_packets = m.adopt(dp.d_packets);
-                m.d_pkt_row = m.adopt(dp.d_pkt_row);
+                m.mat.d_packets = m.adopt(dp.d_packets);
+                m.mat.d_pkt_row = m.adopt(dp.d_pkt_row);
                 S.d_coo_col = m.adopt(dp.d_col);
                 S.d_coo_val = m.adopt(dp.d_val);
                 S.packed_on_device = true;
@@ -1198,8 +1247,8 @@ static int pack_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
     bool uniform = np > 0 && ppp > 0 && (uint64_t)np * ppp <= 0xFFFFFFFFull && m.pm.part_count[np - 1] >= 1u && m.pm.part_count[np - 1] <= ppp;
     for (size_t p = 0; uniform && p < np; ++p)
         uniform = m.pm.part_first[p] == (uint32_t)(p * ppp) && (p + 1 == np || m.pm.part_count[p] == ppp);
-    m.uni_ppp = uniform ? ppp : 0u;
-    m.uni_last = uniform ? m.pm.part_count[np - 1] : 0u;
+    m.mat.uni_ppp = uniform ? ppp : 0u;
+    m.mat.uni_last = uniform ? m.pm.part_count[np - 1] : 0u;
     return TKSPMV_OK;
 }
 
@@ -1209,29 +1258,29 @@ static int pack_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
 // where the 1024-word limit of the exchange allows: with k close to the number of groups the k-th largest maximum
 // is a weak bound (k = 256 on 511 groups ran 2x slower than k = 100).
 static int exchange_geometry(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    const uint32_t waves_per_wg = S.waves_per_wg, n_pub_wg = m.grid - (S.defer_capable ? m.n_sel_wg : 0u);
-    m.gpw = 1;
-    while (n_pub_wg * m.gpw < 4u * (uint32_t)d.k && m.gpw < 8 && m.gpw < waves_per_wg && (waves_per_wg % (m.gpw * 2) == 0) &&
-           m.grid * m.gpw * 2 <= (uint32_t)MAX_GM * 64)
-        m.gpw *= 2;
-    m.n_groups_pub = std::min<uint32_t>(m.grid * m.gpw, MAX_GM * 64);
-    m.n_sets = (std::min<uint32_t>(n_pub_wg * m.gpw, MAX_GM * 64) >= (uint32_t)d.k) ? 1u : 0u;  // 0: exchange disabled, every row >= min_score is a candidate
-    if (!m.n_sets) m.n_groups_pub = 1;
-    m.ovf_cap = std::max<uint32_t>(d.rows, 1u);
+    const uint32_t waves_per_wg = S.waves_per_wg, n_pub_wg = m.grid - (S.defer_capable ? m.batch.n_sel_wg : 0u);
+    m.ex.gpw = 1;
+    while (n_pub_wg * m.ex.gpw < 4u * (uint32_t)d.k && m.ex.gpw < 8 && m.ex.gpw < waves_per_wg && (waves_per_wg % (m.ex.gpw * 2) == 0) &&
+           m.grid * m.ex.gpw * 2 <= (uint32_t)MAX_GM * 64)
+        m.ex.gpw *= 2;
+    m.ex.n_groups_pub = std::min<uint32_t>(m.grid * m.ex.gpw, MAX_GM * 64);
+    m.ex.n_sets = (std::min<uint32_t>(n_pub_wg * m.ex.gpw, MAX_GM * 64) >= (uint32_t)d.k) ? 1u : 0u;  // 0: exchange disabled, every row >= min_score is a candidate
+    if (!m.ex.n_sets) m.ex.n_groups_pub = 1;
+    m.ex.ovf_cap = std::max<uint32_t>(d.rows, 1u);
     m.fmt = stream_format_of(d.precision, m.pm.precision, m.info.packet_entries, d.cols);
     if (m.fmt.c == 0) return fail(err, TKSPMV_ERR_UNSUPPORTED, "no kernel is built for this descriptor's packet stream");  // (the packers accept none)
-    m.cand_cap = m.fmt.xcols <= 1024 ? 2048u : 1024u;  // ListGeom<XCOLS>::CAND_CAP
+    m.ex.cand_cap = m.fmt.xcols <= 1024 ? 2048u : 1024u;  // ListGeom<XCOLS>::CAND_CAP
     // groups (workgroup, local group) whose first wave owns a partition: wave w of streaming workgroup b streams
     // partition w * n_pub_wg + b (n_pub_wg: the streaming workgroups of a sequence launch)
     const uint32_t n_parts = (uint32_t)m.pm.part_first.size();
-    m.groups_with_rows = 0;
+    m.ex.groups_with_rows = 0;
     for (uint32_t b = 0; b < n_pub_wg; ++b)
-        for (uint32_t g = 0; g < m.gpw; ++g) {
-            const uint32_t w0 = g * waves_per_wg / m.gpw;
-            if ((uint64_t)w0 * n_pub_wg + b < n_parts && (uint64_t)b * m.gpw + g < m.n_groups_pub) ++m.groups_with_rows;
+        for (uint32_t g = 0; g < m.ex.gpw; ++g) {
+            const uint32_t w0 = g * waves_per_wg / m.ex.gpw;
+            if ((uint64_t)w0 * n_pub_wg + b < n_parts && (uint64_t)b * m.ex.gpw + g < m.ex.n_groups_pub) ++m.ex.groups_with_rows;
         }
     if (S.C == 8 && d.cols > 1024) return fail(err, TKSPMV_ERR_UNSUPPORTED, "nnz_per_lane = 8 is only built for cols <= 1024");
-    m.lds_bytes = (uint32_t)std::max<size_t>(sizeof(SelectShared), (size_t)m.fmt.xcols * 4 + (size_t)m.cand_cap * 8) +
+    m.ex.lds_bytes = (uint32_t)std::max<size_t>(sizeof(SelectShared), (size_t)m.fmt.xcols * 4 + (size_t)m.ex.cand_cap * 8) +
                   MISC_WORDS * 4;  // all static
     return TKSPMV_OK;
 }
@@ -1244,26 +1293,26 @@ static int upload_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::str
     HIP_TRY(hipEventCreate(&m.ev2));
     const size_t stream_bytes = std::max<size_t>(m.pm.stream_bytes(), 256);
     if (!S.packed_on_device) {  // (the device packer has left the stream and its row table in HBM already)
-        HIP_TRY(m.alloc(m.d_packets, stream_bytes));
-        HIP_TRY(m.alloc(m.d_pkt_row, std::max<size_t>(m.pm.pkt_row.size(), 1) * 4));
+        HIP_TRY(m.alloc(m.mat.d_packets, stream_bytes));
+        HIP_TRY(m.alloc(m.mat.d_pkt_row, std::max<size_t>(m.pm.pkt_row.size(), 1) * 4));
         if (m.pm.stream_bytes())
-            HIP_TRY(hipMemcpy(m.d_packets, m.pm.packets.data(), m.pm.stream_bytes(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(m.mat.d_packets, m.pm.packets.data(), m.pm.stream_bytes(), hipMemcpyHostToDevice));
         if (!m.pm.pkt_row.empty())
-            HIP_TRY(hipMemcpy(m.d_pkt_row, m.pm.pkt_row.data(), m.pm.pkt_row.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(m.mat.d_pkt_row, m.pm.pkt_row.data(), m.pm.pkt_row.size() * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(m.alloc(m.d_part_first, std::max<size_t>(m.pm.part_first.size(), 1) * 4));
-    HIP_TRY(m.alloc(m.d_part_count, std::max<size_t>(m.pm.part_count.size(), 1) * 4));
+    HIP_TRY(m.alloc(m.mat.d_part_first, std::max<size_t>(m.pm.part_first.size(), 1) * 4));
+    HIP_TRY(m.alloc(m.mat.d_part_count, std::max<size_t>(m.pm.part_count.size(), 1) * 4));
     if (!m.pm.part_first.empty()) {
-        HIP_TRY(hipMemcpy(m.d_part_first, m.pm.part_first.data(), m.pm.part_first.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(m.d_part_count, m.pm.part_count.data(), m.pm.part_count.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m.mat.d_part_first, m.pm.part_first.data(), m.pm.part_first.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m.mat.d_part_count, m.pm.part_count.data(), m.pm.part_count.size() * 4, hipMemcpyHostToDevice));
     }
     if (d.stream_replicas > 1 && m.pm.stream_bytes()) {
-        m.d_replicas.push_back(m.d_packets);
+        m.mat.d_replicas.push_back(m.mat.d_packets);
         for (int r = 1; r < d.stream_replicas; ++r) {
             uint8_t *p = nullptr;
             HIP_TRY(m.alloc(p, stream_bytes));
-            HIP_TRY(hipMemcpy(p, m.d_packets, m.pm.stream_bytes(), hipMemcpyDeviceToDevice));
-            m.d_replicas.push_back(p);
+            HIP_TRY(hipMemcpy(p, m.mat.d_packets, m.pm.stream_bytes(), hipMemcpyDeviceToDevice));
+            m.mat.d_replicas.push_back(p);
         }
     }
     // The packed stream now lives in HBM; drop the host copy.
@@ -1274,20 +1323,19 @@ static int upload_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::str
 
 // The host boundary -- x on the device, the BAR path, the pinned staging copy of x and result block -- and the result buffers.
 static int setup_host_boundary(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    HIP_TRY(m.alloc(m.d_x, (size_t)d.cols * 4));
-    if (const char *f = opt("HOST_PATH")) m.host_path = atoi(f);
-    // Host stores into device memory (EngineImpl::bar_x): only where the runtime reports a large BAR, and only after a round trip
+    HIP_TRY(m.alloc(m.host.d_x, (size_t)d.cols * 4));
+    m.host.host_path = (int)opt_int("HOST_PATH", 1);
+    // Host stores into device memory (host.bar_x): only where the runtime reports a large BAR, and only after a round trip
     // has shown that a value stored by the CPU is the value a kernel reads back.
     int large_bar = 0;
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, m.device) != hipSuccess) large_bar = 0;
     (void)hipGetLastError();
-    bool want = large_bar != 0 && m.host_path != 0;
-    if (const char *f = opt("BAR_X")) want = want && atoi(f) != 0;
+    bool want = large_bar != 0 && m.host.host_path != 0 && opt_int("BAR_X", 1) != 0;
     if (want) {
         uint32_t *reg = nullptr;  // (the attribute is returned through the int pointer as an address)
         if (hipDeviceGetAttribute(reinterpret_cast<int *>(&reg), hipDeviceAttributeHdpMemFlushCntl, m.device) != hipSuccess) reg = nullptr;
         (void)hipGetLastError();
-        m.hdp_flush = reg;
+        m.host.hdp_flush = reg;
         want = reg != nullptr;
     }
     if (want) {
@@ -1296,44 +1344,44 @@ static int setup_host_boundary(const tkspmv_desc &d, Setup &S, EngineImpl &m, st
         // earlier round has had the old values in its caches.
         ScratchBuffer<uint32_t> back_dev;
         HIP_TRY(hipMalloc((void **)&back_dev.p, 8));
-        HIP_TRY(hipMemset(m.d_x, 0, (size_t)d.cols * 4));
+        HIP_TRY(hipMemset(m.host.d_x, 0, (size_t)d.cols * 4));
         HIP_TRY(hipDeviceSynchronize());
-        volatile uint32_t *px = reinterpret_cast<volatile uint32_t *>(m.d_x);
+        volatile uint32_t *px = reinterpret_cast<volatile uint32_t *>(m.host.d_x);
         bool ok = true;
         for (uint32_t round = 0; round < 4u && ok; ++round) {
             const uint32_t a = 0x5A17C0DEu + 0x01010101u * round, b = (0xC0DE5A17u ^ d.cols) + 0x00010001u * round;
             px[0] = a;
             px[d.cols - 1] = b;
-            m.flush_hdp();
-            hipLaunchKernelGGL(bar_check_kernel, dim3(1), dim3(64), 0, nullptr, reinterpret_cast<const uint32_t *>(m.d_x), d.cols - 1u, back_dev.p);
+            m.host.flush_hdp();
+            hipLaunchKernelGGL(bar_check_kernel, dim3(1), dim3(64), 0, nullptr, reinterpret_cast<const uint32_t *>(m.host.d_x), d.cols - 1u, back_dev.p);
             uint32_t back[2] = {0, 0};
             HIP_TRY(hipMemcpy(back, back_dev.p, 8, hipMemcpyDeviceToHost));
             ok = back[0] == (d.cols == 1 ? b : a) && back[1] == b;
         }
-        m.bar_x = ok;
-        HIP_TRY(hipMemset(m.d_x, 0, (size_t)d.cols * 4));
+        m.host.bar_x = ok;
+        HIP_TRY(hipMemset(m.host.d_x, 0, (size_t)d.cols * 4));
         HIP_TRY(hipDeviceSynchronize());
     }
-    if (m.host_path) {  // pinned staging copy of x and the host-visible result block (optional: the plain path needs neither)
+    if (m.host.host_path) {  // pinned staging copy of x and the host-visible result block (optional: the plain path needs neither)
         const char *hx = opt("HOST_X");
-        if (hx) m.host_x_direct = std::string(hx) == "direct" || std::string(hx) == "direct_nc";
-        if (const char *f = opt("RUN_EVENTS")) m.run_events = atoi(f) != 0;
+        if (hx) m.host.host_x_direct = std::string(hx) == "direct" || std::string(hx) == "direct_nc";
+        m.host.run_events = opt_int("RUN_EVENTS", 0) != 0;
         const unsigned flags = (hx && std::string(hx) == "direct_nc") ? (hipHostMallocMapped | hipHostMallocNonCoherent) : hipHostMallocMapped;
-        (void)m.alloc(m.h_x, (size_t)d.cols * 4, Mem::Pinned, -1, flags);  // (none: tkspmv_set_query takes the plain path)
-        if (m.h_x && hipHostGetDevicePointer((void **)&m.h_x_dev, m.h_x, 0) != hipSuccess) m.host_x_direct = false;
-        if (m.alloc(m.h_res, ((size_t)2 * d.k + 16) * 4, Mem::Pinned, 0) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&m.h_res_dev, m.h_res, 0) != hipSuccess) {
-            m.release(m.h_res);
-            m.h_res = m.h_res_dev = nullptr;
+        (void)m.alloc(m.host.h_x, (size_t)d.cols * 4, Mem::Pinned, -1, flags);  // (none: tkspmv_set_query takes the plain path)
+        if (m.host.h_x && hipHostGetDevicePointer((void **)&m.host.h_x_dev, m.host.h_x, 0) != hipSuccess) m.host.host_x_direct = false;
+        if (m.alloc(m.host.h_res, ((size_t)2 * d.k + 16) * 4, Mem::Pinned, 0) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&m.host.h_res_dev, m.host.h_res, 0) != hipSuccess) {
+            m.release(m.host.h_res);
+            m.host.h_res = m.host.h_res_dev = nullptr;
         }
         (void)hipGetLastError();
     }
-    HIP_TRY(m.alloc(m.d_out_idx, (size_t)d.k * 4, Mem::Device, 0));
-    HIP_TRY(m.alloc(m.d_out_val, (size_t)d.k * 4, Mem::Device, 0));
-    HIP_TRY(m.alloc(m.d_stats, 32 * 8, Mem::Device, 0));
-    m.collect_stats = opt("STATS") != nullptr;
-    HIP_TRY(m.alloc(m.d_tstart, 128, Mem::Exchange, 0));
-    HIP_TRY(m.alloc(m.d_done, 9 * 128, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.host.d_out_idx, (size_t)d.k * 4, Mem::Device, 0));
+    HIP_TRY(m.alloc(m.host.d_out_val, (size_t)d.k * 4, Mem::Device, 0));
+    HIP_TRY(m.alloc(m.diag.d_stats, 32 * 8, Mem::Device, 0));
+    m.diag.collect_stats = opt("STATS") != nullptr;
+    HIP_TRY(m.alloc(m.host.d_tstart, 128, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.ex.d_done, 9 * 128, Mem::Exchange, 0));
     return TKSPMV_OK;
 }
 
@@ -1341,28 +1389,28 @@ static int setup_host_boundary(const tkspmv_desc &d, Setup &S, EngineImpl &m, st
 static int choose_path(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
     // Fused tail / deferred selection: one workgroup (block + 64 threads) must hold every slot in SEL_PER_THREAD
     // registers per thread.
-    m.fused = (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.block + 64);
-    m.can_defer = S.defer_capable;
-    if (const char *f = opt("FUSED")) m.fused = m.fused && atoi(f) != 0;
-    m.can_batch = m.can_defer && m.n_sets != 0u && is_batchable(m.fmt);
-    if (const char *f = opt("BATCH")) m.can_batch = m.can_batch && atoi(f) != 0;
+    m.defer.fused = (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.block + 64);
+    m.defer.can_defer = S.defer_capable;
+    m.defer.fused = m.defer.fused && opt_int("FUSED", 1) != 0;
+    m.batch.can_batch = m.defer.can_defer && m.ex.n_sets != 0u && is_batchable(m.fmt);
+    m.batch.can_batch = m.batch.can_batch && opt_int("BATCH", 1) != 0;
     // Large k: the scores + radix-select path wherever the threshold exchange is off or next to useless (k above
     // 3/8 of the publishing groups: measured cross-over on the BASELINE matrix, tools/k_probe.py). TKSPMV_RADIX=0/1 forces.
-    m.use_radix = m.n_sets == 0u || (uint64_t)d.k * 8u > (uint64_t)m.n_groups_pub * 3u || d.impl == TKSPMV_IMPL_SCORES_SELECT;
-    if (const char *f = opt("RADIX")) m.use_radix = atoi(f) != 0;
-    if (m.approx_parts) m.use_radix = true;  // scores, then the per-partition selection instead of the radix select
-    if (m.use_radix) {
-        m.can_defer = m.can_batch = false;
-        m.fused = false;
+    m.radix.use_radix = m.ex.n_sets == 0u || (uint64_t)d.k * 8u > (uint64_t)m.ex.n_groups_pub * 3u || d.impl == TKSPMV_IMPL_SCORES_SELECT;
+    m.radix.use_radix = opt_int("RADIX", m.radix.use_radix) != 0;
+    if (m.radix.approx_parts) m.radix.use_radix = true;  // scores, then the per-partition selection instead of the radix select
+    if (m.radix.use_radix) {
+        m.defer.can_defer = m.batch.can_batch = false;
+        m.defer.fused = false;
         const size_t n = std::max<size_t>(d.rows, 1);
-        HIP_TRY(m.alloc(m.d_rscores, n * 4));
+        HIP_TRY(m.alloc(m.radix.d_rscores, n * 4));
         std::vector<float> ninf(n, -std::numeric_limits<float>::infinity());
-        HIP_TRY(hipMemcpy(m.d_rscores, ninf.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(m.alloc(m.d_rhist, 4 * 256 * 4));
+        HIP_TRY(hipMemcpy(m.radix.d_rscores, ninf.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(m.alloc(m.radix.d_rhist, 4 * 256 * 4));
     }
     // (every streaming wave of a sequence launch owns ONE partition: an engine packed with more -- the load-only probe's
     //  TKSPMV_PARTITIONS_HINT -- would silently skip the rest)
-    if (m.pm.part_first.size() > (size_t)S.n_stream_waves) m.can_batch = m.can_defer = false;
+    if (m.pm.part_first.size() > (size_t)S.n_stream_waves) m.batch.can_batch = m.defer.can_defer = false;
     return TKSPMV_OK;
 }
 
@@ -1371,41 +1419,39 @@ static int choose_path(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
 static int setup_multi(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
     int mq = d.multi_q;
     if (d.impl == TKSPMV_IMPL_ROW_PER_LANE && mq == 0) mq = 1;
-    if (const char *f = opt("MULTI_Q")) mq = atoi(f);
+    mq = (int)opt_int("MULTI_Q", mq);
     if (mq != 0 && mq != 1 && mq != 2 && mq != 4 && mq != 8) return fail(err, TKSPMV_ERR_INVALID, "multi_q must be 0 (off), 1, 2, 4 or 8");
     // A threshold is the k-th largest of the published group maxima. With k above a quarter of the groups it forms late
     // and stays weak; with 8 queries per pass the private lists are half as long (64 entries) and the held slices
     // fewer: measured at k = 500 (while that kernel still ran one workgroup per CU) every wave ran into its bounded
     // wait and then poured its rows into the overflow list, 2 ms per query. Such engines run 4 queries per pass.
-    if (mq == 8 && (uint32_t)d.k * 4u > m.n_groups_pub) mq = 4;
-    m.multi_q = mq;
+    if (mq == 8 && (uint32_t)d.k * 4u > m.ex.n_groups_pub) mq = 4;
+    m.multi.multi_q = mq;
     // One or two queries per pass: a launch makes several passes (MULTI_PASSES; default: as many as the MULTI_Q_MAX queries of
     // a group allow -- 8 or 4), each pass with its own queries and exchange-state sets. (4 and 8 per pass: one pass per launch.)
-    m.multi_group = mq;
+    m.multi.multi_group = mq;
     if (mq == 1 || mq == 2) {
-        int passes = MULTI_Q_MAX / mq;
-        if (const char *f = opt("MULTI_PASSES")) passes = std::min(std::max(atoi(f), 1), passes);
-        m.multi_group = passes * mq;
+        m.multi.multi_group = (int)opt_int("MULTI_PASSES", MULTI_Q_MAX / mq, 1, MULTI_Q_MAX / mq) * mq;
     }
     // 8 queries per pass need 91 registers: with 9 waves per workgroup only one workgroup fits a CU (the dispatcher wants
     // 6 waves on one SIMD for two); with 8 waves -- 7 streaming + the server -- two fit at up to 128 registers.
-    m.multi_stream_waves = (m.multi_q >= 8 && S.waves_per_wg == 8u) ? 7u : S.waves_per_wg;
+    m.multi.multi_stream_waves = (m.multi.multi_q >= 8 && S.waves_per_wg == 8u) ? 7u : S.waves_per_wg;
     // (k above half of the groups: the threshold is next to useless -- k = 1000 on 1024 groups measured 3.6 ms per query
     // through the multi-query kernel against 0.2 ms one query per pass; such engines keep the ordinary sequence)
     // The selector workgroups of a multi-query launch have multi_stream_waves * 64 + 64 threads and hold SEL_PER_THREAD
     // slots each in registers: every slot of the grid must fit (with 7 streaming waves that is 4096 slots = 512
     // workgroups, fewer than the 576 the ordinary launch geometry allows).
-    m.can_multi = mq > 0 && !m.use_radix && m.can_defer && m.n_sets != 0u && d.cols <= SELL_XCOLS &&
+    m.multi.can_multi = mq > 0 && !m.radix.use_radix && m.defer.can_defer && m.ex.n_sets != 0u && d.cols <= SELL_XCOLS &&
                   (d.precision == TKSPMV_F32 || d.precision == TKSPMV_Q1_7_F32) && m.pm.nnz > 0 &&
-                  m.grid > 2u * (uint32_t)MULTI_Q_MAX && (uint32_t)d.k * 2u <= m.n_groups_pub &&
-                  (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.multi_stream_waves * 64u + 64u) &&
+                  m.grid > 2u * (uint32_t)MULTI_Q_MAX && (uint32_t)d.k * 2u <= m.ex.n_groups_pub &&
+                  (uint64_t)m.grid * WG_SLOTS <= (uint64_t)SEL_PER_THREAD * (m.multi.multi_stream_waves * 64u + 64u) &&
                   // (the kernel stages x with TWO words per thread -- multi_kernel's XI --: a workgroup narrower than 512 threads
                   //  would leave the columns from 2 x blockDim on unwritten in LDS and score against garbage, ADVICE r4;
                   //  such geometries -- threads_per_wg <= 384 -- keep the ordinary sequence)
-                  2u * (m.multi_stream_waves * 64u + 64u) >= SELL_XCOLS;
-    if (m.can_multi) {
+                  2u * (m.multi.multi_stream_waves * 64u + 64u) >= SELL_XCOLS;
+    if (m.multi.can_multi) {
         // the first multi_group workgroups of a multi-query launch are its selectors (one per query of the previous launch), the others stream
-        const uint32_t n_multi_waves = (m.grid - (uint32_t)m.multi_group) * m.multi_stream_waves;
+        const uint32_t n_multi_waves = (m.grid - (uint32_t)m.multi.multi_group) * m.multi.multi_stream_waves;
         SellMatrix sm;
         std::string perr;
         const auto t_sell = std::chrono::steady_clock::now();
@@ -1419,42 +1465,41 @@ static int setup_multi(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
             DeviceSell ds;
             perr = pack_wsell_device(d.rows, d.cols, d.nnz, d.row, d.col, d.val, n_multi_waves, sv, S.d_coo_col, S.d_coo_val, ds);
             sm = std::move(ds.meta);
-            m.d_sell_packets = m.adopt(ds.d_packets);
+            m.multi.d_sell_packets = m.adopt(ds.d_packets);
         } else {
             perr = pack_wsell(d.rows, d.cols, d.nnz, d.row, d.col, d.val, n_multi_waves, sm, sv);
         }
         S.sell_pack_us = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_sell).count(), 0xFFFFFFFFll);
-        m.sell_packet_bytes = sm.packet_bytes;
-        m.sell_byte_values = sv == SellValues::Q1_7_RND;
-        m.sell_c12 = sm.cw_bits == 12;
+        m.multi.sell_packet_bytes = sm.packet_bytes;
+        S.sell_values = sv != SellValues::Q1_7_RND ? 0 : (sm.cw_bits == 12 ? 2 : 1);
         if (!perr.empty()) return fail(err, perr.find("failed:") != std::string::npos ? TKSPMV_ERR_DEVICE : TKSPMV_ERR_INVALID, perr);
-        m.sell_parts = (uint32_t)sm.part_first.size();
-        S.sell_bytes = sm.stream_bytes() + sm.slice_rows.size() * 4 + (uint64_t)m.sell_parts * 12;
-        if (!m.d_sell_packets) {
-            HIP_TRY(m.alloc(m.d_sell_packets, std::max<size_t>(sm.stream_bytes(), 256)));
-            HIP_TRY(hipMemcpy(m.d_sell_packets, sm.packets.data(), sm.stream_bytes(), hipMemcpyHostToDevice));
+        m.multi.sell_parts = (uint32_t)sm.part_first.size();
+        S.sell_bytes = sm.stream_bytes() + sm.slice_rows.size() * 4 + (uint64_t)m.multi.sell_parts * 12;
+        if (!m.multi.d_sell_packets) {
+            HIP_TRY(m.alloc(m.multi.d_sell_packets, std::max<size_t>(sm.stream_bytes(), 256)));
+            HIP_TRY(hipMemcpy(m.multi.d_sell_packets, sm.packets.data(), sm.stream_bytes(), hipMemcpyHostToDevice));
         }
-        HIP_TRY(m.alloc(m.d_sell_rows, sm.slice_rows.size() * 4));
-        HIP_TRY(hipMemcpy(m.d_sell_rows, sm.slice_rows.data(), sm.slice_rows.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(m.alloc(m.d_sell_part_first, (size_t)m.sell_parts * 4));
-        HIP_TRY(m.alloc(m.d_sell_part_count, (size_t)m.sell_parts * 4));
-        HIP_TRY(m.alloc(m.d_sell_part_slice0, (size_t)m.sell_parts * 4));
-        HIP_TRY(hipMemcpy(m.d_sell_part_first, sm.part_first.data(), (size_t)m.sell_parts * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(m.d_sell_part_count, sm.part_count.data(), (size_t)m.sell_parts * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(m.d_sell_part_slice0, sm.part_slice0.data(), (size_t)m.sell_parts * 4, hipMemcpyHostToDevice));
-        HIP_TRY(m.alloc(m.d_multi_out_idx, 2 * (size_t)MULTI_Q_MAX * d.k * 4));
-        HIP_TRY(m.alloc(m.d_multi_out_val, 2 * (size_t)MULTI_Q_MAX * d.k * 4));
-        HIP_TRY(hipStreamCreateWithFlags(&m.side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m.ev_join, hipEventDisableTiming));
-        if (const char *f = opt("MULTI_CHAINS")) m.multi_chains = atoi(f) >= 2 ? 2 : 1;
+        HIP_TRY(m.alloc(m.multi.d_sell_rows, sm.slice_rows.size() * 4));
+        HIP_TRY(hipMemcpy(m.multi.d_sell_rows, sm.slice_rows.data(), sm.slice_rows.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(m.alloc(m.multi.d_sell_part_first, (size_t)m.multi.sell_parts * 4));
+        HIP_TRY(m.alloc(m.multi.d_sell_part_count, (size_t)m.multi.sell_parts * 4));
+        HIP_TRY(m.alloc(m.multi.d_sell_part_slice0, (size_t)m.multi.sell_parts * 4));
+        HIP_TRY(hipMemcpy(m.multi.d_sell_part_first, sm.part_first.data(), (size_t)m.multi.sell_parts * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m.multi.d_sell_part_count, sm.part_count.data(), (size_t)m.multi.sell_parts * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m.multi.d_sell_part_slice0, sm.part_slice0.data(), (size_t)m.multi.sell_parts * 4, hipMemcpyHostToDevice));
+        HIP_TRY(m.alloc(m.multi.d_multi_out_idx, 2 * (size_t)MULTI_Q_MAX * d.k * 4));
+        HIP_TRY(m.alloc(m.multi.d_multi_out_val, 2 * (size_t)MULTI_Q_MAX * d.k * 4));
+        HIP_TRY(hipStreamCreateWithFlags(&m.multi.side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&m.multi.ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&m.multi.ev_join, hipEventDisableTiming));
+        m.multi.multi_chains = opt_int("MULTI_CHAINS", 2) >= 2 ? 2 : 1;
         if (d.stream_replicas > 1) {
-            m.d_sell_replicas.push_back(m.d_sell_packets);
+            m.multi.d_sell_replicas.push_back(m.multi.d_sell_packets);
             for (int r = 1; r < d.stream_replicas; ++r) {
                 uint8_t *p = nullptr;
                 HIP_TRY(m.alloc(p, sm.stream_bytes()));
-                HIP_TRY(hipMemcpy(p, m.d_sell_packets, sm.stream_bytes(), hipMemcpyDeviceToDevice));
-                m.d_sell_replicas.push_back(p);
+                HIP_TRY(hipMemcpy(p, m.multi.d_sell_packets, sm.stream_bytes(), hipMemcpyDeviceToDevice));
+                m.multi.d_sell_replicas.push_back(p);
             }
         }
     }
@@ -1466,14 +1511,14 @@ static int setup_multi(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
 // The checks of workgroup-local thresholds: the verdict words, the failure estimate that picks the mode, the carried priors and
 // their signatures, and the pacing settings.
 static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    HIP_TRY(m.alloc(m.d_tickets, 2 * BATCH_MAX * 32 * 4, Mem::Exchange, 0));  // (one block per launch parity: EngineImpl::bside)
-    HIP_TRY(m.alloc(m.d_verdict, 512, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.batch.d_tickets, BATCH_MAX * 32 * 4, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.trust.d_verdict, 512, Mem::Exchange, 0));
     // the host's side of the verdicts (EngineImpl::settle); without it every local launch keeps its repair launch in the stream
-    if (const char *f = opt("REPAIR")) m.repair_by_host = std::string(f) != "stream";
-    if (m.alloc(m.h_verdict, (size_t)EngineImpl::VERDICT_RING * 8, Mem::Pinned, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&m.h_verdict_dev, m.h_verdict, 0) != hipSuccess) {
-        m.release(m.h_verdict);
-        m.h_verdict = m.h_verdict_dev = nullptr;
+    if (const char *f = opt("REPAIR")) m.trust.repair_by_host = std::string(f) != "stream";
+    if (m.alloc(m.trust.h_verdict, (size_t)EngineImpl::Trust::VERDICT_RING * 8, Mem::Pinned, 0) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&m.trust.h_verdict_dev, m.trust.h_verdict, 0) != hipSuccess) {
+        m.release(m.trust.h_verdict);
+        m.trust.h_verdict = m.trust.h_verdict_dev = nullptr;
         (void)hipGetLastError();
     }
     // Workgroup-local thresholds pay when they practically never fail the selection's check (a failure costs the query a
@@ -1483,7 +1528,7 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     // them in different packets, ~lambda^2 / 2; a single-packet partition has no second one). Mode 1 forms the threshold a
     // packet earlier: preferred where it is safe. And a workgroup keeps its 8 best rows: 9 of the k best in one workgroup
     // fail too (Poisson tail at k / workgroups).
-    const double n_parts = (double)std::max<size_t>(m.pm.part_first.size(), 1), n_wg = (double)(m.grid - m.n_sel_wg);
+    const double n_parts = (double)std::max<size_t>(m.pm.part_first.size(), 1), n_wg = (double)(m.grid - m.batch.n_sel_wg);
     const double lam = std::min(1.0, (double)d.k / n_parts);
     const double per_part = (double)m.pm.n_packets / n_parts;
     const double a = std::max(1.0, std::floor(n_parts / n_wg));
@@ -1493,19 +1538,19 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     tail9 = std::max(tail9, 0.0);
     const double p1 = n_wg * (std::pow(lam, a) + tail9);
     const double p2 = n_wg * (std::pow(per_part < 1.5 ? lam : std::min(1.0, 0.5 * lam * lam), a) + tail9);
-    m.single_mode = m.grid > 512u ? 0u : (p1 <= 1e-4 ? 1u : (p2 <= 1e-3 ? 2u : 0u));  // (512: select_local's record count)
+    m.local.single_mode = m.grid > 512u ? 0u : (p1 <= 1e-4 ? 1u : (p2 <= 1e-3 ? 2u : 0u));  // (512: select_local's record count)
     // Back-to-back queries: beyond ~1.3M rows the device-wide exchange is as fast and checks nothing (small_matrix). ONE query per
     // launch has no such cross-over -- without a previous query in flight the exchange's threshold arrives a third into the
     // partition, a carried local one is there from the first packet: 58.4 against 67.5 us at 3M rows -- so single_kernel serves
     // tkspmv_run wherever the failure estimate allows it.
-    m.use_local = S.small_matrix ? m.single_mode : 0u;
+    m.local.use_local = S.small_matrix ? m.local.single_mode : 0u;
     if (opt("DEBUG_OCC"))
         fprintf(stderr, "[tkspmv] small matrix %d: %u selector workgroups, %.0f partitions of %.1f packets, %.0f per workgroup; local thresholds fail with p = %.2e (mode 1) / %.2e (mode 2): mode %u\n",
-                (int)S.small_matrix, m.n_sel_wg, n_parts, per_part, a, p1, p2, m.use_local);
-    HIP_TRY(m.alloc(m.d_wg_prior, ((size_t)m.grid + 32) * 4, Mem::Exchange, 0));  // priors | countdown words
-    if (!opt("SIGNATURES") || atoi(opt("SIGNATURES")) != 0) HIP_TRY(m.alloc(m.d_wg_sig, (size_t)m.grid * 8 * 4, Mem::Device, 0));
-    if (const char *f = opt("LOCAL_BETA")) m.local_beta = (float)atof(f);
-    if (const char *f = opt("LOCAL")) m.use_local = m.single_mode = m.grid > 512u ? 0u : (uint32_t)std::max(0, std::min(2, atoi(f)));
+                (int)S.small_matrix, m.batch.n_sel_wg, n_parts, per_part, a, p1, p2, m.local.use_local);
+    HIP_TRY(m.alloc(m.local.d_wg_prior, ((size_t)m.grid + 32) * 4, Mem::Exchange, 0));  // priors | countdown words
+    if (opt_int("SIGNATURES", 1) != 0) HIP_TRY(m.alloc(m.local.d_wg_sig, (size_t)m.grid * 8 * 4, Mem::Device, 0));
+    if (const char *f = opt("LOCAL_BETA")) m.local.local_beta = (float)atof(f);
+    if (opt_set("LOCAL")) m.local.use_local = m.local.single_mode = m.grid > 512u ? 0u : (uint32_t)opt_int("LOCAL", 0, 0, 2);
     // Pacing by rank, with local thresholds only (with the device-wide exchange the cold phase of every query is governor enough, §3.0):
     // the longer the partitions, the longer the pause (size sweeps on two boxes, tools/ab_rank.sh: best at 0 / 1 / 2 units of 256 cycles
     // up to 575k / 830k / 1.3M rows of 20 non-zeros).
@@ -1515,20 +1560,18 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     // (round 5, with the pause behind the packet's arithmetic: from ~330k rows up a pause of ONE unit per level pays -- 500k rows: 9.03
     //  against 9.86 us per query unpaced, 10.0 at two units; 250k rows: 5.8 either way -- and tkspmv_create's measurement may still
     //  choose none)
-    if (m.use_local) m.pace_quads = m.pm.n_packets <= 25000u ? 0u : (m.pm.n_packets <= 45000u ? 1u : (m.pm.n_packets <= 65000u ? 2u : 2u * std::max(1u, (m.pm.packet_bytes + 352u) / 704u)));
-    if (const char *f = opt("PACE_LEVELS")) m.pace_levels = (uint32_t)std::max(1, std::min(8, atoi(f)));
-    if (const char *f = opt("PACE")) m.pace_quads = (uint32_t)std::max(0, std::min(32, atoi(f)));
-    if (const char *f = opt("PACE_BASE")) m.pace_base = (uint32_t)std::max(0, std::min(64, atoi(f)));
-    if (const char *f = opt("PACE_CARRY")) m.pace_carry = atoi(f) != 0;
-    if (const char *f = opt("PACE_ADAPT")) m.pace_adapt_on = atoi(f) != 0;
-    if (const char *f = opt("PACE_PERIOD")) m.pace_period_ns = (uint32_t)std::max(0, std::min(10000000, atoi(f)));
-    if (const char *f = opt("RANGE_PERIOD")) {
-        m.range_period_set = true;
-        m.range_period_ns = (uint32_t)std::max(0, std::min(10000000, atoi(f)));
-    }
-    if (m.use_local && m.pace_quads != 0u) {
-        HIP_TRY(m.alloc(m.d_wg_pace, (size_t)m.grid * 4, Mem::Device, 0));
-        HIP_TRY(m.alloc(m.d_pace_adapt, 128, Mem::Exchange, 0));
+    if (m.local.use_local) m.local.pace_quads = m.pm.n_packets <= 25000u ? 0u : (m.pm.n_packets <= 45000u ? 1u : (m.pm.n_packets <= 65000u ? 2u : 2u * std::max(1u, (m.pm.packet_bytes + 352u) / 704u)));
+    m.local.pace_levels = (uint32_t)opt_int("PACE_LEVELS", m.local.pace_levels, 1, 8);
+    m.local.pace_quads = (uint32_t)opt_int("PACE", m.local.pace_quads, 0, 32);
+    m.local.pace_base = (uint32_t)opt_int("PACE_BASE", 0, 0, 64);
+    m.local.pace_carry = opt_int("PACE_CARRY", 1) != 0;
+    m.local.pace_adapt_on = opt_int("PACE_ADAPT", 1) != 0;
+    m.local.pace_period_ns = (uint32_t)opt_int("PACE_PERIOD", 0, 0, 10000000);
+    m.range.range_period_set = opt_set("RANGE_PERIOD");
+    m.range.range_period_ns = (uint32_t)opt_int("RANGE_PERIOD", 0, 0, 10000000);
+    if (m.local.use_local && m.local.pace_quads != 0u) {
+        HIP_TRY(m.alloc(m.local.d_wg_pace, (size_t)m.grid * 4, Mem::Device, 0));
+        HIP_TRY(m.alloc(m.local.d_pace_adapt, 128, Mem::Exchange, 0));
     }
     return TKSPMV_OK;
 }
@@ -1536,19 +1579,19 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
 // single_kernel serves tkspmv_run where the engine streams with local thresholds: a format it is built for (has_single_kernel),
 // at most 512 workgroups (select_local's first cut), one partition per wave of ITS launch (8 waves x grid).
 static int setup_single(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    m.can_single = m.single_mode != 0u && has_single_kernel(m.fmt) && m.grid <= 512u && m.block == 512u &&
-                   d.impl == TKSPMV_IMPL_STREAM && !m.use_radix && m.fused && m.host_path && m.h_res != nullptr &&
+    m.single.can_single = m.local.single_mode != 0u && has_single_kernel(m.fmt) && m.grid <= 512u && m.block == 512u &&
+                   d.impl == TKSPMV_IMPL_STREAM && !m.radix.use_radix && m.defer.fused && m.host.host_path && m.host.h_res != nullptr &&
                    m.pm.part_first.size() <= (size_t)m.grid * 8u;
-    if (const char *f = opt("SINGLE")) m.can_single = m.can_single && atoi(f) != 0;
-    if (!m.can_single) return TKSPMV_OK;
-    HIP_TRY(m.alloc(m.d_lslots, (size_t)m.grid * SINGLE_REC_STRIDE * 8, Mem::Device, 0xFF));  // (a 128-byte line per workgroup: single_kernel's selector)
+    m.single.can_single = m.single.can_single && opt_int("SINGLE", 1) != 0;
+    if (!m.single.can_single) return TKSPMV_OK;
+    HIP_TRY(m.alloc(m.single.d_lslots, (size_t)m.grid * SINGLE_REC_STRIDE * 8, Mem::Device, 0xFF));  // (a 128-byte line per workgroup: single_kernel's selector)
     // workgroup 0 selects (LocalParams::ready) where the partitions fit the grid's other workgroups; option SINGLE_SELECTOR=0:
     // round 4's scheme (every workgroup streams, the one that draws the last ticket selects)
-    if (m.pm.part_first.size() <= (size_t)(m.grid - 1u) * 8u && m.grid >= 2u && (!opt("SINGLE_SELECTOR") || atoi(opt("SINGLE_SELECTOR")) != 0))
-        HIP_TRY(m.alloc(m.d_lready, (size_t)m.grid * 4, Mem::Exchange, 0));
-    HIP_TRY(m.alloc(m.d_lused, (size_t)m.grid * 4, Mem::Device, 0));
-    HIP_TRY(m.alloc(m.d_lprior, ((size_t)m.grid + 32) * 4, Mem::Exchange, 0));
-    HIP_TRY(m.alloc(m.d_lstatus, 128, Mem::Exchange, 0));
+    if (m.pm.part_first.size() <= (size_t)(m.grid - 1u) * 8u && m.grid >= 2u && opt_int("SINGLE_SELECTOR", 1) != 0)
+        HIP_TRY(m.alloc(m.single.d_lready, (size_t)m.grid * 4, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.single.d_lused, (size_t)m.grid * 4, Mem::Device, 0));
+    HIP_TRY(m.alloc(m.single.d_lprior, ((size_t)m.grid + 32) * 4, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(m.single.d_lstatus, 128, Mem::Exchange, 0));
     return TKSPMV_OK;
 }
 
@@ -1561,71 +1604,62 @@ static int setup_single(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::stri
 // (select_body): 32 MB at 1M rows, 320 MB at 10M. Multi-query engines keep one list per set (their groups' selections are
 // owed across launches).
 static int setup_exchange_sets(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    if (const char *f = opt("BATCH_MAX")) m.batch_max = std::max(1, std::min(BATCH_MAX, atoi(f)));
-    const int n_sets_alloc = m.can_multi ? EngineImpl::N_STATE : (m.can_batch ? m.batch_max : (m.can_defer ? 2 : 1));
+    using Sets = EngineImpl::ExchangeSets;
+    m.batch.batch_max = (int)opt_int("BATCH_MAX", BATCH_MAX, 1, BATCH_MAX);
+    const int n_sets_alloc = m.multi.can_multi ? Sets::N_STATE : (m.batch.can_batch ? m.batch.batch_max : (m.defer.can_defer ? 2 : 1));
     const size_t ns = (size_t)n_sets_alloc;
     // (engines that stream with checked local thresholds use the lists for repairs and behind a closed gate only: two; a power of two)
-    int want_lists = m.use_local ? 2 : 4;
-    if (const char *f = opt("OVF_LISTS")) want_lists = atoi(f);
+    int want_lists = (int)opt_int("OVF_LISTS", m.local.use_local ? 2 : 4);
     // (the deferred scheme streams query i + 1 into one set while workgroup 0 selects query i from the other: its two sets need
     //  private lists -- with OVF_LISTS=1 they shared one, the stream appended while the selection read and reset it)
-    if (m.can_defer) want_lists = std::max(want_lists, 2);
+    if (m.defer.can_defer) want_lists = std::max(want_lists, 2);
     want_lists = std::min(std::min(want_lists, 4), n_sets_alloc);
-    m.ovf_lists = m.can_multi ? (uint32_t)n_sets_alloc : (want_lists >= 4 ? 4u : (want_lists >= 2 ? 2u : 1u));
-    const size_t nl = m.ovf_lists;
-    EngineImpl::ExState &E0 = m.st[0];  // (the other sets point into its blocks)
-    HIP_TRY(m.alloc(E0.gmax, ns * EngineImpl::GMAX_WORDS * 4, Mem::Exchange, 0));
-    HIP_TRY(m.alloc(E0.tau_g, ns * EngineImpl::STATE_WORD_STRIDE * 4, Mem::Exchange, 0));
-    HIP_TRY(m.alloc(E0.ovf_count, nl * EngineImpl::STATE_WORD_STRIDE * 4, Mem::Device, 0));
+    m.ex.ovf_lists = m.multi.can_multi ? (uint32_t)n_sets_alloc : (want_lists >= 4 ? 4u : (want_lists >= 2 ? 2u : 1u));
+    const size_t nl = m.ex.ovf_lists;
+    Sets::ExState &E0 = m.ex.st[0];  // (the other sets point into its blocks)
+    HIP_TRY(m.alloc(E0.gmax, ns * Sets::GMAX_WORDS * 4, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(E0.tau_g, ns * Sets::STATE_WORD_STRIDE * 4, Mem::Exchange, 0));
+    HIP_TRY(m.alloc(E0.ovf_count, nl * Sets::STATE_WORD_STRIDE * 4, Mem::Device, 0));
     HIP_TRY(m.alloc(E0.wg_cand, ns * m.grid * WG_SLOTS * 8, Mem::Device, 0xFF));
-    HIP_TRY(m.alloc(E0.ovf, nl * m.ovf_cap * 8));
-    const size_t n_unit = std::max(ns, 2 * (size_t)BATCH_MAX);  // (the batch kernel's scale words: one block per launch parity)
-    HIP_TRY(m.alloc(E0.unit_inv, n_unit * EngineImpl::STATE_WORD_STRIDE * 4));
-    std::vector<float> ones(n_unit * EngineImpl::STATE_WORD_STRIDE, 1.0f);
+    HIP_TRY(m.alloc(E0.ovf, nl * m.ex.ovf_cap * 8));
+    const size_t n_unit = std::max(ns, (size_t)BATCH_MAX);  // (the batch kernel's scale words)
+    HIP_TRY(m.alloc(E0.unit_inv, n_unit * Sets::STATE_WORD_STRIDE * 4));
+    std::vector<float> ones(n_unit * Sets::STATE_WORD_STRIDE, 1.0f);
     HIP_TRY(hipMemcpy(E0.unit_inv, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
     for (int si = 1; si < n_sets_alloc; ++si) {
-        EngineImpl::ExState &E = m.st[si];
-        E.gmax = E0.gmax + (size_t)si * EngineImpl::GMAX_WORDS;
-        E.tau_g = E0.tau_g + (size_t)si * EngineImpl::STATE_WORD_STRIDE;
-        E.ovf_count = E0.ovf_count + ((size_t)si % nl) * EngineImpl::STATE_WORD_STRIDE;
+        Sets::ExState &E = m.ex.st[si];
+        E.gmax = E0.gmax + (size_t)si * Sets::GMAX_WORDS;
+        E.tau_g = E0.tau_g + (size_t)si * Sets::STATE_WORD_STRIDE;
+        E.ovf_count = E0.ovf_count + ((size_t)si % nl) * Sets::STATE_WORD_STRIDE;
         E.wg_cand = E0.wg_cand + (size_t)si * m.grid * WG_SLOTS;
-        E.ovf = E0.ovf + ((size_t)si % nl) * m.ovf_cap;
-        E.unit_inv = E0.unit_inv + (size_t)si * EngineImpl::STATE_WORD_STRIDE;
+        E.ovf = E0.ovf + ((size_t)si % nl) * m.ex.ovf_cap;
+        E.unit_inv = E0.unit_inv + (size_t)si * Sets::STATE_WORD_STRIDE;
     }
-    HIP_TRY(m.alloc(m.d_ovf_epoch, 128, Mem::Exchange, 0));
-    if (m.can_batch) {
+    HIP_TRY(m.alloc(m.ex.d_ovf_epoch, 128, Mem::Exchange, 0));
+    if (m.batch.can_batch) {
         // the workgroups' records of local mode, one block per set; the scratch results of queries that share the last one's buffer
-        // (twice BATCH_MAX sets each: one block per launch parity, EngineImpl::bside)
-        const size_t nr = 2 * (size_t)BATCH_MAX;
-        HIP_TRY(m.alloc(m.d_rec_slots, nr * m.grid * WG_SLOTS * 8, Mem::Device, 0xFF));
-        HIP_TRY(m.alloc(m.d_rec_used, nr * m.grid * 4, Mem::Device, 0));
-        HIP_TRY(m.alloc(m.d_alias_idx, nr * d.k * 4));
-        HIP_TRY(m.alloc(m.d_alias_val, nr * d.k * 4));
-        if (m.use_local) {
-            if (const char *f = opt("OVERLAP")) m.overlap_launches = atoi(f) != 0;
-            if (m.overlap_launches) {  // (the second stream exists only where it is used: every stream is one more for a device-wide wait to visit)
-                HIP_TRY(hipStreamCreateWithFlags(&m.bside, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&m.ev_bfork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&m.ev_bjoin, hipEventDisableTiming));
-            }
-        }
+        const size_t nr = (size_t)BATCH_MAX;
+        HIP_TRY(m.alloc(m.batch.d_rec_slots, nr * m.grid * WG_SLOTS * 8, Mem::Device, 0xFF));
+        HIP_TRY(m.alloc(m.batch.d_rec_used, nr * m.grid * 4, Mem::Device, 0));
+        HIP_TRY(m.alloc(m.batch.d_alias_idx, nr * d.k * 4));
+        HIP_TRY(m.alloc(m.batch.d_alias_val, nr * d.k * 4));
     }
-    m.info.state_bytes = ns * (EngineImpl::GMAX_WORDS * 4 + 2 * EngineImpl::STATE_WORD_STRIDE * 4 + (uint64_t)m.grid * WG_SLOTS * 8) +
-                         nl * ((uint64_t)m.ovf_cap * 8 + EngineImpl::STATE_WORD_STRIDE * 4) +
-                         (m.can_batch ? 2 * (uint64_t)BATCH_MAX * ((uint64_t)m.grid * WG_SLOTS * 8 + (uint64_t)m.grid * 4) : 0);
+    m.info.state_bytes = ns * (Sets::GMAX_WORDS * 4 + 2 * Sets::STATE_WORD_STRIDE * 4 + (uint64_t)m.grid * WG_SLOTS * 8) +
+                         nl * ((uint64_t)m.ex.ovf_cap * 8 + Sets::STATE_WORD_STRIDE * 4) +
+                         (m.batch.can_batch ? (uint64_t)BATCH_MAX * ((uint64_t)m.grid * WG_SLOTS * 8 + (uint64_t)m.grid * 4) : 0);
     return TKSPMV_OK;
 }
 
 // The buffers of the tracing and statistics options and the DEBUG_OCC occupancy report.
 static int setup_diagnostics(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    m.collect_stamps = opt("STAMPS") != nullptr;
-    if (opt("WG_TIMES") && m.use_local) HIP_TRY(m.alloc(m.d_wg_times, (size_t)(BATCH_MAX + 1) * m.grid * 8, Mem::Device, 0));
+    m.diag.collect_stamps = opt("STAMPS") != nullptr;
+    if (opt("WG_TIMES") && m.local.use_local) HIP_TRY(m.alloc(m.diag.d_wg_times, (size_t)(BATCH_MAX + 1) * m.grid * 8, Mem::Device, 0));
     if (opt("TRACE")) {
-        m.trace_words = (size_t)(m.grid + 1) * 9 * 8;
-        HIP_TRY(m.alloc(m.d_trace, m.trace_words * 4 * 8, Mem::Device, 0));
+        m.diag.trace_words = (size_t)(m.grid + 1) * 9 * 8;
+        HIP_TRY(m.alloc(m.diag.d_trace, m.diag.trace_words * 4 * 8, Mem::Device, 0));
     }
-    m.dbg_kernels = m.collect_stats || m.collect_stamps || m.d_trace != nullptr;
-    if (m.dbg_kernels && !has_tracing_twins(m.fmt))
+    m.diag.dbg_kernels = m.diag.collect_stats || m.diag.collect_stamps || m.diag.d_trace != nullptr;
+    if (m.diag.dbg_kernels && !has_tracing_twins(m.fmt))
         fprintf(stderr, "[tkspmv] tracing / statistics hooks exist in the fp32, 4-entries-per-lane, <= 1024-column kernels only: "
                         "this engine runs without them\n");
     return TKSPMV_OK;
@@ -1634,11 +1668,18 @@ static int setup_diagnostics(const tkspmv_desc &d, Setup &S, EngineImpl &m, std:
 // The kernels of this engine's format (behind setup_diagnostics: an engine that traces takes the tracing twins), and the DEBUG_OCC
 // occupancy report about them.
 static int choose_kernels(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    m.kern = kernels_for(m.fmt, m.dbg_kernels);
+    m.kern = kernels_for(m.fmt, m.diag.dbg_kernels);
+    if (m.multi.can_multi) {  // [value type of the row-per-lane copy][queries per pass: 1, 2, 4, 8]
+        static const multi_fn fns[3][4] = {{&multi_kernel<1, VT_F32>, &multi_kernel<2, VT_F32>, &multi_kernel<4, VT_F32>, &multi_kernel<8, VT_F32>},
+                                           {&multi_kernel<1, VT_Q17>, &multi_kernel<2, VT_Q17>, &multi_kernel<4, VT_Q17>, &multi_kernel<8, VT_Q17>},
+                                           {&multi_kernel<1, VT_Q17C12>, &multi_kernel<2, VT_Q17C12>, &multi_kernel<4, VT_Q17C12>, &multi_kernel<8, VT_Q17C12>}};
+        const int q = m.multi.multi_q;
+        m.kern.multi = fns[S.sell_values][q <= 1 ? 0 : (q <= 2 ? 1 : (q <= 4 ? 2 : 3))];
+    }
     if (opt("DEBUG_OCC")) {
         int n1 = -1, n2 = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, reinterpret_cast<const void *>(m.kern.stream[0]), (int)m.block + 64, 0);
-        if (m.can_batch)
+        if (m.batch.can_batch)
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, reinterpret_cast<const void *>(m.kern.batch[0]), (int)m.block + 64, 0);
         fprintf(stderr, "[tkspmv] workgroups per CU by the runtime's occupancy calculator: stream kernel %d, batch kernel %d; LDS per CU %zu\n",
                 n1, n2, S.lds_per_cu);
@@ -1651,21 +1692,38 @@ static int fill_engine_info(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::
     m.info.precision = d.precision;  // the API's enum (fill_info reports the value type of the stream)
     m.info.grid = m.grid;
     m.info.block = m.block;
-    m.info.n_groups = m.n_sets ? m.n_groups_pub : 0;
-    m.info.lds_bytes = m.lds_bytes;
+    m.info.n_groups = m.ex.n_sets ? m.ex.n_groups_pub : 0;
+    m.info.lds_bytes = m.ex.lds_bytes;
     m.info.partitions = d.partitions > 1 ? d.partitions : 1;
     m.info.k_per_partition = d.k_per_partition > 0 ? d.k_per_partition : d.k;
     m.info.device = m.device;
     m.info.num_cus = S.num_cus;
-    m.info.multi_q = m.can_multi ? (uint32_t)m.multi_q : 0u;
-    m.info.multi_bytes = m.can_multi ? S.sell_bytes : 0u;
+    m.info.multi_q = m.multi.can_multi ? (uint32_t)m.multi.multi_q : 0u;
+    m.info.multi_bytes = m.multi.can_multi ? S.sell_bytes : 0u;
     m.info.pack_us = S.pack_us;
     m.info.multi_pack_us = S.sell_pack_us;
     m.info.pack_on_device = S.packed_on_device ? 1u : 0u;
     m.info.claim_sets = 0u;
-    m.info.batch_mode = (m.can_batch ? (m.n_sel_wg | (m.use_local << 8)) : 0u) | (std::min<uint32_t>(S.n_parts_hint, 0xFFFFu) << 16);
+    m.info.batch_mode = (m.batch.can_batch ? (m.batch.n_sel_wg | (m.local.use_local << 8)) : 0u) | (std::min<uint32_t>(S.n_parts_hint, 0xFFFFu) << 16);
     return TKSPMV_OK;
 }
+
+// Pointer lists of a back-to-back sequence: query i = dev_xs + (i % n_x) * cols; its result goes to dev_idx / dev_val + i * k, or,
+// where none are given, into the engine's own pair (every query: the last one wins).
+struct SequenceLists {
+    std::vector<const float *> xs;
+    std::vector<uint32_t *> oi;
+    std::vector<float *> ov;
+    SequenceLists(const EngineImpl &m, const float *dev_xs, int32_t n_x, int32_t count, uint32_t *dev_idx = nullptr, float *dev_val = nullptr)
+        : xs(count), oi(count), ov(count) {
+        const size_t stride = dev_idx ? (size_t)m.desc.k : 0;
+        for (int i = 0; i < count; ++i) {
+            xs[i] = dev_xs + (size_t)(i % n_x) * m.desc.cols;
+            oi[i] = (dev_idx ? dev_idx : m.host.d_out_idx) + (size_t)i * stride;
+            ov[i] = (dev_val ? dev_val : m.host.d_out_val) + (size_t)i * stride;
+        }
+    }
+};
 
 // ---- pacing, tuned on THIS box for THIS matrix (round 5) ----------------------------------------------------------------------
 // The pause per packet of the workgroups that lead the field (BatchParams::pace_quads x pace_levels) decides whether the eight
@@ -1678,44 +1736,32 @@ static const uint32_t PACE_CANDIDATES[][2] = {{2, 6}, {2, 7}, {3, 5}, {4, 4}, {2
 constexpr int N_PACE_CANDIDATES = (int)(sizeof(PACE_CANDIDATES) / sizeof(PACE_CANDIDATES[0]));
 
 // The measurement's synthetic queries: one launch of the batch kernel on the engine's stream.
-struct TuneQueries {
-    int nq;
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    void launch(const EngineImpl &m) const { m.launch_batch(xs.data(), oi.data(), ov.data(), nq, m.stream); }
-};
+static void tune_launch(EngineImpl &m, const SequenceLists &Q) { m.launch_batch(Q.xs.data(), Q.oi.data(), Q.ov.data(), (int)Q.xs.size(), m.stream); }
 
 // Pauses by rank: ms per two launches of every candidate (the better of two passes); leaves the best one in m.
-static int tune_rank_pauses(EngineImpl &m, const TuneQueries &Q, float (&best_ms)[N_PACE_CANDIDATES], int &best, std::string &err) {
+static int tune_rank_pauses(EngineImpl &m, const SequenceLists &Q, float (&best_ms)[N_PACE_CANDIDATES], int &best, std::string &err) {
     for (float &b : best_ms) b = 1e30f;
     // (a GPU that has idled streams 10-15 % slower for its first ~20 ms -- 19.4 us per query falling to 16.7 over thirty launches,
     //  tools/launch_series.py --: the settings are compared on a GPU that has been busy for 64 launches)
-    m.pace_quads = PACE_CANDIDATES[0][0];
-    m.pace_levels = PACE_CANDIDATES[0][1];
-    for (int w = 0; w < 64; ++w) Q.launch(m);
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    m.local.pace_quads = PACE_CANDIDATES[0][0];
+    m.local.pace_levels = PACE_CANDIDATES[0][1];
+    for (int w = 0; w < 64; ++w) tune_launch(m, Q);
+    if (const int st = m.wait_idle(err)) return st;
     for (int pass = 0; pass < 2; ++pass)
         for (int c = 0; c < N_PACE_CANDIDATES; ++c) {
-            m.pace_quads = PACE_CANDIDATES[c][0];
-            m.pace_levels = PACE_CANDIDATES[c][1];
-            Q.launch(m);  // (settles the pauses the setting leads to)
-            HIP_TRY(hipEventRecord(m.ev0, m.stream));
-            Q.launch(m);
-            Q.launch(m);
-            HIP_TRY(hipEventRecord(m.ev1, m.stream));
-            HIP_TRY(hipEventSynchronize(m.ev1));
-            HIP_TRY(m.settle());
+            m.local.pace_quads = PACE_CANDIDATES[c][0];
+            m.local.pace_levels = PACE_CANDIDATES[c][1];
+            tune_launch(m, Q);  // (settles the pauses the setting leads to)
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
+            if (const int st = m.bracket_ms(ms, err, [&] { tune_launch(m, Q); tune_launch(m, Q); })) return st;
+            HIP_TRY(m.settle());
             best_ms[c] = std::min(best_ms[c], ms);
         }
     best = 0;
     for (int c = 1; c < N_PACE_CANDIDATES; ++c)
         if (best_ms[c] < best_ms[best]) best = c;
-    m.pace_quads = PACE_CANDIDATES[best][0];
-    m.pace_levels = PACE_CANDIDATES[best][1];
+    m.local.pace_quads = PACE_CANDIDATES[best][0];
+    m.local.pace_levels = PACE_CANDIDATES[best][1];
     return TKSPMV_OK;
 }
 
@@ -1724,20 +1770,19 @@ static int tune_rank_pauses(EngineImpl &m, const TuneQueries &Q, float (&best_ms
 // is too long by. The best period sits 5-6 % under the time per query of the pauses by rank just measured (rank_ms per two launches;
 // 15.8 us on the pool's fast boxes, 16.0 on a medium one): a coarse grid around that, then half a per cent either side of its best;
 // kept in m.pace_period_ns only if it beats the pauses by rank. Returns the fine search's best period and its ms per two launches.
-static uint32_t tune_timetable(EngineImpl &m, const TuneQueries &Q, float rank_ms, float &period_ms) {
+static uint32_t tune_timetable(EngineImpl &m, const SequenceLists &Q, float rank_ms, float &period_ms) {
     // (ms per TWO launches, the mean over `launches` of them in one go, the better of `passes` such series)
     // (a HIP call that fails leaves `measure_failed` set: the timetable is then not taken, the pauses by rank stay)
     bool measure_failed = false;
     auto measure = [&](uint32_t ns, int passes, int launches) -> float {
-        m.pace_period_ns = ns;
+        m.local.pace_period_ns = ns;
         float b = 1e30f;
         for (int pass = 0; pass < passes; ++pass) {
-            Q.launch(m);
-            bool ok = hipEventRecord(m.ev0, m.stream) == hipSuccess;
-            for (int l = 0; l < launches; ++l) Q.launch(m);
-            ok = ok && hipEventRecord(m.ev1, m.stream) == hipSuccess && hipEventSynchronize(m.ev1) == hipSuccess && m.settle() == hipSuccess;
+            tune_launch(m, Q);
             float ms = 0;
-            ok = ok && hipEventElapsedTime(&ms, m.ev0, m.ev1) == hipSuccess && hipGetLastError() == hipSuccess;
+            std::string why;
+            const bool ok = m.bracket_ms(ms, why, [&] { for (int l = 0; l < launches; ++l) tune_launch(m, Q); }) == TKSPMV_OK &&
+                            m.wait_idle(why) == TKSPMV_OK && hipGetLastError() == hipSuccess;
             if (!ok) {
                 measure_failed = true;
                 return 1e30f;
@@ -1748,7 +1793,7 @@ static uint32_t tune_timetable(EngineImpl &m, const TuneQueries &Q, float rank_m
     };
     period_ms = 1e30f;
     uint32_t period_ns = 0;
-    const double rank_ns = (double)rank_ms * 1e6 / (2.0 * Q.nq);  // per query
+    const double rank_ns = (double)rank_ms * 1e6 / (2.0 * (double)Q.xs.size());  // per query
     static const double grid[] = {0.90, 0.915, 0.93, 0.945, 0.96, 0.975};
     for (double g : grid) {
         const uint32_t ns = (uint32_t)(rank_ns * g);
@@ -1775,19 +1820,19 @@ static uint32_t tune_timetable(EngineImpl &m, const TuneQueries &Q, float rank_m
             period_ns = ns;
         }
     }
-    m.pace_period_ns = (!measure_failed && period_ms < rank_ms * 0.999f) ? period_ns : 0u;
+    m.local.pace_period_ns = (!measure_failed && period_ms < rank_ms * 0.999f) ? period_ns : 0u;
     return period_ns;
 }
 
 // Engines of checked local thresholds that pace at all (every packet size since the pause sits behind the arithmetic: fp16 and the
 // fixed-point streams gain as fp32 does); options PACE / PACE_LEVELS / PACE_BASE / AUTOTUNE=0 keep the static settings.
 static int autotune_pacing(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
-    if (!(m.use_local && m.can_batch && m.pace_quads != 0u && !opt("PACE") && !opt("PACE_LEVELS") && !opt("PACE_BASE") &&
-          (!opt("AUTOTUNE") || atoi(opt("AUTOTUNE")) != 0)))
+    if (!(m.local.use_local && m.batch.can_batch && m.local.pace_quads != 0u && !opt("PACE") && !opt("PACE_LEVELS") && !opt("PACE_BASE") &&
+          opt_int("AUTOTUNE", 1) != 0))
         return TKSPMV_OK;
     // (launches of 32 queries up to the headline's size; fewer queries per launch on larger matrices, so that the measurement stays
     //  at ~150 ms of streaming: 10M rows -- 5.3 ms per launch of 32 -- would spend 1.3 s on it)
-    const int nq = std::max(4, std::min(std::min((int)BATCH_MAX, m.batch_max), (int)(32ull * 80000ull / std::max<uint64_t>(m.pm.n_packets, 1))));
+    const int nq = std::max(4, std::min(std::min((int)BATCH_MAX, m.batch.batch_max), (int)(32ull * 80000ull / std::max<uint64_t>(m.pm.n_packets, 1))));
     std::vector<float> hx((size_t)nq * d.cols);
     uint32_t lcg = 0x1234567u;
     for (float &v : hx) {
@@ -1797,11 +1842,10 @@ static int autotune_pacing(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::s
     ScratchBuffer<float> tx;
     HIP_TRY(hipMalloc((void **)&tx.p, hx.size() * 4));
     HIP_TRY(hipMemcpy(tx.p, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-    TuneQueries Q{nq, std::vector<const float *>(nq), std::vector<uint32_t *>(nq, m.d_out_idx), std::vector<float *>(nq, m.d_out_val)};
-    for (int i = 0; i < nq; ++i) Q.xs[i] = tx.p + (size_t)i * d.cols;
+    const SequenceLists Q(m, tx.p, nq, nq);  // (into the engine's own result pair)
     const auto t_tune = std::chrono::steady_clock::now();
-    const bool adapt_was = m.pace_adapt_on;
-    m.pace_adapt_on = false;  // (the periods are measured as they are given)
+    const bool adapt_was = m.local.pace_adapt_on;
+    m.local.pace_adapt_on = false;  // (the periods are measured as they are given)
     float best_ms[N_PACE_CANDIDATES];
     int best = 0;
     if (const int st = tune_rank_pauses(m, Q, best_ms, best, err)) return st;
@@ -1810,23 +1854,23 @@ static int autotune_pacing(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::s
     if (!opt("PACE_PERIOD")) period_ns = tune_timetable(m, Q, best_ms[best], period_ms);
     const uint32_t tune_us = (uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_tune).count();
     // the engine starts as if nothing had run: no carried thresholds, no pauses, no counters, no trust
-    HIP_TRY(hipMemset(m.d_wg_prior, 0, ((size_t)m.grid + 32) * 4));
-    if (m.d_wg_pace) HIP_TRY(hipMemset(m.d_wg_pace, 0, (size_t)m.grid * 4));
-    if (m.d_wg_sig) HIP_TRY(hipMemset(m.d_wg_sig, 0, (size_t)m.grid * 8 * 4));
-    m.clean_seen = m.distrust_left = 0u;
-    m.trusted_launches = m.late_repairs = 0;
-    m.pace_tune_launches = (uint32_t)m.batch_launches;
-    m.batch_launches = 0;
-    HIP_TRY(hipMemset(m.d_verdict, 0, 512));
-    HIP_TRY(hipMemset(m.d_out_idx, 0, (size_t)d.k * 4));
-    HIP_TRY(hipMemset(m.d_out_val, 0, (size_t)d.k * 4));
-    m.pace_tuned_us = tune_us ? tune_us : 1u;
-    m.pace_adapt_on = adapt_was;
+    HIP_TRY(hipMemset(m.local.d_wg_prior, 0, ((size_t)m.grid + 32) * 4));
+    if (m.local.d_wg_pace) HIP_TRY(hipMemset(m.local.d_wg_pace, 0, (size_t)m.grid * 4));
+    if (m.local.d_wg_sig) HIP_TRY(hipMemset(m.local.d_wg_sig, 0, (size_t)m.grid * 8 * 4));
+    m.trust.clean_seen = m.trust.distrust_left = 0u;
+    m.trust.trusted_launches = m.trust.late_repairs = 0;
+    m.local.pace_tune_launches = (uint32_t)m.batch.batch_launches;
+    m.batch.batch_launches = 0;
+    HIP_TRY(hipMemset(m.trust.d_verdict, 0, 512));
+    HIP_TRY(hipMemset(m.host.d_out_idx, 0, (size_t)d.k * 4));
+    HIP_TRY(hipMemset(m.host.d_out_val, 0, (size_t)d.k * 4));
+    m.local.pace_tuned_us = tune_us ? tune_us : 1u;
+    m.local.pace_adapt_on = adapt_was;
     if (opt("DEBUG_OCC")) {
         fprintf(stderr, "[tkspmv] pacing tuned in %u us:", tune_us);
         for (int c = 0; c < N_PACE_CANDIDATES; ++c)
             fprintf(stderr, " %ux%u %.2f us/q%s", PACE_CANDIDATES[c][0], PACE_CANDIDATES[c][1], best_ms[c] * 1e3 / (2 * nq), c == best ? "*" : "");
-        fprintf(stderr, "; timetable %u ns: %.2f us/q%s\n", period_ns, period_ms * 1e3 / (2 * nq), m.pace_period_ns ? " (kept)" : " (pauses by rank kept)");
+        fprintf(stderr, "; timetable %u ns: %.2f us/q%s\n", period_ns, period_ms * 1e3 / (2 * nq), m.local.pace_period_ns ? " (kept)" : " (pauses by rank kept)");
     }
     return TKSPMV_OK;
 }
@@ -1878,38 +1922,38 @@ int Engine::set_query(const float *host_x, double *elapsed_ns, std::string &err)
     if (!host_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
     auto t0 = std::chrono::high_resolution_clock::now();
     HIP_TRY(hipSetDevice(m.device));
-    if (m.bar_x) {
+    if (m.host.bar_x) {
         // (a launch enqueued earlier may still be reading d_x: tkspmv_run clears x_pending, the asynchronous entry points do not)
-        if (m.x_pending) HIP_TRY(hipStreamSynchronize(m.stream));
-        std::memcpy(m.d_x, host_x, (size_t)m.desc.cols * 4);
-        m.flush_hdp();  // (sfence, HDP flush register written and read back: the stores are in memory before the launch's doorbell)
-        m.x_pending = true;
-        m.d_x_cur = m.d_x;
-        m.have_query = true;
+        if (m.host.x_pending) HIP_TRY(hipStreamSynchronize(m.stream));
+        std::memcpy(m.host.d_x, host_x, (size_t)m.desc.cols * 4);
+        m.host.flush_hdp();  // (sfence, HDP flush register written and read back: the stores are in memory before the launch's doorbell)
+        m.host.x_pending = true;
+        m.host.d_x_cur = m.host.d_x;
+        m.host.have_query = true;
         if (elapsed_ns)
             *elapsed_ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::high_resolution_clock::now() - t0).count();
         return TKSPMV_OK;
     }
-    if (m.host_path && m.h_x) {
+    if (m.host.host_path && m.host.h_x) {
         // (an earlier upload from the staging copy must have been consumed before it is overwritten)
-        if (m.x_pending) HIP_TRY(hipStreamSynchronize(m.stream));
-        std::memcpy(m.h_x, host_x, (size_t)m.desc.cols * 4);
-        if (!m.host_x_direct) {
-            HIP_TRY(hipMemcpyAsync(m.d_x, m.h_x, (size_t)m.desc.cols * 4, hipMemcpyHostToDevice, m.stream));
+        if (m.host.x_pending) HIP_TRY(hipStreamSynchronize(m.stream));
+        std::memcpy(m.host.h_x, host_x, (size_t)m.desc.cols * 4);
+        if (!m.host.host_x_direct) {
+            HIP_TRY(hipMemcpyAsync(m.host.d_x, m.host.h_x, (size_t)m.desc.cols * 4, hipMemcpyHostToDevice, m.stream));
             HIP_TRY(hipEventRecord(m.ev2, m.stream));  // a launch on another stream waits for this upload (order_x)
         }
-        m.x_pending = true;
-        m.d_x_cur = m.host_x_direct ? m.h_x_dev : m.d_x;
-        m.have_query = true;
+        m.host.x_pending = true;
+        m.host.d_x_cur = m.host.host_x_direct ? m.host.h_x_dev : m.host.d_x;
+        m.host.have_query = true;
         if (elapsed_ns)
             *elapsed_ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::high_resolution_clock::now() - t0).count();
         return TKSPMV_OK;
     } else {
-        HIP_TRY(hipMemcpyAsync(m.d_x, host_x, (size_t)m.desc.cols * 4, hipMemcpyHostToDevice, m.stream));
+        HIP_TRY(hipMemcpyAsync(m.host.d_x, host_x, (size_t)m.desc.cols * 4, hipMemcpyHostToDevice, m.stream));
         HIP_TRY(hipStreamSynchronize(m.stream));
     }
-    m.d_x_cur = m.d_x;
-    m.have_query = true;
+    m.host.d_x_cur = m.host.d_x;
+    m.host.have_query = true;
     if (elapsed_ns)
         *elapsed_ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(
                           std::chrono::high_resolution_clock::now() - t0)
@@ -1919,8 +1963,8 @@ int Engine::set_query(const float *host_x, double *elapsed_ns, std::string &err)
 
 int Engine::set_query_device(const float *dev_x, std::string &err) {
     if (!dev_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
-    impl_->d_x_cur = dev_x;
-    impl_->have_query = true;
+    impl_->host.d_x_cur = dev_x;
+    impl_->host.have_query = true;
     return TKSPMV_OK;
 }
 
@@ -1932,36 +1976,16 @@ static int enqueue_on(EngineImpl &m, void *stream, bool writes_result, std::stri
     HIP_TRY(hipSetDevice(m.device));
     if (const int st = launch(s)) return st;
     HIP_TRY(hipGetLastError());
-    if (writes_result) {
-        m.ran = true;
-        m.last_on_host = false;
-    }
+    if (writes_result) m.host.result_on_device();
     return TKSPMV_OK;
 }
-
-// Pointer lists of a back-to-back sequence: query i = dev_xs + (i % n_x) * cols; its result goes to dev_idx / dev_val + i * k, or,
-// where none are given, into the engine's own pair (every query: the last one wins).
-struct SequenceLists {
-    std::vector<const float *> xs;
-    std::vector<uint32_t *> oi;
-    std::vector<float *> ov;
-    SequenceLists(const EngineImpl &m, const float *dev_xs, int32_t n_x, int32_t count, uint32_t *dev_idx = nullptr, float *dev_val = nullptr)
-        : xs(count), oi(count), ov(count) {
-        const size_t stride = dev_idx ? (size_t)m.desc.k : 0;
-        for (int i = 0; i < count; ++i) {
-            xs[i] = dev_xs + (size_t)(i % n_x) * m.desc.cols;
-            oi[i] = (dev_idx ? dev_idx : m.d_out_idx) + (size_t)i * stride;
-            ov[i] = (dev_val ? dev_val : m.d_out_val) + (size_t)i * stride;
-        }
-    }
-};
 
 int Engine::enqueue(const float *dev_x, uint32_t *dev_idx, float *dev_val, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
     if (const int st = m.resolve_query(dev_x, 1, err)) return st;
     return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
         HIP_TRY(m.order_x(dev_x, s));
-        m.launch_query(dev_x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
+        m.launch_query(dev_x, dev_idx ? dev_idx : m.host.d_out_idx, dev_val ? dev_val : m.host.d_out_val, s);
         return TKSPMV_OK;
     });
 }
@@ -2000,7 +2024,7 @@ int Engine::enqueue_list(const float *const *dev_xs, uint32_t *const *dev_idx, f
 int Engine::enqueue_multi(const float *dev_xs, int32_t count, uint32_t *dev_idx, float *dev_val, void *stream,
                           std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs && count == 1) dev_xs = m.d_x_cur;  // the vector installed by tkspmv_set_query / set_query_device
+    if (!dev_xs && count == 1) dev_xs = m.host.d_x_cur;  // the vector installed by tkspmv_set_query / set_query_device
     if (!dev_xs || count < 0 || (dev_idx == nullptr) != (dev_val == nullptr)) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_multi");
     return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
         const SequenceLists L(m, dev_xs, count > 0 ? count : 1, count, dev_idx, dev_val);
@@ -2024,12 +2048,12 @@ int Engine::set_filter(const uint32_t *host_mask, std::string &err) {
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipStreamSynchronize(m.stream));  // (a filtered query enqueued earlier may still read the installed mask)
     if (!host_mask) {
-        m.have_filter = false;
+        m.filter.have_filter = false;
         return TKSPMV_OK;
     }
-    if (!m.d_filter) HIP_TRY(m.alloc(m.d_filter, (size_t)m.mask_words() * 4));
-    HIP_TRY(hipMemcpy(m.d_filter, host_mask, (size_t)m.mask_words() * 4, hipMemcpyHostToDevice));
-    m.have_filter = true;
+    if (!m.filter.d_filter) HIP_TRY(m.alloc(m.filter.d_filter, (size_t)m.mask_words() * 4));
+    HIP_TRY(hipMemcpy(m.filter.d_filter, host_mask, (size_t)m.mask_words() * 4, hipMemcpyHostToDevice));
+    m.filter.have_filter = true;
     return TKSPMV_OK;
 }
 
@@ -2039,18 +2063,17 @@ int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t 
     if (const char *why = m.filter_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr))
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_filtered (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)");
-    if (!dev_mask && !m.have_filter) return fail(err, TKSPMV_ERR_INVALID, "no allow-mask given and none installed (tkspmv_set_filter)");
+    if (!dev_mask && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "no allow-mask given and none installed (tkspmv_set_filter)");
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
         // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
         // after the filtered queries did. Settle them now (the host waits for the engine's stream once).
-        if (!m.pending_checks.empty()) {
-            HIP_TRY(hipStreamSynchronize(m.stream));
-            HIP_TRY(m.settle());
+        if (!m.trust.pending_checks.empty()) {
+            if (const int st = m.wait_idle(err)) return st;
         }
         HIP_TRY(m.order_x(dev_xs, s));
         const SequenceLists L(m, dev_xs, count, count, dev_idx, dev_val);
-        m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, L.oi.data(), L.ov.data(), count, s);
+        m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.filter.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, L.oi.data(), L.ov.data(), count, s);
         return TKSPMV_OK;
     });
 }
@@ -2076,29 +2099,28 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
     if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
     if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx))
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)");
-    if (use_filter && !m.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
     const float *installed = nullptr;
     if (const int st = m.resolve_query(installed, 1, err)) return st;
     HIP_TRY(hipSetDevice(m.device));
-    if (!m.d_range_word) HIP_TRY(m.alloc(m.d_range_word, 128, Mem::Device, 0));
-    if (capacity > m.range_cap) {
+    if (!m.range.d_range_word) HIP_TRY(m.alloc(m.range.d_range_word, 128, Mem::Device, 0));
+    if (capacity > m.range.range_cap) {
         HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's launch is long complete: run_range waits itself)
-        HIP_TRY(m.grow_scratch(m.range_cap, capacity, {{(void **)&m.d_range_idx, (size_t)capacity * 4}, {(void **)&m.d_range_val, (size_t)capacity * 4}}));
+        HIP_TRY(m.grow_scratch(m.range.range_cap, capacity, {{(void **)&m.range.d_range_idx, (size_t)capacity * 4}, {(void **)&m.range.d_range_val, (size_t)capacity * 4}}));
     }
-    HIP_TRY(hipMemcpy(m.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
-    const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.d_range_word), use_filter ? m.d_filter : nullptr, 0,
-                                 capacity ? m.d_range_idx : nullptr, capacity ? m.d_range_val : nullptr, capacity, m.d_range_word + 1, nullptr, err);
+    HIP_TRY(hipMemcpy(m.range.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
+    const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word), use_filter ? m.filter.d_filter : nullptr, 0,
+                                 capacity ? m.range.d_range_idx : nullptr, capacity ? m.range.d_range_val : nullptr, capacity, m.range.d_range_word + 1, nullptr, err);
     if (st != TKSPMV_OK) return st;
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());  // (the host has just waited for the engine's stream)
-    m.x_pending = false;
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    m.host.x_pending = false;
     uint32_t found = 0u;
-    HIP_TRY(hipMemcpy(&found, m.d_range_word + 1, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&found, m.range.d_range_word + 1, 4, hipMemcpyDeviceToHost));
     *count = found;
     const size_t kept = std::min<size_t>(found, capacity);
     if (kept) {
-        HIP_TRY(hipMemcpy(idx, m.d_range_idx, kept * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(val, m.d_range_val, kept * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(idx, m.range.d_range_idx, kept * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(val, m.range.d_range_val, kept * 4, hipMemcpyDeviceToHost));
         sort_tuples(kept, idx, val);
     }
     return TKSPMV_OK;
@@ -2129,8 +2151,7 @@ int Engine::row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs
     HIP_TRY(hipMemcpy(d_rows.p, host_rows, (size_t)count * 4, hipMemcpyHostToDevice));
     m.launch_row_vectors(d_rows.p, count, d_xs.p, d_len.p, m.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());  // (the host has just waited for the engine's stream)
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
     HIP_TRY(hipMemcpy(host_xs, d_xs.p, xs_bytes, hipMemcpyDeviceToHost));
     if (host_len) HIP_TRY(hipMemcpy(host_len, d_len.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
@@ -2142,27 +2163,26 @@ int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclud
     if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     HIP_TRY(hipSetDevice(m.device));
     const size_t k = (size_t)m.desc.k, cols = m.desc.cols;
-    const uint32_t chunk_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(EngineImpl::SIMILAR_MAX_ROWS, EngineImpl::SIMILAR_MAX_BYTES / (cols * 4)));
+    const uint32_t chunk_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(EngineImpl::Similar::SIMILAR_MAX_ROWS, EngineImpl::Similar::SIMILAR_MAX_BYTES / (cols * 4)));
     const uint32_t want = std::min<uint32_t>((uint32_t)count, chunk_max);
-    if (want > m.sim_cap) {
-        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: run_similar waits itself)
-        HIP_TRY(m.settle());
-        HIP_TRY(m.grow_scratch(m.sim_cap, want, {{(void **)&m.d_sim_rows, (size_t)want * 4}, {(void **)&m.d_sim_xs, (size_t)want * cols * 4},
-                                                 {(void **)&m.d_sim_idx, (size_t)want * k * 4}, {(void **)&m.d_sim_val, (size_t)want * k * 4}}));
+    if (want > m.similar.sim_cap) {
+        if (const int st = m.wait_idle(err)) return st;  // (an earlier call's chunks are long complete: run_similar waits itself)
+        HIP_TRY(m.grow_scratch(m.similar.sim_cap, want, {{(void **)&m.similar.d_sim_rows, (size_t)want * 4}, {(void **)&m.similar.d_sim_xs, (size_t)want * cols * 4},
+                                                 {(void **)&m.similar.d_sim_idx, (size_t)want * k * 4}, {(void **)&m.similar.d_sim_val, (size_t)want * k * 4}}));
     }
-    for (int32_t i0 = 0; i0 < count; i0 += (int32_t)m.sim_cap) {
-        const int32_t c = std::min<int32_t>((int32_t)m.sim_cap, count - i0);
+    for (int32_t i0 = 0; i0 < count; i0 += (int32_t)m.similar.sim_cap) {
+        const int32_t c = std::min<int32_t>((int32_t)m.similar.sim_cap, count - i0);
         // upload ids, row vectors, the batch sequence, then WAIT: under REPAIR=host a trusted batch launch may be repaired from the
         // host's next wait (settle()); the repair reads the query vectors again and writes the results again, so the scratch vectors
         // must not be overwritten and the results not be read before the engine has settled.
-        HIP_TRY(hipMemcpy(m.d_sim_rows, host_rows + i0, (size_t)c * 4, hipMemcpyHostToDevice));
-        m.launch_row_vectors(m.d_sim_rows, c, m.d_sim_xs, nullptr, m.stream);
+        HIP_TRY(hipMemcpy(m.similar.d_sim_rows, host_rows + i0, (size_t)c * 4, hipMemcpyHostToDevice));
+        m.launch_row_vectors(m.similar.d_sim_rows, c, m.similar.d_sim_xs, nullptr, m.stream);
         HIP_TRY(hipGetLastError());
-        int st = enqueue_batch(m.d_sim_xs, c, m.d_sim_idx, m.d_sim_val, nullptr, err);
+        int st = enqueue_batch(m.similar.d_sim_xs, c, m.similar.d_sim_idx, m.similar.d_sim_val, nullptr, err);
         if (st == TKSPMV_OK) st = synchronize(err);
         if (st != TKSPMV_OK) return st;
-        HIP_TRY(hipMemcpy(idx + (size_t)i0 * k, m.d_sim_idx, (size_t)c * k * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(val + (size_t)i0 * k, m.d_sim_val, (size_t)c * k * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(idx + (size_t)i0 * k, m.similar.d_sim_idx, (size_t)c * k * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(val + (size_t)i0 * k, m.similar.d_sim_val, (size_t)c * k * 4, hipMemcpyDeviceToHost));
     }
     if (exclude_self) {
         // the query's own row leaves its list: the rest moves up, the last slot becomes the pad (0, 0.0f)
@@ -2185,28 +2205,24 @@ int Engine::time_multi(const float *dev_xs, int32_t n_x, int32_t iters, double *
     EngineImpl &m = *impl_;
     if (!dev_xs || n_x < 1 || iters < 1 || !ns_per_query) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_multi");
     HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
-    HIP_TRY(hipEventRecord(m.ev0, m.stream));
-    {
+    if (const int st = m.wait_idle(err)) return st;
+    float ms = 0;
+    const int timed = m.bracket_ms(ms, err, [&] {
         SequenceLists L(m, dev_xs, n_x, iters);
-        if (m.d_multi_out_idx) {  // a result buffer per query in flight (two groups): the two chains may run
+        if (m.multi.d_multi_out_idx) {  // a result buffer per query in flight (two groups): the two chains may run
             for (int i = 0; i < iters; ++i) {
                 const size_t slot = (size_t)(i % (2 * MULTI_Q_MAX)) * (size_t)m.desc.k;
-                L.oi[i] = m.d_multi_out_idx + slot;
-                L.ov[i] = m.d_multi_out_val + slot;
+                L.oi[i] = m.multi.d_multi_out_idx + slot;
+                L.ov[i] = m.multi.d_multi_out_val + slot;
             }
         }
         m.launch_multi_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
-    }
-    HIP_TRY(hipEventRecord(m.ev1, m.stream));
-    HIP_TRY(hipEventSynchronize(m.ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
+    });
+    if (timed != TKSPMV_OK) return timed;
     *ns_per_query = (double)ms * 1e6 / iters;
-    if (m.collect_stats) {  // TKSPMV_STATS=1: candidate-path counters of the multi-query kernel, per query
+    if (m.diag.collect_stats) {  // TKSPMV_STATS=1: candidate-path counters of the multi-query kernel, per query
         unsigned long long st[32];
-        HIP_TRY(hipMemcpy(st, m.d_stats, sizeof(st), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st, m.diag.d_stats, sizeof(st), hipMemcpyDeviceToHost));
         const double n = (double)iters;
         fprintf(stderr, "[tkspmv multi stats per query] judged slices: offers %.1f rows %.1f (tau<=0: %.1f) overflowed %.1f | held slices: offers %.1f rows %.1f "
                         "(tau<=0: %.1f) overflowed %.1f | waits %.1f, %.2f us each\n",
@@ -2214,15 +2230,14 @@ int Engine::time_multi(const float *dev_xs, int32_t n_x, int32_t iters, double *
                 st[12] ? st[13] * 0.01 / st[12] : 0.0);
         // (kept for tkspmv_debug_counters: the guard of the passes' threshold exchange is a COUNT -- waves that ran into their
         //  bounded wait, rows that overflowed a list -- not a wall clock)
-        m.multi_stat_queries += (uint64_t)iters;
-        m.multi_waits += st[12];
-        m.multi_wait_ticks += st[13];
-        m.multi_rows_offered += st[5] + st[9];
-        m.multi_rows_overflowed += st[7] + st[11];
-        HIP_TRY(hipMemset(m.d_stats, 0, 32 * 8));
+        m.multi.multi_stat_queries += (uint64_t)iters;
+        m.multi.multi_waits += st[12];
+        m.multi.multi_wait_ticks += st[13];
+        m.multi.multi_rows_offered += st[5] + st[9];
+        m.multi.multi_rows_overflowed += st[7] + st[11];
+        HIP_TRY(hipMemset(m.diag.d_stats, 0, 32 * 8));
     }
-    m.ran = true;
-    m.last_on_host = false;
+    m.host.result_on_device();
     return TKSPMV_OK;
 }
 
@@ -2230,7 +2245,7 @@ int Engine::enqueue_deferred(const float *dev_x, uint32_t *dev_idx, float *dev_v
     EngineImpl &m = *impl_;
     if (!dev_x) return fail(err, TKSPMV_ERR_INVALID, "query vector is NULL");
     return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
-        m.launch_deferred(dev_x, dev_idx ? dev_idx : m.d_out_idx, dev_val ? dev_val : m.d_out_val, s);
+        m.launch_deferred(dev_x, dev_idx ? dev_idx : m.host.d_out_idx, dev_val ? dev_val : m.host.d_out_val, s);
         return TKSPMV_OK;
     });
 }
@@ -2245,20 +2260,20 @@ int Engine::drain(void *stream, std::string &err) {
 
 int Engine::run(double *kernel_ns, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
+    if (!m.host.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
     HIP_TRY(hipSetDevice(m.device));
     // The fused single launch can hand its result to the host itself (see h_res); the other launch schemes (radix select,
     // row per lane, unfused selection) complete in stream order and are waited for with the event.
-    const bool to_host = m.host_path && m.h_res && m.fused && !m.use_radix && !(m.desc.impl == TKSPMV_IMPL_ROW_PER_LANE && m.can_multi);
-    const bool events = kernel_ns && (m.run_events || !to_host);
+    const bool to_host = m.host.host_path && m.host.h_res && m.defer.fused && !m.radix.use_radix && !(m.desc.impl == TKSPMV_IMPL_ROW_PER_LANE && m.multi.can_multi);
+    const bool events = kernel_ns && (m.host.run_events || !to_host);
     const auto t_host0 = std::chrono::steady_clock::now();
     if (events) HIP_TRY(hipEventRecord(m.ev0, m.stream));
     // The result flag of the launch with the current epoch, polled (never longer than 2 s), and the block behind it verified.
     auto wait_flag = [&]() -> bool {
-        volatile uint32_t *flag = m.h_res + 2 * (size_t)m.desc.k;
+        volatile uint32_t *flag = m.host.h_res + 2 * (size_t)m.desc.k;
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t spins = 0;; ++spins) {
-            if (*flag == m.host_epoch && m.result_block_complete(m.host_epoch)) return true;
+            if (*flag == m.host.host_epoch && m.result_block_complete(m.host.host_epoch)) return true;
             __builtin_ia32_pause();
             if ((spins & 0xFFFFu) == 0xFFFFu && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return false;
         }
@@ -2267,30 +2282,30 @@ int Engine::run(double *kernel_ns, std::string &err) {
     double own_ticks = 0.0;  // the launches' own durations (100 MHz ticks: first workgroup's entry -> result flag)
     if (to_host) {
         m.drain(m.stream);
-        if (m.can_single) {
+        if (m.single.can_single) {
             // workgroup-local thresholds, checked by the selection (kernels/local.hpp); a failed check -- a query unlike the ones
             // before it -- sends the query through the exact launch below
-            m.launch_single(m.d_x_cur, m.d_out_idx, m.d_out_val, m.stream, true);
+            m.launch_single(m.host.d_x_cur, m.host.d_out_idx, m.host.d_out_val, m.stream, true);
             HIP_TRY(hipGetLastError());
             seen = wait_flag();
-            if (seen) own_ticks += (double)m.h_res[2 * (size_t)m.desc.k + 1];
+            if (seen) own_ticks += (double)m.host.h_res[2 * (size_t)m.desc.k + 1];
         }
-        if (!m.can_single || !seen || m.h_res[2 * (size_t)m.desc.k + 5] != 0u) {
-            if (m.can_single) ++m.single_repairs;
-            m.h_res[2 * (size_t)m.desc.k + 5] = 0u;  // (only single_kernel writes the status word: the exact launch's block has none)
-            m.launch_stream(m.d_x_cur, m.d_out_idx, m.d_out_val, m.stream, true);
+        if (!m.single.can_single || !seen || m.host.h_res[2 * (size_t)m.desc.k + 5] != 0u) {
+            if (m.single.can_single) ++m.single.single_repairs;
+            m.host.h_res[2 * (size_t)m.desc.k + 5] = 0u;  // (only single_kernel writes the status word: the exact launch's block has none)
+            m.launch_stream(m.host.d_x_cur, m.host.d_out_idx, m.host.d_out_val, m.stream, true);
             HIP_TRY(hipGetLastError());
             seen = wait_flag();
-            if (seen) own_ticks += (double)m.h_res[2 * (size_t)m.desc.k + 1];
+            if (seen) own_ticks += (double)m.host.h_res[2 * (size_t)m.desc.k + 1];
         }
     } else {
-        m.launch_query(m.d_x_cur, m.d_out_idx, m.d_out_val, m.stream);
+        m.launch_query(m.host.d_x_cur, m.host.d_out_idx, m.host.d_out_val, m.stream);
     }
     HIP_TRY(hipGetLastError());
     if (events) HIP_TRY(hipEventRecord(m.ev1, m.stream));
     if (!seen) HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(m.settle());
-    m.x_pending = false;  // the kernel has read x: the staging copy is free again
+    m.host.x_pending = false;  // the kernel has read x: the staging copy is free again
     if (kernel_ns && !events) {
         // the kernels' own durations, or the host clock if the flag never came
         if (seen) *kernel_ns = own_ticks * 10.0;
@@ -2306,34 +2321,31 @@ int Engine::run(double *kernel_ns, std::string &err) {
         HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
         *kernel_ns = (double)ms * 1e6;
     }
-    m.ran = true;
-    m.last_on_host = seen;
+    m.host.ran = true;
+    m.host.last_on_host = seen;
     return TKSPMV_OK;
 }
 
 int Engine::synchronize(std::string &err) {
     HIP_TRY(hipSetDevice(impl_->device));
     impl_->drain(impl_->stream);
-    HIP_TRY(hipStreamSynchronize(impl_->stream));
-    HIP_TRY(impl_->settle());
-    return TKSPMV_OK;
+    return impl_->wait_idle(err);
 }
 
 int Engine::read(uint32_t *idx, float *val, int32_t *n, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.ran) return fail(err, TKSPMV_ERR_STATE, "no query has been run");
-    if (m.last_on_host) {  // tkspmv_run left the result in pinned host memory
-        if (idx) std::memcpy(idx, m.h_res, (size_t)m.desc.k * 4);
-        if (val) std::memcpy(val, m.h_res + m.desc.k, (size_t)m.desc.k * 4);
+    if (!m.host.ran) return fail(err, TKSPMV_ERR_STATE, "no query has been run");
+    if (m.host.last_on_host) {  // tkspmv_run left the result in pinned host memory
+        if (idx) std::memcpy(idx, m.host.h_res, (size_t)m.desc.k * 4);
+        if (val) std::memcpy(val, m.host.h_res + m.desc.k, (size_t)m.desc.k * 4);
         if (n) *n = m.desc.k;
         return TKSPMV_OK;
     }
     HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
-    m.x_pending = false;
-    if (idx) HIP_TRY(hipMemcpy(idx, m.d_out_idx, (size_t)m.desc.k * 4, hipMemcpyDeviceToHost));
-    if (val) HIP_TRY(hipMemcpy(val, m.d_out_val, (size_t)m.desc.k * 4, hipMemcpyDeviceToHost));
+    if (const int st = m.wait_idle(err)) return st;
+    m.host.x_pending = false;
+    if (idx) HIP_TRY(hipMemcpy(idx, m.host.d_out_idx, (size_t)m.desc.k * 4, hipMemcpyDeviceToHost));
+    if (val) HIP_TRY(hipMemcpy(val, m.host.d_out_val, (size_t)m.desc.k * 4, hipMemcpyDeviceToHost));
     if (n) *n = m.desc.k;
     return TKSPMV_OK;
 }
@@ -2345,78 +2357,76 @@ int Engine::debug_counters(unsigned long long *out, int n, std::string &err) {
     EngineImpl &m = *impl_;
     if (!out || n < 6) return fail(err, TKSPMV_ERR_INVALID, "debug_counters needs room for 6 values");
     HIP_TRY(hipSetDevice(m.device));
-    if (m.stream) HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    if (const int st = m.wait_idle(err)) return st;
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (m.d_wg_prior) HIP_TRY(hipMemcpy(w, m.d_wg_prior + m.grid, sizeof(w), hipMemcpyDeviceToHost));
+    if (m.local.d_wg_prior) HIP_TRY(hipMemcpy(w, m.local.d_wg_prior + m.grid, sizeof(w), hipMemcpyDeviceToHost));
     out[0] = w[3];
     out[1] = w[1];
     out[2] = w[0];
-    out[3] = m.batch_launches;
-    out[4] = w[(m.batch_launches & 1u) ? 7 : 4];  // launches the gate of the local thresholds stays closed for (the next launch's copy)
+    out[3] = m.batch.batch_launches;
+    out[4] = w[(m.batch.batch_launches & 1u) ? 7 : 4];  // launches the gate of the local thresholds stays closed for (the next launch's copy)
     out[5] = w[5];  // length of its latest closure
     if (n >= 10) {  // tkspmv_run through single_kernel: launches, queries sent on through the exact launch, failed checks, suspension
         uint32_t s[4] = {0, 0, 0, 0};
-        if (m.d_lprior) HIP_TRY(hipMemcpy(s, m.d_lprior + m.grid, sizeof(s), hipMemcpyDeviceToHost));
-        out[6] = m.single_launches;
-        out[7] = m.single_repairs;
+        if (m.single.d_lprior) HIP_TRY(hipMemcpy(s, m.single.d_lprior + m.grid, sizeof(s), hipMemcpyDeviceToHost));
+        out[6] = m.single.single_launches;
+        out[7] = m.single.single_repairs;
         out[8] = s[3];
         out[9] = s[0];
     }
     if (n >= 12) {  // round 5: batch launches that went out without a repair launch behind them, and the late repairs they cost
-        out[10] = m.trusted_launches;
-        out[11] = m.late_repairs;
+        out[10] = m.trust.trusted_launches;
+        out[11] = m.trust.late_repairs;
     }
     if (n >= 14) {  // the pacing in force: quantum | levels << 8 | base << 16, and what tkspmv_create's measurement of it took (us; 0: not measured)
-        out[12] = m.pace_quads | (m.pace_levels << 8) | (m.pace_base << 16) | ((uint64_t)m.pace_period_ns << 32);  // (upper half: the timetable's period, ns per query; 0: pauses by rank)
-        out[13] = m.pace_tuned_us | ((uint64_t)m.pace_tune_launches << 32);  // (upper half: the batch launches the measurement made)
+        out[12] = m.local.pace_quads | (m.local.pace_levels << 8) | (m.local.pace_base << 16) | ((uint64_t)m.local.pace_period_ns << 32);  // (upper half: the timetable's period, ns per query; 0: pauses by rank)
+        out[13] = m.local.pace_tuned_us | ((uint64_t)m.local.pace_tune_launches << 32);  // (upper half: the batch launches the measurement made)
     }
     if (n >= 19) {  // option STATS, summed over the tkspmv_time_multi calls so far: queries, bounded waits for a threshold (count, ticks of 10 ns), rows offered / overflowed
-        out[14] = m.multi_stat_queries;
-        out[15] = m.multi_waits;
-        out[16] = m.multi_wait_ticks;
-        out[17] = m.multi_rows_offered;
-        out[18] = m.multi_rows_overflowed;
+        out[14] = m.multi.multi_stat_queries;
+        out[15] = m.multi.multi_waits;
+        out[16] = m.multi.multi_wait_ticks;
+        out[17] = m.multi.multi_rows_offered;
+        out[18] = m.multi.multi_rows_overflowed;
     }
     return TKSPMV_OK;
 }
 
 int Engine::read_trace(unsigned long long *host, size_t max_words, size_t *words, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.d_trace && m.d_wg_times) {  // option WG_TIMES: [BATCH_MAX + 1][grid] hand-over stamps of the last batch launch
+    if (!m.diag.d_trace && m.diag.d_wg_times) {  // option WG_TIMES: [BATCH_MAX + 1][grid] hand-over stamps of the last batch launch
         HIP_TRY(hipSetDevice(m.device));
         HIP_TRY(hipDeviceSynchronize());
         const size_t n = std::min(max_words, (size_t)(BATCH_MAX + 1) * m.grid);
-        HIP_TRY(hipMemcpy(host, m.d_wg_times, n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host, m.diag.d_wg_times, n * 8, hipMemcpyDeviceToHost));
         if (words) *words = n;
         return TKSPMV_OK;
     }
-    if (!m.d_trace) return fail(err, TKSPMV_ERR_STATE, "tracing is off (set TKSPMV_TRACE=1 before tkspmv_create)");
+    if (!m.diag.d_trace) return fail(err, TKSPMV_ERR_STATE, "tracing is off (set TKSPMV_TRACE=1 before tkspmv_create)");
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipDeviceSynchronize());
-    const size_t n = std::min(max_words, m.trace_words * 4);
-    HIP_TRY(hipMemcpy(host, m.d_trace, n * 8, hipMemcpyDeviceToHost));
+    const size_t n = std::min(max_words, m.diag.trace_words * 4);
+    HIP_TRY(hipMemcpy(host, m.diag.d_trace, n * 8, hipMemcpyDeviceToHost));
     if (words) *words = n;
     return TKSPMV_OK;
 }
 
 int Engine::result_device(const uint32_t **dev_idx, const float **dev_val) {
-    if (dev_idx) *dev_idx = impl_->d_out_idx;
-    if (dev_val) *dev_val = impl_->d_out_val;
+    if (dev_idx) *dev_idx = impl_->host.d_out_idx;
+    if (dev_val) *dev_val = impl_->host.d_out_val;
     return TKSPMV_OK;
 }
 
 int Engine::scores(float *host_y, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!m.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed");
+    if (!m.host.have_query) return fail(err, TKSPMV_ERR_STATE, "no query vector installed");
     HIP_TRY(hipSetDevice(m.device));
-    if (!m.d_scores) HIP_TRY(m.alloc(m.d_scores, std::max<size_t>(m.desc.rows, 1) * 4));
-    HIP_TRY(hipMemsetAsync(m.d_scores, 0, std::max<size_t>(m.desc.rows, 1) * 4, m.stream));
-    m.launch_scores(m.d_x_cur, m.stream);
+    if (!m.diag.d_scores) HIP_TRY(m.alloc(m.diag.d_scores, std::max<size_t>(m.desc.rows, 1) * 4));
+    HIP_TRY(hipMemsetAsync(m.diag.d_scores, 0, std::max<size_t>(m.desc.rows, 1) * 4, m.stream));
+    m.launch_scores(m.host.d_x_cur, m.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host_y, m.d_scores, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost, m.stream));
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    HIP_TRY(hipMemcpyAsync(host_y, m.diag.d_scores, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost, m.stream));
+    if (const int st = m.wait_idle(err)) return st;
     return TKSPMV_OK;
 }
 
@@ -2430,12 +2440,12 @@ int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double
     HIP_TRY(hipStreamSynchronize(m.stream));
     const double h1 = host_times ? now_us() : 0.0;
     // (batch launches on one stream: the bracket's events travel with the first and the last kernel; any other path records them)
-    const int ext_mode = opt("EXT_EVENTS") ? atoi(opt("EXT_EVENTS")) : 1;
-    const bool ext = m.can_batch && !(m.overlap_launches && m.bside) && ext_mode != 0;
-    m.ext_record = ext && ext_mode == 2;
+    const int ext_mode = (int)opt_int("EXT_EVENTS", 1);
+    const bool ext = m.batch.can_batch && ext_mode != 0;
+    m.batch.ext_record = ext && ext_mode == 2;
     if (ext) {
-        m.ext_start = m.ev0;
-        m.ext_stop = m.ev1;
+        m.batch.ext_start = m.ev0;
+        m.batch.ext_stop = m.ev1;
     } else {
         HIP_TRY(hipEventRecord(m.ev0, m.stream));
     }
@@ -2445,8 +2455,8 @@ int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double
     }
     if (!ext) HIP_TRY(hipEventRecord(m.ev1, m.stream));
     const double h2 = host_times ? now_us() : 0.0;
-    if (m.ext_start || m.ext_stop) {  // (cannot happen: every batch path launches through launch_batch)
-        m.ext_start = m.ext_stop = nullptr;
+    if (m.batch.ext_start || m.batch.ext_stop) {  // (cannot happen: every batch path launches through launch_batch)
+        m.batch.ext_start = m.batch.ext_stop = nullptr;
         err = "time_queries: the region's events were not attached to its launches";
         return TKSPMV_ERR_STATE;
     }
@@ -2469,8 +2479,7 @@ int Engine::time_queries(const float *dev_xs, int32_t n_x, int32_t iters, double
         fprintf(stderr, "[tkspmv] time_queries(%d): entry + wait for the idle stream %.1f us, lists + launches %.1f, until the end event is seen %.1f (the region itself %.1f), verdicts %.1f, elapsed time %.1f\n",
                 iters, h1 - h0, h2 - h1, h3 - h2, (double)ms * 1e3, h4 - h3, now_us() - h4);
     *ns_per_query = (double)ms * 1e6 / iters;
-    m.ran = true;
-    m.last_on_host = false;
+    m.host.result_on_device();
     return TKSPMV_OK;
 }
 
@@ -2482,8 +2491,7 @@ int Engine::time_query_batches(const float *dev_xs, int32_t n_x, int32_t iters, 
     EngineImpl &m = *impl_;
     if (!dev_xs || n_x < 1 || iters < 1 || reps < 1 || reps > 4096 || !ns_per_query) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to time_query_batches");
     HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    if (const int st = m.wait_idle(err)) return st;
     ScratchEvents scratch_events((size_t)reps + 1);
     std::vector<hipEvent_t> &evs = scratch_events.e;
     for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
@@ -2501,8 +2509,7 @@ int Engine::time_query_batches(const float *dev_xs, int32_t n_x, int32_t iters, 
         HIP_TRY(hipEventElapsedTime(&ms, evs[(size_t)r], evs[(size_t)r + 1]));
         ns_per_query[r] = (double)ms * 1e6 / iters;
     }
-    m.ran = true;
-    m.last_on_host = false;
+    m.host.result_on_device();
     return TKSPMV_OK;
 }
 
@@ -2516,14 +2523,14 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
     HIP_TRY(hipSetDevice(m.device));
     const uint32_t stream_block = m.block;  // the streaming waves of a workgroup (the server wave of a sequence launch aside)
     ReadProbeParams R{};
-    R.n_replicas = m.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(m.d_replicas.size(), 8);
-    for (uint32_t r = 0; r < 8u; ++r) R.replicas[r] = m.d_replicas.empty() ? m.d_packets : m.d_replicas[r % m.d_replicas.size()];
-    R.part_first = m.d_part_first;
-    R.part_count = m.d_part_count;
+    R.n_replicas = m.mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(m.mat.d_replicas.size(), 8);
+    for (uint32_t r = 0; r < 8u; ++r) R.replicas[r] = m.mat.packets(r);
+    R.part_first = m.mat.d_part_first;
+    R.part_count = m.mat.d_part_count;
     R.n_parts = (uint32_t)m.pm.part_first.size();
     R.n_pass = (uint32_t)passes;
-    if (const char *f = opt("READ_PROBE_MAP")) R.map = (uint32_t)atoi(f);
-    if (const char *f = opt("READ_PROBE_PERIOD")) R.period = (uint32_t)std::min<uint64_t>(0xFFFFFF00ull, (uint64_t)std::max(0, atoi(f)) * 256u / 10u);  // ns per pass: the probe on a timetable
+    R.map = (uint32_t)opt_int("READ_PROBE_MAP", 0);
+    R.period = period_units((uint64_t)opt_int("READ_PROBE_PERIOD", 0, 0, 0x7FFFFFFF));  // ns per pass: the probe on a timetable
     ScratchBuffer<uint32_t> sink;
     const size_t n_end = (size_t)m.grid * 16;
     HIP_TRY(hipMalloc((void **)&sink.p, (size_t)m.grid * 16 * 4 + (size_t)(passes + 2) * 128 + n_end * 8));
@@ -2553,19 +2560,14 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
         }
     }
     if (!fn) return fail(err, TKSPMV_ERR_UNSUPPORTED, "no read probe for this packet size");
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    if (const int st = m.wait_idle(err)) return st;
     R.n_pass = 2;  // (warm-up: code object, clocks)
     HIP_TRY(hipMemsetAsync(R.claim, 0, (size_t)(passes + 2) * 128, m.stream));
     hipLaunchKernelGGL(fn, dim3(m.grid), dim3(stream_block), 0, m.stream, R);
     R.n_pass = (uint32_t)passes;
     HIP_TRY(hipMemsetAsync(R.claim, 0, (size_t)(passes + 2) * 128, m.stream));
-    HIP_TRY(hipEventRecord(m.ev0, m.stream));
-    hipLaunchKernelGGL(fn, dim3(m.grid), dim3(stream_block), 0, m.stream, R);
-    HIP_TRY(hipEventRecord(m.ev1, m.stream));
-    HIP_TRY(hipEventSynchronize(m.ev1));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
+    if (const int st = m.bracket_ms(ms, err, [&] { hipLaunchKernelGGL(fn, dim3(m.grid), dim3(stream_block), 0, m.stream, R); })) return st;
     HIP_TRY(hipGetLastError());
     if (want_ends) {
         std::vector<unsigned long long> te(n_end);
@@ -2610,23 +2612,19 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
     if (!dev_xs || n_x < 1 || iters < 1 || !out) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to profile");
     std::memset(out, 0, sizeof(*out));
     HIP_TRY(hipSetDevice(m.device));
-    HIP_TRY(hipStreamSynchronize(m.stream));
-    HIP_TRY(m.settle());
+    if (const int st = m.wait_idle(err)) return st;
     unsigned long long st0[8], st1[8];
-    HIP_TRY(hipMemcpy(st0, m.d_stats, sizeof(st0), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st0, m.diag.d_stats, sizeof(st0), hipMemcpyDeviceToHost));
     const size_t stride = m.desc.cols;
     // (1) whole queries back-to-back
-    HIP_TRY(hipEventRecord(m.ev0, m.stream));
-    {
+    float ms = 0;
+    const int timed = m.bracket_ms(ms, err, [&] {
         const SequenceLists L(m, dev_xs, n_x, iters);
         m.launch_sequence(L.xs.data(), L.oi.data(), L.ov.data(), iters, m.stream);
-    }
-    HIP_TRY(hipEventRecord(m.ev1, m.stream));
-    HIP_TRY(hipEventSynchronize(m.ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, m.ev0, m.ev1));
+    });
+    if (timed != TKSPMV_OK) return timed;
     out->query_ns = (double)ms * 1e6 / iters;
-    HIP_TRY(hipMemcpy(st1, m.d_stats, sizeof(st1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st1, m.diag.d_stats, sizeof(st1), hipMemcpyDeviceToHost));
     out->candidates_avg = (double)(st1[0] - st0[0]) / (double)std::max<unsigned long long>(1, st1[1] - st0[1]);
     out->slow_paths_avg = (double)(st1[4] - st0[4]) / (double)std::max<unsigned long long>(1, st1[1] - st0[1]);
     out->appended_avg = (double)(st1[5] - st0[5]) / (double)std::max<unsigned long long>(1, st1[1] - st0[1]);
@@ -2635,16 +2633,17 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
     // next kernel to the interval).
     double t_stream = 0, t_select = 0;
     {
-        std::vector<hipEvent_t> evs((size_t)iters * 2 + 1);
+        ScratchEvents scratch_events((size_t)iters * 2 + 1);
+        std::vector<hipEvent_t> &evs = scratch_events.e;
         for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
         for (int i = 0; i < iters; ++i) {
             const float *x = dev_xs + (size_t)(i % n_x) * stride;
             HIP_TRY(hipEventRecord(evs[2 * i], m.stream));
-            if (m.use_radix) m.launch_query(x, m.d_out_idx, m.d_out_val, m.stream);  // (scores + radix select + selection)
-            else if (m.can_single) m.launch_single(x, m.d_out_idx, m.d_out_val, m.stream, false);  // (what tkspmv_run launches)
-            else m.launch_stream(x, m.d_out_idx, m.d_out_val, m.stream);
+            if (m.radix.use_radix) m.launch_query(x, m.host.d_out_idx, m.host.d_out_val, m.stream);  // (scores + radix select + selection)
+            else if (m.single.can_single) m.launch_single(x, m.host.d_out_idx, m.host.d_out_val, m.stream, false);  // (what tkspmv_run launches)
+            else m.launch_stream(x, m.host.d_out_idx, m.host.d_out_val, m.stream);
             HIP_TRY(hipEventRecord(evs[2 * i + 1], m.stream));
-            if (!m.fused && !m.use_radix) m.launch_select(m.d_out_idx, m.d_out_val, m.stream);
+            if (!m.defer.fused && !m.radix.use_radix) m.launch_select(m.host.d_out_idx, m.host.d_out_val, m.stream);
         }
         HIP_TRY(hipEventRecord(evs[2 * iters], m.stream));
         HIP_TRY(hipEventSynchronize(evs[2 * iters]));
@@ -2655,19 +2654,15 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
             t_stream += a;
             t_select += b;
         }
-        for (auto &e : evs) (void)hipEventDestroy(e);
     }
     // (3) SpMV-only variant (hw_spmv_only_time of the reference's GPU host): full y written, no top-k
     {
-        if (!m.d_scores) HIP_TRY(m.alloc(m.d_scores, std::max<size_t>(m.desc.rows, 1) * 4));
-        HIP_TRY(hipEventRecord(m.ev0, m.stream));
-        for (int i = 0; i < iters; ++i) {
-            m.launch_scores(dev_xs + (size_t)(i % n_x) * stride, m.stream);
-        }
-        HIP_TRY(hipEventRecord(m.ev1, m.stream));
-        HIP_TRY(hipEventSynchronize(m.ev1));
+        if (!m.diag.d_scores) HIP_TRY(m.alloc(m.diag.d_scores, std::max<size_t>(m.desc.rows, 1) * 4));
         float ms2 = 0;
-        HIP_TRY(hipEventElapsedTime(&ms2, m.ev0, m.ev1));
+        const int st = m.bracket_ms(ms2, err, [&] {
+            for (int i = 0; i < iters; ++i) m.launch_scores(dev_xs + (size_t)(i % n_x) * stride, m.stream);
+        });
+        if (st != TKSPMV_OK) return st;
         out->scores_kernel_ns = (double)ms2 * 1e6 / iters;
     }
     // (4) what the event bracket itself costs around one launch: the same bracket around an empty kernel with
@@ -2675,45 +2670,43 @@ int Engine::profile(const float *dev_xs, int32_t n_x, int32_t iters, tkspmv_timi
     double t_null = 0;
     {
         const int n = iters < 200 ? iters : 200;
-        std::vector<hipEvent_t> evs((size_t)n * 2);
+        ScratchEvents scratch_events((size_t)n * 2);
+        std::vector<hipEvent_t> &evs = scratch_events.e;
         for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
         for (int i = 0; i < n; ++i) {
             HIP_TRY(hipEventRecord(evs[2 * i], m.stream));
-            hipLaunchKernelGGL(null_kernel, dim3(m.grid), dim3(m.block + 64), 0, m.stream, m.st[0].gmax);
+            hipLaunchKernelGGL(null_kernel, dim3(m.grid), dim3(m.block + 64), 0, m.stream, m.ex.st[0].gmax);
             HIP_TRY(hipEventRecord(evs[2 * i + 1], m.stream));
-            if (!m.fused && !m.use_radix) m.launch_select(m.d_out_idx, m.d_out_val, m.stream);
+            if (!m.defer.fused && !m.radix.use_radix) m.launch_select(m.host.d_out_idx, m.host.d_out_val, m.stream);
         }
-        HIP_TRY(hipStreamSynchronize(m.stream));
-        HIP_TRY(m.settle());
+        if (const int st = m.wait_idle(err)) return st;
         for (int i = 0; i < n; ++i) {
             float a = 0;
             HIP_TRY(hipEventElapsedTime(&a, evs[2 * i], evs[2 * i + 1]));
             t_null += a;
         }
-        for (auto &e : evs) (void)hipEventDestroy(e);
         t_null = t_null * 1e6 / n;
     }
     out->event_bracket_ns = t_null;
     out->stream_kernel_ns = t_stream * 1e6 / iters;
     out->select_kernel_ns = t_select * 1e6 / iters;
     out->n_queries = (uint32_t)iters;
-    if (m.collect_stats) {
+    if (m.diag.collect_stats) {
         unsigned long long sx[14];
-        HIP_TRY(hipMemcpy(sx, m.d_stats, sizeof(sx), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sx, m.diag.d_stats, sizeof(sx), hipMemcpyDeviceToHost));
         const double nsel = (double)std::max<unsigned long long>(1, sx[1]);
         fprintf(stderr, "[tkspmv stats] selections %llu, general-path selections %llu, max candidates %llu, overflow entries per selection %.1f; "
                         "per selection: waves that waited for a threshold at the end of their partition %.1f (%.1f us in all)\n",
                 sx[1], sx[3], sx[2], (double)sx[8] / nsel, (double)sx[10] / nsel, (double)sx[9] / 100.0 / nsel);
     }
-    if (m.collect_stamps) {
+    if (m.diag.collect_stamps) {
         unsigned long long st[16];
-        HIP_TRY(hipMemcpy(st, m.d_stats + 16, sizeof(st), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st, m.diag.d_stats + 16, sizeof(st), hipMemcpyDeviceToHost));
         fprintf(stderr, "[tkspmv stamps, shader cycles since stream end of the last workgroup] flush_issued %lld flush_done %lld ticket %lld loads %lld keys %lld ranked %lld end %lld\n",
                 (long long)(st[1] - st[0]), (long long)(st[2] - st[0]), (long long)(st[3] - st[0]), (long long)(st[4] - st[0]),
                 (long long)(st[5] - st[0]), (long long)(st[6] - st[0]), (long long)(st[7] - st[0]));
     }
-    m.ran = true;
-    m.last_on_host = false;
+    m.host.result_on_device();
     return TKSPMV_OK;
 }
 

@@ -38,7 +38,6 @@ static const OptionDef k_options[] = {
      "who looks at the verdict of a launch of checked local thresholds: host = the launch goes out alone once the verdicts the host has seen are clean, "
      "and tkspmv_synchronize / tkspmv_read (any engine call that waits for the engine's stream) repair a flagged query with an exact launch; "
      "stream = the exact launch follows every local launch in the stream (always so on a caller's stream and for 64 launches after an observed failure)"},
-    {"OVERLAP", "behaviour", "0 | 1 (default 0)", "1: consecutive launches of one sequence of checked local thresholds alternate between two streams while they go out trusted (REPAIR=host): the next launch's ramp fills the previous one's tail -- the second stream is created only then; 0: one launch at a time"},
     {"FUSED", "behaviour", "0 | 1 (default 1 where the selection fits one workgroup)", "0: stream and selection as two launches"},
     {"RADIX", "behaviour", "0 | 1 (default: k above 3/8 of the publishing groups)", "1: scores + radix select instead of thresholded streaming"},
     {"MULTI_Q", "behaviour", "0 | 1 | 3 | 5 | 8 (default by size; desc.multi_q wins)", "queries per pass of the small-matrix kernel (multi_kernel); 0 = off"},

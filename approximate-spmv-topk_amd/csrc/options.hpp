@@ -22,6 +22,11 @@ inline long opt_int(const char *name, long dflt) {
     const char *v = opt(name);
     return v ? atol(v) : dflt;
 }
+// ... clamped to [lo, hi] where the option is set (the default is taken as it is)
+inline long opt_int(const char *name, long dflt, long lo, long hi) {
+    const char *v = opt(name);
+    return v ? (atol(v) < lo ? lo : (atol(v) > hi ? hi : atol(v))) : dflt;
+}
 
 int option_count();
 const OptionDef *option_def(int i);
