@@ -6,11 +6,10 @@
 //
 //   count_kernel     row lengths (one atomic per entry), validation of ordering and ranges
 //   scan_*           exclusive prefix sums of the row lengths and of the placeholder-expanded lengths (empty row -> 1 entry)
-//   cuts_kernel      the greedy partition cuts of fill_partitions() -- a chain of P dependent searches, done by ONE wave with
-//                    64-ary searches over the prefix sums (4 probes per partition instead of 20 binary steps), including the
-//                    loop that grows the partition capacity until the cuts fit the wave count
+//   cuts_kernel      the partition cuts (partition_cuts.hpp, the host packer's rule) -- a chain of P dependent searches, done by ONE
+//                    wave with 64-ary searches over the prefix sums (4 probes per partition instead of 20 binary steps)
 //   scatter_kernel   every COO entry finds its packet slot (row start + offset -> partition by binary search in LDS) and
-//                    writes its value (converted by the SAME functions as the host packer, wbscsr.hpp) and column word
+//                    stores itself there with the host packer's store_entry (wbscsr.hpp)
 //   holes_kernel     placeholder entries of empty rows
 //
 // Output bytes are identical to pack_wbscsr()'s (tests/test_gpu_device_pack.py compares streams and side tables).
@@ -22,6 +21,7 @@
 #include <vector>
 
 #include "device_pack.hpp"
+#include "partition_cuts.hpp"
 #include "wsell.hpp"
 
 namespace tkspmv {
@@ -161,65 +161,16 @@ struct CutsOut {
     uint32_t n_parts, m, n_packets_lo, n_packets_hi, overflow;
 };
 
-// The greedy cuts of fill_partitions(): a partition takes rows while their expanded entries fit `cap`; at least one row.
-// part tables are written for up to P_max partitions; returns the number of partitions the capacity leads to.
-// bal_B != 0: balanced cuts (wbscsr.cpp, fill_partitions_balanced) -- partition p may take PE x (floor((p + 1) B / P) - floor(p B / P))
-// entries instead of `cap`.
-__device__ uint32_t cut_pass(const unsigned long long *__restrict__ S, uint32_t n_rows, unsigned long long cap, uint32_t P_max,
-                             uint32_t *__restrict__ part_row0, uint32_t lane, unsigned long long bal_B = 0ull, unsigned long long PE = 0ull) {
-    uint32_t a = 0, parts = 0;
-    while (a < n_rows) {
-        if (parts < P_max && lane == 0) part_row0[parts] = a;
-        if (bal_B != 0ull) {
-            const unsigned long long p = parts, P = P_max;
-            cap = PE * (p < P ? ((p + 1ull) * bal_B) / P - (p * bal_B) / P : (bal_B + P - 1ull) / P);
-        }
-        ++parts;
-        if (parts > P_max) return parts;  // too many: the caller grows the capacity
-        const unsigned long long target = S[a] + cap;
-        // rows a .. b-1 with S[b] - S[a] <= cap, b >= a + 1: b = (first index in (a, n] with S[idx] > target) - 1, or n
-        uint32_t b;
-        if (S[n_rows] <= target) {
-            b = n_rows;
-        } else {
-            const uint32_t f = first_above(S, a, n_rows, target, lane);  // S[f] > target, S[f - 1] <= target
-            b = f - 1u;
-            if (b <= a) b = a + 1u;  // a row longer than the capacity gets a partition of its own
-        }
-        a = b;
-    }
-    return parts;
-}
-
 __global__ void __launch_bounds__(64) cuts_kernel(const unsigned long long *__restrict__ S, uint32_t n_rows, uint32_t PE,
                                                   uint32_t P_hint, uint32_t min_packets, uint32_t balanced, uint32_t *__restrict__ part_row0,
                                                   uint32_t *__restrict__ part_rows, uint32_t *__restrict__ part_first,
                                                   uint32_t *__restrict__ part_count, CutsOut *__restrict__ out) {
     const uint32_t lane = threadIdx.x;
-    const unsigned long long E = S[n_rows];
-    const unsigned long long total_packets_lb = (E + PE - 1) / PE;
-    unsigned long long max_parts = total_packets_lb / min_packets;
-    if (max_parts < 1) max_parts = 1;
-    const uint32_t P = (uint32_t)(P_hint < max_parts ? P_hint : max_parts);
-    unsigned long long m = (E + (unsigned long long)P * PE - 1) / ((unsigned long long)P * PE);
-    if (m < 1) m = 1;
-    uint32_t used;
-    for (;;) {
-        used = cut_pass(S, n_rows, m * PE, P, part_row0, lane);
-        if (used <= P) break;
-        ++m;  // padding pushed the cuts over the wave count: allow one more packet per partition
-    }
-    // balanced cuts where the uniform ones miss P by more than 1/8 (wbscsr.cpp: the same rule, the same arithmetic)
-    if (balanced != 0u && P >= 2u && total_packets_lb >= 2ull * P &&
-        (balanced == 2u ? (unsigned long long)used * 32ull < (unsigned long long)P * 31ull : (unsigned long long)used * 8ull < (unsigned long long)P * 7ull)) {
-        unsigned long long B = total_packets_lb > P ? total_packets_lb : P;
-        for (;;) {
-            used = cut_pass(S, n_rows, 0ull, P, part_row0, lane, B, PE);
-            if (used <= P) break;
-            B += (B / 64ull) > 1ull ? (B / 64ull) : 1ull;
-        }
-        m = (B + P - 1ull) / P;
-    }
+    const PartitionCuts cuts = cut_partitions(
+        S, n_rows, PE, P_hint, min_packets, balanced,
+        [lane](const unsigned long long *S, uint32_t lo, uint32_t hi, unsigned long long target) { return first_above(S, lo, hi, target, lane); },
+        [=](uint32_t p, uint32_t r) { if (lane == 0) part_row0[p] = r; });
+    const uint32_t used = cuts.n_parts;
     __threadfence();  // lane 0's table writes are read by the other lanes below
     __syncthreads();
     unsigned long long n_packets = 0;
@@ -246,7 +197,7 @@ __global__ void __launch_bounds__(64) cuts_kernel(const unsigned long long *__re
     }
     if (lane == 0) {
         out->n_parts = used;
-        out->m = (uint32_t)m;
+        out->m = cuts.packets_per_partition;
         out->n_packets_lo = (uint32_t)n_packets;
         out->n_packets_hi = (uint32_t)(n_packets >> 32);
         out->overflow = n_packets > 0xFFFFFFFFull ? 1u : 0u;
@@ -263,7 +214,7 @@ struct ScatterParams {
     uint32_t n_parts, n_rows;
     uint8_t *packets;
     uint32_t *pkt_row;
-    uint32_t C, PE, packet_bytes, vb, precision, fixed_width;
+    uint32_t C, PE, packet_bytes, precision, fixed_width;
 };
 
 constexpr uint32_t PART_LDS = 8192;  // partitions whose first rows are searched in LDS (beyond: in global memory)
@@ -287,37 +238,9 @@ __device__ __forceinline__ void place(const ScatterParams &P, uint32_t r, unsign
     uint8_t *pkt = P.packets + (size_t)pk * P.packet_bytes;
     // the first row that ends in a packet is the row of its first entry (wbscsr.cpp)
     if (ss == 0u) P.pkt_row[pk] = r;
-    if ((Precision)P.precision == Precision::FIXED20) {
-        *reinterpret_cast<uint32_t *>(pkt + (size_t)slot * 4) = fixed20_word(to_fixed(v, P.fixed_width), (uint32_t)(cw >> COLW_COL_SHIFT), cw & 3u);
-        return;
-    }
-    if ((Precision)P.precision == Precision::FIXED26) {  // (zeroed stream: the lane's E collects 6 bits from each of its 4 entries)
-        const uint32_t colv = (uint32_t)(cw >> COLW_COL_SHIFT);
-        *reinterpret_cast<uint32_t *>(pkt + (size_t)slot * 4) = fixed26_d(to_fixed(v, P.fixed_width), colv, cw & 3u);
-        const uint32_t e = fixed26_e(slot & 3u, colv);
-        if (e) atomicOr(reinterpret_cast<uint32_t *>(pkt + (size_t)P.PE * 4) + (slot >> 2), e);
-        return;
-    }
-    if ((Precision)P.precision == Precision::F32C12) {
-        *reinterpret_cast<float *>(pkt + (size_t)slot * 4) = v;
-        // split 12-bit plane (wbscsr.hpp colw12s_*): the entry's bits are OR-ed into the lane's dword A and halfword B of the
-        // zeroed stream (four entries share them; B through the dword it shares with the pair's other lane)
-        const uint32_t t = slot & 255u, lane = t >> 2;
-        uint32_t *plane = reinterpret_cast<uint32_t *>(pkt + (size_t)P.PE * 4 + (size_t)(slot >> 8) * 384u);
-        uint32_t a, b;
-        colw12s_bits(t & 3u, cw, a, b);
-        if (a) atomicOr(&plane[colw12s_a_offset(lane) >> 2], a);
-        if (b) atomicOr(&plane[(lane >> 1) * 3u + 1u], b << ((lane & 1u) * 16u));
-        return;
-    }
-    switch ((Precision)P.precision) {
-        case Precision::F32: *reinterpret_cast<float *>(pkt + (size_t)slot * 4) = v; break;
-        case Precision::F16: *reinterpret_cast<uint16_t *>(pkt + (size_t)slot * 2) = to_half(v); break;
-        case Precision::FIXED: *reinterpret_cast<uint32_t *>(pkt + (size_t)slot * 4) = to_fixed(v, P.fixed_width); break;
-        case Precision::Q1_7_RND: pkt[slot] = to_q1_7_rnd(v); break;
-        default: pkt[slot] = to_q1_7(v); break;
-    }
-    *reinterpret_cast<uint16_t *>(pkt + (size_t)P.PE * P.vb + (size_t)slot * 2) = cw;
+    // (zeroed stream: the entries that share a dword -- FIXED26's E, F32C12's split plane -- OR their bits into it)
+    store_entry(pkt, (Precision)P.precision, P.PE, slot, P.fixed_width, cw, v,
+                [](uint8_t *w, uint32_t bits) { if (bits) atomicOr(reinterpret_cast<uint32_t *>(w), bits); });
 }
 
 __global__ void __launch_bounds__(256) scatter_kernel(const ScatterParams P) {
@@ -377,13 +300,7 @@ std::string pack_wbscsr_device(uint32_t rows, uint32_t cols, uint64_t nnz, const
                                const float *val, Precision precision, uint32_t C, uint32_t n_partitions_hint,
                                uint32_t min_packets_per_partition, uint32_t fixed_width, DevicePacked &out, int &kind) {
     kind = 1;
-    if (C != 4 && C != 8) return "nnz_per_lane must be 4 or 8";
-    if (precision == Precision::FIXED26 ? (fixed_width < 8 || fixed_width > FIXED26_MAX_WIDTH || cols > FIXED26_MAX_COLS || C != 4)
-        : precision == Precision::FIXED20 ? (fixed_width < 8 || fixed_width > FIXED20_MAX_WIDTH || cols > FIXED20_MAX_COLS)
-                                        : (precision == Precision::FIXED ? (fixed_width < 8 || fixed_width > 32) : fixed_width != 0))
-        return "fixed_width must be in [8, 32] for fixed-point values (bit-packed: at most 20 bits and 1024 columns) and 0 otherwise";
-    if (cols == 0 || cols > MAX_COLS) return "cols must be in [1, 16384]";
-    if (precision == Precision::F32C12 && (cols > F32C12_MAX_COLS || C != 4)) return "12-bit column words need at most 1024 columns and 4 entries per lane";
+    if (const std::string bad = stream_args_error(precision, C, cols, fixed_width); !bad.empty()) return bad;
     if (nnz > 0 && (!row || !col)) return "row/col arrays are NULL";
     if (n_partitions_hint == 0) n_partitions_hint = 1;
     if (min_packets_per_partition == 0) min_packets_per_partition = 1;
@@ -451,16 +368,14 @@ std::string pack_wbscsr_device(uint32_t rows, uint32_t cols, uint64_t nnz, const
 
     // ---- partition cuts ---------------------------------------------------------------------------------------------------
     const uint32_t PE = pm.packet_entries;
-    const uint64_t total_packets_lb = (E + PE - 1) / PE;
-    const uint32_t P_cap = (uint32_t)std::min<uint64_t>(n_partitions_hint, std::max<uint64_t>(1, total_packets_lb / min_packets_per_partition));
+    const uint32_t P_cap = partition_limit(E, PE, n_partitions_hint, min_packets_per_partition);
     DP_TRY(hipMalloc(&d_pr0.p, (size_t)P_cap * 4));
     DP_TRY(hipMalloc(&d_prows.p, (size_t)P_cap * 4));
     DP_TRY(hipMalloc(&d_pfirst.p, (size_t)P_cap * 4));
     DP_TRY(hipMalloc(&d_pcount.p, (size_t)P_cap * 4));
     DP_TRY(hipMalloc(&d_cuts.p, sizeof(CutsOut)));
-    const uint32_t balanced = opt("BALANCED_CUTS") ? (uint32_t)std::max(0, std::min(2, atoi(opt("BALANCED_CUTS")))) : 1u;
     hipLaunchKernelGGL(cuts_kernel, dim3(1), dim3(64), 0, 0, d_exp_start.as<unsigned long long>(), n_rows, PE, n_partitions_hint,
-                       min_packets_per_partition, balanced, d_pr0.as<uint32_t>(), d_prows.as<uint32_t>(), d_pfirst.as<uint32_t>(),
+                       min_packets_per_partition, balanced_cuts_option(), d_pr0.as<uint32_t>(), d_prows.as<uint32_t>(), d_pfirst.as<uint32_t>(),
                        d_pcount.as<uint32_t>(), d_cuts.as<CutsOut>());
     CutsOut cuts{};
     DP_TRY(hipMemcpy(&cuts, d_cuts.p, sizeof(cuts), hipMemcpyDeviceToHost));
@@ -502,7 +417,6 @@ std::string pack_wbscsr_device(uint32_t rows, uint32_t cols, uint64_t nnz, const
     S.C = C;
     S.PE = PE;
     S.packet_bytes = pm.packet_bytes;
-    S.vb = value_bytes(precision);
     S.precision = (uint32_t)precision;
     S.fixed_width = fixed_width;
     hipLaunchKernelGGL(scatter_kernel, dim3(grid_nnz), dim3(256), 0, 0, S);
@@ -551,7 +465,7 @@ void free_device_packed(DevicePacked &dp) {
 // ids, exactly as the host packer does. What costs the host packer its time is the fill -- 256 slots per chunk, every
 // one a scattered copy -- and that is one kernel here: a wave per slice, lane l writes the 16 (or 4) value bytes and
 // the 8 column-word bytes of its slots in every chunk of the slice, reading its row's entries from the COO in HBM.
-// Same bytes as fill_wsell_host.
+// Same bytes as fill_wsell_host: both take a slot's contents from sell_slot (wsell.hpp).
 // ------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -583,24 +497,10 @@ __global__ void __launch_bounds__(64) sell_scatter_kernel(const SellScatterParam
         uint16_t cw[4];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t e = 4 * c + j;
-            if (have && e < ln.n) {
-                v[j] = P.val ? P.val[ln.src + e] : 1.0f;
-                qv[j] = to_q1_7_rnd(v[j]);
-                cw[j] = (uint16_t)(P.col[ln.src + e] << 2);
-            } else if (!have && e == 0) {
-                v[j] = -__builtin_huge_valf();
-                qv[j] = 1;
-                cw[j] = (uint16_t)(P.pad_one << 2);
-            } else {
-                v[j] = 0.0f;
-                qv[j] = 0;
-                cw[j] = (uint16_t)(P.pad_neutral << 2);
-            }
-            if (c + 1 == nc) {
-                if (j == 0) cw[j] |= SELL_LAST_CHUNK;
-                if (j >= 1) cw[j] |= (uint16_t)((depth >> (2 * (j - 1))) & 3u);
-            }
+            const SellSlot slot = sell_slot(have, ln.n, depth, c, nc, j, P.pad_neutral, P.pad_one, P.col + ln.src, P.val ? P.val + ln.src : nullptr);
+            v[j] = slot.v;
+            qv[j] = slot.q;
+            cw[j] = slot.cw;
         }
         if (P.vb == 4u) *reinterpret_cast<float4 *>(pkt + (size_t)l * 16) = make_float4(v[0], v[1], v[2], v[3]);
         else *reinterpret_cast<uint32_t *>(pkt + (size_t)l * 4) = (uint32_t)qv[0] | ((uint32_t)qv[1] << 8) | ((uint32_t)qv[2] << 16) | ((uint32_t)qv[3] << 24);

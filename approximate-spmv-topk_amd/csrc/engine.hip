@@ -1075,8 +1075,7 @@ Engine::~Engine() {
 // (fp32 and fp16 values: every size, wbscsr.hpp; byte and fixed-point values keep round 4's limit -- their kernels are bound by
 //  arithmetic, and there the local thresholds lose beyond it: Q1.7 bytes at 1M x 512 x 40, 154k packets: 33.0 against 24.7 us)
 static uint64_t local_matrix_packets(int32_t precision) {
-    if (opt_set("SMALL_PACKETS")) return (uint64_t)opt_int("SMALL_PACKETS", 0);
-    return (precision == TKSPMV_F32 || precision == TKSPMV_F16) ? LOCAL_MATRIX_PACKETS : 100000ull;
+    return small_packets_limit((precision == TKSPMV_F32 || precision == TKSPMV_F16) ? LOCAL_MATRIX_PACKETS : 100000ull);
 }
 static uint32_t small_matrix_settings(const tkspmv_desc &d, uint32_t grid, bool defer_capable, uint32_t C, bool *small_out) {
     const uint64_t packets_lb = d.nnz / (64u * (uint64_t)std::max(C, 1u));

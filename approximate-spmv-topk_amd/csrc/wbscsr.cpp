@@ -1,66 +1,19 @@
 // wbscsr.cpp -- host packer / decoder for the wave block-streaming CSR layout (see wbscsr.hpp).
 // Role of the reference's SpMV::packet_coo / packet_coo_partition (src/fpga/src/host_spmv_bscsr.cpp:133-248).
 #include "wbscsr.hpp"
-#include <cstdlib>
 
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
-#include <algorithm>
-#include <cstring>
+#include "partition_cuts.hpp"
 
 namespace tkspmv {
 
-namespace {
-
-// Greedy fill: walk rows in order, open a new partition when the next row does not fit in `cap` entries.
-// Returns the number of partitions; optionally records the first row of each.
-uint32_t fill_partitions(const std::vector<uint32_t> &len, uint64_t cap, std::vector<uint32_t> *first_rows) {
-    uint32_t parts = 0;
-    uint64_t s = 0;
-    bool open = false;
-    for (uint32_t r = 0; r < (uint32_t)len.size(); ++r) {
-        uint64_t L = len[r] ? len[r] : 1;  // empty row -> one placeholder entry
-        if (!open || s + L > cap) {
-            ++parts;
-            if (first_rows) first_rows->push_back(r);
-            s = 0;
-            open = true;
-        }
-        s += L;
-    }
-    return parts;
-}
-
-// The same with a capacity per partition: partition p may take PE x (floor((p + 1) B / P) - floor(p B / P)) entries -- B packets
-// dealt out over P partitions, floor(B / P) or ceil(B / P) each (balanced cuts, pack_wbscsr below); partitions beyond P (the caller
-// will grow B) take ceil(B / P).
-uint32_t fill_partitions_balanced(const std::vector<uint32_t> &len, uint64_t PE, uint64_t B, uint64_t P, std::vector<uint32_t> *first_rows) {
-    uint32_t parts = 0;
-    uint64_t s = 0, cap = 0;
-    bool open = false;
-    for (uint32_t r = 0; r < (uint32_t)len.size(); ++r) {
-        uint64_t L = len[r] ? len[r] : 1;
-        if (!open || s + L > cap) {
-            const uint64_t p = parts;
-            cap = PE * (p < P ? ((p + 1) * B) / P - (p * B) / P : (B + P - 1) / P);
-            ++parts;
-            if (first_rows) first_rows->push_back(r);
-            s = 0;
-            open = true;
-        }
-        s += L;
-    }
-    return parts;
-}
-
-}  // namespace
-
-uint64_t small_matrix_packets() {
-    if (const char *f = opt("SMALL_PACKETS")) return (uint64_t)atoll(f);
-    return SMALL_MATRIX_PACKETS;
-}
+uint64_t small_packets_limit(uint64_t dflt) { return opt_set("SMALL_PACKETS") ? (uint64_t)opt_int("SMALL_PACKETS", 0) : dflt; }
+uint32_t balanced_cuts_option() { return (uint32_t)opt_int("BALANCED_CUTS", 1, 0, 2); }
 uint32_t min_packets_per_partition_for(uint64_t nnz, uint32_t C, uint32_t cols) {
     if (const char *f = opt("MIN_PACKETS")) return (uint32_t)std::max(1, atoi(f));
     const uint64_t packets = nnz / (64u * (uint64_t)std::max(C, 1u));
@@ -68,10 +21,7 @@ uint32_t min_packets_per_partition_for(uint64_t nnz, uint32_t C, uint32_t cols) 
     return packets <= small_matrix_packets() / 10u ? 1u : 2u;  // (up to ~2 packets per streaming wave: one each)
 }
 
-std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32_t *row, const uint32_t *col,
-                        const float *val, Precision precision, uint32_t C, uint32_t n_partitions_hint,
-                        uint32_t min_packets_per_partition, PackedMatrix &out, int &kind, uint32_t fixed_width) {
-    kind = 1;
+std::string stream_args_error(Precision precision, uint32_t C, uint32_t cols, uint32_t fixed_width) {
     if (C != 4 && C != 8) return "nnz_per_lane must be 4 or 8";
     if (precision == Precision::FIXED26 ? (fixed_width < 8 || fixed_width > FIXED26_MAX_WIDTH || cols > FIXED26_MAX_COLS || C != 4)
         : precision == Precision::FIXED20 ? (fixed_width < 8 || fixed_width > FIXED20_MAX_WIDTH || cols > FIXED20_MAX_COLS)
@@ -79,6 +29,14 @@ std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32
         return "fixed_width must be in [8, 32] for fixed-point values (bit-packed: at most 20 / 26 bits, 1024 columns; 26: 4 entries per lane) and 0 otherwise";
     if (cols == 0 || cols > MAX_COLS) return "cols must be in [1, 16384]";
     if (precision == Precision::F32C12 && (cols > F32C12_MAX_COLS || C != 4)) return "12-bit column words need at most 1024 columns and 4 entries per lane";
+    return "";
+}
+
+std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32_t *row, const uint32_t *col,
+                        const float *val, Precision precision, uint32_t C, uint32_t n_partitions_hint,
+                        uint32_t min_packets_per_partition, PackedMatrix &out, int &kind, uint32_t fixed_width) {
+    kind = 1;
+    if (const std::string bad = stream_args_error(precision, C, cols, fixed_width); !bad.empty()) return bad;
     if (nnz > 0 && (!row || !col)) return "row/col arrays are NULL";
     if (n_partitions_hint == 0) n_partitions_hint = 1;
     if (min_packets_per_partition == 0) min_packets_per_partition = 1;
@@ -121,45 +79,17 @@ std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32
         return "";
     }
 
-    // Partition count: never more partitions than packets / min_packets.
-    uint64_t total_packets_lb = (E + PE - 1) / PE;
-    uint64_t max_parts = std::max<uint64_t>(1, total_packets_lb / min_packets_per_partition);
-    uint32_t P = (uint32_t)std::min<uint64_t>(n_partitions_hint, max_parts);
-    uint64_t m = std::max<uint64_t>(1, (E + (uint64_t)P * PE - 1) / ((uint64_t)P * PE));
-    std::vector<uint32_t> first_rows;
-    for (;;) {
-        uint32_t used = fill_partitions(len, m * PE, nullptr);
-        if (used <= P) break;
-        ++m;  // padding pushed us over the wave count: allow one more packet per partition
-    }
-    // Balanced cuts (round 5). Partitions of m packets each come to fewer than the P asked for whenever E / (P x PE) is not close
-    // below an integer -- 125k rows of 20: 3229 partitions of 3 packets for 4064 waves --, and a batch kernel's workgroups then
-    // stream 6 or 7 partitions each: the launch waits for the ones with 7 (4.62 against 4.99 us per query with all at 8 of 2-3 packets).
-    // Where the uniform cut misses P by more than 1/8, the packets are dealt out instead: B of them over P partitions, floor(B / P) or
-    // ceil(B / P) each, B grown from the lower bound until the rows fit. (Measured: at 250k and 500k rows -- 3847 and 3824 uniform
-    // partitions, 94 % of the waves -- dealing out gains nothing, 5.98 against 5.83 and 8.5-8.7 against 8.7: those keep the uniform
-    // table, from which the kernels derive a wave's range without a load.)
-    uint32_t used_uniform = fill_partitions(len, m * PE, nullptr);
-    // (not below two packets per partition: 50k rows dealt out one packet per wave measure 3.88 against 3.66 us per query)
-    const int bal_opt = opt("BALANCED_CUTS") ? atoi(opt("BALANCED_CUTS")) : 1;  // (2: already where the uniform cut misses P by 1/32 -- tuning runs)
-    if (P >= 2 && total_packets_lb >= 2u * (uint64_t)P && bal_opt != 0 &&
-        (bal_opt == 2 ? (uint64_t)used_uniform * 32u < (uint64_t)P * 31u : (uint64_t)used_uniform * 8u < (uint64_t)P * 7u)) {
-        uint64_t B = std::max<uint64_t>(total_packets_lb, P);
-        for (;;) {
-            if (fill_partitions_balanced(len, PE, B, P, nullptr) <= P) break;
-            B += std::max<uint64_t>(1, B / 64);
-        }
-        fill_partitions_balanced(len, PE, B, P, &first_rows);
-        m = (B + P - 1) / P;
-    } else {
-        fill_partitions(len, m * PE, &first_rows);
-    }
-    const uint32_t n_parts = (uint32_t)first_rows.size();
-    out.packets_per_partition = (uint32_t)m;
+    std::vector<EntrySum> row_start(len.size() + 1, 0);  // entry offset of each row in the placeholder-expanded stream
+    for (size_t r = 0; r < len.size(); ++r) row_start[r + 1] = row_start[r] + (len[r] ? len[r] : 1);
+    std::vector<uint32_t> first_rows(partition_limit(E, PE, n_partitions_hint, min_packets_per_partition));
+    const PartitionCuts cuts = cut_partitions(
+        row_start.data(), (uint32_t)len.size(), PE, n_partitions_hint, min_packets_per_partition, balanced_cuts_option(),
+        [](const EntrySum *S, uint32_t lo, uint32_t hi, EntrySum target) { return (uint32_t)(std::upper_bound(S + lo + 1, S + hi + 1, target) - S); },
+        [&](uint32_t p, uint32_t r) { first_rows[p] = r; });
+    const uint32_t n_parts = cuts.n_parts;
+    out.packets_per_partition = cuts.packets_per_partition;
 
     // Packet counts per partition.
-    std::vector<uint64_t> row_start(len.size() + 1, 0);  // entry offset of each row in the placeholder-expanded stream
-    for (size_t r = 0; r < len.size(); ++r) row_start[r + 1] = row_start[r] + (len[r] ? len[r] : 1);
     out.part_first.resize(n_parts);
     out.part_count.resize(n_parts);
     out.part_row0.resize(n_parts);
@@ -182,7 +112,6 @@ std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32
     out.packets.assign((size_t)n_packets * out.packet_bytes, 0);
     out.pkt_row.assign((size_t)n_packets, 0);
 
-    const uint32_t vb = value_bytes(precision);
     // Fill packets partition by partition.
     uint64_t src = 0;  // index into the COO
     for (uint32_t p = 0; p < n_parts; ++p) {
@@ -212,40 +141,7 @@ std::string pack_wbscsr(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32
                 // Rows are contiguous, so the first row that ENDS in a packet is the row of its first entry
                 // (if that row does not end here, no row does and the value is unused).
                 if (stream_slot == 0) prow[pk] = r;
-                if (precision == Precision::FIXED20) {  // value, column and flags in one dword; no column-word region
-                    const uint32_t w = fixed20_word(to_fixed(v, fixed_width), (uint32_t)(cw >> COLW_COL_SHIFT), cw & 3u);
-                    std::memcpy(pkt + (size_t)slot * 4, &w, 4);
-                    continue;
-                }
-                if (precision == Precision::F32C12) {
-                    std::memcpy(pkt + (size_t)slot * 4, &v, 4);
-                    colw12s_store(pkt + (size_t)PE * 4, slot, cw);
-                    continue;
-                }
-                if (precision == Precision::FIXED26) {  // 5 bytes per entry: a dword of the 16-byte plane + 6 bits of the lane's E
-                    const uint32_t colv = (uint32_t)(cw >> COLW_COL_SHIFT);
-                    const uint32_t w = fixed26_d(to_fixed(v, fixed_width), colv, cw & 3u);
-                    std::memcpy(pkt + (size_t)slot * 4, &w, 4);
-                    uint32_t e;
-                    std::memcpy(&e, pkt + (size_t)PE * 4 + (size_t)(slot >> 2) * 4, 4);
-                    e |= fixed26_e(slot & 3u, colv);
-                    std::memcpy(pkt + (size_t)PE * 4 + (size_t)(slot >> 2) * 4, &e, 4);
-                    continue;
-                }
-                if (precision == Precision::F32) {
-                    std::memcpy(pkt + (size_t)slot * 4, &v, 4);
-                } else if (precision == Precision::F16) {
-                    const uint16_t hv = to_half(v);
-                    std::memcpy(pkt + (size_t)slot * 2, &hv, 2);
-                } else if (precision == Precision::FIXED) {
-                    const uint32_t q = to_fixed(v, fixed_width);
-                    std::memcpy(pkt + (size_t)slot * 4, &q, 4);
-                } else if (precision == Precision::Q1_7_RND) {
-                    pkt[slot] = to_q1_7_rnd(v);
-                } else {
-                    pkt[slot] = to_q1_7(v);
-                }
-                std::memcpy(pkt + (size_t)PE * vb + (size_t)slot * 2, &cw, 2);
+                store_entry(pkt, precision, PE, slot, fixed_width, cw, v, PlainOr());
             }
         }
     }
@@ -259,7 +155,6 @@ void decode_wbscsr(const PackedMatrix &pm, std::vector<uint32_t> &row, std::vect
     col.clear();
     val.clear();
     const uint32_t PE = pm.packet_entries;
-    const uint32_t vb = value_bytes(pm.precision);
     for (size_t p = 0; p < pm.part_first.size(); ++p) {
         uint32_t r = pm.part_row0[p];
         uint32_t rows_left = pm.part_rows[p];
@@ -267,43 +162,11 @@ void decode_wbscsr(const PackedMatrix &pm, std::vector<uint32_t> &row, std::vect
             const uint8_t *pkt = pm.packets.data() + (size_t)(pm.part_first[p] + k) * pm.packet_bytes;
             for (uint32_t ss = 0; ss < PE && rows_left; ++ss) {
                 const uint32_t s = slot_to_index(ss, pm.C);
-                uint16_t cw;
-                float v;
-                if (pm.precision == Precision::FIXED20) {
-                    uint32_t w;
-                    std::memcpy(&w, pkt + (size_t)s * 4, 4);
-                    cw = (uint16_t)(w & 0xFFFu);
-                    v = from_fixed(w & 0xFFFFF000u);
-                } else if (pm.precision == Precision::FIXED26) {
-                    uint32_t w, e;
-                    std::memcpy(&w, pkt + (size_t)s * 4, 4);
-                    std::memcpy(&e, pkt + (size_t)PE * 4 + (size_t)(s >> 2) * 4, 4);
-                    const uint32_t colv = ((w >> 2) & 15u) | (((e >> (6u * (s & 3u))) & 63u) << 4);
-                    cw = (uint16_t)((colv << COLW_COL_SHIFT) | (w & 3u));
-                    v = from_fixed(w & 0xFFFFFFC0u);
-                } else if (pm.precision == Precision::F32C12) {
-                    cw = colw12s_load(pkt + (size_t)PE * 4, s);
-                } else {
-                    std::memcpy(&cw, pkt + (size_t)PE * vb + (size_t)s * 2, 2);
-                }
-                if (pm.precision == Precision::FIXED20 || pm.precision == Precision::FIXED26) {
-                } else if (pm.precision == Precision::F32 || pm.precision == Precision::F32C12) {
-                    std::memcpy(&v, pkt + (size_t)s * 4, 4);
-                } else if (pm.precision == Precision::F16) {
-                    uint16_t hv;
-                    std::memcpy(&hv, pkt + (size_t)s * 2, 2);
-                    v = from_half(hv);
-                } else if (pm.precision == Precision::FIXED) {
-                    uint32_t q;
-                    std::memcpy(&q, pkt + (size_t)s * 4, 4);
-                    v = from_fixed(q);
-                } else {
-                    v = from_q1_7(pkt[s]);
-                }
+                const uint16_t cw = load_colw(pkt, pm.precision, PE, s);
                 if (!(cw & COLW_SKIP)) {
                     row.push_back(r);
                     col.push_back((uint32_t)(cw >> COLW_COL_SHIFT));
-                    val.push_back(v);
+                    val.push_back(load_value(pkt, pm.precision, s));
                 }
                 if (cw & COLW_ROW_END) {
                     ++r;
@@ -410,13 +273,7 @@ std::string load_packed(const char *path, PackedMatrix &pm) {
          hd.precision != (uint32_t)Precision::F16 && hd.precision != (uint32_t)Precision::FIXED &&
          hd.precision != (uint32_t)Precision::Q1_7_RND && hd.precision != (uint32_t)Precision::FIXED20 &&
          hd.precision != (uint32_t)Precision::F32C12 && hd.precision != (uint32_t)Precision::FIXED26) ||
-        (hd.precision == (uint32_t)Precision::F32C12 && (hd.cols > F32C12_MAX_COLS || hd.C != 4)) ||
-        (hd.precision == (uint32_t)Precision::FIXED26
-             ? (hd.fixed_width < 8 || hd.fixed_width > FIXED26_MAX_WIDTH || hd.cols > FIXED26_MAX_COLS || hd.C != 4)
-         : hd.precision == (uint32_t)Precision::FIXED20
-             ? (hd.fixed_width < 8 || hd.fixed_width > FIXED20_MAX_WIDTH || hd.cols > FIXED20_MAX_COLS)
-             : (hd.precision == (uint32_t)Precision::FIXED ? (hd.fixed_width < 8 || hd.fixed_width > 32) : hd.fixed_width != 0)) ||
-        (hd.C != 4 && hd.C != 8) ||
+        !stream_args_error((Precision)hd.precision, hd.C, hd.cols, hd.fixed_width).empty() ||
         hd.packet_entries != 64 * hd.C ||
         hd.packet_bytes != packet_bytes_for((Precision)hd.precision, hd.packet_entries) ||
         hd.packed_entries != (uint64_t)hd.n_packets * hd.packet_entries)
@@ -468,31 +325,10 @@ std::string load_packed(const char *path, PackedMatrix &pm) {
         if (out.pkt_row[p] >= hd.rows) return "packet row table out of range";
     }
     // column ids: the kernels read x[col] from LDS without a bounds check
-    if (hd.cols == 0 || hd.cols > MAX_COLS) return "column count out of range";
-    {
-        const size_t vbytes = (size_t)hd.packet_entries * value_bytes((Precision)hd.precision);
-        for (uint32_t p = 0; p < hd.n_packets; ++p) {
-            const uint8_t *cwp = out.packets.data() + (size_t)p * hd.packet_bytes + vbytes;
-            for (uint32_t s = 0; s < hd.packet_entries; ++s) {
-                uint16_t cw;
-                if (hd.precision == (uint32_t)Precision::FIXED20) {
-                    uint32_t w;
-                    std::memcpy(&w, out.packets.data() + (size_t)p * hd.packet_bytes + (size_t)s * 4, 4);
-                    cw = (uint16_t)(w & 0xFFFu);
-                } else if (hd.precision == (uint32_t)Precision::FIXED26) {
-                    uint32_t w, e;
-                    const uint8_t *pk = out.packets.data() + (size_t)p * hd.packet_bytes;
-                    std::memcpy(&w, pk + (size_t)s * 4, 4);
-                    std::memcpy(&e, pk + (size_t)hd.packet_entries * 4 + (size_t)(s >> 2) * 4, 4);
-                    cw = (uint16_t)(((((w >> 2) & 15u) | (((e >> (6u * (s & 3u))) & 63u) << 4)) << COLW_COL_SHIFT) | (w & 3u));
-                } else if (hd.precision == (uint32_t)Precision::F32C12) {
-                    cw = colw12s_load(cwp, s);
-                } else {
-                    std::memcpy(&cw, cwp + (size_t)s * 2, 2);
-                }
-                if ((uint32_t)(cw >> COLW_COL_SHIFT) >= hd.cols) return "column id out of range in the packet stream";
-            }
-        }
+    for (uint32_t p = 0; p < hd.n_packets; ++p) {
+        const uint8_t *pkt = out.packets.data() + (size_t)p * hd.packet_bytes;
+        for (uint32_t s = 0; s < hd.packet_entries; ++s)
+            if ((uint32_t)(load_colw(pkt, out.precision, hd.packet_entries, s) >> COLW_COL_SHIFT) >= hd.cols) return "column id out of range in the packet stream";
     }
     pm = std::move(out);
     return "";

@@ -29,8 +29,8 @@
 
 #include "options.hpp"
 
-// The conversions and the slot arithmetic below are shared, source for source, by the host packer (wbscsr.cpp) and the
-// device packer (device_pack.hip): one definition, so the two cannot drift apart.
+// The conversions, the slot arithmetic and the entry codec below are shared, source for source, by the host packer (wbscsr.cpp)
+// and the device packer (device_pack.hip): one definition, so the two cannot drift apart.
 #if defined(__HIP__)
 #define TKSPMV_HD __host__ __device__
 #else
@@ -120,19 +120,6 @@ TKSPMV_HD inline void colw12s_bits(uint32_t j, uint16_t cw, uint32_t &a, uint32_
     a = j == 0u ? ((col << 2) | skip) : (j == 1u ? ((col << 12) | (skip << 1)) : (j == 2u ? (col << 22) : 0u));
     b = (j == 2u ? skip : (j == 3u ? ((col << 2) | (skip << 1)) : 0u)) | (end << (12u + j));
 }
-inline void colw12s_store(uint8_t *planes, uint32_t slot, uint16_t cw) {  // into a zeroed plane
-    const uint32_t t = slot & 255u, lane = t >> 2;
-    uint8_t *pl = planes + (size_t)(slot >> 8) * 384u;
-    uint32_t a, b, A;
-    uint16_t Bv;
-    colw12s_bits(t & 3u, cw, a, b);
-    std::memcpy(&A, pl + colw12s_a_offset(lane), 4);
-    std::memcpy(&Bv, pl + colw12s_b_offset(lane), 2);
-    A |= a;
-    Bv = (uint16_t)(Bv | b);
-    std::memcpy(pl + colw12s_a_offset(lane), &A, 4);
-    std::memcpy(pl + colw12s_b_offset(lane), &Bv, 2);
-}
 TKSPMV_HD inline uint16_t colw12s_load(const uint8_t *planes, uint32_t slot) {  // (also the row lookup's, on the device: row_lookup.hpp)
     const uint32_t t = slot & 255u, lane = t >> 2, j = t & 3u;
     const uint8_t *pl = planes + (size_t)(slot >> 8) * 384u;
@@ -202,7 +189,7 @@ TKSPMV_HD inline uint16_t to_half(float f) {
     if (rem > half || (rem == half && (q & 1u))) ++q;  // a carry out of the mantissa bumps the exponent, as it should
     return (uint16_t)(sign | q);
 }
-inline float from_half(uint16_t hbits) {
+TKSPMV_HD inline float from_half(uint16_t hbits) {
     const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16, e = (hbits >> 10) & 31u, m = hbits & 0x3FFu;
     uint32_t x;
     if (e == 31u) {
@@ -220,7 +207,7 @@ inline float from_half(uint16_t hbits) {
         x = sign | (ee << 23) | ((mm & 0x3FFu) << 13);
     }
     float f;
-    std::memcpy(&f, &x, 4);
+    __builtin_memcpy(&f, &x, 4);
     return f;
 }
 
@@ -232,7 +219,7 @@ TKSPMV_HD inline uint8_t to_q1_7(float v) {
     if (s >= 255.0f) return 255;
     return (uint8_t)s;  // truncation
 }
-inline float from_q1_7(uint32_t q) { return (float)q * (1.0f / 128.0f); }
+TKSPMV_HD inline float from_q1_7(uint32_t q) { return (float)q * (1.0f / 128.0f); }
 // The same format rounded to nearest, ties up, saturating (ap_ufixed<8,1,AP_RND,AP_SAT>): the value stream of
 // TKSPMV_Q1_7_F32, whose arithmetic is fp32 -- there the quantisation of the values is the only error, and rounding
 // halves it (precision@100 against the fp32 gold on BASELINE configs[4]: 0.97 rounded, 0.94 truncated).
@@ -256,7 +243,74 @@ TKSPMV_HD inline uint32_t to_fixed(float v, uint32_t W) {
     const uint32_t q = s >= top ? (W == 32u ? 0xFFFFFFFFu : (1u << W) - 1u) : (uint32_t)s;  // truncation
     return q << (32u - W);
 }
-inline float from_fixed(uint32_t q) { return (float)q * (1.0f / 2147483648.0f); }
+TKSPMV_HD inline float from_fixed(uint32_t q) { return (float)q * (1.0f / 2147483648.0f); }
+
+// ---- the entry codec: where an entry's value, column word and flags lie in a packet, for every Precision. The ONE definition
+// behind the host packer's fill loop, the device packer's place(), decode_wbscsr and load_packed's column check. -------------------
+template <class T> TKSPMV_HD inline void put(uint8_t *p, T v) { __builtin_memcpy(__builtin_assume_aligned(p, sizeof(T)), &v, sizeof(T)); }
+template <class T> TKSPMV_HD inline T get(const uint8_t *p) {
+    T v;
+    __builtin_memcpy(&v, __builtin_assume_aligned(p, sizeof(T)), sizeof(T));
+    return v;
+}
+// How bits are OR-ed into a dword that several entries of the zeroed stream share (FIXED26's E, F32C12's split plane): plainly
+// where one thread fills the stream; the device packer, a thread per entry, passes an atomicOr (device_pack.hip).
+struct PlainOr {
+    TKSPMV_HD void operator()(uint8_t *p, uint32_t bits) const { put<uint32_t>(p, get<uint32_t>(p) | bits); }
+};
+// Stores the entry (value v, column word cw) at `slot` (= slot_to_index of its stream slot) of the zeroed packet `pkt` of PE entries.
+// (always_inline: left as a call per entry, it slowed the host packer's fill loop by about a tenth.)
+template <class Or32>
+TKSPMV_HD inline __attribute__((always_inline)) void store_entry(uint8_t *pkt, Precision p, uint32_t PE, uint32_t slot, uint32_t fixed_width, uint16_t cw, float v, Or32 or32) {
+    const uint32_t col = (uint32_t)(cw >> COLW_COL_SHIFT), flags = cw & 3u;
+    switch (p) {
+        case Precision::FIXED20: put<uint32_t>(pkt + (size_t)slot * 4, fixed20_word(to_fixed(v, fixed_width), col, flags)); return;
+        case Precision::FIXED26:  // a dword of the 16-byte plane + 6 bits of the lane's E
+            put<uint32_t>(pkt + (size_t)slot * 4, fixed26_d(to_fixed(v, fixed_width), col, flags));
+            or32(pkt + (size_t)PE * 4 + (size_t)(slot >> 2) * 4, fixed26_e(slot & 3u, col));
+            return;
+        case Precision::F32C12: {  // the entry's 12 bits go into the lane's dword A and halfword B (B through the dword it shares with the pair's other lane)
+            put<float>(pkt + (size_t)slot * 4, v);
+            const uint32_t t = slot & 255u, lane = t >> 2;
+            uint8_t *plane = pkt + (size_t)PE * 4 + (size_t)(slot >> 8) * 384u;
+            uint32_t a, b;
+            colw12s_bits(t & 3u, cw, a, b);
+            or32(plane + colw12s_a_offset(lane), a);
+            or32(plane + colw12s_b_offset(lane & ~1u), b << ((lane & 1u) * 16u));
+            return;
+        }
+        case Precision::F32: put<float>(pkt + (size_t)slot * 4, v); break;
+        case Precision::F16: put<uint16_t>(pkt + (size_t)slot * 2, to_half(v)); break;
+        case Precision::FIXED: put<uint32_t>(pkt + (size_t)slot * 4, to_fixed(v, fixed_width)); break;
+        case Precision::Q1_7_RND: pkt[slot] = to_q1_7_rnd(v); break;
+        case Precision::Q1_7: pkt[slot] = to_q1_7(v); break;
+    }
+    put<uint16_t>(pkt + (size_t)PE * value_bytes(p) + (size_t)slot * 2, cw);
+}
+// The column word (column << 2 | SKIP | ROW_END) and the value, as float, of the entry at `slot`.
+TKSPMV_HD inline uint16_t load_colw(const uint8_t *pkt, Precision p, uint32_t PE, uint32_t slot) {
+    switch (p) {
+        case Precision::FIXED20: return (uint16_t)(get<uint32_t>(pkt + (size_t)slot * 4) & 0xFFFu);
+        case Precision::FIXED26: {
+            const uint32_t w = get<uint32_t>(pkt + (size_t)slot * 4), e = get<uint32_t>(pkt + (size_t)PE * 4 + (size_t)(slot >> 2) * 4);
+            const uint32_t col = ((w >> 2) & 15u) | (((e >> (6u * (slot & 3u))) & 63u) << 4);
+            return (uint16_t)((col << COLW_COL_SHIFT) | (w & 3u));
+        }
+        case Precision::F32C12: return colw12s_load(pkt + (size_t)PE * 4, slot);
+        default: return get<uint16_t>(pkt + (size_t)PE * value_bytes(p) + (size_t)slot * 2);
+    }
+}
+TKSPMV_HD inline float load_value(const uint8_t *pkt, Precision p, uint32_t slot) {
+    switch (p) {
+        case Precision::FIXED20: return from_fixed(get<uint32_t>(pkt + (size_t)slot * 4) & 0xFFFFF000u);
+        case Precision::FIXED26: return from_fixed(get<uint32_t>(pkt + (size_t)slot * 4) & 0xFFFFFFC0u);
+        case Precision::FIXED: return from_fixed(get<uint32_t>(pkt + (size_t)slot * 4));
+        case Precision::F32:
+        case Precision::F32C12: return get<float>(pkt + (size_t)slot * 4);
+        case Precision::F16: return from_half(get<uint16_t>(pkt + (size_t)slot * 2));
+        default: return from_q1_7(pkt[slot]);
+    }
+}
 
 struct PackedMatrix {
     uint32_t rows = 0, cols = 0;
@@ -292,8 +346,14 @@ constexpr uint64_t SMALL_MATRIX_PACKETS = 55000;
 //  non-zeros -- beyond, the device-wide exchange was as fast. With the timetable of round 5 the local kernel wins at every size
 //  measured: 24.4 against 25.9 us per query at 1.5M rows, 32.9 / 34.3 at 2M, 48.6 / 52.4 at 3M, 83.7 / 86.2 at 5M, 159.4 / 172.1 at 10M.)
 constexpr uint64_t LOCAL_MATRIX_PACKETS = 4000000;
-uint64_t small_matrix_packets();
+uint64_t small_packets_limit(uint64_t dflt);  // TKSPMV_SMALL_PACKETS where it is set (this limit and the engine's: engine.hip), else dflt
+inline uint64_t small_matrix_packets() { return small_packets_limit(SMALL_MATRIX_PACKETS); }
 uint32_t min_packets_per_partition_for(uint64_t nnz, uint32_t C, uint32_t cols);
+uint32_t balanced_cuts_option();  // TKSPMV_BALANCED_CUTS, clamped to 0..2 (default 1): partition_cuts.hpp
+
+// What is wrong with the arguments of a stream ("" = nothing): one text for the host packer, the device packer and, as an
+// "inconsistent header", load_packed.
+std::string stream_args_error(Precision precision, uint32_t C, uint32_t cols, uint32_t fixed_width);
 
 // Packs a row-sorted COO. Returns empty string on success, else an error message.
 // kind: 0 ok, 1 invalid, 2 not sorted.

@@ -7,7 +7,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 
 namespace tkspmv {
 
@@ -139,41 +138,20 @@ std::string plan_wsell(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32_
 void fill_wsell_host(const SellPlan &plan, const uint32_t *col, const float *val, SellMatrix &out) {
     const uint32_t vb = (uint32_t)out.values, PB = out.packet_bytes;
     out.packets.assign((size_t)out.n_chunks * PB, 0);
-    const float neg_inf = -std::numeric_limits<float>::infinity();
     for (uint32_t so = 0; so < out.n_slices; ++so) {
         const uint32_t s = plan.stream_slice[so], nc = plan.n_chunks_of[so], chunk = plan.chunk0[so];
         for (uint32_t l = 0; l < 64; ++l) {
             const SellLane &ln = plan.lanes[(size_t)s * 64 + l];
             const bool have = ln.row != SELL_NO_ROW;
+            const uint64_t src = have ? plan.start[ln.row] + ln.first : 0;
             for (uint32_t c = 0; c < nc; ++c) {
                 uint8_t *pkt = out.packets.data() + (size_t)(chunk + c) * PB;
                 for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t e = 4 * c + j;
-                    float v;
-                    uint8_t qv;  // byte values
-                    uint16_t cw;
-                    if (have && e < ln.n) {
-                        const uint64_t src = plan.start[ln.row] + ln.first + e;
-                        v = val ? val[src] : 1.0f;
-                        qv = to_q1_7_rnd(v);
-                        cw = (uint16_t)(col[src] << 2);
-                    } else if (!have && e == 0) {
-                        v = neg_inf;  // a lane without a row: its sum is -inf
-                        qv = 1;       // (byte values: the PAD_ONE slot holds -inf)
-                        cw = (uint16_t)(out.pad_one << 2);
-                    } else {
-                        v = 0.0f;  // (+0.0) * (-0.0) = -0.0: leaves every sum as it is
-                        qv = 0;
-                        cw = (uint16_t)(out.pad_neutral << 2);
-                    }
-                    if (c + 1 == nc) {  // flags of the slice's last chunk
-                        if (j == 0) cw |= SELL_LAST_CHUNK;
-                        if (j >= 1) cw |= (uint16_t)((ln.depth >> (2 * (j - 1))) & 3u);  // segment index, 2 bits per word
-                    }
-                    if (vb == 4u) std::memcpy(pkt + ((size_t)l * 4 + j) * 4, &v, 4);
-                    else pkt[(size_t)l * 4 + j] = qv;
-                    if (out.cw_bits == 12) colw12_store(pkt + 256u * vb, l * 4 + j, cw);
-                    else std::memcpy(pkt + 256u * vb + ((size_t)l * 4 + j) * 2, &cw, 2);
+                    const SellSlot slot = sell_slot(have, ln.n, ln.depth, c, nc, j, out.pad_neutral, out.pad_one, col + src, val ? val + src : nullptr);
+                    if (vb == 4u) std::memcpy(pkt + ((size_t)l * 4 + j) * 4, &slot.v, 4);
+                    else pkt[(size_t)l * 4 + j] = slot.q;
+                    if (out.cw_bits == 12) colw12_store(pkt + 256u * vb, l * 4 + j, slot.cw);
+                    else std::memcpy(pkt + 256u * vb + ((size_t)l * 4 + j) * 2, &slot.cw, 2);
                 }
             }
         }

@@ -35,6 +35,8 @@
 #include <string>
 #include <vector>
 
+#include "wbscsr.hpp"
+
 namespace tkspmv {
 
 constexpr uint32_t SELL_XCOLS = 1024;                  // columns the multi-query kernel is built for
@@ -94,6 +96,36 @@ struct SellPlan {
     std::vector<uint32_t> chunk0;        // [n_slices] first chunk of the slice at stream position so
     std::vector<uint32_t> n_chunks_of;   // [n_slices] its chunk count
 };
+// What slot j (0..3) of chunk c holds on a lane of a slice of nc chunks: the fp32 value, the byte value and the column word. One
+// definition for fill_wsell_host and the device packer's sell_scatter_kernel. `have`: the lane has a row, whose n entries on this
+// lane start at col / val (val == NULL: every value is 1.0); depth = index of the lane's segment in its row.
+struct SellSlot {
+    float v;
+    uint8_t q;
+    uint16_t cw;
+};
+TKSPMV_HD inline SellSlot sell_slot(bool have, uint32_t n, uint32_t depth, uint32_t c, uint32_t nc, uint32_t j, uint32_t pad_neutral,
+                                    uint32_t pad_one, const uint32_t *col, const float *val) {
+    const uint32_t e = 4 * c + j;
+    SellSlot s;
+    if (have && e < n) {
+        s.v = val ? val[e] : 1.0f;
+        s.q = to_q1_7_rnd(s.v);
+        s.cw = (uint16_t)(col[e] << 2);
+    } else if (!have && e == 0) {
+        s.v = -__builtin_huge_valf();  // a lane without a row: its sum is -inf
+        s.q = 1;                       // (byte values: the PAD_ONE slot holds -inf)
+        s.cw = (uint16_t)(pad_one << 2);
+    } else {
+        s.v = 0.0f;  // (+0.0) * (-0.0) = -0.0: leaves every sum as it is
+        s.q = 0;
+        s.cw = (uint16_t)(pad_neutral << 2);
+    }
+    if (c + 1 == nc)  // flags of the slice's last chunk: "last chunk" on word 0, the segment index on words 1..3, 2 bits per word
+        s.cw |= j == 0 ? SELL_LAST_CHUNK : (uint16_t)((depth >> (2 * (j - 1))) & 3u);
+    return s;
+}
+
 // Fills out everything of `out` but `packets` (validated like pack_wbscsr). Returns an empty string on success.
 std::string plan_wsell(uint32_t rows, uint32_t cols, uint64_t nnz, const uint32_t *row, const uint32_t *col,
                        uint32_t n_partitions_hint, SellValues values, SellPlan &plan, SellMatrix &out);

@@ -37,7 +37,7 @@ def _coo(pkg, lens, cols, seed=0):
     return pkg.CooMatrix(len(lens), cols, np.array(r, np.uint32), np.array(c, np.uint32), np.array(v, np.float32))
 
 
-@pytest.mark.parametrize("precision,width", [("F32", 0), ("F16", 0), ("Q1_7", 0), ("Q1_7_F32", 0), ("FIXED", 20), ("FIXED", 32)])
+@pytest.mark.parametrize("precision,width", [("F32", 0), ("F16", 0), ("Q1_7", 0), ("Q1_7_F32", 0), ("FIXED", 20), ("FIXED", 24), ("FIXED", 32)])
 @pytest.mark.parametrize("rows,cols,nnz,dist,seed,hint", [(20000, 1024, 20, "gamma", 1, 4088), (3000, 512, 40, "uniform", 2, 4088),
                                                           (150000, 300, 25, "gamma", 3, 512), (700, 64, 5, "uniform", 4, 4088),
                                                           (125000, 1024, 20, "gamma", 5, 4064), (40000, 512, 40, "uniform", 6, 1200)])  # (the last two: balanced cuts)
@@ -47,8 +47,7 @@ def test_generated_matrices_pack_identically(pkg, precision, width, rows, cols, 
     _same(pkg.Packed(m, **kw), pkg.Packed(m, on_device=True, **kw))
 
 
-@pytest.mark.parametrize("C", [4, 8])
-@pytest.mark.parametrize("name,lens,cols,hint", [
+EDGE_LAYOUTS = [  # (name, row lengths, cols, partition hint); tests/test_packed_layout_pins.py pins the host packer's bytes for them
     ("empty rows and long rows", [0, 3, 0, 0, 700, 1, 0, 256, 257, 0, 5] * 30, 128, 64),
     ("one row", [17], 32, 4088),
     ("one entry", [1], 1, 4088),
@@ -56,7 +55,11 @@ def test_generated_matrices_pack_identically(pkg, precision, width, rows, cols, 
     ("rows of exactly one packet", [256] * 40 + [512] * 10, 256, 16),
     ("giant row among small ones", [2] * 500 + [5000] + [2] * 500, 512, 32),
     ("many tiny rows", [1] * 20000, 64, 4088),
-])
+]
+
+
+@pytest.mark.parametrize("C", [4, 8])
+@pytest.mark.parametrize("name,lens,cols,hint", EDGE_LAYOUTS)
 def test_edge_layouts_pack_identically(pkg, C, name, lens, cols, hint):
     m = _coo(pkg, lens, cols, seed=len(lens))
     kw = dict(k=8, nnz_per_lane=C, n_wave_partitions=hint)
@@ -64,6 +67,33 @@ def test_edge_layouts_pack_identically(pkg, C, name, lens, cols, hint):
     _same(a, b)
     r, c, v = b.decode()  # decode(pack(A)) == A through the device packer too
     assert np.array_equal(r, m.row) and np.array_equal(c, m.col) and np.array_equal(v, m.val)
+
+
+@pytest.mark.parametrize("flag", ["-1", "3"])
+def test_balanced_cuts_option_is_read_alike_by_both_packers(pkg, monkeypatch, flag):
+    """TKSPMV_BALANCED_CUTS outside its documented 0..2 is clamped, in one place (wbscsr.cpp: balanced_cuts_option), for both
+    packers: -1 cuts like 0, 3 like 2. Before the option had one reader the host packer took every value other than 0 and 2 for
+    1 and the device packer clamped, so this case FAILED: TKSPMV_DEVICE_PACK=0 and =1 built different partition tables from one
+    matrix. The 125k-row shard is a matrix whose uniform cut misses the waves asked for by more than 1/8 (3229 for 4064)."""
+    m = pkg.generate_matrix(125000, 1024, 20, "gamma", 5)
+    kw = dict(k=100, nnz_per_lane=4, n_wave_partitions=4064)
+    monkeypatch.setenv("TKSPMV_BALANCED_CUTS", flag)
+    host, dev = pkg.Packed(m, **kw), pkg.Packed(m, on_device=True, **kw)
+    _same(host, dev)
+    monkeypatch.setenv("TKSPMV_BALANCED_CUTS", "0" if flag == "-1" else "2")
+    _same(host, pkg.Packed(m, **kw))
+
+
+def test_bad_stream_arguments_are_refused_like_the_host_packer_does(pkg):
+    """(tests/test_packed_layout_pins.py has the host packer's and load_packed's side of this.)"""
+    m = _coo(pkg, [3, 4, 5], 16)
+    for kw in (dict(fixed_width=27), dict(precision=pkg.FIXED, fixed_width=7), dict(nnz_per_lane=5), dict(nnz_per_lane=8, precision=pkg.FIXED, fixed_width=40)):
+        err = []
+        for on_device in (False, True):
+            with pytest.raises(pkg.TkspmvError) as e:
+                pkg.Packed(m, on_device=on_device, **kw)
+            err.append((e.value.status, e.value.message))
+        assert err[0] == err[1] and err[0][0] == pkg._lib.ERR_INVALID, (kw, err)
 
 
 def test_errors_match_the_host_packer(pkg):
