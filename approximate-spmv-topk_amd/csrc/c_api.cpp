@@ -28,6 +28,66 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
+// The score of one located row from its own packets: reduce_core (kernels/packet_math.hpp) restated lane by lane, what
+// score_rows_kernel (kernels/score_rows.hpp) runs on the device. Per packet of the run: products inside the run, +0.0f outside; every
+// slot's own ROW_END mask; the carry +0.0f in front of the first packet. Every sum and product is a separately rounded fp32 operation
+// (-ffp-contract=off), in the kernel's order.
+static float score_located_row(const HostRowView &V, const RowRun &run, const float *x) {
+    const uint32_t C = V.C;
+    float carry = 0.0f, score = 0.0f;
+    for (uint32_t pk = run.first_pkt; pk <= run.last_pkt; ++pk) {
+        float s[64][8], head[64], tail[64], vv[64], t[64];
+        bool end[64][8];
+        uint64_t H = 0;  // lanes that hold a row end
+        for (uint32_t l = 0; l < 64u; ++l) {
+            float p[8];
+            for (uint32_t j = 0; j < C; ++j) {
+                const uint32_t ss = l * C + j;
+                const uint16_t w = V.word(pk, ss);
+                const bool inside = (pk > run.first_pkt || ss >= run.first_slot) && (pk < run.last_pkt || ss <= run.last_slot);
+                p[j] = inside ? V.value(pk, ss) * x[w >> COLW_COL_SHIFT] : 0.0f;
+                end[l][j] = (w & COLW_ROW_END) != 0;
+                if (end[l][j]) H |= 1ull << l;
+            }
+            if (l == 0u) p[0] = p[0] + carry;
+            s[l][0] = p[0];
+            for (uint32_t j = 1; j < C; ++j) s[l][j] = (end[l][j - 1] ? 0.0f : s[l][j - 1]) + p[j];
+            head[l] = s[l][C - 1];
+            for (uint32_t j = C - 1; j-- > 0u;)
+                if (end[l][j]) head[l] = s[l][j];
+            tail[l] = end[l][C - 1] ? 0.0f : s[l][C - 1];
+        }
+        // the clipped scan: the lane masks of reduce_core, bit for bit
+        const uint64_t M1 = ~H, M2 = M1 & (M1 << 1), M4 = M2 & (M2 << 2), M8 = M4 & (M4 << 4);
+        const uint64_t X16 = M1 & 0xFFFF0000FFFF0000ull, P16 = X16 & ~(X16 + 0x0001000000010000ull);
+        const uint32_t Z32 = (uint32_t)(M1 >> 32);
+        const uint64_t P32 = (uint64_t)(Z32 & ~(Z32 + 1u)) << 32;
+        for (uint32_t l = 0; l < 64u; ++l) vv[l] = tail[l];
+        const uint64_t masks[4] = {M1, M2, M4, M8};
+        for (uint32_t step = 0; step < 4u; ++step) {  // row_shr:1, 2, 4, 8 inside each row of 16 lanes; a lane without a source adds +0.0f
+            const uint32_t d = 1u << step;
+            for (uint32_t l = 0; l < 64u; ++l) t[l] = vv[l] + ((l & 15u) >= d ? vv[l - d] : 0.0f);
+            for (uint32_t l = 0; l < 64u; ++l)
+                if ((masks[step] >> l) & 1u) vv[l] = t[l];
+        }
+        for (uint32_t l = 0; l < 64u; ++l) t[l] = ((l >> 4) & 1u) ? vv[(l & ~15u) - 1u] + vv[l] : vv[l];  // row_bcast:15: lane 15 -> row 1, lane 47 -> row 3
+        for (uint32_t l = 0; l < 64u; ++l)
+            if ((P16 >> l) & 1u) vv[l] = t[l];
+        for (uint32_t l = 32; l < 64u; ++l) t[l] = vv[31] + vv[l];  // row_bcast:31: lane 31 -> rows 2 and 3
+        for (uint32_t l = 32; l < 64u; ++l)
+            if ((P32 >> l) & 1u) vv[l] = t[l];
+        carry = vv[63];
+        if (pk == run.last_pkt) {  // expand(): the first row end of a lane yields S, later ones their own s[j]
+            const uint32_t l = run.last_slot / C, j = run.last_slot % C;
+            bool earlier = false;
+            for (uint32_t i = 0; i < j; ++i) earlier = earlier || end[l][i];
+            const float S = (l == 0u ? 0.0f : vv[l - 1u]) + head[l];
+            score = earlier ? s[l][j] : S;
+        }
+    }
+    return score;
+}
+
 extern "C" {
 
 const char *tkspmv_last_error(void) { return g_err.c_str(); }
@@ -100,6 +160,14 @@ int tkspmv_row_vectors(tkspmv_t *h, const uint32_t *host_rows, int32_t count, fl
 }
 int tkspmv_run_similar(tkspmv_t *h, const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val) {
     ENGINE_CALL(run_similar(host_rows, count, exclude_self, idx, val, err))
+}
+int tkspmv_enqueue_score_rows(tkspmv_t *h, const float *dev_xs, int32_t count, const uint32_t *dev_rows, int32_t n_rows, int64_t rows_stride,
+                              float *dev_scores, void *stream) {
+    ENGINE_CALL(enqueue_score_rows(dev_xs, count, dev_rows, n_rows, rows_stride, dev_scores, stream, err))
+}
+int tkspmv_score_rows(tkspmv_t *h, const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride,
+                      float *host_scores) {
+    ENGINE_CALL(score_rows(host_xs, count, host_rows, n_rows, rows_stride, host_scores, err))
 }
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
@@ -368,6 +436,26 @@ int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, f
             col[out] = (uint32_t)(V.word(pk, ss) >> COLW_COL_SHIFT);
             val[out] = V.value(pk, ss);
         }
+    }
+    return TKSPMV_OK;
+}
+
+int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint32_t *rows, int32_t n_rows, float *scores) {
+    if (!p || !x || !rows || !scores || n_rows < 1) return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix, vector, rows and scores given, n_rows >= 1)");
+    const PackedMatrix &pm = p->pm;
+    for (int32_t i = 0; i < n_rows; ++i)
+        if (rows[i] >= pm.rows) return fail(TKSPMV_ERR_INVALID, "row out of range (>= rows)");
+    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
+        return fail(TKSPMV_ERR_UNSUPPORTED, "rows are scored in fp32 packet streams only (TKSPMV_F32)");
+    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
+    const uint32_t PE = pm.packet_entries;
+    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
+                        pm.precision == Precision::F32C12};
+    for (int32_t i = 0; i < n_rows; ++i) {
+        RowRun run{0u, 0u, 0u, 0u};
+        scores[i] = 0.0f;  // a row without entries: a placeholder, or no packets at all
+        if (locate_row(V, rows[i], pm.n_packets, (uint32_t)pm.part_first.size(), PE, run) && row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot)) != 0u)
+            scores[i] = score_located_row(V, run, x);
     }
     return TKSPMV_OK;
 }

@@ -49,6 +49,7 @@
 #include "kernels/read_probe.hpp"
 #include "kernels/range_kernel.hpp"
 #include "kernels/row_vectors.hpp"
+#include "kernels/score_rows.hpp"
 
 namespace tkspmv {
 
@@ -99,6 +100,7 @@ typedef void (*stream_fn)(const StreamParams, const SelectParams);
 typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
 typedef void (*range_fn)(const StreamParams, const RangeParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
+typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
 typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
@@ -107,6 +109,7 @@ struct Kernels {
     filter_fn filter[2] = {};  // [SCORES]
     range_fn range[2] = {};    // [FILT]
     row_vectors_fn row_vectors = nullptr;
+    score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
@@ -125,6 +128,7 @@ static Kernels kernels_of(bool dbg) {
         K.range[0] = &range_kernel<C, XCOLS, QM, false, C == 8 ? 2 : 3>;
         K.range[1] = &range_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
         K.row_vectors = &row_vectors_kernel<C, XCOLS, QM == QM_F32C12>;
+        K.score_rows = &score_rows_kernel<C, QM == QM_F32C12>;
     }
     if constexpr (is_batchable(F)) {
         K.batch[0] = &batch_kernel<C, XCOLS, QM, false, false>;
@@ -427,6 +431,18 @@ struct EngineImpl {
         float *d_sim_xs = nullptr, *d_sim_val = nullptr;
         uint32_t sim_cap = 0;  // rows the scratch holds
     } similar;
+
+    // Scores of given rows (tkspmv_enqueue_score_rows, score_rows_kernel) touch no other group but the matrix either. The scratch of
+    // tkspmv_score_rows -- a chunk's query vectors, its row lists and its [queries][rows] scores --, which allocates it on its first
+    // call and grows it to the largest chunk asked for (at most SCORE_MAX_QUERIES queries and SCORE_MAX_BYTES of vectors, and
+    // SCORE_MAX_ROWS list entries per query).
+    struct ScoreRows {
+        static constexpr uint32_t SCORE_MAX_QUERIES = 1024, SCORE_MAX_ROWS = 16384;
+        static constexpr size_t SCORE_MAX_BYTES = (size_t)64 << 20;
+        float *d_sr_xs = nullptr, *d_sr_scores = nullptr;
+        uint32_t *d_sr_rows = nullptr;
+        uint32_t sr_q_cap = 0, sr_row_cap = 0;  // queries and list entries per query the scratch holds
+    } score;
 
     // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
     // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
@@ -856,6 +872,37 @@ struct EngineImpl {
         R.xs = xs;
         R.len = len;
         hipLaunchKernelGGL(kern.row_vectors, dim3((uint32_t)n), dim3(64), 0, s, R);
+    }
+    // Scores of the rows ids + q * stride [0 .. n_rows) for the queries xs[q], q < n_q, into scores[n_q][n_rows], complete in stream
+    // order when this returns. A wave per list entry and chunk of queries: with one list for every query (stride = 0) the queries are
+    // cut into just as many chunks as it takes to fill the device, so that a row is located as few times as possible. The grid's y
+    // counts the chunks: more of them than a grid has go into further launches. Stream copy 0 is read whatever stream_replicas says.
+    void launch_score_rows(const float *xs, int n_q, const uint32_t *ids, int n_rows, size_t stride, float *scores, hipStream_t s) const {
+        ScoreRowsParams R{};
+        R.packets = mat.d_packets;
+        R.pkt_row = mat.d_pkt_row;
+        R.part_first = mat.d_part_first;
+        R.part_count = mat.d_part_count;
+        R.n_packets = pm.n_packets;
+        R.n_parts = (uint32_t)pm.part_first.size();
+        R.packet_bytes = pm.packet_bytes;
+        R.cols = desc.cols;
+        R.rows = desc.rows;
+        R.first_row = desc.first_row;
+        R.ids_stride = stride;
+        R.n_rows = (uint32_t)n_rows;
+        const uint32_t wgs_full = std::max(1u, info.num_cus) * 8u;  // workgroups of 4 waves that fill the device
+        const uint32_t wgs_rows = (uint32_t)(((uint64_t)n_rows + SCORE_ROWS_WAVES - 1u) / SCORE_ROWS_WAVES);
+        const uint32_t chunks = stride != 0u ? (uint32_t)n_q : std::min<uint32_t>((uint32_t)n_q, std::max(1u, wgs_full / wgs_rows));
+        R.q_per_item = ((uint32_t)n_q + chunks - 1u) / chunks;
+        constexpr uint32_t GRID_Y = 65535u;
+        for (uint64_t q = 0; q < (uint64_t)n_q; q += (uint64_t)GRID_Y * R.q_per_item) {
+            R.n_q = (uint32_t)std::min<uint64_t>((uint64_t)n_q - q, (uint64_t)GRID_Y * R.q_per_item);
+            R.xs = xs + q * desc.cols;
+            R.ids = ids + q * stride;
+            R.scores = scores + q * (uint64_t)n_rows;
+            hipLaunchKernelGGL(kern.score_rows, dim3(wgs_rows, (R.n_q + R.q_per_item - 1u) / R.q_per_item), dim3(64u * SCORE_ROWS_WAVES), 0, s, R);
+        }
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -2195,6 +2242,69 @@ int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclud
             std::copy(lv + j + 1, lv + k, lv + j);
             li[k - 1] = 0u;
             lv[k - 1] = 0.0f;
+        }
+    }
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_score_rows(const float *dev_xs, int32_t count, const uint32_t *dev_rows, int32_t n_rows, int64_t rows_stride, float *dev_scores,
+                               void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_rows || !dev_scores || count < 1 || n_rows < 1 || rows_stride < 0 || (rows_stride != 0 && rows_stride < n_rows))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_score_rows (row ids and scores given, count >= 1, n_rows >= 1, rows_stride = 0 or >= n_rows)");
+    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_score_rows(dev_xs, count, dev_rows, n_rows, (size_t)rows_stride, dev_scores, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride, float *host_scores,
+                       std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_rows || !host_scores || count < 1 || n_rows < 1 || rows_stride < 0 || (rows_stride != 0 && rows_stride < n_rows))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to score_rows (row ids and scores given, count >= 1, n_rows >= 1, rows_stride = 0 or >= n_rows)");
+    if (!host_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "host_xs = NULL takes the installed query vector: count must be 1");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    const float *installed = nullptr;
+    if (!host_xs) {
+        if (const int st = m.resolve_query(installed, 1, err)) return st;
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    typedef EngineImpl::ScoreRows SR;
+    const size_t cols = m.desc.cols;
+    const uint32_t q_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(SR::SCORE_MAX_QUERIES, SR::SCORE_MAX_BYTES / (cols * 4)));
+    const uint32_t want_q = std::min<uint32_t>((uint32_t)count, q_max), want_r = std::min<uint32_t>((uint32_t)n_rows, SR::SCORE_MAX_ROWS);
+    if (want_q > m.score.sr_q_cap || want_r > m.score.sr_row_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: score_rows waits itself)
+        const uint32_t q_cap = std::max(want_q, m.score.sr_q_cap), r_cap = std::max(want_r, m.score.sr_row_cap);
+        uint32_t grown = 0;
+        m.score.sr_q_cap = m.score.sr_row_cap = 0;
+        HIP_TRY(m.grow_scratch(grown, 1u, {{(void **)&m.score.d_sr_xs, (size_t)q_cap * cols * 4}, {(void **)&m.score.d_sr_rows, (size_t)q_cap * r_cap * 4},
+                                           {(void **)&m.score.d_sr_scores, (size_t)q_cap * r_cap * 4}}));
+        m.score.sr_q_cap = q_cap;
+        m.score.sr_row_cap = r_cap;
+    }
+    // chunks of queries, and of list entries inside them: vectors and ids up, the launch, wait, scores down. No result is read and no
+    // result buffer written, so the engine need not be settled: the wait is for this call's own launch.
+    for (int32_t q0 = 0; q0 < count; q0 += (int32_t)m.score.sr_q_cap) {
+        const int32_t qc = std::min<int32_t>((int32_t)m.score.sr_q_cap, count - q0);
+        if (host_xs) HIP_TRY(hipMemcpy(m.score.d_sr_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
+        for (int32_t r0 = 0; r0 < n_rows; r0 += (int32_t)m.score.sr_row_cap) {
+            const int32_t rc = std::min<int32_t>((int32_t)m.score.sr_row_cap, n_rows - r0);
+            if (rows_stride == 0)
+                HIP_TRY(hipMemcpy(m.score.d_sr_rows, host_rows + r0, (size_t)rc * 4, hipMemcpyHostToDevice));
+            else
+                HIP_TRY(hipMemcpy2D(m.score.d_sr_rows, (size_t)rc * 4, host_rows + (size_t)q0 * (size_t)rows_stride + r0, (size_t)rows_stride * 4, (size_t)rc * 4,
+                                    (size_t)qc, hipMemcpyHostToDevice));
+            m.launch_score_rows(host_xs ? m.score.d_sr_xs : installed, qc, m.score.d_sr_rows, rc, rows_stride == 0 ? 0u : (size_t)rc, m.score.d_sr_scores, m.stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(m.stream));
+            HIP_TRY(hipMemcpy2D(host_scores + (size_t)q0 * n_rows + r0, (size_t)n_rows * 4, m.score.d_sr_scores, (size_t)rc * 4, (size_t)rc * 4, (size_t)qc,
+                                hipMemcpyDeviceToHost));
         }
     }
     return TKSPMV_OK;

@@ -45,6 +45,12 @@ class Engine {
     int enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream, std::string &err);
     int row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len, std::string &err);
     int run_similar(const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val, std::string &err);
+    // Scores of given rows (score_rows_kernel): what the rows dev_rows + q * rows_stride [0 .. n_rows) (global ids) score for query q, from
+    // the rows' own packets -- no pass over the matrix; score_rows is the host-side counterpart (chunks on engine-owned scratch, waits).
+    int enqueue_score_rows(const float *dev_xs, int32_t count, const uint32_t *dev_rows, int32_t n_rows, int64_t rows_stride, float *dev_scores,
+                           void *stream, std::string &err);
+    int score_rows(const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride, float *host_scores,
+                   std::string &err);
     // enqueue_list through the multi-query path when the engine has one (desc.multi_q), else the ordinary sequence
     int enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                            void *stream, std::string &err);

@@ -43,6 +43,7 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_create(C.byref(self._h), C.byref(d)))
         self.k = int(k)
         self.num_rows, self.num_cols, self.num_nnz = int(num_rows), int(num_cols), nnz
+        self.first_row = int(first_row)
         self.debug = debug
         if vec is not None:
             self.reset(vec)
@@ -65,6 +66,7 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_create_packed(C.byref(self._h), packed._h, C.byref(d)))
         self.k = int(k)
         self.num_rows, self.num_cols, self.num_nnz = info["rows"], info["cols"], info["nnz"]
+        self.first_row = int(first_row)
         self.debug = debug
         if vec is not None:
             self.reset(vec)
@@ -248,6 +250,52 @@ class SpMV:
             _lib.check(_lib.lib().tkspmv_run_similar(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size), int(bool(exclude_self)),
                                                      idx.ctypes.data_as(C.POINTER(C.c_uint32)), val.ctypes.data_as(C.POINTER(C.c_float))))
         return val, idx
+
+    def enqueue_score_rows(self, dev_xs, count, dev_rows, n_rows, dev_scores, rows_stride=0, stream=0):
+        """Scores of given rows: dev_scores[q*n_rows + i] (float32) = what row dev_rows[q*rows_stride + i] (uint32, a GLOBAL row id as
+        queries return them; rows_stride = 0: one list for every query) scores for query q (dev_xs + q*cols; dev_xs = 0 with
+        count = 1: the vector installed by reset()), bit for bit the value every other path reports. Computed from the rows' own
+        packets: the matrix is not streamed. A row without entries scores +0.0, an id outside the engine's rows -inf. No host sync,
+        no engine state touched."""
+        _lib.check(_lib.lib().tkspmv_enqueue_score_rows(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
+                                                        C.c_void_p(int(dev_rows)) if dev_rows else None, int(n_rows), int(rows_stride),
+                                                        C.c_void_p(int(dev_scores)) if dev_scores else None, C.c_void_p(int(stream))))
+
+    def score_rows(self, rows, vecs=None):
+        """enqueue_score_rows with host arrays: float32[count, n_rows] scores of the given global row ids. rows: 1-D (one list for
+        every query) or [count, n_rows] (a list per query); vecs: [count, cols] (or one vector of cols), None: the vector installed
+        by reset(). Waits."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint32)
+        if ids.ndim not in (1, 2):
+            raise ValueError("rows must be a 1-D list or a [count, n_rows] array")
+        xs = None
+        if vecs is not None:
+            xs = np.ascontiguousarray(vecs, dtype=np.float32)
+            xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+            if xs.ndim != 2 or xs.shape[1] != self.num_cols:
+                raise ValueError(f"query vectors must be [count, {self.num_cols}]")
+        count = 1 if xs is None else int(xs.shape[0])
+        if ids.ndim == 2 and ids.shape[0] != count:
+            raise ValueError(f"rows has {ids.shape[0]} lists for {count} queries")
+        n_rows = int(ids.shape[-1])
+        out = np.empty((count, n_rows), dtype=np.float32)
+        if count and n_rows:
+            _lib.check(_lib.lib().tkspmv_score_rows(self._h, xs.ctypes.data_as(C.POINTER(C.c_float)) if xs is not None else None, count,
+                                                    ids.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, n_rows if ids.ndim == 2 else 0,
+                                                    out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def rerank(self, rows, vec=None, k=None):
+        """The given global row ids re-scored for one query (vec; None: the vector installed by reset()) and ordered like
+        read_result -- score descending, then row descending: (values, indices). Ids outside the engine's rows are dropped; at most
+        k are returned if k is given. The scores come from score_rows, the sorting runs on the host."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        ids = ids[(ids.astype(np.int64) >= self.first_row) & (ids.astype(np.int64) < self.first_row + self.num_rows)]
+        val = self.score_rows(ids, vec)[0] if ids.size else np.empty(0, dtype=np.float32)
+        order = np.lexsort((-ids.astype(np.int64), -val.astype(np.float64)))
+        if k is not None:
+            order = order[:int(k)]
+        return val[order], ids[order]
 
     def enqueue_multi(self, dev_xs, count, dev_idx=0, dev_val=0, stream=0):
         """enqueue_batch with several queries per pass over the matrix (info()["multi_q"] of them share every chunk that

@@ -274,6 +274,21 @@ class Packed:
                                                val.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
         return col[:n.value], val[:n.value]
 
+    def score_rows(self, x, rows):
+        """float32 scores of the given LOCAL rows for the vector x, with the bits an engine created from this packed matrix reports
+        (SpMV.score_rows, SpMV.scores): each row's own packets through the streaming kernels' arithmetic, on the host. A row without
+        entries scores +0.0. fp32 values only (TkspmvError ERR_UNSUPPORTED otherwise); ERR_INVALID for a row >= rows."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        xv = np.ascontiguousarray(x, dtype=np.float32)
+        if xv.shape != (self.info()["cols"],):
+            raise ValueError(f"vector has shape {xv.shape}, expected ({self.info()['cols']},)")
+        out = np.empty(ids.size, dtype=np.float32)
+        if ids.size:
+            _lib.check(_lib.lib().tkspmv_packed_score_rows(self._h, xv.ctypes.data_as(C.POINTER(C.c_float)),
+                                                           ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size),
+                                                           out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def raw(self):
         """(packets bytes, packet_bytes, pkt_row, part_first, part_count) as numpy views/copies."""
         pk = C.c_void_p()

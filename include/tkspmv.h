@@ -263,6 +263,30 @@ int tkspmv_row_vectors(tkspmv_t *e, const uint32_t *host_rows, int32_t count, fl
  * moves up, the last slot becomes the pad (0, 0.0f); a list without the row is unchanged. To get k others, create the engine
  * with k + 1. Errors as above (idx and val must be given). */
 int tkspmv_run_similar(tkspmv_t *e, const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val);
+/* Scores of given rows ("what do these rows score for this query?": rescoring candidates that came from elsewhere -- a dense index,
+ * another shard, a cached page --, fusing sparse and dense scores, evaluating labelled (query, row) pairs, pairwise similarities
+ * with tkspmv_enqueue_row_vectors supplying the vectors). Query q is dev_xs + q * cols (dev_xs = NULL with count = 1: the vector
+ * installed by tkspmv_set_query, ordered as tkspmv_enqueue_range orders it); its list is dev_rows + q * rows_stride, n_rows GLOBAL
+ * row ids (desc.first_row + local row: what queries return; rows_stride = 0: one list for every query; the same id may occur any
+ * number of times). dev_scores[q * n_rows + i] receives the score of row dev_rows[q * rows_stride + i] for query q: exactly
+ * count * n_rows floats are written, nothing else. The score is the fp32 value every other path reports for that row and query,
+ * bit for bit -- tkspmv_scores' y[row], what tkspmv_enqueue_range stores, what the top-k lists carry: it is computed from the row's
+ * own packets with the streaming kernels' arithmetic (score_rows_kernel: the row is found by bisecting the packets' row table, a
+ * wave per list entry), so the matrix is not streamed. A row without entries scores +0.0f, an id outside
+ * [first_row, first_row + rows) -inf (bits 0xFF800000: it sorts last in a rerank); desc.min_score plays no part. Asynchronous,
+ * complete in stream order on any stream (NULL: the engine's); reads stream copy 0 and writes dev_scores only: no engine state is
+ * touched, so it may be mixed freely with the other calls, as tkspmv_enqueue_range may.
+ * Errors: TKSPMV_ERR_INVALID (checked before any device call) for a NULL engine, dev_rows or dev_scores, count < 1, n_rows < 1, a
+ * negative rows_stride or one that is neither 0 nor >= n_rows, dev_xs = NULL with count != 1; TKSPMV_ERR_STATE for dev_xs = NULL
+ * with no vector installed; TKSPMV_ERR_UNSUPPORTED when the engine's packet stream is not fp32 (reduced-precision and fixed-point
+ * values) or the engine does not hold the packets. Served wherever tkspmv_enqueue_row_vectors is, the approximate per-partition
+ * engines included. */
+int tkspmv_enqueue_score_rows(tkspmv_t *e, const float *dev_xs, int32_t count, const uint32_t *dev_rows, int32_t n_rows, int64_t rows_stride,
+                              float *dev_scores, void *stream);
+/* The same with host arrays (host_xs = NULL with count = 1: the installed vector); waits. Works in chunks of at most 1024 queries,
+ * 64 MiB of vectors and 16384 list entries per query on engine-owned scratch. */
+int tkspmv_score_rows(tkspmv_t *e, const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride,
+                      float *host_scores);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
@@ -452,6 +476,12 @@ int tkspmv_packed_raw(const tkspmv_packed *p, const void **packets, uint64_t *pa
  * table (csrc/row_lookup.hpp, the lookup the engine's row_vectors_kernel runs), not by decoding the stream. No GPU needed.
  * TKSPMV_ERR_INVALID for row >= rows, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32. */
 int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, float *val, uint32_t capacity, uint32_t *n);
+/* Scores of rows of a packed matrix for one vector x of cols floats: scores[i] = the fp32 score of LOCAL row rows[i], with the bits
+ * an engine created from this packed matrix reports for it (tkspmv_enqueue_score_rows, tkspmv_scores): the row is looked up as
+ * tkspmv_packed_get_row looks it up and its own packets go through the streaming kernels' arithmetic, restated for the host. A row
+ * without entries scores +0.0f. No GPU needed. TKSPMV_ERR_INVALID for a NULL argument, n_rows < 1 or a row >= rows (nothing is
+ * written then), TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32. */
+int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint32_t *rows, int32_t n_rows, float *scores);
 void tkspmv_packed_free(tkspmv_packed *p);
 /* The DEVICE packer (what tkspmv_create uses by default): packs desc's COO with HIP kernels on desc->device
  * and copies the result back into a tkspmv_packed, so that it can be compared byte for byte with tkspmv_pack's
