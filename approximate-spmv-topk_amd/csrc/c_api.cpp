@@ -145,6 +145,14 @@ int tkspmv_enqueue_filtered(tkspmv_t *h, const float *dev_xs, int32_t count, con
     ENGINE_CALL(enqueue_filtered(dev_xs, count, dev_mask, mask_stride_words, dev_idx, dev_val, stream, err))
 }
 int tkspmv_set_filter(tkspmv_t *h, const uint32_t *host_mask) { ENGINE_CALL(set_filter(host_mask, err)) }
+int tkspmv_set_groups(tkspmv_t *h, const uint32_t *host_groups, uint32_t n_groups) { ENGINE_CALL(set_groups(host_groups, n_groups, err)) }
+int tkspmv_enqueue_grouped(tkspmv_t *h, const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words,
+                           uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp, uint32_t *dev_n, void *stream) {
+    ENGINE_CALL(enqueue_grouped(dev_xs, count, dev_mask, mask_stride_words, dev_idx, dev_val, dev_grp, dev_n, stream, err))
+}
+int tkspmv_run_grouped(tkspmv_t *h, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n) {
+    ENGINE_CALL(run_grouped(use_filter, idx, val, grp, n, err))
+}
 int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask,
                          int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream) {
     ENGINE_CALL(enqueue_range(dev_xs, count, dev_thresholds, dev_mask, mask_stride_words, dev_idx, dev_val, capacity, dev_counts, stream, err))

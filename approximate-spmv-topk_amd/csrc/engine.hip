@@ -50,6 +50,7 @@
 #include "kernels/range_kernel.hpp"
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
+#include "kernels/group_select.hpp"
 
 namespace tkspmv {
 
@@ -443,6 +444,27 @@ struct EngineImpl {
         uint32_t *d_sr_rows = nullptr;
         uint32_t sr_q_cap = 0, sr_row_cap = 0;  // queries and list entries per query the scratch holds
     } score;
+
+    // Grouped top-k (tkspmv_enqueue_grouped; group_best_kernel, group_split_kernel, group_ids_kernel) touches no other group but the
+    // matrix either: its scores go to an array of its own, its selection runs on its own histogram, candidate list and counters, and
+    // the selection kernel gets words of this group where it resets exchange state behind itself. The labels are a property of the
+    // index like the allow-mask. No creation stage: tkspmv_set_groups allocates (all of it again when n_groups grows) and is the
+    // only writer; the kernels move the device words and leave them zero behind every query.
+    struct Grouped {
+        bool have_groups = false;
+        uint32_t n_groups = 0, group_cap = 0;  // labels installed; groups the per-group buffers hold
+        uint32_t *d_groups = nullptr;          // [rows]
+        float *d_gy = nullptr;                 // [rows] the scores of the query in flight; -inf where a row has no entry (never written)
+        unsigned long long *d_gkey = nullptr;  // [group_cap] best (order key << 32 | row) per group; zero between queries
+        float *d_gscore = nullptr;             // [group_cap]
+        uint32_t *d_grow = nullptr;            // [group_cap] group -> its representative's row (the selection's pos_to_row)
+        unsigned long long *d_gcand = nullptr; // [group_cap] candidate list of the radix filter
+        // [4][256] histogram | the non-empty-group counter (both zeroed in front of every query) | the candidate counter | the words
+        // the selection kernel zeroes behind itself (threshold word, nine tickets 32 words apart)
+        uint32_t *d_gwords = nullptr;
+        static constexpr uint32_t W_NONEMPTY = 1024, W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32;
+        uint32_t *d_gout_grp = nullptr, *d_gout_n = nullptr;  // engine-owned [k] group ids and n ("the last query wins")
+    } grouped;
 
     // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
     // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
@@ -936,6 +958,81 @@ struct EngineImpl {
             }
         }
         drain(s);
+    }
+    // Why grouped queries are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask).
+    const char *grouped_unsupported(bool with_mask) const {
+        if (radix.approx_parts) return "grouped queries are exact only: partitions > 1 with k > k_per_partition is the approximate per-partition path";
+        if (!mat.d_packets || !mat.d_pkt_row) return "grouped queries stream the wave-BSCSR packets: this engine does not hold them";
+        return with_mask ? filter_unsupported() : nullptr;
+    }
+    // A sequence of grouped queries (query i: x = xs + i * cols, mask = mask + i * stride words or none; results at out_* + i *
+    // out_stride, the number of real entries at out_n + i * n_stride), complete in stream order when this returns: per query the SpMV-only kernel, the reduction to groups, the radix
+    // select over the groups and the selection kernel ranking the groups' representatives. No exchange set, record, verdict, carried
+    // threshold or deferred selection is read or written: the SpMV-only kernels touch none, and the selection kernel is given this
+    // path's own words. Only mat.launch_counter moves.
+    void launch_grouped(const float *xs, int n, const uint32_t *mask, size_t stride, uint32_t *out_idx, float *out_val, uint32_t *out_grp,
+                        size_t out_stride, uint32_t *out_n, size_t n_stride, hipStream_t s) {
+        using namespace grouped_kernels;
+        const Grouped &Q = grouped;
+        GroupParams G{};
+        G.scores = Q.d_gy;
+        G.groups = Q.d_groups;
+        G.gkey = Q.d_gkey;
+        G.gscore = Q.d_gscore;
+        G.grow = Q.d_grow;
+        G.n_nonempty = Q.d_gwords + Grouped::W_NONEMPTY;
+        G.rows = desc.rows;
+        G.n_groups = Q.n_groups;
+        {  // order key of min_score (the device function's host twin)
+            uint32_t u;
+            std::memcpy(&u, &desc.min_score, 4);
+            G.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        }
+        RadixParams R{};
+        R.scores = Q.d_gscore;
+        R.rows = Q.n_groups;
+        R.k = (uint32_t)desc.k;
+        R.kmin = G.kmin;
+        R.hist = Q.d_gwords;
+        R.ovf_cand = Q.d_gcand;
+        R.ovf_count = Q.d_gwords + Grouped::W_COUNT;
+        R.ovf_cap = Q.n_groups;
+        SelectParams S{};  // no slots, no published maxima: every candidate comes from the list, as a group's index
+        S.wg_cand = Q.d_gcand;  // (n_wg = 0: the selection still forms the address of slot 0)
+        S.ovf_cand = Q.d_gcand;
+        S.ovf_count = R.ovf_count;
+        S.ovf_cap = Q.n_groups;
+        S.k = (uint32_t)desc.k;
+        S.first_row = desc.first_row;
+        S.out_scale = 1.0f;  // the scores kernel already wrote final scores
+        S.tau_g = Q.d_gwords + Grouped::W_TAU;
+        S.done_count = Q.d_gwords + Grouped::W_DONE;
+        S.pos_to_row = Q.d_grow;
+        GroupIdsParams I{};
+        I.groups = Q.d_groups;
+        I.n_nonempty = G.n_nonempty;
+        I.k = (uint32_t)desc.k;
+        I.rows = desc.rows;
+        I.first_row = desc.first_row;
+        const uint32_t best_grid = std::max(1u, std::min(std::max(1u, info.num_cus) * 8u, (uint32_t)(((uint64_t)desc.rows + GROUP_THREADS * GROUP_LANE_ROWS - 1u) / (GROUP_THREADS * GROUP_LANE_ROWS))));
+        const uint32_t split_grid = (Q.n_groups + GROUP_THREADS - 1u) / GROUP_THREADS;
+        const uint32_t rgrid = std::max(1u, std::min(256u, (Q.n_groups + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
+        for (int i = 0; i < n; ++i) {
+            const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
+            launch_scores(xs + (size_t)i * desc.cols, s, Q.d_gy, mask ? &F : nullptr);
+            (void)hipMemsetAsync(Q.d_gwords, 0, (Grouped::W_NONEMPTY + 1u) * 4, s);
+            hipLaunchKernelGGL(group_best_kernel, dim3(best_grid), dim3(GROUP_THREADS), 0, s, G);
+            hipLaunchKernelGGL(group_split_kernel, dim3(split_grid), dim3(GROUP_THREADS), 0, s, G);
+            for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
+            hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+            S.out_idx = out_idx + (size_t)i * out_stride;
+            S.out_val = out_val + (size_t)i * out_stride;
+            hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
+            I.idx = S.out_idx;
+            I.grp = out_grp + (size_t)i * out_stride;
+            I.n_out = out_n + (size_t)i * n_stride;
+            hipLaunchKernelGGL(group_ids_kernel, dim3(((uint32_t)desc.k + GROUP_THREADS - 1u) / GROUP_THREADS), dim3(GROUP_THREADS), 0, s, I);
+        }
     }
     // The fused launch hands its result to the host itself: the pinned block, a new epoch, the start stamp (tkspmv_run).
     void hand_to_host(SelectParams &S) {
@@ -2122,6 +2219,82 @@ int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t 
         m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.filter.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, L.oi.data(), L.ov.data(), count, s);
         return TKSPMV_OK;
     });
+}
+
+int Engine::set_groups(const uint32_t *host_groups, uint32_t n_groups, std::string &err) {
+    EngineImpl &m = *impl_;
+    EngineImpl::Grouped &Q = m.grouped;
+    if (host_groups) {  // checked before any device call: a bad label installs nothing
+        if (n_groups == 0u) return fail(err, TKSPMV_ERR_INVALID, "n_groups must be at least 1");
+        for (uint32_t r = 0; r < m.desc.rows; ++r)
+            if (host_groups[r] >= n_groups) return fail(err, TKSPMV_ERR_INVALID, "group label of row " + std::to_string(r) + " is " + std::to_string(host_groups[r]) + ": labels must be below n_groups = " + std::to_string(n_groups));
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(hipStreamSynchronize(m.stream));  // (a grouped query enqueued earlier may still read the installed labels)
+    if (!host_groups) {
+        Q.have_groups = false;
+        return TKSPMV_OK;
+    }
+    Q.have_groups = false;  // (until everything below has succeeded)
+    const size_t rows = std::max<size_t>(m.desc.rows, 1);
+    if (!Q.d_groups) HIP_TRY(m.alloc(Q.d_groups, rows * 4));
+    if (!Q.d_gy) {
+        HIP_TRY(m.alloc(Q.d_gy, rows * 4));
+        const std::vector<float> ninf(rows, -std::numeric_limits<float>::infinity());  // (rows without entries are never written)
+        HIP_TRY(hipMemcpy(Q.d_gy, ninf.data(), rows * 4, hipMemcpyHostToDevice));
+    }
+    if (!Q.d_gwords) HIP_TRY(m.alloc(Q.d_gwords, (size_t)EngineImpl::Grouped::N_WORDS * 4, Mem::Device, 0));
+    if (!Q.d_gout_grp) HIP_TRY(m.alloc(Q.d_gout_grp, (size_t)m.desc.k * 4, Mem::Device, 0xFF));
+    if (!Q.d_gout_n) HIP_TRY(m.alloc(Q.d_gout_n, 4, Mem::Device, 0));
+    if (n_groups > Q.group_cap) {
+        HIP_TRY(m.grow_scratch(Q.group_cap, n_groups, {{(void **)&Q.d_gkey, (size_t)n_groups * 8}, {(void **)&Q.d_gscore, (size_t)n_groups * 4},
+                                                      {(void **)&Q.d_grow, (size_t)n_groups * 4}, {(void **)&Q.d_gcand, (size_t)n_groups * 8}}));
+        HIP_TRY(hipMemset(Q.d_gkey, 0, (size_t)n_groups * 8));
+    }
+    HIP_TRY(hipMemcpy(Q.d_groups, host_groups, (size_t)m.desc.rows * 4, hipMemcpyHostToDevice));
+    Q.n_groups = n_groups;
+    Q.have_groups = true;
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
+                            float *dev_val, uint32_t *dev_grp, uint32_t *dev_n, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) || (dev_idx == nullptr) != (dev_grp == nullptr))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_grouped (count >= 1, mask_stride_words >= 0, dev_idx, dev_val and dev_grp all given or all NULL)");
+    if (const char *why = m.grouped_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no group labels installed (call tkspmv_set_groups first)");
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    const bool own = dev_idx == nullptr;  // the engine-owned result pair, group ids and n: the last query wins
+    return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
+        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
+        // after the grouped queries did. Settle them now (the host waits for the engine's stream once).
+        if (own && !m.trust.pending_checks.empty()) {
+            if (const int st = m.wait_idle(err)) return st;
+        }
+        HIP_TRY(m.order_x(dev_xs, s));
+        const size_t k = own ? 0u : (size_t)m.desc.k;
+        m.launch_grouped(dev_xs, count, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, own ? m.host.d_out_idx : dev_idx, own ? m.host.d_out_val : dev_val,
+                         own ? m.grouped.d_gout_grp : dev_grp, k, dev_n ? dev_n : m.grouped.d_gout_n, dev_n ? 1u : 0u, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const int st = enqueue_grouped(nullptr, 1, use_filter ? m.filter.d_filter : nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, err);
+    if (st != TKSPMV_OK) return st;
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    m.host.x_pending = false;
+    const size_t k = (size_t)m.desc.k;
+    uint32_t found = 0u;
+    HIP_TRY(hipMemcpy(&found, m.grouped.d_gout_n, 4, hipMemcpyDeviceToHost));
+    if (idx) HIP_TRY(hipMemcpy(idx, m.host.d_out_idx, k * 4, hipMemcpyDeviceToHost));
+    if (val) HIP_TRY(hipMemcpy(val, m.host.d_out_val, k * 4, hipMemcpyDeviceToHost));
+    if (grp) HIP_TRY(hipMemcpy(grp, m.grouped.d_gout_grp, k * 4, hipMemcpyDeviceToHost));
+    if (n) *n = (int32_t)found;
+    return TKSPMV_OK;
 }
 
 int Engine::enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,

@@ -34,6 +34,12 @@ class Engine {
     int enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
                          float *dev_val, void *stream, std::string &err);
     int set_filter(const uint32_t *host_mask, std::string &err);
+    // Grouped top-k (group_best_kernel): every row carries a label (set_groups; NULL removes them); a query returns the k best groups,
+    // each by its best eligible row, with that row's group id. run_grouped is the host-side counterpart (installed vector, waits).
+    int set_groups(const uint32_t *host_groups, uint32_t n_groups, std::string &err);
+    int enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                        uint32_t *dev_grp, uint32_t *dev_n, void *stream, std::string &err);
+    int run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err);
     // Range queries (range_kernel): every allowed row with entries that scores >= the query's threshold, unordered; run_range is
     // the host-side counterpart (installed vector, host threshold, waits, sorts).
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,

@@ -180,6 +180,53 @@ class SpMV:
         self.synchronize()
         return self.read_result()
 
+    def set_groups(self, groups, n_groups=None):
+        """Installs the group labels of grouped queries: groups[r] < n_groups for every local row r (n_groups None: the largest
+        label + 1); None removes them. A label >= n_groups raises TkspmvError(ERR_INVALID) and installs nothing."""
+        if groups is None:
+            _lib.check(_lib.lib().tkspmv_set_groups(self._h, None, 0))
+            return
+        g = np.asarray(groups)
+        if g.shape != (self.num_rows,):
+            raise ValueError(f"groups has shape {g.shape}, expected ({self.num_rows},)")
+        if g.size and (g.min() < 0 or g.max() > 0xFFFFFFFF):
+            raise ValueError("group labels must be uint32 values")
+        g = np.ascontiguousarray(g, dtype=np.uint32)
+        if n_groups is None:
+            n_groups = int(g.max()) + 1 if g.size else 1
+        _lib.check(_lib.lib().tkspmv_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_groups)))
+
+    def enqueue_grouped(self, dev_xs, count, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_grp=0, dev_n=0, stream=0):
+        """Grouped top-k of `count` queries (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()): the k best
+        groups of set_groups(), each by its best row. dev_mask: allow-mask(s) as in enqueue_filtered, 0 = unfiltered. dev_idx /
+        dev_val / dev_grp: [count][k] device buffers, all three or none (engine buffers, last query wins); dev_n: [count] real
+        entries per list (optional). Pads are (0, 0.0) with group id 0xFFFFFFFF. No host sync; one grouped call in flight at a time."""
+        _lib.check(_lib.lib().tkspmv_enqueue_grouped(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
+                                                     C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
+                                                     C.c_void_p(int(dev_idx)) if dev_idx else None,
+                                                     C.c_void_p(int(dev_val)) if dev_val else None,
+                                                     C.c_void_p(int(dev_grp)) if dev_grp else None,
+                                                     C.c_void_p(int(dev_n)) if dev_n else None, C.c_void_p(int(stream))))
+
+    def run_grouped(self, vec=None, allow=None, groups=None):
+        """One grouped query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
+        row_mask() words; the query is then restricted to it), set_groups(groups) if given. Returns (values, indices, groups) of
+        the groups that exist for the query, at most k, ordered like read_result."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        if groups is not None:
+            self.set_groups(groups)
+        idx = np.zeros(self.k, dtype=np.uint32)
+        val = np.zeros(self.k, dtype=np.float32)
+        grp = np.zeros(self.k, dtype=np.uint32)
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().tkspmv_run_grouped(self._h, int(allow is not None), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 val.ctypes.data_as(C.POINTER(C.c_float)), grp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+        return val[:n.value], idx[:n.value], grp[:n.value]
+
     def enqueue_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_idx=0, dev_val=0, capacity=0, dev_mask=0, mask_stride=0, stream=0):
         """Range queries: for query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()) every row that
         has entries, is allowed by dev_mask + i*mask_stride words (0: unfiltered) and scores >= dev_thresholds[i]. dev_counts[i]
@@ -391,6 +438,16 @@ def range_spmv(m, vec, threshold, allow=None, **kw):
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
     try:
         return e.run_range(threshold, allow=allow)
+    finally:
+        e.close()
+
+
+def grouped_spmv(m, vec, groups, k=100, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices, groups) of the k best groups of rows (labels
+    groups[r], one per row), each by its best row (among the rows of `allow`, if given), ordered like topk_spmv's result."""
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
+    try:
+        return e.run_grouped(allow=allow, groups=groups)
     finally:
         e.close()
 

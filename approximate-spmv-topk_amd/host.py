@@ -98,6 +98,41 @@ def row_mask(rows, allow=None, exclude=None):
     return np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
 
 
+def collapse_topk(scores, present, groups, k, min_score=0.0, first_row=0):
+    """The contract of grouped top-k (SpMV.enqueue_grouped) restated in numpy, for CPU-side users and as the tests' expectation:
+    from float32 scores[rows], present[rows] (the row is eligible apart from its score: it has entries and is allowed) and
+    groups[rows], the k best groups, each by the eligible row that comes first in the engine's order. Returns (idx[k] uint32 =
+    row + first_row, val[k] float32, grp[k] uint32, n): n real entries, then pads (0, 0.0, 0xFFFFFFFF), like the device call.
+    Ordering and eligibility go by the engine's 64-bit key (order key of the score << 32 | row): a row is eligible when its order
+    key is at least min_score's and its score is above -inf; a larger key comes first."""
+    y = np.ascontiguousarray(scores, dtype=np.float32)
+    g = np.asarray(groups).astype(np.int64)
+    ok = np.asarray(present).astype(bool)
+    if y.ndim != 1 or g.shape != y.shape or ok.shape != y.shape:
+        raise ValueError("scores, present and groups must be 1-D arrays of one length")
+
+    def order_key(f):  # monotone float32 -> uint32, the engine's order_key
+        u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
+        return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+    key = order_key(y)
+    ok = ok & (key >= order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
+    rows = np.flatnonzero(ok)
+    ckey = (key[rows].astype(np.uint64) << np.uint64(32)) | rows.astype(np.uint64)
+    order = np.argsort(ckey, kind="stable")[::-1]  # (keys are unique: they carry the row)
+    rows = rows[order]
+    _, first = np.unique(g[rows], return_index=True)  # each group's first row in that order: its representative
+    reps = rows[np.sort(first)][:int(k)]
+    n = int(reps.size)
+    idx = np.zeros(int(k), dtype=np.uint32)
+    val = np.zeros(int(k), dtype=np.float32)
+    grp = np.full(int(k), 0xFFFFFFFF, dtype=np.uint32)
+    idx[:n] = reps + int(first_row)
+    val[:n] = y[reps]
+    grp[:n] = g[reps]
+    return idx, val, grp, n
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()

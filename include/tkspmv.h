@@ -240,6 +240,44 @@ int tkspmv_enqueue_range(tkspmv_t *e, const float *dev_xs, int32_t count, const 
  * min(*count, capacity) entries are written). TKSPMV_ERR_INVALID for use_filter with no filter installed. */
 int tkspmv_run_range(tkspmv_t *e, float threshold, int32_t use_filter, uint32_t *idx, float *val,
                      uint32_t capacity, uint64_t *count);
+/* Grouped top-k (result collapsing): the k best GROUPS of rows, each shown once by its best row -- the k best documents by
+ * their best passage, products by their best variant. Every local row carries a label group[r] < n_groups, a property of the
+ * index like the allow-mask. For a query a row is ELIGIBLE when it has entries, is allowed by the optional allow-mask, and its
+ * score passes desc.min_score as the engine's exact selection decides it (order key >= the key of min_score, score > -inf). A
+ * group's REPRESENTATIVE is its eligible row that comes first in the result order (score descending, then row id descending); a
+ * group without an eligible row does not exist for that query. The result is the first k representatives in that same order:
+ * the engine's complete ranking of the eligible rows with every row dropped whose group already appeared, cut at k. Hence
+ * group[r] = r gives the engine's exact top-k bit for bit, and one group gives the query's best row alone.
+ *
+ * host_groups: [rows] labels, checked on the host (TKSPMV_ERR_INVALID for n_groups = 0 or a label >= n_groups: nothing is
+ * installed, earlier labels stay); NULL removes them. Waits for the engine's stream first, as tkspmv_set_filter does (a grouped
+ * query on a caller's stream must have been waited for by the caller), and allocates the path's scratch: 8 bytes per row and
+ * 24 bytes per group. */
+int tkspmv_set_groups(tkspmv_t *e, const uint32_t *host_groups, uint32_t n_groups);
+/* Grouped query i = dev_xs + i * cols (NULL with count = 1: the vector installed by tkspmv_set_query). dev_mask /
+ * mask_stride_words: as in tkspmv_enqueue_filtered, but NULL means UNFILTERED. dev_idx / dev_val / dev_grp: [count][k], all
+ * three given or all three NULL (engine-owned buffers, last query wins; tkspmv_read then sees idx / val). Entry j of a list:
+ * the representative's row id + desc.first_row, its score with the bits every other path reports for that row, its group id.
+ * Fewer than k groups exist: the tail is padded with (0, 0.0f) as tkspmv_read documents, with group id 0xFFFFFFFF. dev_n:
+ * [count] or NULL, the number of real entries of each list (a pad and "row 0 scoring +0.0f" differ in the group id and here).
+ * Exact, and bit-reproducible: a group's representative is a maximum, which does not depend on the order rows arrive in.
+ * Every value type is served without a mask; a mask needs the filtered path's kernels (TKSPMV_F32).
+ * Stream contract: complete in stream order on any stream. The call uses scratch owned by the engine, so two grouped calls
+ * must NOT be in flight on two streams at once. It reads and writes no exchange state, carried threshold, verdict or deferred
+ * selection, so it may be mixed freely with the other calls on one stream; with engine-owned outputs it first settles pending
+ * checks of earlier batch launches, as tkspmv_enqueue_filtered does.
+ * Launch scheme per query: the SpMV-only kernel (every row's score), one pass that folds rows into their group's best
+ * (score, row) key, a radix select over the groups, the selection kernel over the selected groups' representatives.
+ * Errors: TKSPMV_ERR_INVALID for count < 1, a negative stride, output pointers partly given; TKSPMV_ERR_UNSUPPORTED on the
+ * approximate per-partition engines, on engines that do not hold the packet stream, and for a mask where
+ * tkspmv_enqueue_filtered reports it; TKSPMV_ERR_STATE with no labels installed or a NULL dev_xs with no query installed. */
+int tkspmv_enqueue_grouped(tkspmv_t *e, const float *dev_xs, int32_t count, const uint32_t *dev_mask,
+                           int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp,
+                           uint32_t *dev_n, void *stream);
+/* The host-side counterpart: the installed query vector, the mask installed by tkspmv_set_filter when use_filter != 0
+ * (TKSPMV_ERR_INVALID if none is); waits; idx / val / grp (host, k entries each, any may be NULL) receive the list, *n the
+ * number of real entries. */
+int tkspmv_run_grouped(tkspmv_t *e, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n);
 /* Queries by stored row ("which rows are closest to row r?": more-like-this, de-duplication, the k-NN self-join A.A^T top-n --
  * the product the reference's CPU comparator sparse_dot_topn exists for). dev_rows[i] is a GLOBAL row id (desc.first_row + local
  * row): exactly what queries return, so results can be fed back. dev_xs + i * cols receives row i as the dense vector of cols

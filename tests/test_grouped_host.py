@@ -1,0 +1,146 @@
+"""Grouped top-k without a GPU: the symbols of every layer, argument checks that come before any device call, the numpy
+restatement of the contract (collapse_topk) pinned to the oracle's selection and to a plain loop, and the resource report of the
+new kernels."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
+CSRC = os.path.join(ROOT, "approximate-spmv-topk_amd", "csrc")
+NAMES = ("tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped")
+# what the existing report tests pick their kernel families by: the new kernels' names must match none of them
+FAMILY_SUBSTRINGS = ("stream_kernel", "batch_kernel", "multi_kernel", "range_kernel", "row_vectors_kernel", "score_rows_kernel", "stream_filter_kernel")
+NEW_KERNELS = ("group_best_kernel", "group_split_kernel", "group_ids_kernel")
+
+
+def test_grouped_symbols_in_every_layer(pkg):
+    hdr = open(os.path.join(ROOT, "include", "tkspmv.h")).read()
+    capi = open(os.path.join(CSRC, "c_api.cpp")).read()
+    lib = pkg._lib.lib()
+    for name in NAMES:
+        assert name in pkg._lib.EXPORTED_SYMBOLS
+        assert f"int {name}(" in hdr and f"int {name}(" in capi
+        assert hasattr(lib, name)
+    for name in ("set_groups", "enqueue_grouped", "run_grouped"):
+        assert callable(getattr(pkg.SpMV, name))
+    assert callable(pkg.grouped_spmv) and "grouped_spmv" in pkg.__all__
+    assert callable(pkg.collapse_topk) and "collapse_topk" in pkg.__all__
+
+
+def test_null_engine_fails_before_any_device_call(pkg):
+    lib = pkg._lib.lib()
+    labels = (C.c_uint32 * 4)(0, 1, 2, 3)
+    n = C.c_int32(7)
+    assert lib.tkspmv_set_groups(None, labels, 4) == pkg._lib.ERR_INVALID
+    assert lib.tkspmv_set_groups(None, None, 0) == pkg._lib.ERR_INVALID
+    assert lib.tkspmv_enqueue_grouped(None, None, 1, None, 0, None, None, None, None, None) == pkg._lib.ERR_INVALID
+    assert lib.tkspmv_run_grouped(None, 0, None, None, None, C.byref(n)) == pkg._lib.ERR_INVALID
+    assert n.value == 7
+
+
+def test_collapse_with_one_row_per_group_is_the_oracles_selection(pkg, oracle):
+    rng = np.random.default_rng(11)
+    rows, k = 5003, 100
+    y = rng.standard_normal(rows).astype(np.float32)
+    present = rng.random(rows) < 0.8
+    for min_score, first_row in ((0.0, 0), (float(np.float32(0.4)), 700), (float(np.float32(-0.3)), 0), (2.5, 0)):
+        idx, val, grp, n = pkg.collapse_topk(y, present, np.arange(rows), k, min_score, first_row)
+        ei, ev = oracle.select_topk(y, present.astype(np.uint8), k, min_score, first_row)
+        assert np.array_equal(idx, ei) and np.array_equal(val.view(np.uint32), ev.view(np.uint32)), min_score
+        assert n == min(k, int((present & (y >= np.float32(min_score))).sum()))
+        assert np.array_equal(grp[:n], idx[:n] - first_row) and np.all(grp[n:] == 0xFFFFFFFF)
+    assert n < k  # (the last case: fewer than k rows above 2.5 -- the pad of the oracle is the pad of collapse_topk)
+
+
+def _order_key(f):
+    u = int(np.array([f], dtype=np.float32).view(np.uint32)[0])
+    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
+
+
+def _loop(y, present, groups, k, min_score, first_row):
+    """The contract as a plain loop: every eligible row by its key, descending; the first row of each group; cut at k."""
+    kmin = _order_key(min_score)
+    keyed = sorted(((_order_key(y[r]) << 32) | r for r in range(len(y)) if present[r] and _order_key(y[r]) >= kmin and y[r] > -np.inf), reverse=True)
+    seen, out = set(), []
+    for key in keyed:
+        r = key & 0xFFFFFFFF
+        if groups[r] not in seen:
+            seen.add(groups[r])
+            out.append(r)
+    return out[:k], len(seen)
+
+
+@pytest.mark.parametrize("name", ["runs", "fewer_than_k", "absent_groups", "more_groups_than_rows", "one_group", "min_score"])
+def test_collapse_matches_a_plain_loop_with_ties(pkg, name):
+    rng = np.random.default_rng(5)
+    rows, k, min_score, first_row = 3001, 50, 0.0, 0
+    y = rng.choice(np.array([-1.0, 0.25, 0.5, 0.5000001, 2.0], dtype=np.float32), rows)  # five values: ties inside groups and across the cut
+    present = rng.random(rows) < 0.9
+    if name == "runs":
+        groups = np.arange(rows) // 7
+    elif name == "fewer_than_k":
+        groups = rng.integers(0, 20, rows)
+    elif name == "absent_groups":
+        groups = rng.integers(0, 400, rows)
+        present &= groups % 3 != 0  # a third of the groups has no present row
+        first_row = 123
+    elif name == "more_groups_than_rows":
+        groups = rng.choice(3 * rows, rows, replace=False)
+    elif name == "one_group":
+        groups = np.zeros(rows, dtype=np.int64)
+    else:
+        groups = np.arange(rows) // 3
+        min_score = 0.5  # the middle value: ties at the threshold itself
+    idx, val, grp, n = pkg.collapse_topk(y, present, groups, k, min_score, first_row)
+    want, n_groups = _loop(y, present, groups, k, min_score, first_row)
+    assert n == len(want) == min(k, n_groups)
+    assert idx[:n].tolist() == [r + first_row for r in want]
+    assert np.array_equal(val[:n].view(np.uint32), y[want].view(np.uint32))
+    assert grp[:n].tolist() == [int(groups[r]) for r in want]
+    assert len(set(grp[:n].tolist())) == n
+    assert np.all(idx[n:] == 0) and np.all(val[n:].view(np.uint32) == 0) and np.all(grp[n:] == 0xFFFFFFFF)
+    if name == "fewer_than_k":
+        assert n == 20 < k
+    if name == "one_group":
+        assert n == 1
+
+
+def test_collapse_treats_signed_zeros_and_minus_infinity_like_the_device(pkg):
+    y = np.array([-0.0, 0.0, -np.inf, 1.0, -np.inf], dtype=np.float32)
+    present = np.ones(5, dtype=bool)
+    idx, val, grp, n = pkg.collapse_topk(y, present, np.arange(5), 5, 0.0)
+    assert n == 2 and idx[:2].tolist() == [3, 1]  # -0.0 sorts below +0.0 = min_score by the order key
+    idx, val, grp, n = pkg.collapse_topk(y, present, np.arange(5), 5, -np.inf)
+    assert n == 3 and idx[:3].tolist() == [3, 1, 0] and val[2].view(np.uint32) == 0x80000000  # -inf is never eligible
+
+
+def _report():
+    if not os.path.exists(REPORT):
+        pytest.skip("no resource report (the library was not built by this Makefile)")
+    kernels, cur = {}, None
+    for ln in open(REPORT):
+        m = re.match(r"\s*Function Name: (\S+)", ln)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)", ln)
+        if m and cur is not None:
+            cur[m.group(1)] = int(m.group(2))
+    return kernels
+
+
+def test_grouped_kernels_in_resource_report():
+    k = _report()
+    for kernel in NEW_KERNELS:
+        found = {n: v for n, v in k.items() if kernel in n}
+        assert len(found) == 1, (kernel, sorted(found))
+        (name, v), = found.items()
+        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (name, v)
+        assert not any(s in name for s in FAMILY_SUBSTRINGS), name
+    best = next(v for n, v in k.items() if "group_best_kernel" in n)
+    assert best["LDS Size [bytes/block]"] == 0, best  # the run reduction stays in registers
+    assert best["VGPRs"] <= 64, best  # 256-thread workgroups at full occupancy
