@@ -67,11 +67,14 @@ __device__ __forceinline__ uint32_t order_key_d(float f) {
 // the persistent batch kernel (18 of its 32 wave slots) -- with 1024 threads and a fixed 64 KB it could not, the merge of batch b
 // waited for the local kernel of batch b+1 to end, and that kernel's successor for the merge (rocprofv3: 113 us per merge launch).
 constexpr uint32_t MERGE_THREADS = 256;
-constexpr uint32_t MERGE_MAX = 8184;  // world * k (+ 8 padding keys: 64 KB of dynamic LDS)
+constexpr uint32_t MERGE_MAX = 8184;  // world * k (+ 8 padding keys: exactly 64 KB of dynamic LDS, the most a block can have)
 
-// gathered: [world][n_q][2][k] u32 (row ids, then score bits); block q merges query q of the batch. Output: the k best
-// by (score desc, row desc); equal keys (the (0, 0.0) fillers several shards may contribute) are ordered by position,
-// so ranks stay unique.
+// gathered: [world][n_q][2][k] u32 (row ids, then score bits); block q merges query q of the batch. Output: the real
+// entries of all lists by (score desc, row desc), cut at k, the tail padded with (0, 0.0f) (include/tkspmv.h states the
+// contract). A shard with fewer than k eligible rows ends its list with fillers (0, bits 0): an entry is one when it is
+// (0, +0.0f) and is the last of its list or followed by another (0, +0.0f) -- row 0 comes at most once in a list, so in
+// tkspmv_read order this is exactly the list's suffix of such entries. Fillers get key 0, below the key of every finite
+// score, whatever min_score the shards ran with; equal keys are ordered by position, so ranks stay unique.
 __global__ void __launch_bounds__(MERGE_THREADS) merge_kernel(const uint32_t *__restrict__ gathered, uint32_t world,
                                                               uint32_t k, uint32_t *__restrict__ out_idx,
                                                               float *__restrict__ out_val) {
@@ -82,7 +85,9 @@ __global__ void __launch_bounds__(MERGE_THREADS) merge_kernel(const uint32_t *__
     for (uint32_t i = tid; i < n; i += MERGE_THREADS) {
         const uint32_t r = i / k, j = i % k;
         const uint32_t *src = gathered + ((size_t)r * n_q + q) * 2 * k;
-        keys[i] = ((unsigned long long)order_key_d(__uint_as_float(src[k + j])) << 32) | src[j];
+        const uint32_t row = src[j], bits = src[k + j];
+        const bool filler = (row | bits) == 0u && (j + 1 == k || (src[j + 1] | src[k + j + 1]) == 0u);
+        keys[i] = filler ? 0ull : ((unsigned long long)order_key_d(__uint_as_float(bits)) << 32) | row;
     }
     if (tid < 8) keys[n + tid] = 0ull;
     __syncthreads();
@@ -100,8 +105,8 @@ __global__ void __launch_bounds__(MERGE_THREADS) merge_kernel(const uint32_t *__
         if (r < k) {
             const uint32_t key32 = (uint32_t)(kx >> 32);
             const uint32_t u = (key32 & 0x80000000u) ? (key32 & 0x7FFFFFFFu) : ~key32;
-            out_idx[r] = (uint32_t)(kx & 0xFFFFFFFFull);
-            out_val[r] = __uint_as_float(u);
+            out_idx[r] = kx ? (uint32_t)(kx & 0xFFFFFFFFull) : 0u;
+            out_val[r] = __uint_as_float(kx ? u : 0u);
         }
     }
 }
@@ -177,7 +182,7 @@ int tkspmv_dist_unique_id(uint8_t *out128) {
 int tkspmv_merge_topk(const uint32_t *dev_gathered, int32_t world, int32_t k, uint32_t *dev_idx, float *dev_val,
                       void *stream) {
     if (!dev_gathered || !dev_idx || !dev_val || world < 1 || k < 1 || (uint64_t)world * k > MERGE_MAX)
-        return dfail(TKSPMV_ERR_INVALID, "bad arguments to tkspmv_merge_topk (world * k must be <= 8192)");
+        return dfail(TKSPMV_ERR_INVALID, "bad arguments to tkspmv_merge_topk (world * k must be <= 8184)");
     hipLaunchKernelGGL(merge_kernel, dim3(1), dim3(MERGE_THREADS), merge_lds((uint32_t)world, (uint32_t)k), (hipStream_t)stream, dev_gathered, (uint32_t)world,
                        (uint32_t)k, dev_idx, dev_val);
     DHIP(hipGetLastError());
@@ -189,7 +194,7 @@ int tkspmv_merge_topk(const uint32_t *dev_gathered, int32_t world, int32_t k, ui
 int tkspmv_merge_topk_batch(const uint32_t *dev_gathered, int32_t world, int32_t n_q, int32_t k, uint32_t *dev_idx, float *dev_val,
                             void *stream) {
     if (!dev_gathered || !dev_idx || !dev_val || world < 1 || k < 1 || n_q < 1 || n_q > MAX_BATCH || (uint64_t)world * k > MERGE_MAX)
-        return dfail(TKSPMV_ERR_INVALID, "bad arguments to tkspmv_merge_topk_batch (world * k must be <= 8192, n_q in [1, 32])");
+        return dfail(TKSPMV_ERR_INVALID, "bad arguments to tkspmv_merge_topk_batch (world * k must be <= 8184, n_q in [1, 32])");
     hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)n_q), dim3(MERGE_THREADS), merge_lds((uint32_t)world, (uint32_t)k), (hipStream_t)stream, dev_gathered, (uint32_t)world,
                        (uint32_t)k, dev_idx, dev_val);
     DHIP(hipGetLastError());

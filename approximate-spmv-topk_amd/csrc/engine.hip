@@ -1382,6 +1382,12 @@ static int pack_matrix(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
             return fail(err, kind == 2 ? TKSPMV_ERR_NOT_SORTED : (perr.find("failed:") != std::string::npos ? TKSPMV_ERR_DEVICE : TKSPMV_ERR_INVALID), perr);
         S.pack_us = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_pack).count(), 0xFFFFFFFFll);
     }
+    // A matrix without entries packs to no packets and no partitions. The launch paths divide the stream among their waves by
+    // the partition table and were written for at least one partition; none of them is specified over an empty table, so such
+    // an engine is refused here (a rank whose shard came out empty answers with k fillers (0, 0.0f) without an engine).
+    if (m.pm.n_packets == 0)
+        return fail(err, TKSPMV_ERR_INVALID, "the matrix has no entries (nnz = 0): an engine needs at least one; a row shard without entries "
+                                             "contributes k fillers (0, 0.0f) to the merge and needs no engine");
     fill_info(m.pm, d.k, &m.info);
     // The packer's usual outcome is a uniform table -- every partition but the last holds packets_per_partition packets, back
     // to back --: the kernels then derive a wave's range from its partition number (no table loads at the head of a launch).

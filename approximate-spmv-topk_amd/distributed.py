@@ -82,15 +82,32 @@ def _order_key(val_f32):
 
 
 def merge_candidates(idx_i64, val_f32, k):
-    """Top-k of the gathered candidates in sort_tuples order (score desc, row desc). Filler entries (0, 0.0)
-    produced by shards with fewer than k qualifying rows sort last among equal scores and are kept only if needed.
-    idx_i64: int64 [n] global row ids, val_f32: float32 [n]."""
-    key = (_order_key(val_f32) << 32) | (idx_i64 & 0xFFFFFFFF)
-    # de-duplicate fillers: several shards may contribute (0, 0.0); a real row id appears in one shard only
-    key_sorted, order = torch.sort(key, descending=True)
-    keep = torch.ones_like(key_sorted, dtype=torch.bool)
-    keep[1:] = key_sorted[1:] != key_sorted[:-1]
-    order = order[keep][:k]
+    """Global top-k of the gathered shard lists; the same contract as tkspmv_merge_topk (include/tkspmv.h).
+    idx_i64: int64 [n] global row ids, val_f32: float32 [n]: consecutive lists of k entries, one per shard (a shorter last
+    list is read as if padded with fillers), each in tkspmv_read order: real entries first, then fillers (0, bits 0x00000000).
+
+    The filler suffix of a list is its maximal suffix of entries with row id 0 and score bits exactly 0; (0, -0.0f) and
+    (r > 0, +0.0f) are real entries. An entry is taken for a filler when it is (0, +0.0f) and is the last of its list or is
+    followed by another (0, +0.0f): row 0 comes at most once in a list, so for lists in tkspmv_read order that is the suffix.
+    The result is every real entry of every list, sorted by (order key of the score descending, row id descending as unsigned
+    32-bit), cut at k; if there are fewer than k, the tail is padded with (0, 0.0f). A filler never outranks a real entry,
+    whatever min_score the shards ran with. One case cannot be told apart: on the shard with first_row = 0, a real last entry
+    "row 0 scoring +0.0f" looks like a filler and is treated as one (this changes the result only when min_score < 0).
+    Non-finite scores have no stated contract. The native kernel also needs world * k <= 8184; this function does not."""
+    n = idx_i64.shape[0]
+    if n % k:  # complete the last list
+        pad = k - n % k
+        idx_i64 = torch.cat([idx_i64, torch.zeros(pad, dtype=idx_i64.dtype, device=idx_i64.device)])
+        val_f32 = torch.cat([val_f32, torch.zeros(pad, dtype=val_f32.dtype, device=val_f32.device)])
+    idx_i64 = idx_i64 & 0xFFFFFFFF
+    zero = ((idx_i64 == 0) & (val_f32.contiguous().view(torch.int32) == 0)).view(-1, k)
+    next_zero = torch.ones_like(zero)
+    next_zero[:, :-1] = zero[:, 1:]
+    real = ~(zero & next_zero).reshape(-1)
+    # order key in [0, 2^32) moved to [-2^31, 2^31), so the 64-bit sort key stays inside int64
+    key = ((_order_key(val_f32) - 0x80000000) << 32) | idx_i64
+    order = torch.nonzero(real).reshape(-1)
+    order = order[torch.sort(key[order], descending=True, stable=True)[1]][:k]
     out_idx = idx_i64[order]
     out_val = val_f32[order]
     if out_idx.shape[0] < k:  # pad like the gold's zero-initialised list

@@ -426,11 +426,26 @@ int tkspmv_device_count(void);
  * queries each if the engine was created with desc.multi_q), then one
  * all-gather and one merge launch per batch on a side stream, overlapping the local step of the next batch (two buffer
  * sets). synchronize / read flush an open batch; a query vector passed to tkspmv_dist_enqueue must stay valid until then. Every rank must issue the same call sequence. RCCL is
- * loaded with dlopen inside tkspmv_dist_create / tkspmv_dist_unique_id: TKSPMV_ERR_UNSUPPORTED if it cannot be loaded. */
+ * loaded with dlopen inside tkspmv_dist_create / tkspmv_dist_unique_id: TKSPMV_ERR_UNSUPPORTED if it cannot be loaded.
+ *
+ * What the merge computes (tkspmv_dist_read*, tkspmv_merge_topk*, and distributed.merge_candidates in the Python package):
+ *   - A shard list is k entries in tkspmv_read order: real entries first, then fillers (row 0, score bits 0x00000000).
+ *   - The FILLER SUFFIX of a list is its maximal suffix of entries with row id 0 and score bits exactly 0x00000000.
+ *     (0, -0.0f) (bits 0x80000000) is a real entry, and so is (r > 0, +0.0f).
+ *   - The merged list is all real entries of all shards, sorted by (order key of the score descending, row id descending as
+ *     unsigned 32-bit), cut at k; if there are fewer than k, the tail is padded with (0, 0.0f). A filler never outranks a real
+ *     entry, for any desc.min_score (with min_score < 0 real scores are negative, and +0.0f would sort above them).
+ *   - One case cannot be told apart: on the shard with first_row = 0, a real LAST entry "row 0 scoring +0.0f" is
+ *     indistinguishable from a filler and is treated as one. This changes the output only when min_score < 0 (otherwise it
+ *     would sort last among the real entries anyway, and the padding restores it). With world = 1 the merged list is the
+ *     engine's own list.
+ *   - Non-finite scores have no stated contract here.
+ *   - Limit: world * k <= 8184 (the merge block keeps world * k 64-bit keys and 8 padding keys in its 64 KiB of LDS), so
+ *     world = 8 with k = 1024 is refused (k <= 1023 at world 8): TKSPMV_ERR_INVALID from tkspmv_dist_create and tkspmv_merge_topk*. */
 typedef struct tkspmv_dist tkspmv_dist_t;
 /* rank 0 creates the 128-byte RCCL unique id and ships it to the other ranks (any transport). */
 int tkspmv_dist_unique_id(uint8_t *out128);
-/* id128 may be NULL when world == 1. The engine must outlive the returned object. */
+/* id128 may be NULL when world == 1. The engine must outlive the returned object. world * k <= 8184 (k: the engine's). */
 int tkspmv_dist_create(tkspmv_dist_t **out, tkspmv_t *engine, const uint8_t *id128, int32_t rank, int32_t world);
 int tkspmv_dist_set_batch(tkspmv_dist_t *d, int32_t batch);                    /* 1..32 queries per exchange */
 int tkspmv_dist_enqueue(tkspmv_dist_t *d, const float *dev_x);                 /* one query, asynchronous */
@@ -445,9 +460,11 @@ int tkspmv_dist_read_batch(tkspmv_dist_t *d, uint32_t *idx, float *val, int32_t 
 int tkspmv_dist_time_exchange(tkspmv_dist_t *d, int32_t iters, double *ns_per_exchange);
 void tkspmv_dist_destroy(tkspmv_dist_t *d);
 const char *tkspmv_dist_last_error(void);
-/* The merge step alone: dev_gathered = [world][2][k] u32 (row ids, then score bits) -> k best, sort_tuples order. */
-/* The merge of an exchange batch as the pipelined step launches it: dev_gathered [world][n_q][2][k], one block per query,
- * results [n_q][k] (n_q <= 32). Lifts the host-side merge of host_spmv_bscsr.cpp:399-448 for a batch of queries. */
+/* The merge of an exchange batch as the pipelined step launches it: dev_gathered [world][n_q][2][k] u32 (row ids, then score
+ * bits), one block per query, results [n_q][k] (1 <= n_q <= 32): exactly n_q * k entries of dev_idx and of dev_val are written.
+ * Lifts the host-side merge of host_spmv_bscsr.cpp:399-448 for a batch of queries. The lists and the result follow the contract
+ * stated above (filler suffix, order, padding); world >= 1, k >= 1 and world * k <= 8184, else TKSPMV_ERR_INVALID and nothing
+ * is launched. */
 int tkspmv_merge_topk_batch(const uint32_t *dev_gathered, int32_t world, int32_t n_q, int32_t k, uint32_t *dev_idx,
                             float *dev_val, void *stream);
 /* Rehearsal without RCCL (which refuses two ranks on one device): the all-gather of the pipelined step goes through host
@@ -456,6 +473,8 @@ int tkspmv_merge_topk_batch(const uint32_t *dev_gathered, int32_t world, int32_t
  * tkspmv_dist_create builds no communicator for world > 1 and the callback is mandatory. */
 typedef int (*tkspmv_host_allgather_fn)(const void *send, void *recv, uint64_t bytes_per_rank, void *user);
 int tkspmv_dist_set_host_exchange(tkspmv_dist_t *d, tkspmv_host_allgather_fn fn, void *user);
+/* The merge step alone, one query: dev_gathered = [world][2][k] u32 -> the k best in dev_idx / dev_val [k]. Same contract and
+ * the same limit (world * k <= 8184) as tkspmv_merge_topk_batch with n_q = 1. */
 int tkspmv_merge_topk(const uint32_t *dev_gathered, int32_t world, int32_t k, uint32_t *dev_idx, float *dev_val,
                       void *stream);
 

@@ -10,10 +10,12 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import merge_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _worker(rank, world, port, k, seed, q):
+def _worker(rank, world, port, k, seed, q, signed=False, min_score=0.0, bounds=None):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -27,23 +29,27 @@ def _worker(rank, world, port, k, seed, q):
         dmod = import_module("approximate_spmv_topk_amd.distributed")
         m = mod.generate_matrix(3000, 256, 12, "gamma", seed)
         x = mod.create_sample_vector(256, True, False, True, seed + 1)
-        bounds = dmod.shard_bounds_by_nnz(m.row, m.rows, world)
+        if signed:  # a general matrix: scores of both signs (values minus 0.5, like _coo(..., neg=True) of test_gpu_engine.py)
+            m = mod.CooMatrix(m.rows, m.cols, m.row, m.col, (m.val - np.float32(0.5)).astype(np.float32))
+        hand_made = bounds is not None
+        if not hand_made:
+            bounds = dmod.shard_bounds_by_nnz(m.row, m.rows, world)
         r0, r1 = bounds[rank]
         lr, lc, lv = dmod.shard_coo(m.row, m.col, m.val, r0, r1)
         y, present = O.scores_f32_seq(lr, lc, lv, x, r1 - r0)
-        li, lvv = O.select_topk(y, present, k, 0.0, first_row=r0)  # what the rank's engine returns (global ids)
+        li, lvv = O.select_topk(y, present, k, min_score, first_row=r0)  # what the rank's engine returns (global ids)
         sh = dmod.ShardedTopK(k, torch.device("cpu"))
         iv, vv = sh.local_views()
         iv.copy_(torch.from_numpy(li.astype(np.int64)).to(torch.int32))
         vv.copy_(torch.from_numpy(lvv))
         gi, gv = sh.step()
         yg, pg = O.scores_f32_seq(m.row, m.col, m.val, x, m.rows)
-        ei, ev = O.select_topk(yg, pg, k)
-        ok = np.array_equal(gi.numpy().astype(np.uint32), ei) and np.array_equal(gv.numpy(), ev)
+        ei, ev = O.select_topk(yg, pg, k, min_score)
+        ok = np.array_equal(gi.numpy().astype(np.uint32), ei) and np.array_equal(gv.numpy().view(np.uint32), ev.view(np.uint32))
         # shards are contiguous, cover every row once and are nnz-balanced
         cover = sum(b - a for a, b in bounds) == m.rows and all(bounds[i][1] == bounds[i + 1][0] for i in range(world - 1))
         nnz_per = [int(((m.row >= a) & (m.row < b)).sum()) for a, b in bounds]
-        balanced = max(nnz_per) - min(nnz_per) <= 400
+        balanced = hand_made or max(nnz_per) - min(nnz_per) <= 400
         q.put((rank, bool(ok), bool(cover), bool(balanced)))
     finally:
         dist.destroy_process_group()
@@ -132,3 +138,61 @@ def test_merge_pads_and_orders():
     assert i.tolist() == [7, 9, 5, 3] and np.allclose(v.tolist(), [0.9, 0.5, 0.5, 0.1])
     i, v = dmod.merge_candidates(idx, val, 8)  # fillers collapse, then padding
     assert i.tolist() == [7, 9, 5, 3, 0, 0, 0, 0] and v.tolist()[4:] == [0.0] * 4
+
+
+def test_sharded_topk_gloo_world2_signed_short_shard():
+    """A signed matrix, min_score = -1e30 and rank 0 owning 37 rows, fewer than k = 2000: its list ends in 1963 fillers. k is
+    above the number of rows that score positive (about half of 3000), so the merged list reaches into the negative scores of
+    rank 1, which the fillers must not outrank. Expected: select_topk over the whole matrix's scores, bit for bit."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 33900 + os.getpid() % 2000
+    bounds = [(0, 37), (37, 3000)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, 2000, 5, q, True, -1e30, bounds)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=120) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(r[0] for r in res) == [0, 1]
+    assert all(r[1] for r in res), "merged top-k of the signed short shards differs from the global oracle"
+    assert all(r[2] and r[3] for r in res)
+
+
+def _dmod():
+    sys.path.insert(0, ROOT)
+    import _pkg
+    from importlib import import_module
+    _pkg.load()
+    return import_module("approximate_spmv_topk_amd.distributed")
+
+
+def _merge_candidates_of(dmod, case):
+    idx = torch.from_numpy(case["idx"].reshape(-1).astype(np.int64))
+    val = torch.from_numpy(case["val"].reshape(-1).copy())
+    i, v = dmod.merge_candidates(idx, val, case["k"])
+    assert i.shape == (case["k"],) and v.shape == (case["k"],) and v.dtype == torch.float32
+    return i.numpy().astype(np.uint32), v.numpy().view(np.uint32)
+
+
+MERGE_TABLE = merge_ref.table()
+
+
+@pytest.mark.parametrize("case", MERGE_TABLE, ids=[c["name"] for c in MERGE_TABLE])
+def test_merge_candidates_against_the_reference(case):
+    """merge_candidates on short, signed and tied lists, bit for bit against tests/merge_ref.py::merge_reference."""
+    got_i, got_v = _merge_candidates_of(_dmod(), case)
+    want_i, want_v = merge_ref.expected(case)
+    print(case["name"], "got", got_i.tolist(), got_v.tolist(), "want", want_i.tolist(), want_v.view(np.uint32).tolist())
+    assert np.array_equal(got_i, want_i) and np.array_equal(got_v, want_v.view(np.uint32))
+
+
+def test_merge_reference_on_the_worked_example():
+    """The reference itself, on the one case whose answer is written down by hand."""
+    by_name = {c["name"]: c for c in MERGE_TABLE}
+    i, v = merge_ref.expected(by_name["example_k4"])
+    assert i.tolist() == [17, 3, 12, 15] and v.tolist() == np.array([0.5, -0.1, -0.2, -0.3], np.float32).tolist()
+    i, v = merge_ref.expected(by_name["example_k8"])
+    assert i.tolist() == [17, 3, 12, 15, 1, 11, 0, 0]
+    assert v.view(np.uint32).tolist() == np.array([0.5, -0.1, -0.2, -0.3, -0.4, -0.5, 0.0, 0.0], np.float32).view(np.uint32).tolist()

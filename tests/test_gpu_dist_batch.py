@@ -88,3 +88,27 @@ def test_two_ranks_on_one_gpu_through_the_pipelined_step(tmp_path):
     for rank, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, f"rank {rank} failed:\n{out[-3000:]}"
         assert "REHEARSAL_OK" in out, out[-3000:]
+
+
+def test_two_ranks_on_short_signed_shards_through_the_pipelined_step(tmp_path):
+    """The same rehearsal (the worker's second mode) on a signed matrix with min_score = -1e30, rank 0 owning 37 rows, fewer than
+    k = 100: 11 queries in exchange batches of 4, every list of the last batch bit for bit against merge_reference over the two
+    shards' order-matched oracle lists."""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29534", WORLD_SIZE="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    procs = []
+    for rank in range(2):
+        e = dict(env, RANK=str(rank), LOCAL_RANK="0")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_dist_host_worker.py"), str(tmp_path), "short-shards"], env=e,
+                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+    outs = []
+    for p in procs:
+        try:
+            out, _ = p.communicate(timeout=120)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        outs.append(out)
+    for rank, (p, out) in enumerate(zip(procs, outs)):
+        assert p.returncode == 0, f"rank {rank} failed:\n{out[-3000:]}"
+        assert "REHEARSAL_OK" in out, out[-3000:]
