@@ -13,6 +13,7 @@ F32, Q1_7, Q1_7_WIDE, F16, FIXED, Q1_7_F32 = 0, 1, 2, 3, 4, 5
 IMPL_STREAM, IMPL_ROW_PER_LANE, IMPL_SCORES_SELECT = 0, 1, 2
 MAX_COLS = 16384
 MAX_K = 1024
+CURSOR_START, CURSOR_AFTER, CURSOR_END = 0, 1, 2  # tkspmv_cursor.state
 
 
 class TkspmvError(RuntimeError):
@@ -48,6 +49,12 @@ class Info(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
 
 
+class Cursor(C.Structure):
+    """tkspmv_cursor: a position in the result order (search-after paging). row is a GLOBAL row id, score_bits the bit pattern
+    of a float32 score; state START ignores both, any state other than START / AFTER acts as END."""
+    _fields_ = [("row", C.c_uint32), ("score_bits", C.c_uint32), ("state", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("stream_kernel_ns", C.c_double), ("select_kernel_ns", C.c_double), ("query_ns", C.c_double),
@@ -79,7 +86,7 @@ class OptionsC(C.Structure):
 # Every symbol include/tkspmv.h declares; tests check the library exports all of them.
 EXPORTED_SYMBOLS = [
     "tkspmv_create", "tkspmv_destroy", "tkspmv_get_info", "tkspmv_set_query", "tkspmv_set_query_device",
-    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_range", "tkspmv_run_range", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
+    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_enqueue_range", "tkspmv_run_range", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
     "tkspmv_time_queries", "tkspmv_time_host_loop", "tkspmv_time_query_batches", "tkspmv_time_stream_read", "tkspmv_enqueue_multi", "tkspmv_time_multi", "tkspmv_profile", "tkspmv_last_error", "tkspmv_device_count", "tkspmv_mtx_read", "tkspmv_mtx_free",
     "tkspmv_mtx_write", "tkspmv_sample_vector", "tkspmv_generate", "tkspmv_generate_rows", "tkspmv_generate_degrees", "tkspmv_options_parse", "tkspmv_pack", "tkspmv_pack_device",
     "tkspmv_sell_roundtrip", "tkspmv_sell_pack_device_check", "tkspmv_packed_info", "tkspmv_packed_decode", "tkspmv_packed_raw", "tkspmv_packed_get_row", "tkspmv_packed_score_rows", "tkspmv_packed_free", "tkspmv_wave_partitions", "tkspmv_packed_save", "tkspmv_packed_load",
@@ -124,6 +131,8 @@ def lib():
     L.tkspmv_set_groups.argtypes = [vp, u32p, C.c_uint32]
     L.tkspmv_enqueue_grouped.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.tkspmv_run_grouped.argtypes = [vp, C.c_int32, u32p, f32p, u32p, C.POINTER(C.c_int32)]
+    L.tkspmv_enqueue_after.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.tkspmv_run_after.argtypes = [vp, C.POINTER(Cursor), C.c_int32, u32p, f32p, C.POINTER(C.c_int32), u32p, C.POINTER(Cursor)]
     L.tkspmv_enqueue_range.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_uint32, vp, vp]
     L.tkspmv_run_range.argtypes = [vp, C.c_float, C.c_int32, u32p, f32p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.tkspmv_enqueue_row_vectors.argtypes = [vp, vp, C.c_int32, vp, vp, vp]

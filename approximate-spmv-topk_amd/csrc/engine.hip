@@ -51,6 +51,7 @@
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
 #include "kernels/group_select.hpp"
+#include "kernels/after_select.hpp"
 
 namespace tkspmv {
 
@@ -465,6 +466,24 @@ struct EngineImpl {
         static constexpr uint32_t W_NONEMPTY = 1024, W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32;
         uint32_t *d_gout_grp = nullptr, *d_gout_n = nullptr;  // engine-owned [k] group ids and n ("the last query wins")
     } grouped;
+
+    // Search-after paging (tkspmv_enqueue_after; after_cut_kernel, after_finish_kernel) touches no other group but the matrix either:
+    // its scores go to an array of its own, the cut at the cursor rewrites that array alone, its selection runs on its own histogram,
+    // candidate list and counters, and the selection kernel gets words of this group where it resets exchange state behind itself.
+    // No creation stage: the first call allocates (ensure_after), 12 bytes per row; the kernels move the device words and leave them
+    // zero behind every query.
+    struct After {
+        float *d_ay = nullptr;                  // [rows] the scores of the query in flight; -inf where a row has no entry (never written)
+        unsigned long long *d_acand = nullptr;  // [rows] candidate list of the radix filter: it keeps EVERY tie at the cut
+        // [4][256] histogram (zeroed in front of every query) | the count of eligible rows behind the cursor (after_finish_kernel
+        // zeroes it) | the candidate counter | the words the selection kernel zeroes behind itself (threshold word, nine tickets 32
+        // words apart)
+        uint32_t *d_awords = nullptr;
+        static constexpr uint32_t W_TOTAL = 1024, W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32;
+        // engine-owned outputs of the host form ("the last query wins"): n, total | the cursor tkspmv_run_after uploads | the next cursor
+        uint32_t *d_aout = nullptr;
+        static constexpr uint32_t O_N = 0, O_TOTAL = 1, O_CURSOR = 4, O_NEXT = 8, N_OUT = 12;
+    } after;
 
     // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
     // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
@@ -1032,6 +1051,92 @@ struct EngineImpl {
             I.grp = out_grp + (size_t)i * out_stride;
             I.n_out = out_n + (size_t)i * n_stride;
             hipLaunchKernelGGL(group_ids_kernel, dim3(((uint32_t)desc.k + GROUP_THREADS - 1u) / GROUP_THREADS), dim3(GROUP_THREADS), 0, s, I);
+        }
+    }
+    // The scratch of the search-after path, allocated by its first call.
+    hipError_t ensure_after() {
+        After &Q = after;
+        const size_t rows = std::max<size_t>(desc.rows, 1);
+        if (!Q.d_ay) {
+            float *y = nullptr;
+            if (const hipError_t e = alloc(y, rows * 4)) return e;
+            const std::vector<float> ninf(rows, -std::numeric_limits<float>::infinity());  // (rows without entries are never written)
+            if (const hipError_t e = hipMemcpy(y, ninf.data(), rows * 4, hipMemcpyHostToDevice)) return e;
+            Q.d_ay = y;
+        }
+        if (!Q.d_acand) {
+            if (const hipError_t e = alloc(Q.d_acand, rows * 8)) return e;
+        }
+        if (!Q.d_awords) {
+            if (const hipError_t e = alloc(Q.d_awords, (size_t)After::N_WORDS * 4, Mem::Device, 0)) return e;
+        }
+        if (!Q.d_aout) {
+            if (const hipError_t e = alloc(Q.d_aout, (size_t)After::N_OUT * 4, Mem::Device, 0)) return e;
+        }
+        return hipSuccess;
+    }
+    // A sequence of search-after queries (query i: x = xs + i * cols, cursor = cursors + i or START, mask = mask + i * stride words or
+    // none; results at out_* + i * out_stride, n / total / next at their arrays' entry i where given), complete in stream
+    // order when this returns: per query the SpMV-only kernel, the cut at the cursor, the radix select over the rows that remain, the
+    // selection kernel and the page's bookkeeping. No exchange set, record, verdict, carried threshold or deferred selection is read
+    // or written: the SpMV-only kernels touch none, and the selection kernel is given this path's own words. Only mat.launch_counter
+    // moves.
+    void launch_after(const float *xs, int n, const tkspmv_cursor *cursors, const uint32_t *mask, size_t stride, uint32_t *out_idx, float *out_val,
+                      size_t out_stride, uint32_t *out_n, uint32_t *out_total, tkspmv_cursor *out_next, hipStream_t s) {
+        using namespace after_kernels;
+        static_assert(sizeof(AfterCursor) == sizeof(tkspmv_cursor) && sizeof(tkspmv_cursor) == 16, "the device reads tkspmv_cursor as four words");
+        const After &Q = after;
+        AfterParams A{};
+        A.y = Q.d_ay;
+        A.total = Q.d_awords + After::W_TOTAL;
+        A.rows = desc.rows;
+        A.first_row = desc.first_row;
+        {  // order key of min_score (the device function's host twin)
+            uint32_t u;
+            std::memcpy(&u, &desc.min_score, 4);
+            A.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        }
+        RadixParams R{};
+        R.scores = Q.d_ay;
+        R.rows = desc.rows;
+        R.k = (uint32_t)desc.k;
+        R.kmin = A.kmin;
+        R.hist = Q.d_awords;
+        R.ovf_cand = Q.d_acand;
+        R.ovf_count = Q.d_awords + After::W_COUNT;
+        R.ovf_cap = desc.rows;
+        SelectParams S{};  // no slots, no published maxima: every candidate comes from the list, as a local row
+        S.wg_cand = Q.d_acand;  // (n_wg = 0: the selection still forms the address of slot 0)
+        S.ovf_cand = Q.d_acand;
+        S.ovf_count = R.ovf_count;
+        S.ovf_cap = desc.rows;
+        S.k = (uint32_t)desc.k;
+        S.first_row = desc.first_row;
+        S.out_scale = 1.0f;  // the scores kernel already wrote final scores
+        S.tau_g = Q.d_awords + After::W_TAU;
+        S.done_count = Q.d_awords + After::W_DONE;
+        AfterFinishParams Z{};
+        Z.total = A.total;
+        Z.k = (uint32_t)desc.k;
+        const uint32_t cut_grid = std::max(1u, std::min(std::max(1u, info.num_cus) * 8u, (uint32_t)(((uint64_t)desc.rows + AFTER_THREADS * AFTER_LANE_ROWS - 1u) / (AFTER_THREADS * AFTER_LANE_ROWS))));
+        const uint32_t rgrid = std::max(1u, std::min(256u, (desc.rows + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
+        for (int i = 0; i < n; ++i) {
+            const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
+            launch_scores(xs + (size_t)i * desc.cols, s, Q.d_ay, mask ? &F : nullptr);
+            (void)hipMemsetAsync(Q.d_awords, 0, 4 * 256 * 4, s);
+            A.cursor = cursors ? reinterpret_cast<const AfterCursor *>(cursors + i) : nullptr;
+            hipLaunchKernelGGL(after_cut_kernel, dim3(cut_grid), dim3(AFTER_THREADS), 0, s, A);
+            for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
+            hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+            S.out_idx = out_idx + (size_t)i * out_stride;
+            S.out_val = out_val + (size_t)i * out_stride;
+            hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
+            Z.idx = S.out_idx;
+            Z.val = S.out_val;
+            Z.n_out = out_n ? out_n + i : nullptr;
+            Z.total_out = out_total ? out_total + i : nullptr;
+            Z.next = out_next ? reinterpret_cast<AfterCursor *>(out_next + i) : nullptr;
+            hipLaunchKernelGGL(after_finish_kernel, dim3(1), dim3(AFTER_FINISH_THREADS), 0, s, Z);
         }
     }
     // The fused launch hands its result to the host itself: the pinned block, a new epoch, the start stamp (tkspmv_run).
@@ -2300,6 +2405,58 @@ int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t 
     if (val) HIP_TRY(hipMemcpy(val, m.host.d_out_val, k * 4, hipMemcpyDeviceToHost));
     if (grp) HIP_TRY(hipMemcpy(grp, m.grouped.d_gout_grp, k * 4, hipMemcpyDeviceToHost));
     if (n) *n = (int32_t)found;
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_after(const float *dev_xs, int32_t count, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
+                          uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_after (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)");
+    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+    if (const char *why = m.grouped_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    const bool own = dev_idx == nullptr;  // the engine-owned result pair: the last query wins
+    return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
+        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
+        // after these queries did. Settle them now (the host waits for the engine's stream once).
+        if (own && !m.trust.pending_checks.empty()) {
+            if (const int st = m.wait_idle(err)) return st;
+        }
+        HIP_TRY(m.ensure_after());
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_after(dev_xs, count, dev_cursors, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, own ? m.host.d_out_idx : dev_idx,
+                       own ? m.host.d_out_val : dev_val, own ? 0u : (size_t)m.desc.k, dev_n, dev_total, dev_next, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
+                      std::string &err) {
+    EngineImpl &m = *impl_;
+    using After = EngineImpl::After;
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    if (const char *why = m.grouped_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
+    if (!m.host.d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(m.ensure_after());
+    uint32_t *const out = m.after.d_aout;
+    // (the cursor words belong to this host form alone, and the host form before this one has waited)
+    if (cursor) HIP_TRY(hipMemcpy(out + After::O_CURSOR, cursor, sizeof(tkspmv_cursor), hipMemcpyHostToDevice));
+    const int st = enqueue_after(nullptr, 1, cursor ? reinterpret_cast<const tkspmv_cursor *>(out + After::O_CURSOR) : nullptr,
+                                 use_filter ? m.filter.d_filter : nullptr, 0, nullptr, nullptr, out + After::O_N, out + After::O_TOTAL,
+                                 reinterpret_cast<tkspmv_cursor *>(out + After::O_NEXT), nullptr, err);
+    if (st != TKSPMV_OK) return st;
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    m.host.x_pending = false;
+    const size_t k = (size_t)m.desc.k;
+    uint32_t words[After::N_OUT];
+    HIP_TRY(hipMemcpy(words, out, sizeof(words), hipMemcpyDeviceToHost));
+    if (idx) HIP_TRY(hipMemcpy(idx, m.host.d_out_idx, k * 4, hipMemcpyDeviceToHost));
+    if (val) HIP_TRY(hipMemcpy(val, m.host.d_out_val, k * 4, hipMemcpyDeviceToHost));
+    if (n) *n = (int32_t)words[After::O_N];
+    if (total) *total = words[After::O_TOTAL];
+    if (next) std::memcpy(next, words + After::O_NEXT, sizeof(tkspmv_cursor));
     return TKSPMV_OK;
 }
 

@@ -40,6 +40,12 @@ class Engine {
     int enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
                         uint32_t *dev_grp, uint32_t *dev_n, void *stream, std::string &err);
     int run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err);
+    // Search-after paging (after_cut_kernel): the k eligible rows that rank strictly behind a cursor, with the hits left and the cursor
+    // of the following page. run_after is the host-side counterpart (installed vector, host cursor, waits).
+    int enqueue_after(const float *dev_xs, int32_t count, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
+                      uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err);
+    int run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
+                  std::string &err);
     // Range queries (range_kernel): every allowed row with entries that scores >= the query's threshold, unordered; run_range is
     // the host-side counterpart (installed vector, host threshold, waits, sorts).
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,

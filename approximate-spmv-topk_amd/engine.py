@@ -15,6 +15,8 @@ import numpy as np
 from . import _lib
 from .host import row_mask
 
+MAX_PAGE = 1000  # ranked_spmv's default page: every page takes the scores + radix-select route whatever k is, so a large page is cheapest
+
 
 class SpMV:
     def __init__(self, x, y, val, num_rows, num_cols, num_nnz=None, vec=None, k=20, debug=0, *, device=-1,
@@ -226,6 +228,56 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_run_grouped(self._h, int(allow is not None), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                  val.ctypes.data_as(C.POINTER(C.c_float)), grp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
         return val[:n.value], idx[:n.value], grp[:n.value]
+
+    def enqueue_after(self, dev_xs, count, dev_cursors=0, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_n=0, dev_total=0, dev_next=0,
+                      stream=0):
+        """Search-after paging of `count` queries (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()): the
+        first k eligible rows that rank strictly behind dev_cursors[i] (_lib.Cursor records in device memory, read in stream
+        order; 0 = from the top for every query). dev_mask: allow-mask(s) as in enqueue_filtered, 0 = unfiltered. dev_idx / dev_val:
+        [count][k] device buffers, both or none (engine buffers, last query wins); dev_n / dev_total: [count] real entries per
+        page and eligible rows behind the cursor, the page included (optional); dev_next: [count] cursors of the following pages
+        (optional; may be dev_cursors itself: the same call again then walks on). Pads are (0, 0.0). No host sync; one such call
+        in flight at a time; the first call allocates about 12 bytes per row."""
+        p = lambda a: C.c_void_p(int(a)) if a else None
+        _lib.check(_lib.lib().tkspmv_enqueue_after(self._h, p(dev_xs), int(count), p(dev_cursors), p(dev_mask), int(mask_stride), p(dev_idx),
+                                                   p(dev_val), p(dev_n), p(dev_total), p(dev_next), C.c_void_p(int(stream))))
+
+    def run_after(self, cursor=None, vec=None, allow=None):
+        """One page with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or row_mask()
+        words; the query is then restricted to it), then the k eligible rows behind `cursor` -- None (from the top) or
+        (row, score_bits, state), as the call before returned it. Returns (idx, val, n, total, next): idx / val of k entries, the
+        first n real, the rest pads; total = the eligible rows behind the cursor, this page included; next = the cursor of the
+        following page, state CURSOR_END when this page was the last."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        return self._run_after(cursor, allow is not None)
+
+    def _run_after(self, cursor, use_filter):
+        cur = None
+        if cursor is not None:
+            row, bits, state = (int(v) for v in cursor)
+            cur = C.byref(_lib.Cursor(row, bits, state, 0))
+        idx = np.zeros(self.k, dtype=np.uint32)
+        val = np.zeros(self.k, dtype=np.float32)
+        n, total, nxt = C.c_int32(0), C.c_uint32(0), _lib.Cursor()
+        _lib.check(_lib.lib().tkspmv_run_after(self._h, cur, int(use_filter), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), C.byref(total), C.byref(nxt)))
+        return idx, val, int(n.value), int(total.value), (int(nxt.row), int(nxt.score_bits), int(nxt.state))
+
+    def pages(self, vec=None, allow=None):
+        """Generator over the complete ranking of the eligible rows, page by page (reset(vec) / set_filter(allow) first, as in
+        run_after): yields (values, indices) of each page's real entries, ordered like read_result, until the cursor says END --
+        no empty trailing page, and no page at all when no row is eligible. The query vector and the mask must stay installed
+        while the generator is in use."""
+        idx, val, n, _, cursor = self.run_after(None, vec, allow)
+        while n:
+            yield val[:n], idx[:n]
+            if cursor[2] == _lib.CURSOR_END:
+                return
+            idx, val, n, _, cursor = self._run_after(cursor, allow is not None)
 
     def enqueue_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_idx=0, dev_val=0, capacity=0, dev_mask=0, mask_stride=0, stream=0):
         """Range queries: for query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()) every row that
@@ -448,6 +500,26 @@ def grouped_spmv(m, vec, groups, k=100, allow=None, **kw):
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
     try:
         return e.run_grouped(allow=allow, groups=groups)
+    finally:
+        e.close()
+
+
+def ranked_spmv(m, vec, n, k=MAX_PAGE, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m with pages of k rows, return (values, indices) of the n best rows (among
+    the rows of `allow`, if given) for ANY n, by search-after paging: ordered like topk_spmv's result, fewer than n when fewer
+    rows are eligible."""
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
+    try:
+        vals, idxs, have = [], [], 0
+        for v, i in e.pages(allow=allow):
+            vals.append(v)
+            idxs.append(i)
+            have += i.size
+            if have >= int(n):
+                break
+        if not vals:
+            return np.empty(0, dtype=np.float32), np.empty(0, dtype=np.uint32)
+        return np.concatenate(vals)[:int(n)], np.concatenate(idxs)[:int(n)]
     finally:
         e.close()
 

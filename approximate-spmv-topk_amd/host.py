@@ -133,6 +133,54 @@ def collapse_topk(scores, present, groups, k, min_score=0.0, first_row=0):
     return idx, val, grp, n
 
 
+def page_after(y, present, k, cursor=None, min_score=0.0, first_row=0, allow=None):
+    """The contract of search-after paging (SpMV.enqueue_after) restated in numpy, for CPU-side users and as the tests' expectation:
+    from float32 y[rows] and present[rows] (the row has entries; allow[rows], if given, restricts further) the first k eligible
+    rows that rank strictly behind `cursor` in the engine's order. cursor: None (from the top) or (row, score_bits, state) as
+    tkspmv_cursor holds them -- a GLOBAL row id, the score's bit pattern, state 0 = START, 1 = AFTER, anything else = END.
+    Returns (idx[k] uint32 = row + first_row, val[k] float32, n, total, next): n real entries, then pads (0, 0.0); total = the
+    eligible rows behind the cursor, the returned ones included; next = (row, score_bits, 1) of the last real entry when
+    total > k, else (0, 0, 2). Ordering, eligibility and the cut go by the engine's 64-bit key (order key of the score << 32 |
+    global row id) and nothing else: a row is eligible when its order key is at least min_score's and its score is above -inf; it
+    ranks behind an AFTER cursor when its key is below the cursor's; a larger key comes first."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    ok = np.asarray(present).astype(bool)
+    if y.ndim != 1 or ok.shape != y.shape:
+        raise ValueError("y and present must be 1-D arrays of one length")
+    if allow is not None:
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.shape != y.shape:
+            raise ValueError("allow must be a bool array of y's length")
+        ok = ok & a
+    k = int(k)
+
+    def order_key(f):  # monotone float32 -> uint32, the engine's order_key
+        u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
+        return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+    key = order_key(y)
+    ok = ok & (key >= order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
+    rows = np.flatnonzero(ok)
+    ckey = (key[rows].astype(np.uint64) << np.uint64(32)) | (rows.astype(np.uint64) + np.uint64(int(first_row)))
+    if cursor is not None:
+        c_row, c_bits, c_state = (int(v) for v in cursor)
+        if c_state == 1:
+            c_key = order_key(np.array([c_bits], dtype=np.uint32).view(np.float32))[0]
+            behind = ckey < ((np.uint64(c_key) << np.uint64(32)) | np.uint64(c_row & 0xFFFFFFFF))
+        else:
+            behind = np.full(rows.shape, c_state == 0)
+        rows, ckey = rows[behind], ckey[behind]
+    total = int(rows.size)
+    page = rows[np.argsort(ckey, kind="stable")[::-1][:k]]  # (keys are unique: they carry the row)
+    n = int(page.size)
+    idx = np.zeros(k, dtype=np.uint32)
+    val = np.zeros(k, dtype=np.float32)
+    idx[:n] = page + int(first_row)
+    val[:n] = y[page]
+    nxt = (int(idx[n - 1]), int(val[n - 1:n].view(np.uint32)[0]), 1) if total > k else (0, 0, 2)
+    return idx, val, n, total, nxt
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()

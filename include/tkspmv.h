@@ -278,6 +278,52 @@ int tkspmv_enqueue_grouped(tkspmv_t *e, const float *dev_xs, int32_t count, cons
  * (TKSPMV_ERR_INVALID if none is); waits; idx / val / grp (host, k entries each, any may be NULL) receive the list, *n the
  * number of real entries. */
 int tkspmv_run_grouped(tkspmv_t *e, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n);
+/* Search-after paging: "the next k". The result order is a strict total order -- score descending by order key, then row id
+ * descending: a 64-bit integer comparison of (order key << 32 | global row id), no float is compared as a float --, so "every
+ * eligible row that ranks strictly behind entry (row, score)" is well defined, stateless and exact across ties. A cursor is such a
+ * position and nothing more: it need not name a row of this engine (a masked row, an empty row, a row of another shard, a score
+ * no row has are all fine). START cuts nothing, END cuts everything. A row is ELIGIBLE exactly as in the grouped call: it has
+ * entries, is allowed by the optional mask, its order key is at least the key of desc.min_score and its score is above -inf. It
+ * ranks behind an AFTER cursor when order_key(score) < order_key(cursor score), or the keys are equal and first_row + local row <
+ * cursor.row. NaN scores and NaN cursor scores have no stated contract. */
+typedef struct { uint32_t row; uint32_t score_bits; uint32_t state; uint32_t reserved; } tkspmv_cursor; /* 16 bytes */
+/* state: 0 = TKSPMV_CURSOR_START (from the top; row / score_bits ignored), 1 = TKSPMV_CURSOR_AFTER, 2 = TKSPMV_CURSOR_END; any other value acts as END */
+#define TKSPMV_CURSOR_START 0u
+#define TKSPMV_CURSOR_AFTER 1u
+#define TKSPMV_CURSOR_END 2u
+/* Query i = dev_xs + i * cols (NULL with count = 1: the vector installed by tkspmv_set_query). dev_cursors: [count] cursors in
+ * DEVICE memory, query i reads dev_cursors[i] when its turn comes in stream order; NULL: START for every query. dev_mask /
+ * mask_stride_words: as in tkspmv_enqueue_grouped (NULL: unfiltered). Outputs of query i:
+ *   dev_idx / dev_val + i * k: the first k eligible rows behind the cursor in the usual order, global ids, the score bits every
+ *     other path reports; a short list is padded with (0, 0.0f). Both given or both NULL (the engine-owned pair, the last query
+ *     wins, tkspmv_read sees it; pending checks of trusted batch launches are then settled first, as tkspmv_enqueue_grouped does).
+ *   dev_n[i] (optional): the number of real entries.
+ *   dev_total[i] (optional): the eligible rows behind the cursor, the returned ones included -- the "hits left".
+ *   dev_next[i] (optional): the cursor of the following page: AFTER(the last real entry) when total > k, END otherwise (n = 0
+ *     included), so a loop "while state != END" ends without an empty trailing page. dev_next may be dev_cursors itself: the
+ *     cursor is read at the start of query i and written at its end, in stream order, so P calls with one buffer walk P pages
+ *     with no host round trip.
+ * Hence with START the list is the engine's exact top-k bit for bit, and the pages concatenated are the engine's complete ranking
+ * of the eligible rows. Row-sharded use: give every shard the SAME cursor (ids are global), merge the shards' pages with
+ * tkspmv_merge_topk; the next cursor is AFTER(the last real merged entry) when the shards' totals sum to more than k, else END (a
+ * shard's own dev_next is not the global one).
+ * Stream contract (the grouped call's): complete in stream order on any stream; reads and writes no exchange set, record, verdict,
+ * carried threshold or deferred selection; the scratch belongs to the engine, so only ONE such call may be in flight at a time. The
+ * FIRST call allocates that scratch, about 12 bytes per row (the scores and a candidate list that holds every tie at the cut).
+ * Launch scheme per query: the SpMV-only kernel, one pass that cuts at the cursor and counts (after_cut_kernel), the radix select,
+ * the selection kernel, one small block for n / total / next.
+ * Errors: TKSPMV_ERR_INVALID, before any device call, for a NULL engine, count < 1, a negative stride, dev_idx / dev_val partly
+ * given, dev_xs = NULL with count != 1; TKSPMV_ERR_STATE for dev_xs = NULL with no vector installed; TKSPMV_ERR_UNSUPPORTED where
+ * tkspmv_enqueue_grouped reports it (approximate per-partition engines, engines that do not hold the packet stream, a mask on
+ * engines without the filtered path's kernels). Every value type is served without a mask. */
+int tkspmv_enqueue_after(tkspmv_t *e, const float *dev_xs, int32_t count, const tkspmv_cursor *dev_cursors,
+                         const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                         uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream);
+/* The host-side counterpart: the installed query vector, a HOST cursor (NULL: START), the mask installed by tkspmv_set_filter when
+ * use_filter != 0 (TKSPMV_ERR_INVALID if none is); waits; idx / val (host, k entries each), *n, *total and *next receive the page
+ * (any may be NULL). */
+int tkspmv_run_after(tkspmv_t *e, const tkspmv_cursor *cursor /* host, NULL = START */, int32_t use_filter,
+                     uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next);
 /* Queries by stored row ("which rows are closest to row r?": more-like-this, de-duplication, the k-NN self-join A.A^T top-n --
  * the product the reference's CPU comparator sparse_dot_topn exists for). dev_rows[i] is a GLOBAL row id (desc.first_row + local
  * row): exactly what queries return, so results can be fed back. dev_xs + i * cols receives row i as the dense vector of cols
