@@ -169,6 +169,14 @@ int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const 
 int tkspmv_run_range(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count) {
     ENGINE_CALL(run_range(threshold, use_filter, idx, val, capacity, count, err))
 }
+int tkspmv_enqueue_facets(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask,
+                          int64_t mask_stride_words, const uint32_t *dev_labels, uint32_t n_bins, uint32_t *dev_counts, tkspmv_facet_best *dev_best,
+                          uint32_t *dev_totals, void *stream) {
+    ENGINE_CALL(enqueue_facets(dev_xs, count, dev_thresholds, dev_mask, mask_stride_words, dev_labels, n_bins, dev_counts, dev_best, dev_totals, stream, err))
+}
+int tkspmv_run_facets(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total) {
+    ENGINE_CALL(run_facets(threshold, use_filter, counts, best, total, err))
+}
 int tkspmv_enqueue_row_vectors(tkspmv_t *h, const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream) {
     ENGINE_CALL(enqueue_row_vectors(dev_rows, count, dev_xs, dev_len, stream, err))
 }

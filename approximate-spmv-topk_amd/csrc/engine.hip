@@ -48,6 +48,7 @@
 #include "kernels/radix_select.hpp"
 #include "kernels/read_probe.hpp"
 #include "kernels/range_kernel.hpp"
+#include "kernels/facet_kernel.hpp"
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
 #include "kernels/group_select.hpp"
@@ -101,6 +102,7 @@ enum class Mem { Device, Exchange, Pinned };  // EngineImpl::alloc: hipMalloc, m
 typedef void (*stream_fn)(const StreamParams, const SelectParams);
 typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
 typedef void (*range_fn)(const StreamParams, const RangeParams);
+typedef void (*facet_fn)(const StreamParams, const FacetParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*batch_fn)(const BatchArgs);
@@ -110,6 +112,7 @@ struct Kernels {
     stream_fn stream[2] = {};  // [SCORES]; [0] is the tracing twin on an engine that traces
     filter_fn filter[2] = {};  // [SCORES]
     range_fn range[2] = {};    // [FILT]
+    facet_fn facet[2] = {};    // [FILT]
     row_vectors_fn row_vectors = nullptr;
     score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
@@ -129,6 +132,8 @@ static Kernels kernels_of(bool dbg) {
         K.filter[1] = &stream_filter_kernel<C, true, XCOLS, QM, NBUF>;
         K.range[0] = &range_kernel<C, XCOLS, QM, false, C == 8 ? 2 : 3>;
         K.range[1] = &range_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
+        K.facet[0] = &facet_kernel<C, XCOLS, QM, false, C == 8 ? 2 : 3>;
+        K.facet[1] = &facet_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
         K.row_vectors = &row_vectors_kernel<C, XCOLS, QM == QM_F32C12>;
         K.score_rows = &score_rows_kernel<C, QM == QM_F32C12>;
     }
@@ -420,7 +425,14 @@ struct EngineImpl {
         uint32_t *d_range_idx = nullptr;
         float *d_range_val = nullptr;
         uint32_t range_cap = 0;
-        uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count
+        uint32_t *d_range_word = nullptr;  // [0] the threshold, [1] the count; tkspmv_run_facets: [2] its threshold, [3] its total
+        // Facet counts (tkspmv_enqueue_facets, facet_kernel) share the range path's scope, timetable and contract. The bins of the
+        // workgroup-private histogram in LDS (option FACET_LDS_BINS, read by setup_verdicts; unset: the column tier's capacity;
+        // 0: global atomics always), and the scratch of tkspmv_run_facets, grown to the largest n_groups asked for.
+        uint32_t facet_lds_bins = 0;
+        uint32_t *d_facet_counts = nullptr;
+        tkspmv_facet_best *d_facet_best = nullptr;
+        uint32_t facet_cap = 0;
     } range;
 
     // Queries by stored row (tkspmv_enqueue_row_vectors, row_vectors_kernel) touch no other group but the matrix either. The
@@ -886,6 +898,48 @@ struct EngineImpl {
             // (the timetable of launch_batch; one partition per wave, or no timetable)
             R.period = (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
             hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
+        }
+    }
+    // n facet queries (launch_range's queries; bin of local row r: labels[r], none when that is >= n_bins), complete in stream order
+    // when this returns: counts, best and totals are zeroed in front, then launches of up to RANGE_MAX queries whose kernels add to
+    // counts / totals and raise best to the maximum of (order key << 32 | global row), then one closing launch that turns the non-zero
+    // maxima into {row, score bits}. No engine state is read or written besides the matrix.
+    void launch_facets(const float *xs, int n, const float *thresholds, const uint32_t *mask, size_t stride, const uint32_t *labels, uint32_t n_bins,
+                       uint32_t *counts, tkspmv_facet_best *best, uint32_t *totals, hipStream_t s) const {
+        const size_t n_out = (size_t)n * n_bins;
+        if (n_out) (void)hipMemsetAsync(counts, 0, n_out * 4, s);
+        if (best && n_out) (void)hipMemsetAsync(best, 0, n_out * 8, s);
+        if (totals) (void)hipMemsetAsync(totals, 0, (size_t)n * 4, s);
+        StreamParams P = stream_params(xs);
+        FacetParams R{};
+        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
+        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
+        R.mask_stride = (uint32_t)stride;
+        R.mask_words = mask_words();
+        R.labels = labels;
+        R.n_bins = n_bins;
+        R.lds_bins = n_bins <= range.facet_lds_bins ? range.facet_lds_bins : 0u;
+        R.first_row = desc.first_row;
+        R.args_tag = FACET_ARGS_TAG;
+        const uint32_t period_ns = range.range_period_set ? range.range_period_ns : local.pace_period_ns;
+        const facet_fn fn = kern.facet[mask != nullptr];
+        for (int i = 0; i < n; i += Range::RANGE_MAX) {
+            const int c = std::min(Range::RANGE_MAX, n - i);
+            R.q0 = (uint32_t)i;
+            R.n_q = (uint32_t)c;
+            R.xs = xs + (size_t)i * desc.cols;
+            R.thresholds = thresholds + i;
+            R.mask = mask ? mask + (size_t)i * stride : nullptr;
+            R.counts = counts + (size_t)i * n_bins;
+            R.best = best ? reinterpret_cast<unsigned long long *>(best) + (size_t)i * n_bins : nullptr;
+            R.totals = totals ? totals + i : nullptr;
+            // (launch_range's timetable)
+            R.period = (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
+        }
+        if (best && n_out) {
+            const uint32_t cgrid = (uint32_t)std::min<size_t>((n_out + 255u) / 256u, 16384u);
+            hipLaunchKernelGGL(facet_close_kernel, dim3(cgrid), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(best), (unsigned long long)n_out);
         }
     }
     // Why stored rows cannot be expanded by this engine (nullptr: they can). Unlike filtered queries, the approximate per-partition
@@ -1823,6 +1877,8 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     m.local.pace_period_ns = (uint32_t)opt_int("PACE_PERIOD", 0, 0, 10000000);
     m.range.range_period_set = opt_set("RANGE_PERIOD");
     m.range.range_period_ns = (uint32_t)opt_int("RANGE_PERIOD", 0, 0, 10000000);
+    const long facet_cap = (long)facet_lds_bins(m.fmt.xcols);
+    m.range.facet_lds_bins = (uint32_t)opt_int("FACET_LDS_BINS", facet_cap, 0, facet_cap);
     if (m.local.use_local && m.local.pace_quads != 0u) {
         HIP_TRY(m.alloc(m.local.d_wg_pace, (size_t)m.grid * 4, Mem::Device, 0));
         HIP_TRY(m.alloc(m.local.d_pace_adapt, 128, Mem::Exchange, 0));
@@ -2505,6 +2561,57 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
         HIP_TRY(hipMemcpy(val, m.range.d_range_val, kept * 4, hipMemcpyDeviceToHost));
         sort_tuples(kept, idx, val);
     }
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_facets(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                           const uint32_t *dev_labels, uint32_t n_bins, uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream,
+                           std::string &err) {
+    EngineImpl &m = *impl_;
+    if (count < 1 || !dev_thresholds || !dev_counts || mask_stride_words < 0 || (dev_labels != nullptr) != (n_bins != 0u) || n_bins > (1u << 30) ||
+        (reinterpret_cast<uintptr_t>(dev_best) & 7u) != 0u)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_facets (count >= 1, thresholds and counts given, mask_stride_words >= 0, dev_labels with "
+                                             "1 <= n_bins <= 2^30 or dev_labels = NULL with n_bins = 0, dev_best 8-byte aligned)");
+    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    if (!dev_labels) {
+        if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no labels given and none installed (call tkspmv_set_groups first)");
+        dev_labels = m.grouped.d_groups;
+        n_bins = m.grouped.n_groups;
+    }
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_facets(dev_xs, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_labels, n_bins, dev_counts, dev_best, dev_totals, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const float *installed = nullptr;
+    if (const int st = m.resolve_query(installed, 1, err)) return st;
+    if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no labels installed (call tkspmv_set_groups first)");
+    HIP_TRY(hipSetDevice(m.device));
+    const uint32_t n_bins = m.grouped.n_groups;
+    if (!m.range.d_range_word) HIP_TRY(m.alloc(m.range.d_range_word, 128, Mem::Device, 0));
+    if (n_bins > m.range.facet_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's launch is long complete: run_facets waits itself)
+        HIP_TRY(m.grow_scratch(m.range.facet_cap, n_bins, {{(void **)&m.range.d_facet_counts, (size_t)n_bins * 4}, {(void **)&m.range.d_facet_best, (size_t)n_bins * 8}}));
+    }
+    HIP_TRY(hipMemcpy(m.range.d_range_word + 2, &threshold, 4, hipMemcpyHostToDevice));
+    const int st = enqueue_facets(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word + 2), use_filter ? m.filter.d_filter : nullptr, 0, nullptr, 0u,
+                                  m.range.d_facet_counts, best ? m.range.d_facet_best : nullptr, m.range.d_range_word + 3, nullptr, err);
+    if (st != TKSPMV_OK) return st;
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    m.host.x_pending = false;
+    uint32_t found = 0u;
+    HIP_TRY(hipMemcpy(&found, m.range.d_range_word + 3, 4, hipMemcpyDeviceToHost));
+    if (total) *total = found;
+    if (counts) HIP_TRY(hipMemcpy(counts, m.range.d_facet_counts, (size_t)n_bins * 4, hipMemcpyDeviceToHost));
+    if (best) HIP_TRY(hipMemcpy(best, m.range.d_facet_best, (size_t)n_bins * 8, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 

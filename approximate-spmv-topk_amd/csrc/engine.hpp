@@ -51,6 +51,12 @@ class Engine {
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
                       uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err);
     int run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err);
+    // Facet counts (facet_kernel): a range query's matches per label -- how many, and which comes first in the result order --
+    // instead of the matches themselves; run_facets is the host-side counterpart (installed vector and labels, host threshold, waits).
+    int enqueue_facets(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                       const uint32_t *dev_labels, uint32_t n_bins, uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream,
+                       std::string &err);
+    int run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err);
     // Queries by stored row (row_vectors_kernel): rows of the matrix, given by the global ids queries return, expanded into the dense
     // vectors every enqueue_* call takes; run_similar = the engine's top-k with each given row as the query (chunks on engine-owned
     // scratch: ids up, row vectors, the batch sequence, wait, results down), the row itself removed from its list on request.

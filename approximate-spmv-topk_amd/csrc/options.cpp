@@ -31,6 +31,7 @@ static const OptionDef k_options[] = {
     {"EXT_EVENTS", "diagnostic", "0 | 1 | 2 (default 1; 2 = the pair recorded right in front of the first and right behind the last launch: 7 us more per region than 1, and the device-wide wait behind the call 11 us cheaper)", "tkspmv_time_queries: 1 = the event pair travels with the region's first and last kernel (hipExtLaunchKernelGGL: the dispatches' own start and end stamps, what rocprofv3 reports); 0 = hipEventRecord before and after (the start stamp then precedes the host's writing of the first dispatch packet: +1.6 us)"},
     {"PACE_PERIOD", "tuning", "ns per query (default: measured at create; 0 = pacing by rank)", "pacing by the clock: every streaming wave keeps a timetable of this many ns per query and sleeps off what it is ahead of it (replaces the pauses by rank)"},
     {"RANGE_PERIOD", "tuning", "ns per query (default: the engine's own timetable period when tkspmv_create kept one; 0 = unpaced)", "range queries (tkspmv_enqueue_range): the timetable of range_kernel's waves, as PACE_PERIOD is the batch kernel's"},
+    {"FACET_LDS_BINS", "tuning", "bins (default: the column tier's capacity, 4096 up to 4096 columns and 512 above; 0 = global atomics always; larger values are clamped to the capacity)", "facet counts (tkspmv_enqueue_facets): calls of at most this many bins deposit into facet_kernel's workgroup-private histogram in LDS, swept to the outputs once per query; calls of more bins deposit with global atomics. Read when the engine is created"},
     {"BALANCED_CUTS", "layout", "0 | 1 | 2 (default 1; 2 = already where the uniform cut misses the count by 1/32: tuning runs; other values are clamped to 0..2)", "1: where partitions of equal capacity come to fewer than the waves asked for by more than 1/8, the packets are dealt out over exactly that many partitions (floor or ceil of the mean each): every workgroup of the batch kernel then streams the same number of partitions; 0: equal capacities always (rounds 1-4)"},
     {"PACE_ADAPT", "behaviour", "0 | 1 (default 1)", "1: the timetable's period lengthens by 1/64 per launch while a quarter of the waves start a launch's last query more than a quarter of a period late (the GPU streams slower than when tkspmv_create measured), and comes back by 1/256 per launch when next to none do; 0: the period stays as measured"},
     {"PACE_BASE", "tuning", "0..64 (default 0)", "pause per packet (s_sleep units) of EVERY workgroup of the batch kernel, whatever its rank: a uniform throttle (tuning runs)"},

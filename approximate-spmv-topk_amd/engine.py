@@ -19,6 +19,8 @@ MAX_PAGE = 1000  # ranked_spmv's default page: every page takes the scores + rad
 
 
 class SpMV:
+    _n_groups = 0  # bins of the labels installed by set_groups (0: none); run_facets sizes its host arrays by it
+
     def __init__(self, x, y, val, num_rows, num_cols, num_nnz=None, vec=None, k=20, debug=0, *, device=-1,
                  first_row=0, min_score=0.0, partitions=1, k_per_partition=0, precision=_lib.F32, waves_per_cu=0,
                  threads_per_wg=0, nnz_per_lane=0, stream_replicas=0, fixed_width=0, multi_q=0, impl=0):
@@ -187,6 +189,7 @@ class SpMV:
         label + 1); None removes them. A label >= n_groups raises TkspmvError(ERR_INVALID) and installs nothing."""
         if groups is None:
             _lib.check(_lib.lib().tkspmv_set_groups(self._h, None, 0))
+            self._n_groups = 0
             return
         g = np.asarray(groups)
         if g.shape != (self.num_rows,):
@@ -197,6 +200,7 @@ class SpMV:
         if n_groups is None:
             n_groups = int(g.max()) + 1 if g.size else 1
         _lib.check(_lib.lib().tkspmv_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_groups)))
+        self._n_groups = int(n_groups)  # (run_facets sizes its arrays by it)
 
     def enqueue_grouped(self, dev_xs, count, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_grp=0, dev_n=0, stream=0):
         """Grouped top-k of `count` queries (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()): the k best
@@ -317,6 +321,38 @@ class SpMV:
             _, _, capacity = self._run_range(threshold, use_filter, 0)
         val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity))
         return val, idx
+
+    def enqueue_facets(self, dev_xs, count, dev_thresholds, dev_counts, n_bins=0, dev_labels=0, dev_best=0, dev_totals=0, dev_mask=0, mask_stride=0,
+                       stream=0):
+        """Facet counts: for query i (dev_xs, dev_thresholds, dev_mask / mask_stride as in enqueue_range) the matches per label.
+        dev_labels: [rows] uint32 labels of the local rows with n_bins bins (a label >= n_bins: no bin); 0 with n_bins = 0: the
+        labels of set_groups(). dev_counts[i*n_bins + b] receives the matches with label b; dev_best (optional, _lib.FacetBest
+        records) each bin's match that comes first in the result order, (0, 0) for an empty bin; dev_totals[i] (optional) all
+        matches. No host sync, no engine state touched."""
+        p = lambda a: C.c_void_p(int(a)) if a else None
+        _lib.check(_lib.lib().tkspmv_enqueue_facets(self._h, p(dev_xs), int(count), p(dev_thresholds), p(dev_mask), int(mask_stride), p(dev_labels),
+                                                    int(n_bins), p(dev_counts), p(dev_best), p(dev_totals), C.c_void_p(int(stream))))
+
+    def run_facets(self, threshold, vec=None, allow=None, groups=None):
+        """One facet query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
+        row_mask() words; the query is then restricted to it), set_groups(groups) if given, then the rows scoring >= threshold
+        counted per installed label. Returns (counts, best_idx, best_val, total): per group its matches and the row id and score
+        of its best match ((0, 0.0) for a group without one), and the number of all matches."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        if groups is not None:
+            self.set_groups(groups)
+        n = max(1, self._n_groups)  # (none installed: the library says so and writes nothing)
+        counts = np.zeros(n, dtype=np.uint32)
+        best = np.zeros((n, 2), dtype=np.uint32)
+        total = C.c_uint64(0)
+        _lib.check(_lib.lib().tkspmv_run_facets(self._h, float(threshold), int(allow is not None), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                best.ctypes.data_as(C.POINTER(_lib.FacetBest)), C.byref(total)))
+        n = self._n_groups
+        return counts[:n], best[:n, 0].copy(), best[:n, 1].copy().view(np.float32), int(total.value)
 
     def enqueue_row_vectors(self, dev_rows, count, dev_xs, dev_len=0, stream=0):
         """Stored rows as dense query vectors: dev_rows[i] (uint32, a GLOBAL row id as queries return them) is expanded into
@@ -490,6 +526,19 @@ def range_spmv(m, vec, threshold, allow=None, **kw):
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
     try:
         return e.run_range(threshold, allow=allow)
+    finally:
+        e.close()
+
+
+def facet_spmv(m, vec, threshold, groups, n_groups=None, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (counts, best_idx, best_val, total) of the rows scoring >=
+    threshold (among the rows of `allow`, if given) per label groups[r] < n_groups (None: the largest label + 1): each label's
+    matches, the row id and score of its best match ((0, 0.0) where it has none), and the number of all matches."""
+    kw.setdefault("k", 8)
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
+    try:
+        e.set_groups(groups, n_groups)
+        return e.run_facets(threshold, allow=allow)
     finally:
         e.close()
 

@@ -181,6 +181,43 @@ def page_after(y, present, k, cursor=None, min_score=0.0, first_row=0, allow=Non
     return idx, val, n, total, nxt
 
 
+def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
+    """The contract of facet counts (SpMV.enqueue_facets) restated in numpy, for CPU-side users and as the tests' expectation:
+    from float32 scores[rows], present[rows] (the row has entries; allow[rows], if given, restricts further) and labels[rows], the
+    rows that match -- score >= threshold, compared as float32: -inf matches every present row, NaN none -- counted per label.
+    Returns (counts uint32[n_bins], best_idx uint32[n_bins], best_val float32[n_bins], total): counts[b] = matches with label b;
+    best_idx[b] / best_val[b] = row + first_row and score of the bin's match that comes first in the engine's order, the maximum
+    of the 64-bit key (order key of the score << 32 | global row id), (0, 0.0) for an empty bin; total = all matches, those whose
+    label is >= n_bins (they belong to no bin) included."""
+    y = np.ascontiguousarray(scores, dtype=np.float32)
+    g = np.asarray(labels).astype(np.int64)
+    ok = np.asarray(present).astype(bool)
+    if y.ndim != 1 or g.shape != y.shape or ok.shape != y.shape:
+        raise ValueError("scores, present and labels must be 1-D arrays of one length")
+    if allow is not None:
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.shape != y.shape:
+            raise ValueError("allow must be a bool array of scores' length")
+        ok = ok & a
+    n_bins = int(n_bins)
+    with np.errstate(invalid="ignore"):
+        ok = ok & (y >= np.float32(threshold))
+    total = int(np.count_nonzero(ok))
+    rows = np.flatnonzero(ok & (g >= 0) & (g < n_bins))
+    u = y[rows].view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)  # the engine's order_key
+    ckey = (key.astype(np.uint64) << np.uint64(32)) | (rows.astype(np.uint64) + np.uint64(int(first_row)))
+    counts = np.bincount(g[rows], minlength=n_bins).astype(np.uint32)
+    bkey = np.zeros(n_bins, dtype=np.uint64)
+    np.maximum.at(bkey, g[rows], ckey)
+    hi = (bkey >> np.uint64(32)).astype(np.uint32)
+    bits = np.where(hi & np.uint32(0x80000000), hi & np.uint32(0x7FFFFFFF), ~hi).astype(np.uint32)  # order_key's inverse
+    filled = counts != 0
+    best_idx = np.where(filled, (bkey & np.uint64(0xFFFFFFFF)).astype(np.uint32), np.uint32(0)).astype(np.uint32)
+    best_val = np.where(filled, bits, np.uint32(0)).astype(np.uint32).view(np.float32)
+    return counts, best_idx, best_val, total
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()

@@ -240,6 +240,43 @@ int tkspmv_enqueue_range(tkspmv_t *e, const float *dev_xs, int32_t count, const 
  * min(*count, capacity) entries are written). TKSPMV_ERR_INVALID for use_filter with no filter installed. */
 int tkspmv_run_range(tkspmv_t *e, float threshold, int32_t use_filter, uint32_t *idx, float *val,
                      uint32_t capacity, uint64_t *count);
+/* Facet counts (aggregation): of the rows that match a range query, how many carry each label, and which is each label's best
+ * hit -- facet counts beside a result list, hit counts per tenant or shard, class histograms of a labelled corpus --, without
+ * writing the matches themselves: the answer is n_bins words per query, accumulated where the matches are found (facet_kernel:
+ * range_kernel's streaming loop with a histogram for a sink). Query i, dev_xs, dev_thresholds[i], dev_mask / mask_stride_words:
+ * exactly as in tkspmv_enqueue_range, and a row MATCHES exactly as there: it has entries, is allowed by the mask, and its fp32
+ * score -- the bits every other path reports -- is >= the threshold compared as floats (-inf: every row with entries; NaN:
+ * nothing; desc.min_score plays no part).
+ * dev_labels: device array of `rows` labels, one per LOCAL row, one array for every query of the call; a row whose label is
+ * >= n_bins belongs to no bin (0xFFFFFFFF: "no facet") and still counts in the total. dev_labels = NULL: the labels installed
+ * by tkspmv_set_groups; n_bins must then be 0 and the engine's n_groups is used.
+ * Outputs of query i: dev_counts[i * n_bins + b] (required) = matches with label b. dev_best[i * n_bins + b] (optional) = the
+ * bin's match that comes first in the result order (order key of the score descending, then global row id descending: the
+ * maximum of order key << 32 | first_row + row): row = its global id, score_bits = its score's bits; an empty bin gives {0, 0},
+ * which dev_counts tells apart from "row 0 scoring +0.0f". dev_totals[i] (optional) = all matches, those of no bin included:
+ * what tkspmv_enqueue_range puts into dev_counts[i]. Exactly count * n_bins entries of dev_counts and of dev_best and count of
+ * dev_totals are written, nothing else. Bit-reproducible from run to run: counts are integers, the best is a maximum.
+ * Stream and state contract: tkspmv_enqueue_range's -- complete in stream order on any stream; reads and writes no result
+ * buffer, exchange set, record, verdict, carried threshold or launch counter and no engine-owned scratch, so any number of calls
+ * may be in flight and it may be mixed freely with every other call. (With dev_labels = NULL the installed labels are read:
+ * tkspmv_set_groups waits for the engine's stream only.) The call zeroes its outputs in stream order, streams the matrix once
+ * per query (launches of up to 32 queries) and, with dev_best, ends with one small launch over count * n_bins entries.
+ * Calls of few bins (option FACET_LDS_BINS; by default up to 4096 bins, 512 above 4096 columns) collect in a histogram per
+ * workgroup in LDS that is added to the outputs once per query; calls of more bins update the outputs with global atomics.
+ * Errors, checked before any device call: TKSPMV_ERR_INVALID for a NULL engine, NULL thresholds or counts, count < 1, a negative
+ * stride, dev_xs = NULL with count != 1, dev_labels given with n_bins = 0, dev_labels = NULL with n_bins != 0, n_bins > 2^30,
+ * a dev_best that is not 8-byte aligned; TKSPMV_ERR_STATE for a NULL dev_xs with no vector installed or NULL dev_labels with no
+ * labels installed; TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_range reports it. */
+typedef struct { uint32_t row; uint32_t score_bits; } tkspmv_facet_best;   /* 8 bytes, 8-byte aligned */
+int tkspmv_enqueue_facets(tkspmv_t *e, const float *dev_xs, int32_t count, const float *dev_thresholds,
+                          const uint32_t *dev_mask, int64_t mask_stride_words,
+                          const uint32_t *dev_labels, uint32_t n_bins,
+                          uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream);
+/* The host-side counterpart: the installed query vector, a host threshold, the labels installed by tkspmv_set_groups, the mask
+ * installed by tkspmv_set_filter when use_filter != 0 (TKSPMV_ERR_INVALID if none is); runs on engine-owned scratch that grows
+ * to n_groups entries, and waits. counts[n_groups] and best[n_groups] (host; either may be NULL) and *total receive the result. */
+int tkspmv_run_facets(tkspmv_t *e, float threshold, int32_t use_filter,
+                      uint32_t *counts, tkspmv_facet_best *best, uint64_t *total);
 /* Grouped top-k (result collapsing): the k best GROUPS of rows, each shown once by its best row -- the k best documents by
  * their best passage, products by their best variant. Every local row carries a label group[r] < n_groups, a property of the
  * index like the allow-mask. For a query a row is ELIGIBLE when it has entries, is allowed by the optional allow-mask, and its
