@@ -43,6 +43,7 @@ class Info(C.Structure):
         ("k", C.c_int32), ("partitions", C.c_int32), ("k_per_partition", C.c_int32), ("precision", C.c_int32),
         ("device", C.c_int32), ("num_cus", C.c_uint32), ("fixed_width", C.c_uint32), ("multi_q", C.c_uint32), ("multi_pack_us", C.c_uint32), ("multi_bytes", C.c_uint64),
         ("pack_us", C.c_uint32), ("pack_on_device", C.c_uint32), ("claim_sets", C.c_uint32), ("batch_mode", C.c_uint32), ("state_bytes", C.c_uint64),
+        ("batch_stream_bytes", C.c_uint64), ("batch_packet_bytes", C.c_uint32), ("batch_compact", C.c_uint32),
     ]
 
     def as_dict(self):

@@ -216,6 +216,13 @@ struct EngineImpl {
         uint32_t *d_pkt_row = nullptr, *d_part_first = nullptr, *d_part_count = nullptr;
         uint32_t uni_ppp = 0, uni_last = 0;  // uniform partition table (StreamParams::uni_ppp): partition q = packets [q * uni_ppp, ...)
         const uint8_t *packets(uint64_t n) const { return d_replicas.empty() ? d_packets : d_replicas[n % d_replicas.size()]; }  // the copy query n streams
+        // The batch kernel's own copies (compact_stream; empty: it streams the canonical ones): the same packets re-encoded at 5 bytes
+        // per entry (wbscsr.hpp F32E5), as many copies as the canonical stream has. Every other kernel reads the canonical stream.
+        std::vector<uint8_t *> d_compact;
+        uint32_t compact_top4 = 0;  // bits 31..28 of every fp32 word of the matrix (StreamParams::top4)
+        bool compact() const { return !d_compact.empty(); }
+        const uint8_t *batch_packets(uint64_t n) const { return compact() ? d_compact[n % d_compact.size()] : packets(n); }  // what query n of the batch path streams
+        uint32_t batch_packet_bytes(const PackedMatrix &pm) const { return compact() ? F32E5_PACKET_BYTES : pm.packet_bytes; }
     } mat;
 
     // The host boundary of the reference loop (reset -> operator() -> read_result, host_spmv_bscsr.cpp:602-632) and the engine's own
@@ -694,6 +701,8 @@ struct EngineImpl {
     BatchArgs batch_args(const float *const *xs, uint32_t *const *out_idx, float *const *out_val, int n) {
         StreamParams P = stream_params(xs[0], 0);
         P.fused = 0u;
+        P.packet_bytes = mat.batch_packet_bytes(pm);
+        P.top4 = mat.compact_top4;
         SelectParams S = select_params(out_idx[0], out_val[0], 0);
         BatchParams B{};
         B.n_q = (uint32_t)n;
@@ -702,7 +711,7 @@ struct EngineImpl {
         for (int q = 0; q < n; ++q) {
             BatchIO &Q = B.io[q];
             Q.x = xs[q];
-            Q.packets = mat.packets(mat.launch_counter + (uint64_t)q);
+            Q.packets = mat.batch_packets(mat.launch_counter + (uint64_t)q);
             Q.out_idx = out_idx[q];
             Q.out_val = out_val[q];
             if (q + 1 < n && out_idx[q] == out_idx[n - 1]) redirect_to_alias(Q, (size_t)q);
@@ -1345,6 +1354,8 @@ void fill_info(const PackedMatrix &pm, int k, tkspmv_info *out) {
     out->precision = (pm.precision == Precision::FIXED20 || pm.precision == Precision::FIXED26) ? (int32_t)Precision::FIXED
                                                        : (pm.precision == Precision::F32C12 ? (int32_t)Precision::F32 : (int32_t)pm.precision);
     out->fixed_width = pm.fixed_width;
+    out->batch_stream_bytes = pm.stream_bytes();  // (an engine that keeps compact copies says so in fill_engine_info)
+    out->batch_packet_bytes = pm.packet_bytes;
 }
 
 int device_count() {
@@ -1865,6 +1876,7 @@ static int setup_verdicts(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::st
     // The pause follows the packet's size (fp32 values with 12-bit columns, 1408 bytes: 2 units; fp16, 896 bytes: 1 -- 15.4 us per query
     // at 1M rows against 16.3 at 2 units and 16.7 with the device-wide exchange).
     // (units of 128 cycles per level)
+    // (the canonical packet's size is read here, ahead of compact_stream: the compact fp32 packets, 1280 bytes, round to the same 2 units)
     // (round 5, with the pause behind the packet's arithmetic: from ~330k rows up a pause of ONE unit per level pays -- 500k rows: 9.03
     //  against 9.86 us per query unpaced, 10.0 at two units; 250k rows: 5.8 either way -- and tkspmv_create's measurement may still
     //  choose none)
@@ -1975,10 +1987,99 @@ static int setup_diagnostics(const tkspmv_desc &d, Setup &S, EngineImpl &m, std:
     return TKSPMV_OK;
 }
 
+// ---- the batch kernel's compact copies (wbscsr.hpp F32E5) ---------------------------------------------------------------------
+// The census of a resident F32C12 stream (f32e5_census_entry over every entry): one thread per lane of a packet, a wave's share
+// reduced in registers, four atomics per wave. out: [0] AND, [1] OR of the words that are not +0.0, [2..3] the bare zeros (64 bits),
+// [4] the odd SKIPs.
+__global__ void __launch_bounds__(256) f32e5_census_kernel(const uint8_t *__restrict__ packets, uint32_t n_packets, uint32_t packet_bytes, uint32_t *__restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = (uint32_t)(t & 63u);
+    uint32_t a = 0xFFFFFFFFu, o = 0u, bare = 0u, odd = 0u;
+    if (t / 64u < n_packets) {  // (whole waves: a packet is a wave's)
+        const uint8_t *pkt = packets + (size_t)(t / 64u) * packet_bytes;
+        for (uint32_t j = 0; j < 4u; ++j) {
+            uint32_t bz, os;
+            f32e5_census_entry(get<uint32_t>(pkt + (size_t)(lane * 4u + j) * 4), colw12s_load(pkt + (size_t)F32E5_PACKET_ENTRIES * 4, lane * 4u + j), a, o, bz, os);
+            bare += bz;
+            odd += os;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        a &= (uint32_t)__shfl_xor((int)a, d);
+        o |= (uint32_t)__shfl_xor((int)o, d);
+        bare += (uint32_t)__shfl_xor((int)bare, d);
+        odd += (uint32_t)__shfl_xor((int)odd, d);
+    }
+    if (lane == 0u) {
+        if (a != 0xFFFFFFFFu) atomicAnd(out + 0, a);
+        if (o != 0u) atomicOr(out + 1, o);
+        if (bare != 0u) atomicAdd(reinterpret_cast<unsigned long long *>(out + 2), (unsigned long long)bare);
+        if (odd != 0u) atomicAdd(out + 4, odd);
+    }
+}
+// The re-encoding, packet for packet: thread t = lane t % 64 of packet t / 64 (f32e5_transcode_lane, the host re-encoder's function).
+__global__ void __launch_bounds__(256) f32e5_transcode_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint32_t n_packets, uint32_t packet_bytes) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t / 64u >= n_packets) return;
+    f32e5_transcode_lane(src + (size_t)(t / 64u) * packet_bytes, dst + (size_t)(t / 64u) * F32E5_PACKET_BYTES, (uint32_t)(t & 63u));
+}
+
+// Engines whose batch kernel reads an F32C12 stream get compact copies of it where the matrix's values allow (option F32_COMPACT=0:
+// never): a device reduction decides (all fp32 words share their top four bits; no +0.0 but placeholders and padding), a device
+// kernel re-encodes the stream into as many copies as the canonical stream has. Entry order, partitions, pkt_row and the tables stay
+// what they are, so does the arithmetic: the results are the canonical stream's bit for bit. Engines that trace stay on F32C12 (the
+// new format has no tracing twin). Behind setup_diagnostics (who traces?), ahead of choose_kernels.
+static int compact_stream(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
+    if (opt_int("F32_COMPACT", 1) == 0 || !m.batch.can_batch || m.diag.dbg_kernels || m.fmt.qm != QM_F32C12 || !f32e5_applies(m.pm) || !m.mat.d_packets)
+        return TKSPMV_OK;
+    ScratchBuffer<uint32_t> census;
+    HIP_TRY(hipMalloc((void **)&census.p, 32));
+    const uint32_t init[8] = {0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    HIP_TRY(hipMemcpy(census.p, init, sizeof(init), hipMemcpyHostToDevice));
+    const uint32_t blocks = (uint32_t)(((uint64_t)m.pm.n_packets * 64u + 255u) / 256u);
+    hipLaunchKernelGGL(f32e5_census_kernel, dim3(blocks), dim3(256), 0, m.stream, m.mat.d_packets, m.pm.n_packets, m.pm.packet_bytes, census.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    uint32_t got[8];
+    HIP_TRY(hipMemcpy(got, census.p, sizeof(got), hipMemcpyDeviceToHost));
+    F32E5Census c;
+    c.all_and = got[0];
+    c.all_or = got[1];
+    c.bare_zeros = (uint64_t)got[2] | ((uint64_t)got[3] << 32);
+    c.odd_skips = got[4];
+    uint32_t top4 = 0u;
+    if (!f32e5_census_eligible(c, f32e5_padding(m.pm), top4)) return TKSPMV_OK;  // signed, zero-bearing or wide-ranged values: the engine runs as it is
+    const size_t bytes = (size_t)m.pm.n_packets * F32E5_PACKET_BYTES;
+    const size_t copies = std::max<size_t>(m.mat.d_replicas.size(), 1);
+    for (size_t r = 0; r < copies; ++r) {
+        uint8_t *p = nullptr;
+        if (m.alloc(p, bytes) != hipSuccess) {  // no room for a second set of copies: the engine streams the canonical ones
+            (void)hipGetLastError();
+            for (uint8_t *q : m.mat.d_compact) m.release(q);
+            m.mat.d_compact.clear();
+            return TKSPMV_OK;
+        }
+        if (r == 0) {
+            hipLaunchKernelGGL(f32e5_transcode_kernel, dim3(blocks), dim3(256), 0, m.stream, m.mat.d_packets, p, m.pm.n_packets, m.pm.packet_bytes);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(m.stream));
+        } else {
+            HIP_TRY(hipMemcpy(p, m.mat.d_compact[0], bytes, hipMemcpyDeviceToDevice));
+        }
+        m.mat.d_compact.push_back(p);
+    }
+    m.mat.compact_top4 = top4;
+    return TKSPMV_OK;
+}
+
 // The kernels of this engine's format (behind setup_diagnostics: an engine that traces takes the tracing twins), and the DEBUG_OCC
 // occupancy report about them.
 static int choose_kernels(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::string &err) {
     m.kern = kernels_for(m.fmt, m.diag.dbg_kernels);
+    if (m.mat.compact()) {  // the batch path streams the compact copies (compact_stream): local thresholds, the exact kernel, both repair modes
+        m.kern.batch[0] = &batch_kernel<4, 1024, QM_F32E5, false, false>;
+        m.kern.batch[1] = &batch_kernel<4, 1024, QM_F32E5, false, true>;
+    }
     if (m.multi.can_multi) {  // [value type of the row-per-lane copy][queries per pass: 1, 2, 4, 8]
         static const multi_fn fns[3][4] = {{&multi_kernel<1, VT_F32>, &multi_kernel<2, VT_F32>, &multi_kernel<4, VT_F32>, &multi_kernel<8, VT_F32>},
                                            {&multi_kernel<1, VT_Q17>, &multi_kernel<2, VT_Q17>, &multi_kernel<4, VT_Q17>, &multi_kernel<8, VT_Q17>},
@@ -2014,6 +2115,9 @@ static int fill_engine_info(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::
     m.info.multi_pack_us = S.sell_pack_us;
     m.info.pack_on_device = S.packed_on_device ? 1u : 0u;
     m.info.claim_sets = 0u;
+    m.info.batch_compact = m.mat.compact() ? 1u : 0u;
+    m.info.batch_packet_bytes = m.mat.batch_packet_bytes(m.pm);
+    m.info.batch_stream_bytes = (uint64_t)m.pm.n_packets * m.info.batch_packet_bytes;
     m.info.batch_mode = (m.batch.can_batch ? (m.batch.n_sel_wg | (m.local.use_local << 8)) : 0u) | (std::min<uint32_t>(S.n_parts_hint, 0xFFFFu) << 16);
     return TKSPMV_OK;
 }
@@ -2189,7 +2293,7 @@ static int create_impl(const tkspmv_desc &d, EngineImpl &m, std::string &err, co
     // (in this order: the descriptor is checked before any device call, and the HIP calls keep one sequence)
     static int (*const stages[])(const tkspmv_desc &, Setup &, EngineImpl &, std::string &) = {
         check_desc,  setup_geometry, pack_matrix,    exchange_geometry,   upload_matrix,     setup_host_boundary, choose_path,
-        setup_multi, setup_verdicts, setup_single, setup_exchange_sets, setup_diagnostics, choose_kernels,      fill_engine_info,
+        setup_multi, setup_verdicts, setup_single, setup_exchange_sets, setup_diagnostics, compact_stream,      choose_kernels,      fill_engine_info,
         autotune_pacing};
     Setup S{prepacked};
     for (auto stage : stages)
@@ -3076,7 +3180,10 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
     const uint32_t stream_block = m.block;  // the streaming waves of a workgroup (the server wave of a sequence launch aside)
     ReadProbeParams R{};
     R.n_replicas = m.mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(m.mat.d_replicas.size(), 8);
-    for (uint32_t r = 0; r < 8u; ++r) R.replicas[r] = m.mat.packets(r);
+    // (what the batch kernel reads: its compact copies where the engine keeps them, the 20-bytes-per-lane probe over 1280-byte packets
+    //  -- the floor of THAT kernel; a caller that rates a pass by the canonical stream's bytes overstates by 1408 / 1280)
+    const uint32_t probe_packet_bytes = m.mat.batch_packet_bytes(m.pm);
+    for (uint32_t r = 0; r < 8u; ++r) R.replicas[r] = m.mat.batch_packets(r);
     R.part_first = m.mat.d_part_first;
     R.part_count = m.mat.d_part_count;
     R.n_parts = (uint32_t)m.pm.part_first.size();
@@ -3091,7 +3198,7 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
     const bool want_ends = opt("READ_PROBE_ENDS") != nullptr;  // (tuning runs: when did the waves of each XCD finish?)
     R.t_end = want_ends ? reinterpret_cast<unsigned long long *>(R.claim + (size_t)(passes + 2) * 32) : nullptr;
     void (*fn)(ReadProbeParams) = nullptr;
-    switch (m.pm.packet_bytes / 64u) {
+    switch (probe_packet_bytes / 64u) {
         case 22: fn = read_probe_kernel<22>; break;
         case 24: fn = read_probe_kernel<24>; break;
         case 48: fn = read_probe_kernel<48>; break;
@@ -3103,7 +3210,7 @@ int Engine::time_stream_read(int32_t passes, double *ns_per_pass, std::string &e
     if (const char *f = opt("READ_PROBE")) {  // "depth,work" (tuning runs; fp32 packets only)
         int depth = 8, work = 0;
         sscanf(f, "%d,%d", &depth, &work);
-        if (m.pm.packet_bytes == 1536u) {
+        if (probe_packet_bytes == 1536u) {
 #define RP(D, W) if (depth == D && work == W) fn = read_probe_kernel<24, D, W>;
             if (depth == 22) fn = read_probe_kernel<22, 8, 1>;  // what 1408-byte packets would cost, read out of this 1536-byte stream
             RP(3, -1) RP(3, -2) RP(4, -2) RP(2, 0) RP(3, 0) RP(4, 0) RP(6, 0) RP(12, 0) RP(16, 0)

@@ -786,7 +786,7 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
     // again (step 0: a fixed number of younger loads lets the compiler wait with a counted vmcnt). fp32 streams are fetched with
     // buffer loads (load_packet_buf): resource = this wave's partition in the query's stream copy. The row base of a packet is
     // looked up on the candidate path only (pkt_row[p0 + jc], a scalar load where round 4 carried one per packet).
-    constexpr bool BUF = C == 4 && (VT == VT_F32 || VT == VT_F32C12);
+    constexpr bool BUF = C == 4 && (VT == VT_F32 || VT == VT_F32C12 || VT == VT_F32E5);
     auto stream_of = [&](uint32_t q) __attribute__((always_inline)) -> const uint8_t * {
         return B.io[qx(q)].packets;
     };
@@ -900,7 +900,7 @@ __device__ __forceinline__ void batch_phase(const StreamParams &P0, const Select
             if (look) clk_now = (uint32_t)__builtin_amdgcn_s_memrealtime();
             const uint32_t tau_bits = lds_load(&mp[MISC_TAU]);
             const float tau = __uint_as_float(tau_bits);
-            const Reduced<C> Rd = reduce_packet<C, QM>(cur, carry, xbase, P0.fixed_mask);
+            const Reduced<C> Rd = reduce_packet<C, QM>(cur, carry, xbase, QM == QM_F32E5 ? P0.top4 : P0.fixed_mask);
             const float trig = trigger_of<C, INT>(Rd);
             if (tpkt_fp != 0u) {
                 // (the clock is read every TKSPMV_CLOCK_STRIDE packets and what the wave is ahead by slept off in one go: half the scalar

@@ -37,6 +37,7 @@ struct StreamParams {
     uint32_t gpw;           // groups per workgroup
     float min_score;
     uint32_t fixed_width, fixed_mask;  // TKSPMV_FIXED: bits per value and the mask of the top fixed_width bits
+    uint32_t top4;  // F32E5 (the batch kernel's compact stream): bits 31..28 of every fp32 word of the matrix, at bits 3..0
     uint32_t *gmax;  // [MAX_GM*64] order keys of the group maxima (zero beyond n_groups_pub)
     uint32_t *tau_g; // one word: order key of the broadcast threshold (monotone, atomic max)
     uint32_t tau_possible;  // 1: at least k publishing groups own rows, so a threshold can form (else nobody waits for one)
@@ -103,6 +104,7 @@ constexpr uint32_t SLOT_INVALID = 0xFFFFFFFFu;  // row id of an unused slot
 //             factors as 20-bit integers.
 // QM_F32C12   fp32 exactly like QM_F32, the column words travelling as 12 bits each in a split plane.
 // QM_FIXED26  fixed point of 21..26 bits in five bytes per entry; the arithmetic is QM_FIXED's.
+// QM_F32E5    fp32 exactly like QM_F32C12, five bytes per entry: the words' common top four bits travel as a kernel argument.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));  // a dwordx2 at a 4-byte boundary
@@ -135,7 +137,7 @@ __device__ __forceinline__ uint32_t scalar_load(const uint32_t *uniform_ptr) {
 // from them when the stream comes from HBM, tools/stream_probe.hip).
 template <int C, int VT>
 struct Pkt {
-    float v[(VT == VT_F32 || VT == VT_FIXED20 || VT == VT_F32C12 || VT == VT_FIXED26) ? C : 1];  // VT_FIXED20, VT_FIXED26: the packed dwords (value | column bits | flags); VT_FIXED26: cw[0] = E (column bits 9..4)
+    float v[(VT == VT_F32 || VT == VT_FIXED20 || VT == VT_F32C12 || VT == VT_FIXED26 || VT == VT_F32E5) ? C : 1];  // VT_FIXED20, VT_FIXED26, VT_F32E5: the packed dwords (value | column bits | flags); VT_FIXED26: cw[0] = E (column bits 9..4); VT_F32E5: cw[0] = E (wbscsr.hpp)
     uint32_t vq[(VT == VT_Q17 || VT == VT_Q17C12) ? C / 4 : (VT == VT_F16 ? C / 2 : 1)];  // VT_Q17C12: byte values with 12-bit column words (row-per-lane chunks)
     uint32_t cw[C / 2];  // VT_F32C12: the two dwords of the pair's 12-byte block that hold the lane's A and the pair's B (split_ab below)
 };
@@ -150,12 +152,12 @@ __device__ __forceinline__ void load_packet(const uint8_t *__restrict__ pk, uint
             o.v[VT == VT_FIXED20 ? 4 * q + 1 : 0] = f.y;
             o.v[VT == VT_FIXED20 ? 4 * q + 2 : 0] = f.z;
             o.v[VT == VT_FIXED20 ? 4 * q + 3 : 0] = f.w;
-        } else if (VT == VT_FIXED26) {  // FIXED26: the lane's four dwords D_j and its dword E
+        } else if (VT == VT_FIXED26 || VT == VT_F32E5) {  // FIXED26, F32E5: the lane's four dwords D_j and its dword E
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + lane * 16));
-            o.v[VT == VT_FIXED26 ? 0 : 0] = f.x;
-            o.v[VT == VT_FIXED26 ? 1 : 0] = f.y;
-            o.v[VT == VT_FIXED26 ? 2 : 0] = f.z;
-            o.v[VT == VT_FIXED26 ? 3 : 0] = f.w;
+            o.v[0] = f.x;
+            o.v[VT == VT_FIXED26 || VT == VT_F32E5 ? 1 : 0] = f.y;
+            o.v[VT == VT_FIXED26 || VT == VT_F32E5 ? 2 : 0] = f.z;
+            o.v[VT == VT_FIXED26 || VT == VT_F32E5 ? 3 : 0] = f.w;
             o.cw[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(pk + 1024 + lane * 4));
         } else if (VT == VT_F32C12) {
             const f32x4 f = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(pk + q * 1024 + lane * 16));
@@ -205,7 +207,7 @@ __device__ __forceinline__ void load_packet(const uint8_t *__restrict__ pk, uint
     }
 }
 
-// The same packet through BUFFER loads (round 5; fp32 streams of 4 entries per lane: VT_F32 and VT_F32C12). A buffer load takes its
+// The same packet through BUFFER loads (round 5; fp32 streams of 4 entries per lane: VT_F32, VT_F32C12 and VT_F32E5). A buffer load takes its
 // address as resource (4 SGPRs: the partition's first byte in the stream copy of the query, its length) + SGPR byte offset (the
 // packet) + VGPR byte offset (the lane's share, the same for every packet): nothing is added per packet on the vector unit -- the
 // flat form spent three 64-bit vector adds per packet on the two addresses --, and the packet pointer is ONE scalar add. Loads
@@ -215,10 +217,10 @@ struct LaneOffsets {
 };
 template <int C, int VT>
 __device__ __forceinline__ LaneOffsets lane_offsets(uint32_t lane) {
-    static_assert(C == 4 && (VT == VT_F32 || VT == VT_F32C12), "buffer-load packets: fp32 values, 4 entries per lane");
+    static_assert(C == 4 && (VT == VT_F32 || VT == VT_F32C12 || VT == VT_F32E5), "buffer-load packets: fp32 values, 4 entries per lane");
     LaneOffsets o;
     o.v = lane * 16u;
-    o.c = VT == VT_F32C12 ? (uint32_t)C * 256u + (lane >> 1) * 12u + (lane & 1u) * 4u : (uint32_t)C * 256u + lane * 8u;
+    o.c = VT == VT_F32C12 ? (uint32_t)C * 256u + (lane >> 1) * 12u + (lane & 1u) * 4u : (VT == VT_F32E5 ? (uint32_t)C * 256u + lane * 4u : (uint32_t)C * 256u + lane * 8u);
     return o;
 }
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -229,9 +231,13 @@ template <int C, int VT>
 __device__ __forceinline__ void load_packet_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t packet_off, const LaneOffsets &lo, Pkt<C, VT> &o) {
     const u32x4 f = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lo.v, packet_off, 2);  // (aux 2: non-temporal, like the flat form)
     o.v[0] = __uint_as_float(f.x);
-    o.v[VT == VT_F32 || VT == VT_F32C12 ? 1 : 0] = __uint_as_float(f.y);
-    o.v[VT == VT_F32 || VT == VT_F32C12 ? 2 : 0] = __uint_as_float(f.z);
-    o.v[VT == VT_F32 || VT == VT_F32C12 ? 3 : 0] = __uint_as_float(f.w);
+    o.v[VT == VT_F32 || VT == VT_F32C12 || VT == VT_F32E5 ? 1 : 0] = __uint_as_float(f.y);
+    o.v[VT == VT_F32 || VT == VT_F32C12 || VT == VT_F32E5 ? 2 : 0] = __uint_as_float(f.z);
+    o.v[VT == VT_F32 || VT == VT_F32C12 || VT == VT_F32E5 ? 3 : 0] = __uint_as_float(f.w);
+    if (VT == VT_F32E5) {  // the 4-byte plane: the lane's dword E
+        o.cw[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, lo.c, packet_off, 2);
+        return;
+    }
     const u32x2 c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lo.c, packet_off, 2);
     o.cw[0] = c.x;
     o.cw[1] = c.y;

@@ -301,6 +301,10 @@ __device__ __forceinline__ void split_ab(const uint32_t d0, const uint32_t d1, u
 template <int C, int QM>
 __device__ __forceinline__ uint32_t packet_flags(const Pkt<C, value_type_of(QM)> &cur) {
     constexpr int VT = value_type_of(QM);
+    if (VT == VT_F32E5) {  // ROW_END 0-3 in the low nibble of D2, ZERO 0-3 in D3's: a placeholder is a ZERO entry that ends a row (padding is ZERO alone)
+        const uint32_t ends = __float_as_uint(cur.v[VT == VT_F32E5 ? 2 : 0]) & 15u, zeros = __float_as_uint(cur.v[VT == VT_F32E5 ? 3 : 0]) & 15u;
+        return ends | ((zeros & ends) << 8);
+    }
     if (VT == VT_F32C12) {  // split 12-bit plane: ROW_END 0-3 at bits 12-15 of the halfword, SKIP 0, 1 in the dword, 2, 3 in the halfword
         uint32_t A, B;
         split_ab(cur.cw[0], cur.cw[1], A, B);
@@ -316,6 +320,7 @@ __device__ __forceinline__ uint32_t packet_flags(const Pkt<C, value_type_of(QM)>
 }
 
 // Products from a packet and the x vector staged in LDS (at LDS byte address xbase), then the reduction.
+// fixed_mask: the fixed-point modes' mask of the bits kept; QM_F32E5: the words' common top four bits (StreamParams::top4).
 template <int C, int QM>
 __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(QM)> &cur, float &carry, const uint32_t xbase,
                                                     const uint32_t fixed_mask = 0u) {
@@ -366,6 +371,42 @@ __device__ __forceinline__ Reduced<C> reduce_packet(const Pkt<C, value_type_of(Q
             any |= w;
         }
         return reduce_core<C, true>(p, m, (any & 1u) != 0u, carry);
+    }
+    if (QM == QM_F32E5) {
+        // Five bytes per entry (wbscsr.hpp F32E5): D0 = w0 & 0x0FFFFFFF | (c0 & 15) << 28, D1 = w1 << 4 | c1 >> 6, D2 = w2 << 4 | ROW_END0..3,
+        // D3 = w3 << 4 | ZERO0..3, E = c0 >> 4 | c2 << 6 | c3 << 16 | (c1 & 63) << 26; every fp32 word is its 28 bits | top4 << 28 (`fixed_mask`
+        // carries top4 here). A value is one instruction (mask + top4 on D0, a funnel shift with top4 on the others); an LDS address two:
+        // the funnel shifts (E, D0) >> 26 and (D1, E) >> 24 bring the two parts of c0 and c1 together at bit 2, c2 and c3 are shifted
+        // down, then mask + base of the x copy. The arithmetic is QM_F32C12's, on the same words.
+        static_assert(QM != QM_F32E5 || C == 4, "F32E5 is built for 4 entries per lane");
+        const uint32_t top4 = fixed_mask;
+        uint32_t mask = 0xFFCu, vmask = 0x0FFFFFFFu;
+        asm("" : "+v"(mask));  // (kept in registers: v_and_or_b32 takes no literal)
+        asm("" : "+v"(vmask));
+        const uint32_t D0 = __float_as_uint(cur.v[0]), D1 = __float_as_uint(cur.v[VT == VT_F32E5 ? 1 : 0]), D2 = __float_as_uint(cur.v[VT == VT_F32E5 ? 2 : 0]),
+                       D3 = __float_as_uint(cur.v[VT == VT_F32E5 ? 3 : 0]), E = cur.cw[0];
+        const uint32_t a0 = and_or(__builtin_amdgcn_alignbit(E, D0, 26), mask, xbase), a1 = and_or(__builtin_amdgcn_alignbit(D1, E, 24), mask, xbase),
+                       a2 = and_or(E >> 4, mask, xbase), a3 = and_or(E >> 14, mask, xbase);
+        float v[4];
+        v[0] = __uint_as_float(and_or(D0, vmask, top4 << 28));
+        v[1] = __uint_as_float(__builtin_amdgcn_alignbit(top4, D1, 4));
+        v[2] = __uint_as_float(__builtin_amdgcn_alignbit(top4, D2, 4));
+        v[3] = __uint_as_float(__builtin_amdgcn_alignbit(top4, D3, 4));
+        // Placeholders of empty rows and the padding behind a partition's last row are +0.0, which no word with top4 says: a
+        // wave-uniform branch, taken for the few packets that hold such an entry.
+        if (__builtin_expect(__any((D3 & 15u) != 0u), 0)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ((D3 >> j) & 1u) ? 0.0f : v[j];
+        }
+        p[0] = __fmul_rn(v[0], lds_f32(a0));
+        p[C > 1 ? 1 : 0] = __fmul_rn(v[1], lds_f32(a1));
+        p[C > 2 ? 2 : 0] = __fmul_rn(v[2], lds_f32(a2));
+        p[C > 3 ? 3 : 0] = __fmul_rn(v[3], lds_f32(a3));
+        m[0] = bit_mask<0>(D2);
+        m[C > 1 ? 1 : 0] = bit_mask<1>(D2);
+        m[C > 2 ? 2 : 0] = bit_mask<2>(D2);
+        m[C > 3 ? 3 : 0] = bit_mask<3>(D2);
+        return reduce_core<C, false>(p, m, (D2 & 15u) != 0u, carry);
     }
     if (QM == QM_F32C12) {
         // fp32 values, split 12-bit plane: A = col0 << 2 | col1 << 12 | col2 << 22 | SKIP0 | SKIP1 << 1,

@@ -56,6 +56,7 @@ static const OptionDef k_options[] = {
     {"HOST_THREADS", "tuning", "count", "threads of the host-side packer and generators"},
     // ---- layout ----
     {"F32_C12", "layout", "0 | 1 (default 1 for <= 4096 columns)", "fp32 values with 12-bit column words (1408-byte packets)"},
+    {"F32_COMPACT", "layout", "0 | 1 (default 1)", "1: where every fp32 value of the matrix shares its top four bits (one sign, one aligned block of 32 binades, no explicit zero) the batch kernel streams copies of the 12-bit-column stream re-encoded at 5 bytes per entry (1280-byte packets, bit-identical results; one more set of stream copies in HBM); 0: it streams the 1408-byte packets"},
     {"SELL_C12", "layout", "0 | 1", "12-bit column words in the row-per-lane (SELL) layout"},
     {"FIXED_UNPACKED", "layout", "set = on", "fixed-point values as one u32 per entry instead of the packed 20..26-bit streams"},
     // ---- multi-GPU ----

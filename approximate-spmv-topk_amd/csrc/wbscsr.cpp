@@ -23,6 +23,7 @@ uint32_t min_packets_per_partition_for(uint64_t nnz, uint32_t C, uint32_t cols) 
 
 std::string stream_args_error(Precision precision, uint32_t C, uint32_t cols, uint32_t fixed_width) {
     if (C != 4 && C != 8) return "nnz_per_lane must be 4 or 8";
+    if (precision == Precision::F32E5) return "the compact fp32 stream is the engine's own re-encoding of an F32C12 stream: no packer writes it, no file holds it";
     if (precision == Precision::FIXED26 ? (fixed_width < 8 || fixed_width > FIXED26_MAX_WIDTH || cols > FIXED26_MAX_COLS || C != 4)
         : precision == Precision::FIXED20 ? (fixed_width < 8 || fixed_width > FIXED20_MAX_WIDTH || cols > FIXED20_MAX_COLS)
                                           : (precision == Precision::FIXED ? (fixed_width < 8 || fixed_width > 32) : fixed_width != 0))

@@ -73,18 +73,33 @@ TKSPMV_HD inline uint32_t slot_to_index(uint32_t s, uint32_t C) {
 //   D_j = value (bits 31..6: the top 26 bits of its left-aligned Q1.31 word) | column bits 3..0 << 2 | SKIP << 1 | ROW_END
 //   E   = column bits 9..4 of entry j at bits 6 j .. 6 j + 5
 // so the value is one mask, the flags sit where FIXED20 has them and the LDS offset of x[col] is (D_j & 0x3C) | field(E) << 6.
-enum class Precision : int32_t { F32 = 0, Q1_7 = 1, F16 = 3, FIXED = 4, Q1_7_RND = 5, FIXED20 = 6, F32C12 = 7, FIXED26 = 8 };
+// F32E5 = fp32 values whose words all share their top four bits (sign + the upper three exponent bits: one sign, one aligned
+// block of 32 binades -- a row-normalised non-negative matrix, the ordinary case, sits in [2^-31, 2)), in 5 BYTES PER ENTRY: 28 bits
+// of value + 10 of column + 2 flags = 40 bits, FIXED26's two planes (a packet is 1024 + 256 = 1280 bytes, 9.1 % fewer than F32C12's
+// 1408) and bit-identical arithmetic: the fp32 word is low28 | top4 << 28, top4 one constant per engine. No packer writes it: the
+// engine re-encodes its resident F32C12 stream at create (f32e5_* below; engine.hip compact_stream) for the batch kernel alone.
+// A lane's five dwords (entries j = 0..3 with fp32 words w_j and columns c_j):
+//   D0 = w0 & 0x0FFFFFFF | (c0 & 15) << 28        D1 = w1 << 4 | c1 >> 6
+//   D2 = w2 << 4 | ROW_END0..3                    D3 = w3 << 4 | ZERO0..3
+//   E  = c0 >> 4 | c2 << 6 | c3 << 16 | (c1 & 63) << 26
+// arranged for the kernel: a value is one instruction (v_and_or_b32 on D0, v_alignbit_b32 with top4 on the others), the LDS offset
+// of x[c] two -- a funnel shift of (E, D0) / (D1, E) brings the column's two parts together, c2 and c3 are shifted down, then one
+// mask + base --, a row-end mask one bit extraction of D2. ZERO_j marks an entry whose value is +0.0, which no word with the
+// engine's top4 can say: the placeholder of an empty row (ZERO and ROW_END: the canonical SKIP) and the padding behind a
+// partition's last row (ZERO alone). Real entries never carry it (f32e5_eligible).
+enum class Precision : int32_t { F32 = 0, Q1_7 = 1, F16 = 3, FIXED = 4, Q1_7_RND = 5, FIXED20 = 6, F32C12 = 7, FIXED26 = 8, F32E5 = 9 };
 constexpr uint32_t FIXED20_MAX_WIDTH = 20, FIXED20_MAX_COLS = 1024, F32C12_MAX_COLS = 1024, FIXED26_MAX_WIDTH = 26, FIXED26_MAX_COLS = 1024;
 
 // bytes of a packet per entry, minus the 2 of a column word (FIXED20: 20-bit value + 10-bit column + 2 flags in 4 bytes)
 TKSPMV_HD inline uint32_t value_bytes(Precision p) {
     return (p == Precision::F32 || p == Precision::FIXED || p == Precision::F32C12) ? 4u
-                                                                                      : (p == Precision::FIXED26 ? 3u : ((p == Precision::F16 || p == Precision::FIXED20) ? 2u : 1u));
+                                                                                      : ((p == Precision::FIXED26 || p == Precision::F32E5) ? 3u : ((p == Precision::F16 || p == Precision::FIXED20) ? 2u : 1u));
 }
 // bytes of a packet of PE entries
 TKSPMV_HD inline uint32_t packet_bytes_for(Precision p, uint32_t PE) {
     return p == Precision::F32C12 ? PE * 4u + PE * 3u / 2u : PE * (value_bytes(p) + 2u);
 }
+
 // 12-bit column words (F32C12): `planes` = start of the packet's column region, `slot` = slot_to_index() of the entry
 // (plane = slot / 256, entry t = slot % 256 of the plane at bit 12 t of the plane's 384 bytes).
 TKSPMV_HD inline void colw12_store(uint8_t *planes, uint32_t slot, uint16_t cw) {
@@ -279,6 +294,7 @@ TKSPMV_HD inline __attribute__((always_inline)) void store_entry(uint8_t *pkt, P
             or32(plane + colw12s_b_offset(lane & ~1u), b << ((lane & 1u) * 16u));
             return;
         }
+        case Precision::F32E5: return;  // (never reached: stream_args_error refuses the value for both packers and for load_packed -- the engine re-encodes whole lanes of F32C12, f32e5_transcode_lane)
         case Precision::F32: put<float>(pkt + (size_t)slot * 4, v); break;
         case Precision::F16: put<uint16_t>(pkt + (size_t)slot * 2, to_half(v)); break;
         case Precision::FIXED: put<uint32_t>(pkt + (size_t)slot * 4, to_fixed(v, fixed_width)); break;
@@ -312,6 +328,78 @@ TKSPMV_HD inline float load_value(const uint8_t *pkt, Precision p, uint32_t slot
     }
 }
 
+// ---- F32E5: the codec of a lane (host and device), the eligibility predicate and the host-side re-encoder ---------------------
+constexpr uint32_t F32E5_VALUE_MASK = 0x0FFFFFFFu, F32E5_PACKET_BYTES = 1280u, F32E5_PACKET_ENTRIES = 256u;
+// The five dwords of a lane from its four fp32 words and column words (column << 2 | SKIP | ROW_END). A word of +0.0 is stored as
+// ZERO (its 28 bits are zero anyway); every other word must carry the engine's top4.
+TKSPMV_HD inline void f32e5_encode_lane(const uint32_t (&w)[4], const uint16_t (&cw)[4], uint32_t (&d)[4], uint32_t &e) {
+    const uint32_t c[4] = {(uint32_t)(cw[0] >> COLW_COL_SHIFT) & 1023u, (uint32_t)(cw[1] >> COLW_COL_SHIFT) & 1023u, (uint32_t)(cw[2] >> COLW_COL_SHIFT) & 1023u,
+                           (uint32_t)(cw[3] >> COLW_COL_SHIFT) & 1023u};
+    const uint32_t ends = (cw[0] & 1u) | ((cw[1] & 1u) << 1) | ((cw[2] & 1u) << 2) | ((cw[3] & 1u) << 3);
+    const uint32_t zeros = (w[0] == 0u ? 1u : 0u) | (w[1] == 0u ? 2u : 0u) | (w[2] == 0u ? 4u : 0u) | (w[3] == 0u ? 8u : 0u);
+    static_assert(COLW_ROW_END == 1u, "ROW_END is bit 0 of a column word");
+    d[0] = (w[0] & F32E5_VALUE_MASK) | ((c[0] & 15u) << 28);
+    d[1] = (w[1] << 4) | (c[1] >> 6);
+    d[2] = (w[2] << 4) | ends;
+    d[3] = (w[3] << 4) | zeros;
+    e = (c[0] >> 4) | (c[2] << 6) | (c[3] << 16) | ((c[1] & 63u) << 26);
+}
+// Entry j of a lane: its fp32 word and its canonical column word.
+TKSPMV_HD inline uint32_t f32e5_word(const uint32_t (&d)[4], uint32_t top4, uint32_t j) {
+    if ((d[3] >> j) & 1u) return 0u;  // ZERO
+    return (j == 0u ? d[0] & F32E5_VALUE_MASK : d[j] >> 4) | (top4 << 28);
+}
+TKSPMV_HD inline uint16_t f32e5_colw(const uint32_t (&d)[4], uint32_t e, uint32_t j) {
+    const uint32_t col = j == 0u ? ((d[0] >> 28) | ((e & 63u) << 4)) : (j == 1u ? (((d[1] & 15u) << 6) | (e >> 26)) : (j == 2u ? (e >> 6) & 1023u : (e >> 16) & 1023u));
+    const uint32_t end = (d[2] >> j) & 1u, zero = (d[3] >> j) & 1u;
+    return (uint16_t)((col << COLW_COL_SHIFT) | ((zero & end) ? COLW_SKIP : 0u) | (end ? COLW_ROW_END : 0u));
+}
+// Lane `lane` of an F32C12 packet of 256 entries re-encoded into the F32E5 packet `dst` (both planes).
+TKSPMV_HD inline void f32e5_transcode_lane(const uint8_t *src, uint8_t *dst, uint32_t lane) {
+    uint32_t w[4], d[4], e;
+    uint16_t cw[4];
+    for (uint32_t j = 0; j < 4u; ++j) {
+        w[j] = get<uint32_t>(src + (size_t)(lane * 4u + j) * 4);
+        cw[j] = colw12s_load(src + (size_t)F32E5_PACKET_ENTRIES * 4, lane * 4u + j);
+    }
+    f32e5_encode_lane(w, cw, d, e);
+    for (uint32_t j = 0; j < 4u; ++j) put<uint32_t>(dst + (size_t)(lane * 4u + j) * 4, d[j]);
+    put<uint32_t>(dst + (size_t)F32E5_PACKET_ENTRIES * 4 + (size_t)lane * 4, e);
+}
+// What the eligibility test sums up over a stream (a reduction: the device forms the same four words with atomics).
+struct F32E5Census {
+    uint32_t all_and = 0xFFFFFFFFu, all_or = 0u;  // over the words that are not +0.0
+    uint64_t bare_zeros = 0;                      // words of +0.0 without SKIP: the padding -- and any explicit zero
+    uint64_t odd_skips = 0;                       // SKIP on a word that is not +0.0, or without ROW_END: no packer writes such an entry
+};
+TKSPMV_HD inline void f32e5_census_entry(uint32_t w, uint16_t cw, uint32_t &all_and, uint32_t &all_or, uint32_t &bare_zero, uint32_t &odd_skip) {
+    const bool skip = (cw & COLW_SKIP) != 0u;
+    if (w != 0u) {
+        all_and &= w;
+        all_or |= w;
+    }
+    bare_zero = (w == 0u && !skip) ? 1u : 0u;
+    odd_skip = (skip && (w != 0u || !(cw & COLW_ROW_END))) ? 1u : 0u;
+}
+// The predicate over the values of real entries: all fp32 words share their bits 31..28 (one sign, one aligned block of 32
+// binades; an explicit 0.0 among normal values, a value of the other sign or a wider span break it). top4: those bits.
+inline bool f32e5_values_eligible(const float *v, uint64_t n, uint32_t &top4) {
+    uint32_t a = 0xFFFFFFFFu, o = 0u;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t w;
+        std::memcpy(&w, v + i, 4);
+        a &= w;
+        o |= w;
+    }
+    top4 = o >> 28;
+    return n != 0 && (a >> 28) == (o >> 28);
+}
+// ... and over a stream's census: the same test on its words that are not +0.0, and no +0.0 but the `padding` entries behind the
+// partitions' last rows and the placeholders (an explicit +0.0 would decode like them: right, but such a matrix stays as it is).
+inline bool f32e5_census_eligible(const F32E5Census &c, uint64_t padding, uint32_t &top4) {
+    top4 = c.all_or >> 28;
+    return c.all_or != 0u && (c.all_and >> 28) == (c.all_or >> 28) && c.bare_zeros == padding && c.odd_skips == 0;
+}
 struct PackedMatrix {
     uint32_t rows = 0, cols = 0;
     uint64_t nnz = 0;
@@ -334,6 +422,37 @@ struct PackedMatrix {
     uint64_t stream_bytes() const { return (uint64_t)n_packets * packet_bytes; }
     uint64_t side_bytes() const { return (uint64_t)pkt_row.size() * 4 + (uint64_t)part_first.size() * 8; }
 };
+
+// The engine's re-encoding of a resident F32C12 stream of 4 entries per lane, on the host (plain C++: the CPU test's subject; the
+// engine runs the same per-lane functions on the device, engine.hip compact_stream). Entry order, partitions, pkt_row and the
+// tables stay what they are: only the packets change, 1408 -> 1280 bytes each.
+inline bool f32e5_applies(const PackedMatrix &pm) {
+    return pm.precision == Precision::F32C12 && pm.C == 4 && pm.packet_entries == F32E5_PACKET_ENTRIES && pm.n_packets != 0;
+}
+inline F32E5Census f32e5_census(const PackedMatrix &pm) {
+    F32E5Census c;
+    for (uint32_t p = 0; p < pm.n_packets; ++p) {
+        const uint8_t *pkt = pm.packets.data() + (size_t)p * pm.packet_bytes;
+        for (uint32_t s = 0; s < F32E5_PACKET_ENTRIES; ++s) {
+            uint32_t bz, os;
+            f32e5_census_entry(get<uint32_t>(pkt + (size_t)s * 4), colw12s_load(pkt + (size_t)F32E5_PACKET_ENTRIES * 4, s), c.all_and, c.all_or, bz, os);
+            c.bare_zeros += bz;
+            c.odd_skips += os;
+        }
+    }
+    return c;
+}
+inline uint64_t f32e5_padding(const PackedMatrix &pm) { return pm.packed_entries - pm.nnz - pm.placeholders; }
+inline bool f32e5_eligible(const PackedMatrix &pm, uint32_t &top4) {
+    top4 = 0u;
+    return f32e5_applies(pm) && f32e5_census_eligible(f32e5_census(pm), f32e5_padding(pm), top4);
+}
+inline void f32e5_transcode(const PackedMatrix &pm, std::vector<uint8_t> &out) {
+    out.assign((size_t)pm.n_packets * F32E5_PACKET_BYTES, 0);
+    for (uint32_t p = 0; p < pm.n_packets; ++p)
+        for (uint32_t lane = 0; lane < WAVE; ++lane)
+            f32e5_transcode_lane(pm.packets.data() + (size_t)p * pm.packet_bytes, out.data() + (size_t)p * F32E5_PACKET_BYTES, lane);
+}
 
 // Shortest partition the packers cut, a property of the matrix alone so that every packer (host, device, tkspmv_pack, the engine)
 // cuts the same partitions: 4 packets; 2 on small matrices (up to SMALL_MATRIX_PACKETS packets: ~700k rows of 20 non-zeros -- where the batch kernel's small-matrix

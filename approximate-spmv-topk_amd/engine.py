@@ -490,6 +490,9 @@ class SpMV:
         return a.value, b.value
 
     def info(self):
+        """tkspmv_info as a dict. batch_compact / batch_packet_bytes / batch_stream_bytes: what the batch kernel streams -- 1280-byte
+        packets re-encoded at 5 bytes per entry where the matrix's fp32 values share their top four bits (option F32_COMPACT), else
+        the canonical stream that packed_bytes counts; the compact copies come on top of it, one per stream replica."""
         i = _lib.Info()
         _lib.check(_lib.lib().tkspmv_get_info(self._h, C.byref(i)))
         return i.as_dict()

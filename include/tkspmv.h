@@ -151,6 +151,12 @@ typedef struct {
     uint64_t state_bytes;         /* device memory of the exchange state of back-to-back queries: the per-query sets (published maxima,
                                      threshold word, one slot per wave, the workgroups' records) and the overflow lists (8 B per row each;
                                      two per engine since round 4, one per query of a launch before) */
+    uint64_t batch_stream_bytes;  /* bytes of ONE copy of the packet stream as the batch kernel (tkspmv_enqueue_batch / _many) reads it:
+                                     n_packets * batch_packet_bytes. Engines whose fp32 values share their top four bits keep such
+                                     copies beside the canonical stream (batch_compact; packed_bytes does not count them): as many
+                                     as desc.stream_replicas, at least one */
+    uint32_t batch_packet_bytes;  /* bytes of a packet in those copies: 1280 where batch_compact, else the canonical packet's */
+    uint32_t batch_compact;       /* 1: the batch kernel streams the stream re-encoded at 5 bytes per entry (option F32_COMPACT) */
 } tkspmv_info;
 
 typedef struct {
