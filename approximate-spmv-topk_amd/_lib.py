@@ -90,10 +90,16 @@ class FacetBest(C.Structure):
     _fields_ = [("row", C.c_uint32), ("score_bits", C.c_uint32)]
 
 
+class Match(C.Structure):
+    """tkspmv_match: a boolean predicate over the 32 clause bits of a row's word W (term predicates): the row matches when
+    (W & must) == must, (W & must_not) == 0 and popcount(W & should) >= min_should."""
+    _fields_ = [("must", C.c_uint32), ("must_not", C.c_uint32), ("should", C.c_uint32), ("min_should", C.c_uint32)]
+
+
 # Every symbol include/tkspmv.h declares; tests check the library exports all of them.
 EXPORTED_SYMBOLS = [
     "tkspmv_create", "tkspmv_destroy", "tkspmv_get_info", "tkspmv_set_query", "tkspmv_set_query_device",
-    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
+    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_match", "tkspmv_run_match", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
     "tkspmv_time_queries", "tkspmv_time_host_loop", "tkspmv_time_query_batches", "tkspmv_time_stream_read", "tkspmv_enqueue_multi", "tkspmv_time_multi", "tkspmv_profile", "tkspmv_last_error", "tkspmv_device_count", "tkspmv_mtx_read", "tkspmv_mtx_free",
     "tkspmv_mtx_write", "tkspmv_sample_vector", "tkspmv_generate", "tkspmv_generate_rows", "tkspmv_generate_degrees", "tkspmv_options_parse", "tkspmv_pack", "tkspmv_pack_device",
     "tkspmv_sell_roundtrip", "tkspmv_sell_pack_device_check", "tkspmv_packed_info", "tkspmv_packed_decode", "tkspmv_packed_raw", "tkspmv_packed_get_row", "tkspmv_packed_score_rows", "tkspmv_packed_free", "tkspmv_wave_partitions", "tkspmv_packed_save", "tkspmv_packed_load",
@@ -144,6 +150,8 @@ def lib():
     L.tkspmv_run_range.argtypes = [vp, C.c_float, C.c_int32, u32p, f32p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.tkspmv_enqueue_facets.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, vp, vp]
     L.tkspmv_run_facets.argtypes = [vp, C.c_float, C.c_int32, u32p, C.POINTER(FacetBest), C.POINTER(C.c_uint64)]
+    L.tkspmv_enqueue_match.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, vp]
+    L.tkspmv_run_match.argtypes = [vp, u32p, C.POINTER(Match), C.c_int32, C.c_int32, u32p, C.POINTER(C.c_uint64)]
     L.tkspmv_enqueue_row_vectors.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     L.tkspmv_row_vectors.argtypes = [vp, u32p, C.c_int32, f32p, u32p]
     L.tkspmv_run_similar.argtypes = [vp, u32p, C.c_int32, C.c_int32, u32p, f32p]

@@ -177,6 +177,14 @@ int tkspmv_enqueue_facets(tkspmv_t *h, const float *dev_xs, int32_t count, const
 int tkspmv_run_facets(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total) {
     ENGINE_CALL(run_facets(threshold, use_filter, counts, best, total, err))
 }
+int tkspmv_enqueue_match(tkspmv_t *h, const uint32_t *dev_clauses, int64_t clause_stride_words, const tkspmv_match *dev_preds, int32_t count,
+                         const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_out, int64_t out_stride_words, uint32_t *dev_counts, void *stream) {
+    ENGINE_CALL(enqueue_match(dev_clauses, clause_stride_words, dev_preds, count, dev_mask, mask_stride_words, dev_out, out_stride_words, dev_counts, stream, err))
+}
+int tkspmv_run_match(tkspmv_t *h, const uint32_t *host_clauses, const tkspmv_match *pred, int32_t use_filter, int32_t install, uint32_t *host_mask,
+                     uint64_t *count) {
+    ENGINE_CALL(run_match(host_clauses, pred, use_filter, install, host_mask, count, err))
+}
 int tkspmv_enqueue_row_vectors(tkspmv_t *h, const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream) {
     ENGINE_CALL(enqueue_row_vectors(dev_rows, count, dev_xs, dev_len, stream, err))
 }

@@ -49,6 +49,7 @@
 #include "kernels/read_probe.hpp"
 #include "kernels/range_kernel.hpp"
 #include "kernels/facet_kernel.hpp"
+#include "kernels/match_kernel.hpp"
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
 #include "kernels/group_select.hpp"
@@ -103,6 +104,7 @@ typedef void (*stream_fn)(const StreamParams, const SelectParams);
 typedef void (*filter_fn)(const StreamParams, const SelectParams, const FilterParams);
 typedef void (*range_fn)(const StreamParams, const RangeParams);
 typedef void (*facet_fn)(const StreamParams, const FacetParams);
+typedef void (*match_fn)(const StreamParams, const MatchParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*batch_fn)(const BatchArgs);
@@ -113,12 +115,19 @@ struct Kernels {
     filter_fn filter[2] = {};  // [SCORES]
     range_fn range[2] = {};    // [FILT]
     facet_fn facet[2] = {};    // [FILT]
+    match_fn match[2] = {};    // [FILT]
     row_vectors_fn row_vectors = nullptr;
     score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
 };
+// Packet buffers of match_kernel. Its loads are 8 bytes per lane (16 at 8 entries), so more than range_kernel's 3 cost few registers;
+// builds with 3, 6 and 8 came out within 4 % of this one, less than the yardstick drifted between them ("Packets in
+// flight"): no count is shown to pay.
+#ifndef TKSPMV_MATCH_NBUF
+#define TKSPMV_MATCH_NBUF 4
+#endif
 // The instantiations of ONE format, every family restricted to the formats it is built for (the predicates of stream_format.hpp).
 template <int C, int XCOLS, int QM>
 static Kernels kernels_of(bool dbg) {
@@ -134,6 +143,8 @@ static Kernels kernels_of(bool dbg) {
         K.range[1] = &range_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
         K.facet[0] = &facet_kernel<C, XCOLS, QM, false, C == 8 ? 2 : 3>;
         K.facet[1] = &facet_kernel<C, XCOLS, QM, true, C == 8 ? 2 : 3>;
+        K.match[0] = &match_kernel<C, XCOLS, QM, false, TKSPMV_MATCH_NBUF>;
+        K.match[1] = &match_kernel<C, XCOLS, QM, true, TKSPMV_MATCH_NBUF>;
         K.row_vectors = &row_vectors_kernel<C, XCOLS, QM == QM_F32C12>;
         K.score_rows = &score_rows_kernel<C, QM == QM_F32C12>;
     }
@@ -441,6 +452,15 @@ struct EngineImpl {
         tkspmv_facet_best *d_facet_best = nullptr;
         uint32_t facet_cap = 0;
     } range;
+
+    // Term predicates (tkspmv_enqueue_match, match_kernel) touch no other group but the matrix. The scratch of tkspmv_run_match,
+    // which allocates it on its first call: the clause table (cols words), the predicate (4 words) and the count (1 word) in one
+    // buffer, and the mask it produces (mask_words() words).
+    struct Match {
+        static constexpr int MATCH_MAX = 32;  // queries per launch
+        uint32_t *d_match_in = nullptr;   // [cols] table | [4] predicate | [1] count
+        uint32_t *d_match_out = nullptr;  // [mask_words()]
+    } match;
 
     // Queries by stored row (tkspmv_enqueue_row_vectors, row_vectors_kernel) touch no other group but the matrix either. The
     // scratch of tkspmv_run_similar -- a chunk's row ids, its vectors and its [chunk][k] results --, which allocates it on its
@@ -949,6 +969,46 @@ struct EngineImpl {
         if (best && n_out) {
             const uint32_t cgrid = (uint32_t)std::min<size_t>((n_out + 255u) / 256u, 16384u);
             hipLaunchKernelGGL(facet_close_kernel, dim3(cgrid), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(best), (unsigned long long)n_out);
+        }
+    }
+    // Why term predicates are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask). Like row
+    // vectors, and unlike filtered queries, the approximate per-partition engines are served: which columns a row has does not depend
+    // on how rows are selected.
+    const char *match_unsupported(bool with_mask) const {
+        if (!kern.match[0]) return "term predicates need an fp32 packet stream (TKSPMV_F32)";
+        if (pm.n_packets != 0u && (!mat.d_packets || !mat.d_pkt_row || !mat.d_part_first)) return "term predicates are read from the wave-BSCSR packets: this engine does not hold them";
+        return with_mask ? filter_unsupported() : nullptr;
+    }
+    // n term predicates (query i: table = clauses + i * cstride words, predicate preds[i], mask = mask + i * mstride words or none;
+    // result at out + i * ostride words, count at counts[i] or none), complete in stream order when this returns: the outputs are
+    // zeroed in front -- the masks' own words only --, then launches of up to MATCH_MAX queries. No engine state is read or written
+    // besides the matrix: the stream copies rotate with the query's number in THIS call.
+    void launch_match(const uint32_t *clauses, size_t cstride, const tkspmv_match *preds, int n, const uint32_t *mask, size_t mstride, uint32_t *out,
+                      size_t ostride, uint32_t *counts, hipStream_t s) const {
+        const size_t words = mask_words();
+        if (n == 1 || ostride == words) (void)hipMemsetAsync(out, 0, (size_t)n * words * 4, s);
+        else (void)hipMemset2DAsync(out, ostride * 4, 0, words * 4, (size_t)n, s);
+        if (counts) (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
+        StreamParams P = stream_params(nullptr);
+        MatchParams R{};
+        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
+        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
+        R.clause_stride = cstride;
+        R.mask_stride = (uint32_t)mstride;
+        R.mask_words = mask_words();
+        R.out_stride = ostride;
+        R.args_tag = MATCH_ARGS_TAG;
+        const match_fn fn = kern.match[mask != nullptr];
+        for (int i = 0; i < n; i += Match::MATCH_MAX) {
+            const int c = std::min(Match::MATCH_MAX, n - i);
+            R.q0 = (uint32_t)i;
+            R.n_q = (uint32_t)c;
+            R.clauses = clauses + (size_t)i * cstride;
+            R.preds = preds + i;
+            R.mask = mask ? mask + (size_t)i * mstride : nullptr;
+            R.out = out + (size_t)i * ostride;
+            R.counts = counts ? counts + i : nullptr;
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
         }
     }
     // Why stored rows cannot be expanded by this engine (nullptr: they can). Unlike filtered queries, the approximate per-partition
@@ -2716,6 +2776,51 @@ int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tk
     if (total) *total = found;
     if (counts) HIP_TRY(hipMemcpy(counts, m.range.d_facet_counts, (size_t)n_bins * 4, hipMemcpyDeviceToHost));
     if (best) HIP_TRY(hipMemcpy(best, m.range.d_facet_best, (size_t)n_bins * 8, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_match(const uint32_t *dev_clauses, int64_t clause_stride_words, const tkspmv_match *dev_preds, int32_t count, const uint32_t *dev_mask,
+                          int64_t mask_stride_words, uint32_t *dev_out, int64_t out_stride_words, uint32_t *dev_counts, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    const int64_t words = (int64_t)m.mask_words();
+    if (!dev_clauses || !dev_preds || !dev_out || count < 1 || clause_stride_words < 0 || mask_stride_words < 0 || out_stride_words < 0 ||
+        (clause_stride_words != 0 && clause_stride_words < (int64_t)m.desc.cols) || (out_stride_words < words && !(out_stride_words == 0 && count == 1)))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_match (table, predicates and output given, count >= 1, strides >= 0, clause_stride_words 0 or "
+                                             ">= cols, out_stride_words >= ceil(rows / 32) or 0 with count = 1)");
+    if (const char *why = m.match_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
+        m.launch_match(dev_clauses, (size_t)clause_stride_words, dev_preds, count, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_out,
+                       (size_t)out_stride_words, dev_counts, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::run_match(const uint32_t *host_clauses, const tkspmv_match *pred, int32_t use_filter, int32_t install, uint32_t *host_mask, uint64_t *count,
+                      std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_clauses || !pred) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_match (clause table and predicate given)");
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    if (const char *why = m.match_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    HIP_TRY(hipSetDevice(m.device));
+    const size_t cols = m.desc.cols, words = m.mask_words();
+    if (!m.match.d_match_in) HIP_TRY(m.alloc(m.match.d_match_in, (cols + 5u) * 4, Mem::Device, 0));
+    if (!m.match.d_match_out) HIP_TRY(m.alloc(m.match.d_match_out, words * 4, Mem::Device, 0));
+    // (the scratch belongs to this host form alone, and the host form before this one has waited)
+    HIP_TRY(hipMemcpy(m.match.d_match_in, host_clauses, cols * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m.match.d_match_in + cols, pred, sizeof(tkspmv_match), hipMemcpyHostToDevice));
+    const int st = enqueue_match(m.match.d_match_in, 0, reinterpret_cast<const tkspmv_match *>(m.match.d_match_in + cols), 1, use_filter ? m.filter.d_filter : nullptr, 0,
+                                 m.match.d_match_out, 0, m.match.d_match_in + cols + 4, nullptr, err);
+    if (st != TKSPMV_OK) return st;
+    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    uint32_t found = 0u;
+    HIP_TRY(hipMemcpy(&found, m.match.d_match_in + cols + 4, 4, hipMemcpyDeviceToHost));
+    if (count) *count = found;
+    if (host_mask) HIP_TRY(hipMemcpy(host_mask, m.match.d_match_out, words * 4, hipMemcpyDeviceToHost));
+    if (install) {  // (as tkspmv_set_filter installs a mask; nothing enqueued on the engine's stream still reads the old one: it has just idled)
+        if (!m.filter.d_filter) HIP_TRY(m.alloc(m.filter.d_filter, words * 4));
+        HIP_TRY(hipMemcpy(m.filter.d_filter, m.match.d_match_out, words * 4, hipMemcpyDeviceToDevice));
+        m.filter.have_filter = true;
+    }
     return TKSPMV_OK;
 }
 

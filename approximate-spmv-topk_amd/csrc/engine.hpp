@@ -57,6 +57,13 @@ class Engine {
                        const uint32_t *dev_labels, uint32_t n_bins, uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream,
                        std::string &err);
     int run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err);
+    // Term predicates (match_kernel): the allow-mask of the rows whose own columns satisfy a boolean predicate over up to 32 clauses
+    // (sets of columns), made on the device from the packets' column plane; run_match is the host-side counterpart (host table and
+    // predicate, waits, optionally installs the result as the engine's filter).
+    int enqueue_match(const uint32_t *dev_clauses, int64_t clause_stride_words, const tkspmv_match *dev_preds, int32_t count, const uint32_t *dev_mask,
+                      int64_t mask_stride_words, uint32_t *dev_out, int64_t out_stride_words, uint32_t *dev_counts, void *stream, std::string &err);
+    int run_match(const uint32_t *host_clauses, const tkspmv_match *pred, int32_t use_filter, int32_t install, uint32_t *host_mask, uint64_t *count,
+                  std::string &err);
     // Queries by stored row (row_vectors_kernel): rows of the matrix, given by the global ids queries return, expanded into the dense
     // vectors every enqueue_* call takes; run_similar = the engine's top-k with each given row as the query (chunks on engine-owned
     // scratch: ids up, row vectors, the batch sequence, wait, results down), the row itself removed from its list on request.

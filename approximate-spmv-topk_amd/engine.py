@@ -322,6 +322,34 @@ class SpMV:
         val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity))
         return val, idx
 
+    def enqueue_match(self, dev_clauses, dev_preds, count, dev_out, out_stride=0, dev_counts=0, clause_stride=0, dev_mask=0, mask_stride=0, stream=0):
+        """Term predicates: for query i the allow-mask of the rows whose own columns satisfy dev_preds[i] (_lib.Match records in device
+        memory) under the clause table dev_clauses + i*clause_stride words (uint32[cols] as bool_query() builds it; 0: one table for
+        every query), restricted to dev_mask + i*mask_stride words (0: unfiltered). dev_out + i*out_stride receives the mask's
+        ceil(rows/32) words (out_stride = 0 with count = 1), valid wherever a mask is accepted; dev_counts[i] (optional) the number of
+        matching rows. No host sync, no engine state touched."""
+        p = lambda a: C.c_void_p(int(a)) if a else None
+        _lib.check(_lib.lib().tkspmv_enqueue_match(self._h, p(dev_clauses), int(clause_stride), p(dev_preds), int(count), p(dev_mask), int(mask_stride),
+                                                   p(dev_out), int(out_stride), p(dev_counts), C.c_void_p(int(stream))))
+
+    def match(self, clauses, pred, allow=None, install=False):
+        """One term predicate with host arrays: clauses (uint32[cols]) and pred (must, must_not, should, min_should) as bool_query()
+        returns them; set_filter(allow) first if given (a bool array of length rows, or row_mask() words; the result is then
+        restricted to it). Returns (mask_words, count): the allow-mask of the matching rows, as row_mask() would pack it, and their
+        number. install=True: the result becomes the engine's installed filter (set_filter's), without leaving the device."""
+        t = np.ascontiguousarray(clauses, dtype=np.uint32)
+        if t.shape != (self.num_cols,):
+            raise ValueError(f"clause table has shape {t.shape}, expected ({self.num_cols},)")
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        rec = _lib.Match(*(int(v) & 0xFFFFFFFF for v in pred))
+        words = np.zeros(max(1, (self.num_rows + 31) // 32), dtype=np.uint32)
+        count = C.c_uint64(0)
+        _lib.check(_lib.lib().tkspmv_run_match(self._h, t.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rec), int(allow is not None), int(bool(install)),
+                                               words.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        return words, int(count.value)
+
     def enqueue_facets(self, dev_xs, count, dev_thresholds, dev_counts, n_bins=0, dev_labels=0, dev_best=0, dev_totals=0, dev_mask=0, mask_stride=0,
                        stream=0):
         """Facet counts: for query i (dev_xs, dev_thresholds, dev_mask / mask_stride as in enqueue_range) the matches per label.

@@ -218,6 +218,82 @@ def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=
     return counts, best_idx, best_val, total
 
 
+def bool_query(cols, must=(), must_not=(), should=(), min_should=0):
+    """A boolean predicate over the rows' own columns (SpMV.match / enqueue_match) from lists of terms. Every item of `must` and of
+    `should` is a column or an iterable of columns ("any of these") and takes one of the 32 clause bits, in this order: must first,
+    then should; all the columns of `must_not` share one further bit. A row matches when it has an entry in every must clause, in none
+    of the must_not columns and in at least min_should of the should clauses.
+    Returns (clauses uint32[cols], (must, must_not, should, min_should)): the clause table -- bit c of clauses[j] set when column j
+    belongs to clause c -- and the predicate's four words. Raises ValueError beyond 32 clauses or for a column outside [0, cols)."""
+    cols = int(cols)
+    clauses = np.zeros(cols, dtype=np.uint32)
+    words = [0, 0, 0]
+    bit = 0
+
+    def columns(item):
+        c = np.asarray(list(item) if hasattr(item, "__iter__") else [item]).astype(np.int64).ravel()
+        if c.size and (c.min() < 0 or c.max() >= cols):
+            raise ValueError(f"a column outside [0, {cols})")
+        return c
+
+    def clause(cs, which):
+        nonlocal bit
+        if bit >= 32:
+            raise ValueError("a predicate holds at most 32 clauses")
+        clauses[cs] |= np.uint32(1 << bit)
+        words[which] |= 1 << bit
+        bit += 1
+
+    for item in must:
+        clause(columns(item), 0)
+    for item in should:
+        clause(columns(item), 2)
+    banned = [columns(item) for item in must_not]
+    if banned:
+        clause(np.concatenate(banned), 1)
+    if int(min_should) < 0:
+        raise ValueError("min_should must be non-negative")
+    return clauses, (words[0], words[1], words[2], int(min_should))
+
+
+def match_rows(row, col, rows, clauses, pred, allow=None):
+    """The contract of term predicates (SpMV.enqueue_match) restated in numpy, for CPU-side users and as the tests' expectation:
+    from the COO's row[nnz] / col[nnz] alone (values play no part: an explicit zero is an entry), the clause table and the
+    predicate (must, must_not, should, min_should), bool[rows]: row r matches when it has entries, allow[r] if given, and its word
+    W(r) -- the OR of clauses[col] over its entries -- has (W & must) == must, (W & must_not) == 0 and
+    popcount(W & should) >= min_should."""
+    rows = int(rows)
+    r = np.asarray(row).astype(np.int64).ravel()
+    c = np.asarray(col).astype(np.int64).ravel()
+    t = np.ascontiguousarray(clauses, dtype=np.uint32)
+    if r.shape != c.shape:
+        raise ValueError("row and col must have one length")
+    if r.size and (r.min() < 0 or r.max() >= rows or c.min() < 0 or c.max() >= t.size):
+        raise ValueError("an entry outside the matrix")
+    must, must_not, should, min_should = (int(v) & 0xFFFFFFFF for v in pred)
+    W = np.zeros(rows, dtype=np.uint32)
+    has = np.zeros(rows, dtype=bool)
+    if r.size:
+        v = t[c]
+        if np.any(r[1:] < r[:-1]):  # (any entry order is a COO: the rows' runs are formed here)
+            order = np.argsort(r, kind="stable")
+            r, v = r[order], v[order]
+        starts = np.flatnonzero(np.concatenate(([True], r[1:] != r[:-1])))
+        W[r[starts]] = np.bitwise_or.reduceat(v, starts)
+        has[r[starts]] = True
+    hits = W & np.uint32(should)
+    pop = np.zeros(rows, dtype=np.int64)
+    for b in range(32):
+        pop += (hits >> np.uint32(b)) & np.uint32(1)
+    ok = has & ((W & np.uint32(must)) == np.uint32(must)) & ((W & np.uint32(must_not)) == 0) & (pop >= min_should)
+    if allow is not None:
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.shape != (rows,):
+            raise ValueError(f"allow must be a bool array of shape ({rows},)")
+        ok &= a
+    return ok
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()

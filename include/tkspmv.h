@@ -283,6 +283,47 @@ int tkspmv_enqueue_facets(tkspmv_t *e, const float *dev_xs, int32_t count, const
  * to n_groups entries, and waits. counts[n_groups] and best[n_groups] (host; either may be NULL) and *total receive the result. */
 int tkspmv_run_facets(tkspmv_t *e, float threshold, int32_t use_filter,
                       uint32_t *counts, tkspmv_facet_best *best, uint64_t *total);
+/* Boolean term predicates: an allow-mask made on the device from the rows' own columns -- "only rows that contain column 17 and one
+ * of {40, 41}, and not column 900", or a term's document frequency -- where tkspmv_set_filter takes a mask the host built. The
+ * kernel (match_kernel) streams the packets' column plane alone: the values never travel.
+ * Clause table: `cols` u32 words; bit c of word j set = column j belongs to clause c (c in 0..31). A clause is a set of columns; a
+ * row satisfies it when it has an entry in any of them. Query i uses dev_clauses + i * clause_stride_words (0: one table for every
+ * query; else >= cols).
+ * Row word: W(r) = the OR of table[col] over the stored entries of local row r. An entry is an entry of the COO the engine was
+ * created from, whatever its value (an explicit 0.0 counts, so does a negative value; a column that occurs several times changes
+ * nothing); placeholders of empty rows and the padding behind a partition's last row are not entries.
+ * Row r MATCHES predicate dev_preds[i] when it has entries, is allowed by the optional dev_mask (dev_mask / mask_stride_words exactly
+ * as in tkspmv_enqueue_range; NULL: unfiltered), (W & must) == must, (W & must_not) == 0 and popcount(W & should) >= min_should.
+ * All-zero fields match every row that has entries; min_should > popcount(should) matches nothing. desc.min_score and
+ * desc.first_row play no part: the mask is over local rows, like every allow-mask.
+ * Outputs of query i: the mask, words = max(1, ceil(rows / 32)) words at dev_out + i * out_stride_words (dev_out required;
+ * out_stride_words >= words, or 0 with count = 1): bit r & 31 of word r >> 5 is set if and only if row r matches. All `words` words
+ * are written and bits at and beyond `rows` are 0, so the result is valid wherever a mask is accepted; words between the masks of a
+ * strided output are not written. dev_out must not overlap dev_mask. dev_counts[i] (optional) = the number of matching rows.
+ * Exact and bit-reproducible: a pure function of the matrix's sparsity pattern.
+ * Stream and state contract: tkspmv_enqueue_range's -- complete in stream order on any stream (NULL: the engine's); reads the
+ * matrix, the table, the predicates and the mask and writes its two outputs; touches no result buffer, exchange set, record,
+ * verdict, carried threshold, launch counter or engine scratch, so any number of calls may be in flight and it mixes freely with
+ * every other call. Query i reads stream copy i % stream_replicas. In stream order the result feeds tkspmv_enqueue_filtered,
+ * _range, _facets, _grouped and _after with no host round trip. The call zeroes its outputs in stream order and streams the column
+ * plane once per query (launches of up to 32 queries).
+ * Errors, checked before any device call: TKSPMV_ERR_INVALID for a NULL engine, table, predicates or output, count < 1, a negative
+ * stride, a clause stride that is neither 0 nor >= cols, an output stride below `words` (except 0 with count = 1);
+ * TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_row_vectors reports it (a packet stream that is not fp32, an engine that does
+ * not hold the packets) -- the approximate per-partition engines are served -- and, with dev_mask, where tkspmv_enqueue_filtered
+ * reports it. */
+typedef struct { uint32_t must, must_not, should, min_should; } tkspmv_match;   /* 16 bytes */
+int tkspmv_enqueue_match(tkspmv_t *e, const uint32_t *dev_clauses, int64_t clause_stride_words,
+                         const tkspmv_match *dev_preds, int32_t count,
+                         const uint32_t *dev_mask, int64_t mask_stride_words,
+                         uint32_t *dev_out, int64_t out_stride_words, uint32_t *dev_counts, void *stream);
+/* The host-side counterpart: a host table (cols words) and a host predicate, the mask installed by tkspmv_set_filter when
+ * use_filter != 0 (TKSPMV_ERR_INVALID if none is); runs on engine-owned scratch allocated on the first call, and waits.
+ * host_mask (`words` words) and *count may each be NULL. install != 0: the result becomes the engine's installed filter, as
+ * tkspmv_set_filter would install it, by a device-to-device copy; with use_filter as well, the new filter is the old one AND the
+ * predicate. */
+int tkspmv_run_match(tkspmv_t *e, const uint32_t *host_clauses, const tkspmv_match *pred,
+                     int32_t use_filter, int32_t install, uint32_t *host_mask, uint64_t *count);
 /* Grouped top-k (result collapsing): the k best GROUPS of rows, each shown once by its best row -- the k best documents by
  * their best passage, products by their best variant. Every local row carries a label group[r] < n_groups, a property of the
  * index like the allow-mask. For a query a row is ELIGIBLE when it has entries, is allowed by the optional allow-mask, and its
