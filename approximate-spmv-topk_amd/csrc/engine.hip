@@ -485,6 +485,10 @@ struct EngineImpl {
         uint32_t sr_q_cap = 0, sr_row_cap = 0;  // queries and list entries per query the scratch holds
     } score;
 
+    // The device words of a path with an array select of its own (d_gwords, d_awords): [4][256] histogram, zeroed per query | word 1024:
+    // the path's own counter | the candidate counter | what the selection kernel zeroes behind itself (threshold word, nine tickets)
+    struct SelectWords { static constexpr uint32_t W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32; };
+
     // Grouped top-k (tkspmv_enqueue_grouped; group_best_kernel, group_split_kernel, group_ids_kernel) touches no other group but the
     // matrix either: its scores go to an array of its own, its selection runs on its own histogram, candidate list and counters, and
     // the selection kernel gets words of this group where it resets exchange state behind itself. The labels are a property of the
@@ -499,10 +503,9 @@ struct EngineImpl {
         float *d_gscore = nullptr;             // [group_cap]
         uint32_t *d_grow = nullptr;            // [group_cap] group -> its representative's row (the selection's pos_to_row)
         unsigned long long *d_gcand = nullptr; // [group_cap] candidate list of the radix filter
-        // [4][256] histogram | the non-empty-group counter (both zeroed in front of every query) | the candidate counter | the words
-        // the selection kernel zeroes behind itself (threshold word, nine tickets 32 words apart)
+        // SelectWords; word 1024 counts the non-empty groups (zeroed in front of every query, with the histogram)
         uint32_t *d_gwords = nullptr;
-        static constexpr uint32_t W_NONEMPTY = 1024, W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32;
+        static constexpr uint32_t W_NONEMPTY = 1024;
         uint32_t *d_gout_grp = nullptr, *d_gout_n = nullptr;  // engine-owned [k] group ids and n ("the last query wins")
     } grouped;
 
@@ -514,11 +517,9 @@ struct EngineImpl {
     struct After {
         float *d_ay = nullptr;                  // [rows] the scores of the query in flight; -inf where a row has no entry (never written)
         unsigned long long *d_acand = nullptr;  // [rows] candidate list of the radix filter: it keeps EVERY tie at the cut
-        // [4][256] histogram (zeroed in front of every query) | the count of eligible rows behind the cursor (after_finish_kernel
-        // zeroes it) | the candidate counter | the words the selection kernel zeroes behind itself (threshold word, nine tickets 32
-        // words apart)
+        // SelectWords; word 1024 counts the eligible rows behind the cursor (after_finish_kernel zeroes it, not the host)
         uint32_t *d_awords = nullptr;
-        static constexpr uint32_t W_TOTAL = 1024, W_COUNT = 1056, W_TAU = 1088, W_DONE = 1120, N_WORDS = W_DONE + 9 * 32;
+        static constexpr uint32_t W_TOTAL = 1024;
         // engine-owned outputs of the host form ("the last query wins"): n, total | the cursor tkspmv_run_after uploads | the next cursor
         uint32_t *d_aout = nullptr;
         static constexpr uint32_t O_N = 0, O_TOTAL = 1, O_CURSOR = 4, O_NEXT = 8, N_OUT = 12;
@@ -898,36 +899,48 @@ struct EngineImpl {
         if (F) hipLaunchKernelGGL(kern.filter[scores], dim3(grid), dim3(block + 64), 0, s, P, S, *F);
         else hipLaunchKernelGGL(kern.stream[scores], dim3(grid), dim3(block + 64), 0, s, P, S);
     }
+    // What launch_range, launch_facets and launch_match share: n queries in launches of at most max_q, each one scan of the matrix. R is
+    // RangeParams, FacetParams or MatchParams, used by field name: the stream copies, the masks' geometry and each launch's q0 / n_q are
+    // filled here; chunk(i, c) points the rest at the queries [i, i + c). Zeroing the outputs in front stays with the caller.
+    template <class Params, class Fn, class Chunk>
+    void launch_scan(Params &R, Fn fn, const StreamParams &P, int n, int max_q, size_t mask_stride, hipStream_t s, Chunk chunk) const {
+        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
+        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
+        R.mask_stride = (uint32_t)mask_stride;
+        R.mask_words = mask_words();
+        for (int i = 0; i < n; i += max_q) {
+            const int c = std::min(max_q, n - i);
+            R.q0 = (uint32_t)i;
+            R.n_q = (uint32_t)c;
+            chunk(i, c);
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
+        }
+    }
+    // The period of a scan launch of c queries that keep a timetable (range and facets; option RANGE_PERIOD): the timetable of
+    // launch_batch; one partition per wave, or no timetable.
+    uint32_t scan_period(int c, const StreamParams &P) const {
+        const uint32_t period_ns = range.range_period_set ? range.range_period_ns : local.pace_period_ns;
+        return (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
+    }
     // n range queries (query i: x = xs + i * cols, threshold thresholds[i], mask = mask + i * stride words or none), complete in
     // stream order when this returns: the counters are zeroed in front, then launches of up to RANGE_MAX queries. No engine state is
     // read or written besides the matrix: the stream copies rotate with the query's number in THIS call.
     void launch_range(const float *xs, int n, const float *thresholds, const uint32_t *mask, size_t stride, uint32_t *idx, float *val,
                       uint32_t capacity, uint32_t *counts, hipStream_t s) const {
         (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
-        StreamParams P = stream_params(xs);
+        const StreamParams P = stream_params(xs);
         RangeParams R{};
-        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
-        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
-        R.mask_stride = (uint32_t)stride;
-        R.mask_words = mask_words();
         R.capacity = capacity;
         R.first_row = desc.first_row;
-        const uint32_t period_ns = range.range_period_set ? range.range_period_ns : local.pace_period_ns;
-        const range_fn fn = kern.range[mask != nullptr];
-        for (int i = 0; i < n; i += Range::RANGE_MAX) {
-            const int c = std::min(Range::RANGE_MAX, n - i);
-            R.q0 = (uint32_t)i;
-            R.n_q = (uint32_t)c;
+        launch_scan(R, kern.range[mask != nullptr], P, n, Range::RANGE_MAX, stride, s, [&](int i, int c) {
             R.xs = xs + (size_t)i * desc.cols;
             R.thresholds = thresholds + i;
             R.mask = mask ? mask + (size_t)i * stride : nullptr;
             R.counts = counts + i;
             R.idx = idx ? idx + (size_t)i * capacity : nullptr;
             R.val = val ? val + (size_t)i * capacity : nullptr;
-            // (the timetable of launch_batch; one partition per wave, or no timetable)
-            R.period = (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
-        }
+            R.period = scan_period(c, P);
+        });
     }
     // n facet queries (launch_range's queries; bin of local row r: labels[r], none when that is >= n_bins), complete in stream order
     // when this returns: counts, best and totals are zeroed in front, then launches of up to RANGE_MAX queries whose kernels add to
@@ -939,33 +952,22 @@ struct EngineImpl {
         if (n_out) (void)hipMemsetAsync(counts, 0, n_out * 4, s);
         if (best && n_out) (void)hipMemsetAsync(best, 0, n_out * 8, s);
         if (totals) (void)hipMemsetAsync(totals, 0, (size_t)n * 4, s);
-        StreamParams P = stream_params(xs);
+        const StreamParams P = stream_params(xs);
         FacetParams R{};
-        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
-        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
-        R.mask_stride = (uint32_t)stride;
-        R.mask_words = mask_words();
         R.labels = labels;
         R.n_bins = n_bins;
         R.lds_bins = n_bins <= range.facet_lds_bins ? range.facet_lds_bins : 0u;
         R.first_row = desc.first_row;
         R.args_tag = FACET_ARGS_TAG;
-        const uint32_t period_ns = range.range_period_set ? range.range_period_ns : local.pace_period_ns;
-        const facet_fn fn = kern.facet[mask != nullptr];
-        for (int i = 0; i < n; i += Range::RANGE_MAX) {
-            const int c = std::min(Range::RANGE_MAX, n - i);
-            R.q0 = (uint32_t)i;
-            R.n_q = (uint32_t)c;
+        launch_scan(R, kern.facet[mask != nullptr], P, n, Range::RANGE_MAX, stride, s, [&](int i, int c) {
             R.xs = xs + (size_t)i * desc.cols;
             R.thresholds = thresholds + i;
             R.mask = mask ? mask + (size_t)i * stride : nullptr;
             R.counts = counts + (size_t)i * n_bins;
             R.best = best ? reinterpret_cast<unsigned long long *>(best) + (size_t)i * n_bins : nullptr;
             R.totals = totals ? totals + i : nullptr;
-            // (launch_range's timetable)
-            R.period = (outlasts_timetable(period_ns, c) || (uint64_t)P.n_parts > (uint64_t)grid * 8u) ? 0u : period_units(period_ns);
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
-        }
+            R.period = scan_period(c, P);
+        });
         if (best && n_out) {
             const uint32_t cgrid = (uint32_t)std::min<size_t>((n_out + 255u) / 256u, 16384u);
             hipLaunchKernelGGL(facet_close_kernel, dim3(cgrid), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(best), (unsigned long long)n_out);
@@ -989,27 +991,18 @@ struct EngineImpl {
         if (n == 1 || ostride == words) (void)hipMemsetAsync(out, 0, (size_t)n * words * 4, s);
         else (void)hipMemset2DAsync(out, ostride * 4, 0, words * 4, (size_t)n, s);
         if (counts) (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
-        StreamParams P = stream_params(nullptr);
         MatchParams R{};
-        R.n_replicas = mat.d_replicas.empty() ? 1u : (uint32_t)std::min<size_t>(mat.d_replicas.size(), 16);
-        for (uint32_t r = 0; r < R.n_replicas; ++r) R.replicas[r] = mat.packets(r);
         R.clause_stride = cstride;
-        R.mask_stride = (uint32_t)mstride;
-        R.mask_words = mask_words();
         R.out_stride = ostride;
         R.args_tag = MATCH_ARGS_TAG;
-        const match_fn fn = kern.match[mask != nullptr];
-        for (int i = 0; i < n; i += Match::MATCH_MAX) {
-            const int c = std::min(Match::MATCH_MAX, n - i);
-            R.q0 = (uint32_t)i;
-            R.n_q = (uint32_t)c;
+        // (no query vector and no timetable: MatchParams has neither xs nor period)
+        launch_scan(R, kern.match[mask != nullptr], stream_params(nullptr), n, Match::MATCH_MAX, mstride, s, [&](int i, int) {
             R.clauses = clauses + (size_t)i * cstride;
             R.preds = preds + i;
             R.mask = mask ? mask + (size_t)i * mstride : nullptr;
             R.out = out + (size_t)i * ostride;
             R.counts = counts ? counts + i : nullptr;
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, R);
-        }
+        });
     }
     // Why stored rows cannot be expanded by this engine (nullptr: they can). Unlike filtered queries, the approximate per-partition
     // engines are served: extraction does not depend on how rows are selected.
@@ -1018,10 +1011,9 @@ struct EngineImpl {
         if (pm.n_packets != 0u && (!mat.d_packets || !mat.d_pkt_row || !mat.d_part_first)) return "row vectors are read from the wave-BSCSR packets: this engine does not hold them";
         return nullptr;
     }
-    // Rows ids[0 .. n) as dense vectors xs[n][cols] (len[n]: their entries, optional), complete in stream order when this returns:
-    // one wave per row. Stream copy 0 is read whatever stream_replicas says.
-    void launch_row_vectors(const uint32_t *ids, int n, float *xs, uint32_t *len, hipStream_t s) const {
-        RowVecParams R{};
+    // The matrix as the kernels that locate stored rows see it: what RowVecParams and ScoreRowsParams share, set by field name.
+    template <class Params>
+    void fill_row_view(Params &R) const {
         R.packets = mat.d_packets;
         R.pkt_row = mat.d_pkt_row;
         R.part_first = mat.d_part_first;
@@ -1032,6 +1024,12 @@ struct EngineImpl {
         R.cols = desc.cols;
         R.rows = desc.rows;
         R.first_row = desc.first_row;
+    }
+    // Rows ids[0 .. n) as dense vectors xs[n][cols] (len[n]: their entries, optional), complete in stream order when this returns:
+    // one wave per row. Stream copy 0 is read whatever stream_replicas says.
+    void launch_row_vectors(const uint32_t *ids, int n, float *xs, uint32_t *len, hipStream_t s) const {
+        RowVecParams R{};
+        fill_row_view(R);
         R.ids = ids;
         R.xs = xs;
         R.len = len;
@@ -1043,16 +1041,7 @@ struct EngineImpl {
     // counts the chunks: more of them than a grid has go into further launches. Stream copy 0 is read whatever stream_replicas says.
     void launch_score_rows(const float *xs, int n_q, const uint32_t *ids, int n_rows, size_t stride, float *scores, hipStream_t s) const {
         ScoreRowsParams R{};
-        R.packets = mat.d_packets;
-        R.pkt_row = mat.d_pkt_row;
-        R.part_first = mat.d_part_first;
-        R.part_count = mat.d_part_count;
-        R.n_packets = pm.n_packets;
-        R.n_parts = (uint32_t)pm.part_first.size();
-        R.packet_bytes = pm.packet_bytes;
-        R.cols = desc.cols;
-        R.rows = desc.rows;
-        R.first_row = desc.first_row;
+        fill_row_view(R);
         R.ids_stride = stride;
         R.n_rows = (uint32_t)n_rows;
         const uint32_t wgs_full = std::max(1u, info.num_cus) * 8u;  // workgroups of 4 waves that fill the device
@@ -1107,6 +1096,51 @@ struct EngineImpl {
         if (!mat.d_packets || !mat.d_pkt_row) return "grouped queries stream the wave-BSCSR packets: this engine does not hold them";
         return with_mask ? filter_unsupported() : nullptr;
     }
+    // The array select -- scores in an array, four radix_hist_kernel passes, radix_filter_kernel, select_kernel -- as launch_grouped,
+    // launch_after and launch_query_radix share it. order_key: the host twin of the device function (kernels/common.hpp).
+    static uint32_t order_key(float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    // The radix select of scores[n] on a path's own words (SelectWords) and candidate list of `cap` entries ...
+    static RadixParams radix_params(const float *scores, uint32_t n, uint32_t k, uint32_t kmin, uint32_t *words, unsigned long long *cand, uint32_t cap) {
+        return RadixParams{scores, n, k, kmin, /*hist*/ words, /*ovf_cand*/ cand, /*ovf_count*/ words + SelectWords::W_COUNT, /*ovf_cap*/ cap};
+    }
+    // ... and the selection kernel behind it: no slots, no published maxima, every candidate comes from the list, as an index into
+    // the array (the caller sets pos_to_row where that is not a local row, and the outputs per query).
+    SelectParams array_select_params(uint32_t *words, unsigned long long *cand, uint32_t cap) const {
+        SelectParams S{};
+        S.wg_cand = cand;  // (n_wg = 0: the selection still forms the address of slot 0)
+        S.ovf_cand = cand;
+        S.ovf_count = words + SelectWords::W_COUNT;
+        S.ovf_cap = cap;
+        S.k = (uint32_t)desc.k;
+        S.first_row = desc.first_row;
+        S.out_scale = 1.0f;  // the scores kernel already wrote final scores
+        S.tau_g = words + SelectWords::W_TAU;
+        S.done_count = words + SelectWords::W_DONE;
+        return S;
+    }
+    // The four histogram passes and the filter pass over R's n scores. The caller has zeroed the histogram in front.
+    static void launch_radix_passes(const RadixParams &R, uint32_t n, hipStream_t s) {
+        const uint32_t rgrid = std::max(1u, std::min(256u, (n + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
+        for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
+        hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+    }
+    // The grid of a kernel whose lanes take lane_rows rows each: enough workgroups of `threads` for `rows`, at most 8 per CU.
+    uint32_t rows_grid(uint32_t rows, uint32_t threads, uint32_t lane_rows) const {
+        return std::max(1u, std::min(std::max(1u, info.num_cus) * 8u, (uint32_t)(((uint64_t)rows + threads * lane_rows - 1u) / (threads * lane_rows))));
+    }
+    // A [rows] score array of a path's own, recorded: -inf where a row has no entry (the scores kernel never writes there).
+    hipError_t alloc_ninf_scores(float *&p) {
+        const std::vector<float> ninf(std::max<size_t>(desc.rows, 1), -std::numeric_limits<float>::infinity());
+        float *y = nullptr;
+        hipError_t e = alloc(y, ninf.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(y, ninf.data(), ninf.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) p = y;  // (*p stays NULL until the array is filled)
+        return e;
+    }
     // A sequence of grouped queries (query i: x = xs + i * cols, mask = mask + i * stride words or none; results at out_* + i *
     // out_stride, the number of real entries at out_n + i * n_stride), complete in stream order when this returns: per query the SpMV-only kernel, the reduction to groups, the radix
     // select over the groups and the selection kernel ranking the groups' representatives. No exchange set, record, verdict, carried
@@ -1125,48 +1159,25 @@ struct EngineImpl {
         G.n_nonempty = Q.d_gwords + Grouped::W_NONEMPTY;
         G.rows = desc.rows;
         G.n_groups = Q.n_groups;
-        {  // order key of min_score (the device function's host twin)
-            uint32_t u;
-            std::memcpy(&u, &desc.min_score, 4);
-            G.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        }
-        RadixParams R{};
-        R.scores = Q.d_gscore;
-        R.rows = Q.n_groups;
-        R.k = (uint32_t)desc.k;
-        R.kmin = G.kmin;
-        R.hist = Q.d_gwords;
-        R.ovf_cand = Q.d_gcand;
-        R.ovf_count = Q.d_gwords + Grouped::W_COUNT;
-        R.ovf_cap = Q.n_groups;
-        SelectParams S{};  // no slots, no published maxima: every candidate comes from the list, as a group's index
-        S.wg_cand = Q.d_gcand;  // (n_wg = 0: the selection still forms the address of slot 0)
-        S.ovf_cand = Q.d_gcand;
-        S.ovf_count = R.ovf_count;
-        S.ovf_cap = Q.n_groups;
-        S.k = (uint32_t)desc.k;
-        S.first_row = desc.first_row;
-        S.out_scale = 1.0f;  // the scores kernel already wrote final scores
-        S.tau_g = Q.d_gwords + Grouped::W_TAU;
-        S.done_count = Q.d_gwords + Grouped::W_DONE;
-        S.pos_to_row = Q.d_grow;
+        G.kmin = order_key(desc.min_score);
+        const RadixParams R = radix_params(Q.d_gscore, Q.n_groups, (uint32_t)desc.k, G.kmin, Q.d_gwords, Q.d_gcand, Q.n_groups);
+        SelectParams S = array_select_params(Q.d_gwords, Q.d_gcand, Q.n_groups);  // (a candidate is a group's index ...
+        S.pos_to_row = Q.d_grow;                                                   //  ... and stands for its representative's row)
         GroupIdsParams I{};
         I.groups = Q.d_groups;
         I.n_nonempty = G.n_nonempty;
         I.k = (uint32_t)desc.k;
         I.rows = desc.rows;
         I.first_row = desc.first_row;
-        const uint32_t best_grid = std::max(1u, std::min(std::max(1u, info.num_cus) * 8u, (uint32_t)(((uint64_t)desc.rows + GROUP_THREADS * GROUP_LANE_ROWS - 1u) / (GROUP_THREADS * GROUP_LANE_ROWS))));
+        const uint32_t best_grid = rows_grid(desc.rows, GROUP_THREADS, GROUP_LANE_ROWS);
         const uint32_t split_grid = (Q.n_groups + GROUP_THREADS - 1u) / GROUP_THREADS;
-        const uint32_t rgrid = std::max(1u, std::min(256u, (Q.n_groups + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
         for (int i = 0; i < n; ++i) {
             const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
             launch_scores(xs + (size_t)i * desc.cols, s, Q.d_gy, mask ? &F : nullptr);
-            (void)hipMemsetAsync(Q.d_gwords, 0, (Grouped::W_NONEMPTY + 1u) * 4, s);
+            (void)hipMemsetAsync(Q.d_gwords, 0, (Grouped::W_NONEMPTY + 1u) * 4, s);  // (the histogram and the non-empty-group counter)
             hipLaunchKernelGGL(group_best_kernel, dim3(best_grid), dim3(GROUP_THREADS), 0, s, G);
             hipLaunchKernelGGL(group_split_kernel, dim3(split_grid), dim3(GROUP_THREADS), 0, s, G);
-            for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
-            hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+            launch_radix_passes(R, Q.n_groups, s);
             S.out_idx = out_idx + (size_t)i * out_stride;
             S.out_val = out_val + (size_t)i * out_stride;
             hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
@@ -1181,17 +1192,13 @@ struct EngineImpl {
         After &Q = after;
         const size_t rows = std::max<size_t>(desc.rows, 1);
         if (!Q.d_ay) {
-            float *y = nullptr;
-            if (const hipError_t e = alloc(y, rows * 4)) return e;
-            const std::vector<float> ninf(rows, -std::numeric_limits<float>::infinity());  // (rows without entries are never written)
-            if (const hipError_t e = hipMemcpy(y, ninf.data(), rows * 4, hipMemcpyHostToDevice)) return e;
-            Q.d_ay = y;
+            if (const hipError_t e = alloc_ninf_scores(Q.d_ay)) return e;
         }
         if (!Q.d_acand) {
             if (const hipError_t e = alloc(Q.d_acand, rows * 8)) return e;
         }
         if (!Q.d_awords) {
-            if (const hipError_t e = alloc(Q.d_awords, (size_t)After::N_WORDS * 4, Mem::Device, 0)) return e;
+            if (const hipError_t e = alloc(Q.d_awords, (size_t)SelectWords::N_WORDS * 4, Mem::Device, 0)) return e;
         }
         if (!Q.d_aout) {
             if (const hipError_t e = alloc(Q.d_aout, (size_t)After::N_OUT * 4, Mem::Device, 0)) return e;
@@ -1214,43 +1221,20 @@ struct EngineImpl {
         A.total = Q.d_awords + After::W_TOTAL;
         A.rows = desc.rows;
         A.first_row = desc.first_row;
-        {  // order key of min_score (the device function's host twin)
-            uint32_t u;
-            std::memcpy(&u, &desc.min_score, 4);
-            A.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        }
-        RadixParams R{};
-        R.scores = Q.d_ay;
-        R.rows = desc.rows;
-        R.k = (uint32_t)desc.k;
-        R.kmin = A.kmin;
-        R.hist = Q.d_awords;
-        R.ovf_cand = Q.d_acand;
-        R.ovf_count = Q.d_awords + After::W_COUNT;
-        R.ovf_cap = desc.rows;
-        SelectParams S{};  // no slots, no published maxima: every candidate comes from the list, as a local row
-        S.wg_cand = Q.d_acand;  // (n_wg = 0: the selection still forms the address of slot 0)
-        S.ovf_cand = Q.d_acand;
-        S.ovf_count = R.ovf_count;
-        S.ovf_cap = desc.rows;
-        S.k = (uint32_t)desc.k;
-        S.first_row = desc.first_row;
-        S.out_scale = 1.0f;  // the scores kernel already wrote final scores
-        S.tau_g = Q.d_awords + After::W_TAU;
-        S.done_count = Q.d_awords + After::W_DONE;
+        A.kmin = order_key(desc.min_score);
+        const RadixParams R = radix_params(Q.d_ay, desc.rows, (uint32_t)desc.k, A.kmin, Q.d_awords, Q.d_acand, desc.rows);
+        SelectParams S = array_select_params(Q.d_awords, Q.d_acand, desc.rows);  // (a candidate is a local row)
         AfterFinishParams Z{};
         Z.total = A.total;
         Z.k = (uint32_t)desc.k;
-        const uint32_t cut_grid = std::max(1u, std::min(std::max(1u, info.num_cus) * 8u, (uint32_t)(((uint64_t)desc.rows + AFTER_THREADS * AFTER_LANE_ROWS - 1u) / (AFTER_THREADS * AFTER_LANE_ROWS))));
-        const uint32_t rgrid = std::max(1u, std::min(256u, (desc.rows + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
+        const uint32_t cut_grid = rows_grid(desc.rows, AFTER_THREADS, AFTER_LANE_ROWS);
         for (int i = 0; i < n; ++i) {
             const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
             launch_scores(xs + (size_t)i * desc.cols, s, Q.d_ay, mask ? &F : nullptr);
-            (void)hipMemsetAsync(Q.d_awords, 0, 4 * 256 * 4, s);
+            (void)hipMemsetAsync(Q.d_awords, 0, 4 * 256 * 4, s);  // (the histogram alone: after_finish_kernel zeroes W_TOTAL itself)
             A.cursor = cursors ? reinterpret_cast<const AfterCursor *>(cursors + i) : nullptr;
             hipLaunchKernelGGL(after_cut_kernel, dim3(cut_grid), dim3(AFTER_THREADS), 0, s, A);
-            for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
-            hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+            launch_radix_passes(R, desc.rows, s);
             S.out_idx = out_idx + (size_t)i * out_stride;
             S.out_val = out_val + (size_t)i * out_stride;
             hipLaunchKernelGGL(select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, S);
@@ -1302,11 +1286,7 @@ struct EngineImpl {
         R.scores = radix.d_rscores;
         R.rows = desc.rows;
         R.k = (uint32_t)desc.k;
-        {  // order key of min_score (the device function's host twin)
-            uint32_t u;
-            std::memcpy(&u, &desc.min_score, 4);
-            R.kmin = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        }
+        R.kmin = order_key(desc.min_score);
         R.hist = radix.d_rhist;
         R.ovf_cand = ex.st[0].ovf;
         R.ovf_count = ex.st[0].ovf_count;
@@ -1324,9 +1304,7 @@ struct EngineImpl {
             hipLaunchKernelGGL(partition_topk_kernel, dim3((uint32_t)desc.partitions), dim3(RADIX_THREADS), 0, s, Q);
         } else {
             (void)hipMemsetAsync(radix.d_rhist, 0, 4 * 256 * 4, s);
-            const uint32_t rgrid = std::max(1u, std::min(256u, (desc.rows + RADIX_THREADS * 4u - 1u) / (RADIX_THREADS * 4u)));
-            for (int pass = 0; pass < 4; ++pass) hipLaunchKernelGGL(radix_hist_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R, pass);
-            hipLaunchKernelGGL(radix_filter_kernel, dim3(rgrid), dim3(RADIX_THREADS), 0, s, R);
+            launch_radix_passes(R, desc.rows, s);
         }
         SelectParams S = select_params(out_idx, out_val, 0);
         S.use_gmax = 0u;  // no threshold word in this path
@@ -1371,6 +1349,24 @@ struct EngineImpl {
         if (count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
         if (!host.d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
         dev_xs = host.d_x_cur;
+        return TKSPMV_OK;
+    }
+    // use_filter of the tkspmv_run_* host forms names the mask tkspmv_set_filter installed: that mask, or NULL without use_filter.
+    int installed_mask(int32_t use_filter, const uint32_t *&mask_out, std::string &err) const {
+        if (use_filter && !filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+        mask_out = use_filter ? filter.d_filter : nullptr;
+        return TKSPMV_OK;
+    }
+    // A call's own masks are mask_stride_words apart; the installed mask, or none, serves every query of the call.
+    static size_t stride_of(const uint32_t *dev_mask, int64_t mask_stride_words) { return dev_mask ? (size_t)mask_stride_words : 0u; }
+    // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
+    // after the queries about to be enqueued did (own: they write it). Settle them now (the host waits for the engine's stream once).
+    int settle_before_owned_result(bool own, std::string &err) { return own && !trust.pending_checks.empty() ? wait_idle(err) : TKSPMV_OK; }
+    // The tail of a host form that ran the installed query vector: the host waits and looks at the verdicts, and nothing reads the
+    // staging copy of x any more. (tkspmv_run_match reads no query vector and leaves x_pending alone: it calls wait_idle itself.)
+    int finish_host_form(std::string &err) {
+        if (const int st = wait_idle(err)) return st;
+        host.x_pending = false;
         return TKSPMV_OK;
     }
     // Replaces the buffers of a scratch set that grows on demand (run_range, run_similar) by larger ones: all released, then all
@@ -1781,10 +1777,7 @@ static int choose_path(const tkspmv_desc &d, Setup &S, EngineImpl &m, std::strin
     if (m.radix.use_radix) {
         m.defer.can_defer = m.batch.can_batch = false;
         m.defer.fused = false;
-        const size_t n = std::max<size_t>(d.rows, 1);
-        HIP_TRY(m.alloc(m.radix.d_rscores, n * 4));
-        std::vector<float> ninf(n, -std::numeric_limits<float>::infinity());
-        HIP_TRY(hipMemcpy(m.radix.d_rscores, ninf.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(m.alloc_ninf_scores(m.radix.d_rscores));  // (m.desc: setup_geometry)
         HIP_TRY(m.alloc(m.radix.d_rhist, 4 * 256 * 4));
     }
     // (every streaming wave of a sequence launch owns ONE partition: an engine packed with more -- the load-only probe's
@@ -2540,14 +2533,10 @@ int Engine::enqueue_filtered(const float *dev_xs, int32_t count, const uint32_t 
     if (!dev_mask && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "no allow-mask given and none installed (tkspmv_set_filter)");
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     return enqueue_on(m, stream, true, err, [&](hipStream_t s) -> int {
-        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
-        // after the filtered queries did. Settle them now (the host waits for the engine's stream once).
-        if (!m.trust.pending_checks.empty()) {
-            if (const int st = m.wait_idle(err)) return st;
-        }
+        if (const int st = m.settle_before_owned_result(true, err)) return st;  // (whatever buffers the call names: unconditionally)
         HIP_TRY(m.order_x(dev_xs, s));
         const SequenceLists L(m, dev_xs, count, count, dev_idx, dev_val);
-        m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.filter.d_filter, dev_mask ? (size_t)mask_stride_words : 0u, L.oi.data(), L.ov.data(), count, s);
+        m.launch_filtered(L.xs.data(), dev_mask ? dev_mask : m.filter.d_filter, m.stride_of(dev_mask, mask_stride_words), L.oi.data(), L.ov.data(), count, s);
         return TKSPMV_OK;
     });
 }
@@ -2569,12 +2558,8 @@ int Engine::set_groups(const uint32_t *host_groups, uint32_t n_groups, std::stri
     Q.have_groups = false;  // (until everything below has succeeded)
     const size_t rows = std::max<size_t>(m.desc.rows, 1);
     if (!Q.d_groups) HIP_TRY(m.alloc(Q.d_groups, rows * 4));
-    if (!Q.d_gy) {
-        HIP_TRY(m.alloc(Q.d_gy, rows * 4));
-        const std::vector<float> ninf(rows, -std::numeric_limits<float>::infinity());  // (rows without entries are never written)
-        HIP_TRY(hipMemcpy(Q.d_gy, ninf.data(), rows * 4, hipMemcpyHostToDevice));
-    }
-    if (!Q.d_gwords) HIP_TRY(m.alloc(Q.d_gwords, (size_t)EngineImpl::Grouped::N_WORDS * 4, Mem::Device, 0));
+    if (!Q.d_gy) HIP_TRY(m.alloc_ninf_scores(Q.d_gy));
+    if (!Q.d_gwords) HIP_TRY(m.alloc(Q.d_gwords, (size_t)EngineImpl::SelectWords::N_WORDS * 4, Mem::Device, 0));
     if (!Q.d_gout_grp) HIP_TRY(m.alloc(Q.d_gout_grp, (size_t)m.desc.k * 4, Mem::Device, 0xFF));
     if (!Q.d_gout_n) HIP_TRY(m.alloc(Q.d_gout_n, 4, Mem::Device, 0));
     if (n_groups > Q.group_cap) {
@@ -2598,14 +2583,10 @@ int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     const bool own = dev_idx == nullptr;  // the engine-owned result pair, group ids and n: the last query wins
     return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
-        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
-        // after the grouped queries did. Settle them now (the host waits for the engine's stream once).
-        if (own && !m.trust.pending_checks.empty()) {
-            if (const int st = m.wait_idle(err)) return st;
-        }
+        if (const int st = m.settle_before_owned_result(own, err)) return st;
         HIP_TRY(m.order_x(dev_xs, s));
         const size_t k = own ? 0u : (size_t)m.desc.k;
-        m.launch_grouped(dev_xs, count, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, own ? m.host.d_out_idx : dev_idx, own ? m.host.d_out_val : dev_val,
+        m.launch_grouped(dev_xs, count, dev_mask, m.stride_of(dev_mask, mask_stride_words), own ? m.host.d_out_idx : dev_idx, own ? m.host.d_out_val : dev_val,
                          own ? m.grouped.d_gout_grp : dev_grp, k, dev_n ? dev_n : m.grouped.d_gout_n, dev_n ? 1u : 0u, s);
         return TKSPMV_OK;
     });
@@ -2613,11 +2594,10 @@ int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *
 
 int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
     EngineImpl &m = *impl_;
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
-    const int st = enqueue_grouped(nullptr, 1, use_filter ? m.filter.d_filter : nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, err);
-    if (st != TKSPMV_OK) return st;
-    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
-    m.host.x_pending = false;
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err)) return st;
+    if (const int st = enqueue_grouped(nullptr, 1, mask, 0, nullptr, nullptr, nullptr, nullptr, nullptr, err)) return st;
+    if (const int st = m.finish_host_form(err)) return st;
     const size_t k = (size_t)m.desc.k;
     uint32_t found = 0u;
     HIP_TRY(hipMemcpy(&found, m.grouped.d_gout_n, 4, hipMemcpyDeviceToHost));
@@ -2638,14 +2618,10 @@ int Engine::enqueue_after(const float *dev_xs, int32_t count, const tkspmv_curso
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     const bool own = dev_idx == nullptr;  // the engine-owned result pair: the last query wins
     return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
-        // Checks of trusted batch launches still pending under REPAIR=host: a late repair would write the engine-owned result pair
-        // after these queries did. Settle them now (the host waits for the engine's stream once).
-        if (own && !m.trust.pending_checks.empty()) {
-            if (const int st = m.wait_idle(err)) return st;
-        }
+        if (const int st = m.settle_before_owned_result(own, err)) return st;
         HIP_TRY(m.ensure_after());
         HIP_TRY(m.order_x(dev_xs, s));
-        m.launch_after(dev_xs, count, dev_cursors, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, own ? m.host.d_out_idx : dev_idx,
+        m.launch_after(dev_xs, count, dev_cursors, dev_mask, m.stride_of(dev_mask, mask_stride_words), own ? m.host.d_out_idx : dev_idx,
                        own ? m.host.d_out_val : dev_val, own ? 0u : (size_t)m.desc.k, dev_n, dev_total, dev_next, s);
         return TKSPMV_OK;
     });
@@ -2655,7 +2631,8 @@ int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t 
                       std::string &err) {
     EngineImpl &m = *impl_;
     using After = EngineImpl::After;
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err)) return st;
     if (const char *why = m.grouped_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
     if (!m.host.d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
     HIP_TRY(hipSetDevice(m.device));
@@ -2663,12 +2640,10 @@ int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t 
     uint32_t *const out = m.after.d_aout;
     // (the cursor words belong to this host form alone, and the host form before this one has waited)
     if (cursor) HIP_TRY(hipMemcpy(out + After::O_CURSOR, cursor, sizeof(tkspmv_cursor), hipMemcpyHostToDevice));
-    const int st = enqueue_after(nullptr, 1, cursor ? reinterpret_cast<const tkspmv_cursor *>(out + After::O_CURSOR) : nullptr,
-                                 use_filter ? m.filter.d_filter : nullptr, 0, nullptr, nullptr, out + After::O_N, out + After::O_TOTAL,
-                                 reinterpret_cast<tkspmv_cursor *>(out + After::O_NEXT), nullptr, err);
-    if (st != TKSPMV_OK) return st;
-    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
-    m.host.x_pending = false;
+    if (const int st = enqueue_after(nullptr, 1, cursor ? reinterpret_cast<const tkspmv_cursor *>(out + After::O_CURSOR) : nullptr, mask, 0, nullptr, nullptr,
+                                     out + After::O_N, out + After::O_TOTAL, reinterpret_cast<tkspmv_cursor *>(out + After::O_NEXT), nullptr, err))
+        return st;
+    if (const int st = m.finish_host_form(err)) return st;
     const size_t k = (size_t)m.desc.k;
     uint32_t words[After::N_OUT];
     HIP_TRY(hipMemcpy(words, out, sizeof(words), hipMemcpyDeviceToHost));
@@ -2691,7 +2666,7 @@ int Engine::enqueue_range(const float *dev_xs, int32_t count, const float *dev_t
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
         HIP_TRY(m.order_x(dev_xs, s));
-        m.launch_range(dev_xs, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_idx, dev_val, capacity, dev_counts, s);
+        m.launch_range(dev_xs, count, dev_thresholds, dev_mask, m.stride_of(dev_mask, mask_stride_words), dev_idx, dev_val, capacity, dev_counts, s);
         return TKSPMV_OK;
     });
 }
@@ -2701,7 +2676,8 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
     if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
     if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx))
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)");
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err)) return st;
     const float *installed = nullptr;
     if (const int st = m.resolve_query(installed, 1, err)) return st;
     HIP_TRY(hipSetDevice(m.device));
@@ -2711,11 +2687,10 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
         HIP_TRY(m.grow_scratch(m.range.range_cap, capacity, {{(void **)&m.range.d_range_idx, (size_t)capacity * 4}, {(void **)&m.range.d_range_val, (size_t)capacity * 4}}));
     }
     HIP_TRY(hipMemcpy(m.range.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
-    const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word), use_filter ? m.filter.d_filter : nullptr, 0,
-                                 capacity ? m.range.d_range_idx : nullptr, capacity ? m.range.d_range_val : nullptr, capacity, m.range.d_range_word + 1, nullptr, err);
-    if (st != TKSPMV_OK) return st;
-    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
-    m.host.x_pending = false;
+    if (const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word), mask, 0, capacity ? m.range.d_range_idx : nullptr,
+                                     capacity ? m.range.d_range_val : nullptr, capacity, m.range.d_range_word + 1, nullptr, err))
+        return st;
+    if (const int st = m.finish_host_form(err)) return st;
     uint32_t found = 0u;
     HIP_TRY(hipMemcpy(&found, m.range.d_range_word + 1, 4, hipMemcpyDeviceToHost));
     *count = found;
@@ -2746,7 +2721,7 @@ int Engine::enqueue_facets(const float *dev_xs, int32_t count, const float *dev_
     }
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
         HIP_TRY(m.order_x(dev_xs, s));
-        m.launch_facets(dev_xs, count, dev_thresholds, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_labels, n_bins, dev_counts, dev_best, dev_totals, s);
+        m.launch_facets(dev_xs, count, dev_thresholds, dev_mask, m.stride_of(dev_mask, mask_stride_words), dev_labels, n_bins, dev_counts, dev_best, dev_totals, s);
         return TKSPMV_OK;
     });
 }
@@ -2754,7 +2729,8 @@ int Engine::enqueue_facets(const float *dev_xs, int32_t count, const float *dev_
 int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err) {
     EngineImpl &m = *impl_;
     if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err)) return st;
     const float *installed = nullptr;
     if (const int st = m.resolve_query(installed, 1, err)) return st;
     if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no labels installed (call tkspmv_set_groups first)");
@@ -2766,11 +2742,10 @@ int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tk
         HIP_TRY(m.grow_scratch(m.range.facet_cap, n_bins, {{(void **)&m.range.d_facet_counts, (size_t)n_bins * 4}, {(void **)&m.range.d_facet_best, (size_t)n_bins * 8}}));
     }
     HIP_TRY(hipMemcpy(m.range.d_range_word + 2, &threshold, 4, hipMemcpyHostToDevice));
-    const int st = enqueue_facets(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word + 2), use_filter ? m.filter.d_filter : nullptr, 0, nullptr, 0u,
-                                  m.range.d_facet_counts, best ? m.range.d_facet_best : nullptr, m.range.d_range_word + 3, nullptr, err);
-    if (st != TKSPMV_OK) return st;
-    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
-    m.host.x_pending = false;
+    if (const int st = enqueue_facets(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word + 2), mask, 0, nullptr, 0u, m.range.d_facet_counts,
+                                      best ? m.range.d_facet_best : nullptr, m.range.d_range_word + 3, nullptr, err))
+        return st;
+    if (const int st = m.finish_host_form(err)) return st;
     uint32_t found = 0u;
     HIP_TRY(hipMemcpy(&found, m.range.d_range_word + 3, 4, hipMemcpyDeviceToHost));
     if (total) *total = found;
@@ -2789,7 +2764,7 @@ int Engine::enqueue_match(const uint32_t *dev_clauses, int64_t clause_stride_wor
                                              ">= cols, out_stride_words >= ceil(rows / 32) or 0 with count = 1)");
     if (const char *why = m.match_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
-        m.launch_match(dev_clauses, (size_t)clause_stride_words, dev_preds, count, dev_mask, dev_mask ? (size_t)mask_stride_words : 0u, dev_out,
+        m.launch_match(dev_clauses, (size_t)clause_stride_words, dev_preds, count, dev_mask, m.stride_of(dev_mask, mask_stride_words), dev_out,
                        (size_t)out_stride_words, dev_counts, s);
         return TKSPMV_OK;
     });
@@ -2799,7 +2774,8 @@ int Engine::run_match(const uint32_t *host_clauses, const tkspmv_match *pred, in
                       std::string &err) {
     EngineImpl &m = *impl_;
     if (!host_clauses || !pred) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_match (clause table and predicate given)");
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err)) return st;
     if (const char *why = m.match_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
     HIP_TRY(hipSetDevice(m.device));
     const size_t cols = m.desc.cols, words = m.mask_words();
@@ -2808,10 +2784,11 @@ int Engine::run_match(const uint32_t *host_clauses, const tkspmv_match *pred, in
     // (the scratch belongs to this host form alone, and the host form before this one has waited)
     HIP_TRY(hipMemcpy(m.match.d_match_in, host_clauses, cols * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m.match.d_match_in + cols, pred, sizeof(tkspmv_match), hipMemcpyHostToDevice));
-    const int st = enqueue_match(m.match.d_match_in, 0, reinterpret_cast<const tkspmv_match *>(m.match.d_match_in + cols), 1, use_filter ? m.filter.d_filter : nullptr, 0,
-                                 m.match.d_match_out, 0, m.match.d_match_in + cols + 4, nullptr, err);
-    if (st != TKSPMV_OK) return st;
-    if (const int st = m.wait_idle(err)) return st;  // (the host has just waited for the engine's stream)
+    if (const int st = enqueue_match(m.match.d_match_in, 0, reinterpret_cast<const tkspmv_match *>(m.match.d_match_in + cols), 1, mask, 0, m.match.d_match_out, 0,
+                                     m.match.d_match_in + cols + 4, nullptr, err))
+        return st;
+    // (no query vector was read: x_pending stays -- clearing it could free the staging copy under a query in flight on a caller's stream)
+    if (const int st = m.wait_idle(err)) return st;
     uint32_t found = 0u;
     HIP_TRY(hipMemcpy(&found, m.match.d_match_in + cols + 4, 4, hipMemcpyDeviceToHost));
     if (count) *count = found;
