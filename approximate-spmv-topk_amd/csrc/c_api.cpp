@@ -162,6 +162,17 @@ int tkspmv_run_after(tkspmv_t *h, const tkspmv_cursor *cursor, int32_t use_filte
                      tkspmv_cursor *next) {
     ENGINE_CALL(run_after(cursor, use_filter, idx, val, n, total, next, err))
 }
+int tkspmv_set_boost(tkspmv_t *h, const float *host_weight, const float *host_bias) { ENGINE_CALL(set_boost(host_weight, host_bias, err)) }
+int tkspmv_enqueue_boosted(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                           const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                           uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream) {
+    ENGINE_CALL(enqueue_boosted(dev_xs, count, dev_weight, dev_bias, boost_stride, dev_cursors, dev_mask, mask_stride_words, dev_idx, dev_val, dev_n,
+                                dev_total, dev_next, stream, err))
+}
+int tkspmv_run_boosted(tkspmv_t *h, const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total,
+                       tkspmv_cursor *next) {
+    ENGINE_CALL(run_boosted(cursor, use_filter, idx, val, n, total, next, err))
+}
 int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask,
                          int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream) {
     ENGINE_CALL(enqueue_range(dev_xs, count, dev_thresholds, dev_mask, mask_stride_words, dev_idx, dev_val, capacity, dev_counts, stream, err))

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +55,7 @@
 #include "kernels/score_rows.hpp"
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
+#include "kernels/boost_cut.hpp"
 
 namespace tkspmv {
 
@@ -524,6 +526,18 @@ struct EngineImpl {
         uint32_t *d_aout = nullptr;
         static constexpr uint32_t O_N = 0, O_TOTAL = 1, O_CURSOR = 4, O_NEXT = 8, N_OUT = 12;
     } after;
+
+    // Boosted top-k (tkspmv_enqueue_boosted; boost_cut_kernel) is the search-after path with a per-row transform of the scores fused
+    // into its cut: it runs on that path's scratch (ensure_after) and owns nothing but the boost tkspmv_set_boost installed.
+    struct Boost {
+        float *d_weight = nullptr, *d_bias = nullptr;  // [rows] each, allocated by the first tkspmv_set_boost that gives one
+        bool have_weight = false, have_bias = false;   // what the installed boost consists of (neither: none is installed)
+    } boost;
+    // The boost of a call: query i reads weight + i * stride and bias + i * stride (either may be NULL: no multiply / no add).
+    struct BoostSpec {
+        const float *weight, *bias;
+        size_t stride;
+    };
 
     // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
     // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
@@ -1210,11 +1224,14 @@ struct EngineImpl {
     // order when this returns: per query the SpMV-only kernel, the cut at the cursor, the radix select over the rows that remain, the
     // selection kernel and the page's bookkeeping. No exchange set, record, verdict, carried threshold or deferred selection is read
     // or written: the SpMV-only kernels touch none, and the selection kernel is given this path's own words. Only mat.launch_counter
-    // moves.
+    // moves. With a boost (tkspmv_enqueue_boosted) boost_cut_kernel takes the cut's place: the transform, the cut and the count in one
+    // pass; everything behind it reads the transformed scores.
     void launch_after(const float *xs, int n, const tkspmv_cursor *cursors, const uint32_t *mask, size_t stride, uint32_t *out_idx, float *out_val,
-                      size_t out_stride, uint32_t *out_n, uint32_t *out_total, tkspmv_cursor *out_next, hipStream_t s) {
+                      size_t out_stride, uint32_t *out_n, uint32_t *out_total, tkspmv_cursor *out_next, hipStream_t s, const BoostSpec *boost = nullptr) {
         using namespace after_kernels;
+        using namespace boost_kernels;
         static_assert(sizeof(AfterCursor) == sizeof(tkspmv_cursor) && sizeof(tkspmv_cursor) == 16, "the device reads tkspmv_cursor as four words");
+        static_assert(BOOST_THREADS == AFTER_THREADS && BOOST_LANE_ROWS == AFTER_LANE_ROWS, "the two cut kernels share one grid");
         const After &Q = after;
         AfterParams A{};
         A.y = Q.d_ay;
@@ -1233,7 +1250,13 @@ struct EngineImpl {
             launch_scores(xs + (size_t)i * desc.cols, s, Q.d_ay, mask ? &F : nullptr);
             (void)hipMemsetAsync(Q.d_awords, 0, 4 * 256 * 4, s);  // (the histogram alone: after_finish_kernel zeroes W_TOTAL itself)
             A.cursor = cursors ? reinterpret_cast<const AfterCursor *>(cursors + i) : nullptr;
-            hipLaunchKernelGGL(after_cut_kernel, dim3(cut_grid), dim3(AFTER_THREADS), 0, s, A);
+            if (boost) {
+                BoostParams B{A, boost->weight ? boost->weight + (size_t)i * boost->stride : nullptr, boost->bias ? boost->bias + (size_t)i * boost->stride : nullptr, 0u};
+                B.wide = ((reinterpret_cast<uintptr_t>(B.weight) | reinterpret_cast<uintptr_t>(B.bias)) & 15u) == 0u ? 1u : 0u;  // (NULL counts as aligned)
+                hipLaunchKernelGGL(boost_cut_kernel, dim3(cut_grid), dim3(BOOST_THREADS), 0, s, B);
+            } else {
+                hipLaunchKernelGGL(after_cut_kernel, dim3(cut_grid), dim3(AFTER_THREADS), 0, s, A);
+            }
             launch_radix_passes(R, desc.rows, s);
             S.out_idx = out_idx + (size_t)i * out_stride;
             S.out_val = out_val + (size_t)i * out_stride;
@@ -2608,13 +2631,19 @@ int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t 
     return TKSPMV_OK;
 }
 
-int Engine::enqueue_after(const float *dev_xs, int32_t count, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
-                          uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err) {
-    EngineImpl &m = *impl_;
-    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr))
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_after (count >= 1, mask_stride_words >= 0, dev_idx and dev_val both given or both NULL)");
+// Search-after pages, plain (boost NULL, both arrays NULL) or boosted: the argument checks, the error order and the launch are one.
+static int enqueue_pages(EngineImpl &m, const char *what, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                         bool boosted, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
+                         float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err) {
+    if (count < 1 || boost_stride < 0 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr))
+        return fail(err, TKSPMV_ERR_INVALID, std::string("bad arguments to ") + what + " (count >= 1, strides >= 0, dev_idx and dev_val both given or both NULL)");
     if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
     if (const char *why = m.grouped_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
+    EngineImpl::BoostSpec spec{dev_weight, dev_bias, (size_t)boost_stride};
+    if (boosted && !dev_weight && !dev_bias) {  // both NULL: the installed boost, one pair for every query
+        if (!m.boost.have_weight && !m.boost.have_bias) return fail(err, TKSPMV_ERR_STATE, "no boost installed (call tkspmv_set_boost first, or give dev_weight / dev_bias)");
+        spec = EngineImpl::BoostSpec{m.boost.have_weight ? m.boost.d_weight : nullptr, m.boost.have_bias ? m.boost.d_bias : nullptr, 0u};
+    }
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     const bool own = dev_idx == nullptr;  // the engine-owned result pair: the last query wins
     return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
@@ -2622,25 +2651,40 @@ int Engine::enqueue_after(const float *dev_xs, int32_t count, const tkspmv_curso
         HIP_TRY(m.ensure_after());
         HIP_TRY(m.order_x(dev_xs, s));
         m.launch_after(dev_xs, count, dev_cursors, dev_mask, m.stride_of(dev_mask, mask_stride_words), own ? m.host.d_out_idx : dev_idx,
-                       own ? m.host.d_out_val : dev_val, own ? 0u : (size_t)m.desc.k, dev_n, dev_total, dev_next, s);
+                       own ? m.host.d_out_val : dev_val, own ? 0u : (size_t)m.desc.k, dev_n, dev_total, dev_next, s, boosted ? &spec : nullptr);
         return TKSPMV_OK;
     });
 }
 
-int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
-                      std::string &err) {
-    EngineImpl &m = *impl_;
+int Engine::enqueue_after(const float *dev_xs, int32_t count, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
+                          uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err) {
+    return enqueue_pages(*impl_, "enqueue_after", dev_xs, count, nullptr, nullptr, 0, false, dev_cursors, dev_mask, mask_stride_words, dev_idx, dev_val, dev_n,
+                         dev_total, dev_next, stream, err);
+}
+
+int Engine::enqueue_boosted(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                            const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                            uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err) {
+    return enqueue_pages(*impl_, "enqueue_boosted", dev_xs, count, dev_weight, dev_bias, boost_stride, true, dev_cursors, dev_mask, mask_stride_words, dev_idx,
+                         dev_val, dev_n, dev_total, dev_next, stream, err);
+}
+
+// The host forms of the two: the installed vector, a host cursor, the installed mask (and boost); waits.
+static int run_page(EngineImpl &m, bool boosted, const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total,
+                    tkspmv_cursor *next, std::string &err) {
     using After = EngineImpl::After;
     const uint32_t *mask = nullptr;
     if (const int st = m.installed_mask(use_filter, mask, err)) return st;
     if (const char *why = m.grouped_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
     if (!m.host.d_x_cur) return fail(err, TKSPMV_ERR_STATE, "no query vector installed (call tkspmv_set_query first)");
+    if (boosted && !m.boost.have_weight && !m.boost.have_bias) return fail(err, TKSPMV_ERR_STATE, "no boost installed (call tkspmv_set_boost first)");
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(m.ensure_after());
     uint32_t *const out = m.after.d_aout;
-    // (the cursor words belong to this host form alone, and the host form before this one has waited)
+    // (the cursor words belong to these host forms alone, and the host form before this one has waited)
     if (cursor) HIP_TRY(hipMemcpy(out + After::O_CURSOR, cursor, sizeof(tkspmv_cursor), hipMemcpyHostToDevice));
-    if (const int st = enqueue_after(nullptr, 1, cursor ? reinterpret_cast<const tkspmv_cursor *>(out + After::O_CURSOR) : nullptr, mask, 0, nullptr, nullptr,
+    if (const int st = enqueue_pages(m, boosted ? "run_boosted" : "run_after", nullptr, 1, nullptr, nullptr, 0, boosted,
+                                     cursor ? reinterpret_cast<const tkspmv_cursor *>(out + After::O_CURSOR) : nullptr, mask, 0, nullptr, nullptr,
                                      out + After::O_N, out + After::O_TOTAL, reinterpret_cast<tkspmv_cursor *>(out + After::O_NEXT), nullptr, err))
         return st;
     if (const int st = m.finish_host_form(err)) return st;
@@ -2652,6 +2696,36 @@ int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t 
     if (n) *n = (int32_t)words[After::O_N];
     if (total) *total = words[After::O_TOTAL];
     if (next) std::memcpy(next, words + After::O_NEXT, sizeof(tkspmv_cursor));
+    return TKSPMV_OK;
+}
+
+int Engine::run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
+                      std::string &err) {
+    return run_page(*impl_, false, cursor, use_filter, idx, val, n, total, next, err);
+}
+
+int Engine::run_boosted(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
+                        std::string &err) {
+    return run_page(*impl_, true, cursor, use_filter, idx, val, n, total, next, err);
+}
+
+int Engine::set_boost(const float *host_weight, const float *host_bias, std::string &err) {
+    EngineImpl &m = *impl_;
+    EngineImpl::Boost &Q = m.boost;
+    for (const float *a : {host_weight, host_bias})  // checked before any device call: a bad entry installs nothing
+        for (uint32_t r = 0; a && r < m.desc.rows; ++r)
+            if (!std::isfinite(a[r]))
+                return fail(err, TKSPMV_ERR_INVALID, std::string(a == host_weight ? "weight" : "bias") + " of row " + std::to_string(r) + " is not finite");
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(hipStreamSynchronize(m.stream));  // (a boosted query enqueued earlier may still read the installed arrays)
+    Q.have_weight = Q.have_bias = false;  // (until everything below has succeeded; both NULL: removed)
+    const size_t bytes = std::max<size_t>(m.desc.rows, 1) * 4;
+    if (host_weight && !Q.d_weight) HIP_TRY(m.alloc(Q.d_weight, bytes));
+    if (host_bias && !Q.d_bias) HIP_TRY(m.alloc(Q.d_bias, bytes));
+    if (host_weight) HIP_TRY(hipMemcpy(Q.d_weight, host_weight, (size_t)m.desc.rows * 4, hipMemcpyHostToDevice));
+    if (host_bias) HIP_TRY(hipMemcpy(Q.d_bias, host_bias, (size_t)m.desc.rows * 4, hipMemcpyHostToDevice));
+    Q.have_weight = host_weight != nullptr;
+    Q.have_bias = host_bias != nullptr;
     return TKSPMV_OK;
 }
 

@@ -46,6 +46,15 @@ class Engine {
                       uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err);
     int run_after(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
                   std::string &err);
+    // Boosted top-k (boost_cut_kernel): search-after pages over s' = weight[r] * s + bias[r] (two separately rounded fp32 operations;
+    // either array may be absent), on the search-after path's scratch. set_boost installs the pair that both-NULL calls and run_boosted,
+    // the host-side counterpart of run_after, name; both NULL removes it.
+    int set_boost(const float *host_weight, const float *host_bias, std::string &err);
+    int enqueue_boosted(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                        const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                        uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err);
+    int run_boosted(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
+                    std::string &err);
     // Range queries (range_kernel): every allowed row with entries that scores >= the query's threshold, unordered; run_range is
     // the host-side counterpart (installed vector, host threshold, waits, sorts).
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,

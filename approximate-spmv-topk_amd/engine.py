@@ -259,7 +259,7 @@ class SpMV:
             self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
         return self._run_after(cursor, allow is not None)
 
-    def _run_after(self, cursor, use_filter):
+    def _run_after(self, cursor, use_filter, boosted=False):
         cur = None
         if cursor is not None:
             row, bits, state = (int(v) for v in cursor)
@@ -267,8 +267,9 @@ class SpMV:
         idx = np.zeros(self.k, dtype=np.uint32)
         val = np.zeros(self.k, dtype=np.float32)
         n, total, nxt = C.c_int32(0), C.c_uint32(0), _lib.Cursor()
-        _lib.check(_lib.lib().tkspmv_run_after(self._h, cur, int(use_filter), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                               val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), C.byref(total), C.byref(nxt)))
+        run = _lib.lib().tkspmv_run_boosted if boosted else _lib.lib().tkspmv_run_after
+        _lib.check(run(self._h, cur, int(use_filter), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                       val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), C.byref(total), C.byref(nxt)))
         return idx, val, int(n.value), int(total.value), (int(nxt.row), int(nxt.score_bits), int(nxt.state))
 
     def pages(self, vec=None, allow=None):
@@ -282,6 +283,55 @@ class SpMV:
             if cursor[2] == _lib.CURSOR_END:
                 return
             idx, val, n, _, cursor = self._run_after(cursor, allow is not None)
+
+    def set_boost(self, weight=None, bias=None):
+        """Installs the boost of boosted queries: float32 weight[r] and bias[r] for every local row r, either may be None (no
+        multiply / no add); both None removes it. The boosted score of a row is weight[r] * score + bias[r], two separately
+        rounded float32 operations (host.boost_scores restates it). An entry that is not finite raises TkspmvError(ERR_INVALID) and
+        installs nothing."""
+        arrays = []
+        for name, a in (("weight", weight), ("bias", bias)):
+            if a is not None:
+                if np.shape(a) != (self.num_rows,):
+                    raise ValueError(f"{name} has shape {np.shape(a)}, expected ({self.num_rows},)")
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            arrays.append(a)
+        _lib.check(_lib.lib().tkspmv_set_boost(self._h, *(a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None for a in arrays)))
+
+    def enqueue_boosted(self, dev_xs, count, dev_weight=0, dev_bias=0, boost_stride=0, dev_cursors=0, dev_mask=0, mask_stride=0, dev_idx=0,
+                        dev_val=0, dev_n=0, dev_total=0, dev_next=0, stream=0):
+        """enqueue_after over boosted scores: query i reads float32 dev_weight + i*boost_stride and dev_bias + i*boost_stride
+        (device arrays of rows floats by local row; the stride in floats, 0 = one pair for every query; either may be 0: no
+        multiply / no add; both 0: the boost installed by set_boost). Every other argument and the outputs are enqueue_after's,
+        read on the boosted score: the cursors' score_bits are boosted scores, and min_score applies to them. No host sync; one
+        enqueue_after or enqueue_boosted call in flight at a time (they share their scratch)."""
+        p = lambda a: C.c_void_p(int(a)) if a else None
+        _lib.check(_lib.lib().tkspmv_enqueue_boosted(self._h, p(dev_xs), int(count), p(dev_weight), p(dev_bias), int(boost_stride), p(dev_cursors),
+                                                     p(dev_mask), int(mask_stride), p(dev_idx), p(dev_val), p(dev_n), p(dev_total), p(dev_next),
+                                                     C.c_void_p(int(stream))))
+
+    def run_boosted(self, cursor=None, vec=None, allow=None, weight=None, bias=None):
+        """run_after over boosted scores: reset(vec) / set_filter(allow) if given, set_boost(weight, bias) if either is given
+        (else the boost installed before), then the k eligible rows behind `cursor` in the order of the boosted scores. Returns
+        run_after's tuple (idx, val, n, total, next); val holds boosted scores."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            a = np.asarray(allow)
+            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        if weight is not None or bias is not None:
+            self.set_boost(weight, bias)
+        return self._run_after(cursor, allow is not None, True)
+
+    def boosted_pages(self, vec=None, allow=None, weight=None, bias=None):
+        """pages() over boosted scores (arguments as in run_boosted): yields (values, indices) of each page's real entries until the
+        cursor says END. The query vector, the mask and the boost must stay installed while the generator is in use."""
+        idx, val, n, _, cursor = self.run_boosted(None, vec, allow, weight, bias)
+        while n:
+            yield val[:n], idx[:n]
+            if cursor[2] == _lib.CURSOR_END:
+                return
+            idx, val, n, _, cursor = self._run_after(cursor, allow is not None, True)
 
     def enqueue_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_idx=0, dev_val=0, capacity=0, dev_mask=0, mask_stride=0, stream=0):
         """Range queries: for query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()) every row that
@@ -600,6 +650,18 @@ def ranked_spmv(m, vec, n, k=MAX_PAGE, allow=None, **kw):
         if not vals:
             return np.empty(0, dtype=np.float32), np.empty(0, dtype=np.uint32)
         return np.concatenate(vals)[:int(n)], np.concatenate(idxs)[:int(n)]
+    finally:
+        e.close()
+
+
+def boosted_spmv(m, vec, k, weight=None, bias=None, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices) of the k rows (among the rows of `allow`, if
+    given) with the best boosted scores weight[r] * score + bias[r] (either array may be None, not both), ordered like
+    topk_spmv's result; values are boosted scores."""
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
+    try:
+        idx, val, n, _, _ = e.run_boosted(allow=allow, weight=weight, bias=bias)
+        return val[:n], idx[:n]
     finally:
         e.close()
 

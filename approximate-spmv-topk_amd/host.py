@@ -181,6 +181,38 @@ def page_after(y, present, k, cursor=None, min_score=0.0, first_row=0, allow=Non
     return idx, val, n, total, nxt
 
 
+def boost_scores(y, weight=None, bias=None):
+    """The contract of boosted top-k (SpMV.enqueue_boosted) restated in numpy: from float32 y[rows] the boosted scores
+    weight[r] * y[r] + bias[r] as two separately rounded float32 operations (either array may be None: no multiply / no add;
+    subnormal products and sums are kept, as the device keeps them). An entry of -inf (a row without entries, a masked row) stays
+    -inf whatever weight and bias say; a result that is not finite (NaN, +inf, -inf) becomes -inf: such a row is never eligible.
+    The expected page of a boosted query is page_after(boost_scores(y, weight, bias), present, ...)."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if y.ndim != 1:
+        raise ValueError("y must be a 1-D array")
+    t = y.copy()
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for a, op in ((weight, np.multiply), (bias, np.add)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.shape != y.shape:
+                    raise ValueError(f"weight and bias must have y's shape {y.shape}")
+                t = op(t, a, dtype=np.float32)
+    ninf = np.float32(-np.inf)
+    return np.where((y == ninf) | ~np.isfinite(t), ninf, t).astype(np.float32)
+
+
+def cosine_weights(m):
+    """Weights that turn the engine's dot products into cosines by row (SpMV.set_boost(weight=...) with a query of norm 1):
+    1 / ||row r||_2 of CooMatrix m, the squares summed in float64 and the result rounded once to float32; 0.0 for a row without
+    entries or of norm 0."""
+    sq = np.zeros(int(m.rows), dtype=np.float64)
+    np.add.at(sq, np.asarray(m.row, dtype=np.int64), np.asarray(m.val, dtype=np.float64) ** 2)
+    w = np.zeros(int(m.rows), dtype=np.float64)
+    np.divide(1.0, np.sqrt(sq), out=w, where=sq > 0)
+    return w.astype(np.float32)
+
+
 def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
     """The contract of facet counts (SpMV.enqueue_facets) restated in numpy, for CPU-side users and as the tests' expectation:
     from float32 scores[rows], present[rows] (the row has entries; allow[rows], if given, restricts further) and labels[rows], the

@@ -392,7 +392,8 @@ typedef struct { uint32_t row; uint32_t score_bits; uint32_t state; uint32_t res
  * tkspmv_merge_topk; the next cursor is AFTER(the last real merged entry) when the shards' totals sum to more than k, else END (a
  * shard's own dev_next is not the global one).
  * Stream contract (the grouped call's): complete in stream order on any stream; reads and writes no exchange set, record, verdict,
- * carried threshold or deferred selection; the scratch belongs to the engine, so only ONE such call may be in flight at a time. The
+ * carried threshold or deferred selection; the scratch belongs to the engine, so only ONE such call may be in flight at a time
+ * (tkspmv_enqueue_boosted runs on the same scratch: the rule covers both kinds of call together). The
  * FIRST call allocates that scratch, about 12 bytes per row (the scores and a candidate list that holds every tie at the cut).
  * Launch scheme per query: the SpMV-only kernel, one pass that cuts at the cursor and counts (after_cut_kernel), the radix select,
  * the selection kernel, one small block for n / total / next.
@@ -408,6 +409,46 @@ int tkspmv_enqueue_after(tkspmv_t *e, const float *dev_xs, int32_t count, const 
  * (any may be NULL). */
 int tkspmv_run_after(tkspmv_t *e, const tkspmv_cursor *cursor /* host, NULL = START */, int32_t use_filter,
                      uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next);
+/* Boosted top-k (a "function score"): search-after pages over a per-row transform of the score. With s the fp32 score every other
+ * path reports for LOCAL row r (weight and bias are indexed like masks and group labels),
+ *     t  = weight ? weight[r] * s : s
+ *     s' = bias   ? t + bias[r]   : t
+ * as two separately rounded fp32 operations (__fmul_rn, __fadd_rn: never one fma; fp32 subnormals are kept, in products and sums
+ * alike, on the device as in the host restatement). A row whose score is -inf -- it has no entries, or the mask excludes it --
+ * stays -inf whatever weight and bias say; a row whose s' is not finite (NaN, +inf, -inf) is not eligible. Everything else is
+ * tkspmv_enqueue_after's contract read on s': eligible = order key of s' >= order key of desc.min_score; the order = order key of s'
+ * descending, then global row id descending; a cursor's score_bits are a boosted score; n / total / next, the pads (0, 0.0f) and the
+ * row-sharded recipe (the same cursor for every shard, global ids, each shard its own slice of weight and bias) are unchanged. Hence
+ * weight = all 1.0f without a bias, and bias = all -0.0f without a weight, give tkspmv_enqueue_after's lists bit for bit (a bias
+ * of +0.0f does not: it turns a score of -0.0f into +0.0f). Uses: static priors (s + b[r]), demotions (w[r] * s), cosine instead of
+ * the dot product (w[r] = 1 / |row r|, no re-packing), exact hybrid fusion with a per-query bias (sparse score + alpha * dense
+ * score[r]: the top-k of the SUM over all rows), bottom-k (w = -1 with desc.min_score = -inf).
+ * tkspmv_set_boost installs a pair of HOST arrays of desc.rows floats each in engine-owned device memory (freed by
+ * tkspmv_destroy); either may be NULL (no multiply / no add), both NULL removes the installed boost. An entry that is not finite
+ * gives TKSPMV_ERR_INVALID and installs nothing: the boost installed before stays. The call waits for the engine's stream. */
+int tkspmv_set_boost(tkspmv_t *e, const float *host_weight, const float *host_bias);
+/* tkspmv_enqueue_after with a boost: query i reads dev_weight + i * boost_stride and dev_bias + i * boost_stride (DEVICE arrays
+ * of desc.rows floats, the stride in floats, 0 = one pair for every query; no alignment is required: 16-byte loads are used where
+ * pointer and stride allow them). One of the two may be NULL (no multiply / no add); BOTH NULL names the boost tkspmv_set_boost
+ * installed. Every other argument, dev_next == dev_cursors and the engine-owned outputs for dev_idx = dev_val = NULL included, is
+ * exactly tkspmv_enqueue_after's.
+ * Stream contract: tkspmv_enqueue_after's. The call runs on the search-after path's scratch (allocated by the first call of either
+ * kind), so "only ONE such call in flight at a time" covers tkspmv_enqueue_after and tkspmv_enqueue_boosted TOGETHER. No exchange
+ * set, record, verdict, carried threshold or deferred selection is read or written.
+ * Launch scheme per query: the SpMV-only kernel, ONE pass that transforms, cuts at the cursor and counts (boost_cut_kernel, in
+ * after_cut_kernel's place: no launch is added), the radix select, the selection kernel, one small block for n / total / next.
+ * Errors, in this order: TKSPMV_ERR_INVALID, before any device call, for a NULL engine, count < 1, a negative boost_stride or
+ * mask_stride_words, dev_idx / dev_val partly given, dev_xs = NULL with count != 1; TKSPMV_ERR_UNSUPPORTED where
+ * tkspmv_enqueue_after reports it; TKSPMV_ERR_STATE for both arrays NULL with no boost installed, or dev_xs = NULL with no vector
+ * installed. Every value type is served without a mask. Not available in range, facet and grouped queries. */
+int tkspmv_enqueue_boosted(tkspmv_t *e, const float *dev_xs, int32_t count,
+                           const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                           const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
+                           uint32_t *dev_idx, float *dev_val, uint32_t *dev_n, uint32_t *dev_total,
+                           tkspmv_cursor *dev_next, void *stream);
+/* tkspmv_run_after with the installed boost (TKSPMV_ERR_STATE if none is installed). */
+int tkspmv_run_boosted(tkspmv_t *e, const tkspmv_cursor *cursor /* host, NULL = START */, int32_t use_filter,
+                       uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next);
 /* Queries by stored row ("which rows are closest to row r?": more-like-this, de-duplication, the k-NN self-join A.A^T top-n --
  * the product the reference's CPU comparator sparse_dot_topn exists for). dev_rows[i] is a GLOBAL row id (desc.first_row + local
  * row): exactly what queries return, so results can be fed back. dev_xs + i * cols receives row i as the dense vector of cols
