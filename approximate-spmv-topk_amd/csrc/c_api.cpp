@@ -1,7 +1,9 @@
 // c_api.cpp -- extern "C" surface declared in include/tkspmv.h (plain pointers and sizes only).
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 
@@ -31,8 +33,10 @@ static int fail(int code, const std::string &msg) {
 // The score of one located row from its own packets: reduce_core (kernels/packet_math.hpp) restated lane by lane, what
 // score_rows_kernel (kernels/score_rows.hpp) runs on the device. Per packet of the run: products inside the run, +0.0f outside; every
 // slot's own ROW_END mask; the carry +0.0f in front of the first packet. Every sum and product is a separately rounded fp32 operation
-// (-ffp-contract=off), in the kernel's order.
-static float score_located_row(const HostRowView &V, const RowRun &run, const float *x) {
+// (-ffp-contract=off), in the kernel's order. product(value, column word) is the product of one slot inside the run: v * x[col] for a
+// score, a function of v alone for a row statistic (row_stats_kernel, kernels/row_stats.hpp).
+template <class Product>
+static float reduce_located_row(const HostRowView &V, const RowRun &run, Product product) {
     const uint32_t C = V.C;
     float carry = 0.0f, score = 0.0f;
     for (uint32_t pk = run.first_pkt; pk <= run.last_pkt; ++pk) {
@@ -45,7 +49,7 @@ static float score_located_row(const HostRowView &V, const RowRun &run, const fl
                 const uint32_t ss = l * C + j;
                 const uint16_t w = V.word(pk, ss);
                 const bool inside = (pk > run.first_pkt || ss >= run.first_slot) && (pk < run.last_pkt || ss <= run.last_slot);
-                p[j] = inside ? V.value(pk, ss) * x[w >> COLW_COL_SHIFT] : 0.0f;
+                p[j] = inside ? product(V.value(pk, ss), w) : 0.0f;
                 end[l][j] = (w & COLW_ROW_END) != 0;
                 if (end[l][j]) H |= 1ull << l;
             }
@@ -86,6 +90,15 @@ static float score_located_row(const HostRowView &V, const RowRun &run, const fl
         }
     }
     return score;
+}
+static float score_located_row(const HostRowView &V, const RowRun &run, const float *x) {
+    return reduce_located_row(V, run, [x](float v, uint16_t w) { return v * x[w >> COLW_COL_SHIFT]; });
+}
+// The cosine weight of a row whose squares sum to l2sq (inv_l2_of, kernels/row_stats.hpp): two separately rounded fp32 operations;
+// +0.0f where the sum is 0, +inf or NaN.
+static float inv_l2_of(float l2sq) {
+    const float w = 1.0f / std::sqrt(l2sq);
+    return (l2sq > 0.0f && l2sq < std::numeric_limits<float>::infinity()) ? w : 0.0f;
 }
 
 extern "C" {
@@ -213,6 +226,9 @@ int tkspmv_score_rows(tkspmv_t *h, const float *host_xs, int32_t count, const ui
                       float *host_scores) {
     ENGINE_CALL(score_rows(host_xs, count, host_rows, n_rows, rows_stride, host_scores, err))
 }
+int tkspmv_enqueue_row_stats(tkspmv_t *h, int32_t kind, float *dev_out, void *stream) { ENGINE_CALL(enqueue_row_stats(kind, dev_out, stream, err)) }
+int tkspmv_row_stats(tkspmv_t *h, int32_t kind, float *host_out) { ENGINE_CALL(row_stats(kind, host_out, err)) }
+int tkspmv_set_boost_cosine(tkspmv_t *h) { ENGINE_CALL(set_boost_cosine(err)) }
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
 int tkspmv_result_device(tkspmv_t *h, const uint32_t **dev_idx, const float **dev_val) {
@@ -500,6 +516,31 @@ int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint3
         scores[i] = 0.0f;  // a row without entries: a placeholder, or no packets at all
         if (locate_row(V, rows[i], pm.n_packets, (uint32_t)pm.part_first.size(), PE, run) && row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot)) != 0u)
             scores[i] = score_located_row(V, run, x);
+    }
+    return TKSPMV_OK;
+}
+
+int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
+    if (!p || !out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
+        return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix and output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
+    const PackedMatrix &pm = p->pm;
+    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
+        return fail(TKSPMV_ERR_UNSUPPORTED, "row statistics are taken from fp32 packet streams only (TKSPMV_F32)");
+    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
+    const uint32_t PE = pm.packet_entries;
+    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
+                        pm.precision == Precision::F32C12};
+    for (uint32_t r = 0; r < pm.rows; ++r) {
+        RowRun run{0u, 0u, 0u, 0u};
+        out[r] = 0.0f;  // a row without entries: a placeholder, or no packets at all
+        if (!locate_row(V, r, pm.n_packets, (uint32_t)pm.part_first.size(), PE, run) || row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot)) == 0u)
+            continue;
+        switch (kind) {
+            case TKSPMV_ROW_NNZ: out[r] = reduce_located_row(V, run, [](float, uint16_t) { return 1.0f; }); break;
+            case TKSPMV_ROW_L1: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return std::fabs(v); }); break;
+            case TKSPMV_ROW_L2SQ: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return v * v; }); break;
+            default: out[r] = inv_l2_of(reduce_located_row(V, run, [](float v, uint16_t) { return v * v; })); break;
+        }
     }
     return TKSPMV_OK;
 }

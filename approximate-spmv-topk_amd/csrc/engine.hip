@@ -53,6 +53,7 @@
 #include "kernels/match_kernel.hpp"
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
+#include "kernels/row_stats.hpp"
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
 #include "kernels/boost_cut.hpp"
@@ -109,6 +110,7 @@ typedef void (*facet_fn)(const StreamParams, const FacetParams);
 typedef void (*match_fn)(const StreamParams, const MatchParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*score_rows_fn)(const ScoreRowsParams);
+typedef void (*row_stats_fn)(const StreamParams, const RowStatsParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
 typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
@@ -120,6 +122,7 @@ struct Kernels {
     match_fn match[2] = {};    // [FILT]
     row_vectors_fn row_vectors = nullptr;
     score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
+    row_stats_fn row_stats[4] = {};      // [kind: TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2] (no x at all: likewise)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
@@ -149,6 +152,10 @@ static Kernels kernels_of(bool dbg) {
         K.match[1] = &match_kernel<C, XCOLS, QM, true, TKSPMV_MATCH_NBUF>;
         K.row_vectors = &row_vectors_kernel<C, XCOLS, QM == QM_F32C12>;
         K.score_rows = &score_rows_kernel<C, QM == QM_F32C12>;
+        K.row_stats[TKSPMV_ROW_NNZ] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_NNZ>;
+        K.row_stats[TKSPMV_ROW_L1] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L1>;
+        K.row_stats[TKSPMV_ROW_L2SQ] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L2SQ>;
+        K.row_stats[TKSPMV_ROW_INV_L2] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_INV_L2>;
     }
     if constexpr (is_batchable(F)) {
         K.batch[0] = &batch_kernel<C, XCOLS, QM, false, false>;
@@ -486,6 +493,12 @@ struct EngineImpl {
         uint32_t *d_sr_rows = nullptr;
         uint32_t sr_q_cap = 0, sr_row_cap = 0;  // queries and list entries per query the scratch holds
     } score;
+
+    // Row statistics (tkspmv_enqueue_row_stats, row_stats_kernel) touch no other group but the matrix either. The scratch of
+    // tkspmv_row_stats -- rows floats --, which allocates it on its first call.
+    struct RowStats {
+        float *d_rs_out = nullptr;  // [rows]
+    } stats;
 
     // The device words of a path with an array select of its own (d_gwords, d_awords): [4][256] histogram, zeroed per query | word 1024:
     // the path's own counter | the candidate counter | what the selection kernel zeroes behind itself (threshold word, nine tickets)
@@ -1070,6 +1083,16 @@ struct EngineImpl {
             R.scores = scores + q * (uint64_t)n_rows;
             hipLaunchKernelGGL(kern.score_rows, dim3(wgs_rows, (R.n_q + R.q_per_item - 1u) / R.q_per_item), dim3(64u * SCORE_ROWS_WAVES), 0, s, R);
         }
+    }
+    // One statistic of every local row into out[0 .. rows), complete in stream order when this returns: out is zeroed in front (rows
+    // without entries are never written by the kernel), then one pass over stream copy 0 with the scan kernels' geometry. No engine
+    // state is read or written besides the matrix.
+    void launch_row_stats(int kind, float *out, hipStream_t s) const {
+        if (desc.rows == 0u) return;
+        (void)hipMemsetAsync(out, 0, (size_t)desc.rows * 4, s);
+        if (pm.n_packets == 0u) return;
+        const RowStatsParams R{mat.d_packets, out, desc.rows};
+        hipLaunchKernelGGL(kern.row_stats[kind], dim3(grid), dim3(512), 0, s, stream_params(nullptr), R);
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -3010,6 +3033,48 @@ int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host
                                 hipMemcpyDeviceToHost));
         }
     }
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_row_stats (output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_row_stats(kind, dev_out, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::row_stats(int32_t kind, float *host_out, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to row_stats (output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    if (m.desc.rows == 0u) return TKSPMV_OK;
+    HIP_TRY(hipSetDevice(m.device));
+    if (!m.stats.d_rs_out) HIP_TRY(m.alloc(m.stats.d_rs_out, (size_t)m.desc.rows * 4));
+    // No result is read and no result buffer written, so the engine need not be settled: the wait is for this call's own launch.
+    m.launch_row_stats(kind, m.stats.d_rs_out, m.stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(hipMemcpy(host_out, m.stats.d_rs_out, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::set_boost_cosine(std::string &err) {
+    EngineImpl &m = *impl_;
+    EngineImpl::Boost &Q = m.boost;
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    HIP_TRY(hipSetDevice(m.device));
+    HIP_TRY(hipStreamSynchronize(m.stream));  // (a boosted query enqueued earlier may still read the installed arrays)
+    Q.have_weight = Q.have_bias = false;  // (until the launch below has completed; the state aimed at is set_boost(w, NULL)'s)
+    if (!Q.d_weight) HIP_TRY(m.alloc(Q.d_weight, std::max<size_t>(m.desc.rows, 1) * 4));
+    m.launch_row_stats(TKSPMV_ROW_INV_L2, Q.d_weight, m.stream);  // (the weights never visit the host; finite by construction)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    Q.have_weight = true;
     return TKSPMV_OK;
 }
 

@@ -85,6 +85,12 @@ class Engine {
                            void *stream, std::string &err);
     int score_rows(const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride, float *host_scores,
                    std::string &err);
+    // Row statistics (row_stats_kernel): one float per local row -- entry count, L1 norm, squared L2 norm or the cosine weight 1 / L2 --
+    // from one pass over the packet stream, summed in the streaming kernels' order; row_stats is the host-side counterpart (engine-owned
+    // scratch, waits); set_boost_cosine installs the cosine weights as the boost (set_boost(w, NULL)'s state) without leaving the device.
+    int enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::string &err);
+    int row_stats(int32_t kind, float *host_out, std::string &err);
+    int set_boost_cosine(std::string &err);
     // enqueue_list through the multi-query path when the engine has one (desc.multi_q), else the ordinary sequence
     int enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                            void *stream, std::string &err);

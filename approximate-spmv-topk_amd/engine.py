@@ -298,6 +298,13 @@ class SpMV:
             arrays.append(a)
         _lib.check(_lib.lib().tkspmv_set_boost(self._h, *(a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None for a in arrays)))
 
+    def set_cosine(self):
+        """Installs the cosine weights 1 / ||row r||_2 (row_stats(ROW_INV_L2)) as the boost and removes any installed bias: the state
+        of set_boost(weight=w), with w computed on the device from the matrix the engine holds -- no COO needed, so engines made by
+        from_packed have it too. With a query of norm 1, run_boosted() then returns cosines. The sums of squares are float32 in the
+        engine's own order (host.cosine_weights sums in float64: the weights can differ in the last bits)."""
+        _lib.check(_lib.lib().tkspmv_set_boost_cosine(self._h))
+
     def enqueue_boosted(self, dev_xs, count, dev_weight=0, dev_bias=0, boost_stride=0, dev_cursors=0, dev_mask=0, mask_stride=0, dev_idx=0,
                         dev_val=0, dev_n=0, dev_total=0, dev_next=0, stream=0):
         """enqueue_after over boosted scores: query i reads float32 dev_weight + i*boost_stride and dev_bias + i*boost_stride
@@ -498,6 +505,20 @@ class SpMV:
                                                     out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def enqueue_row_stats(self, kind, dev_out, stream=0):
+        """Row statistics: dev_out[r] (float32, rows of them, by LOCAL row) = one statistic of row r, kind = _lib.ROW_NNZ (stored
+        entries), ROW_L1 (sum of |v|), ROW_L2SQ (sum of v*v) or ROW_INV_L2 (the cosine weight 1/sqrt(L2SQ); 0.0 where that sum is 0,
+        inf or NaN). The sums are float32 in the order every streaming path sums a row's score in; a row without entries gives
+        +0.0. One pass over the matrix. No host sync, no engine state touched. ROW_INV_L2 or ROW_NNZ in a device array of the
+        caller's is what per-query or combined weights for enqueue_boosted(dev_weight=...) are made from."""
+        _lib.check(_lib.lib().tkspmv_enqueue_row_stats(self._h, int(kind), C.c_void_p(int(dev_out)) if dev_out else None, C.c_void_p(int(stream))))
+
+    def row_stats(self, kind):
+        """enqueue_row_stats with a host array: float32[rows] of the given kind. Waits."""
+        out = np.empty(max(self.num_rows, 1), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:self.num_rows]
+
     def rerank(self, rows, vec=None, k=None):
         """The given global row ids re-scored for one query (vec; None: the vector installed by reset()) and ordered like
         read_result -- score descending, then row descending: (values, indices). Ids outside the engine's rows are dropped; at most
@@ -661,6 +682,22 @@ def boosted_spmv(m, vec, k, weight=None, bias=None, allow=None, **kw):
     e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
     try:
         idx, val, n, _, _ = e.run_boosted(allow=allow, weight=weight, bias=bias)
+        return val[:n], idx[:n]
+    finally:
+        e.close()
+
+
+def cosine_spmv(m, vec, k, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices) of the k rows (among the rows of `allow`, if
+    given) with the largest cosine to vec, ordered like topk_spmv's result; values are cosines. vec is scaled to norm 1 (the norm
+    in float64, every entry rounded once to float32; a zero vector stays zero) and the rows' weights come from set_cosine()."""
+    v = np.asarray(vec, dtype=np.float64)
+    norm = float(np.sqrt(np.sum(v * v)))
+    x = (v / norm if norm > 0 else v).astype(np.float32)
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=x, k=k, **kw)
+    try:
+        e.set_cosine()
+        idx, val, n, _, _ = e.run_boosted(allow=allow)
         return val[:n], idx[:n]
     finally:
         e.close()

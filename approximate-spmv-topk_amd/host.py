@@ -205,12 +205,23 @@ def boost_scores(y, weight=None, bias=None):
 def cosine_weights(m):
     """Weights that turn the engine's dot products into cosines by row (SpMV.set_boost(weight=...) with a query of norm 1):
     1 / ||row r||_2 of CooMatrix m, the squares summed in float64 and the result rounded once to float32; 0.0 for a row without
-    entries or of norm 0."""
+    entries or of norm 0. The device recipe (SpMV.set_cosine, SpMV.row_stats(ROW_INV_L2)) sums in float32 in the engine's own
+    order and can differ from this one in the last bits."""
     sq = np.zeros(int(m.rows), dtype=np.float64)
     np.add.at(sq, np.asarray(m.row, dtype=np.int64), np.asarray(m.val, dtype=np.float64) ** 2)
     w = np.zeros(int(m.rows), dtype=np.float64)
     np.divide(1.0, np.sqrt(sq), out=w, where=sq > 0)
     return w.astype(np.float32)
+
+
+def inv_l2(l2sq):
+    """The finish of the ROW_INV_L2 row statistic (SpMV.row_stats, Packed.row_stats) restated in numpy, for CPU-side users and as
+    the tests' expectation: from float32 sums of squares the cosine weights float32(1) / sqrt(l2sq), two separately rounded
+    float32 operations (subnormals kept); 0.0 where l2sq is 0, inf or NaN, so every weight is finite."""
+    s = np.ascontiguousarray(l2sq, dtype=np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        w = np.divide(np.float32(1), np.sqrt(s, dtype=np.float32), dtype=np.float32)
+    return np.where((s > 0) & np.isfinite(s), w, np.float32(0)).astype(np.float32)
 
 
 def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
@@ -516,6 +527,15 @@ class Packed:
                                                            ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size),
                                                            out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def row_stats(self, kind):
+        """float32[rows]: one statistic of every row (kind: _lib.ROW_NNZ entries, ROW_L1 sum of |v|, ROW_L2SQ sum of v*v, ROW_INV_L2
+        the cosine weight 1/sqrt(L2SQ), 0.0 where that sum is 0, inf or NaN), with the bits an engine created from this packed
+        matrix reports (SpMV.row_stats): the sums are formed in the streaming kernels' order, on the host. A row without entries
+        gives +0.0. fp32 values only (TkspmvError ERR_UNSUPPORTED otherwise); ERR_INVALID for a kind outside 0..3."""
+        out = np.empty(max(int(self.info()["rows"]), 1), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_packed_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:int(self.info()["rows"])]
 
     def raw(self):
         """(packets bytes, packet_bytes, pkt_row, part_first, part_count) as numpy views/copies."""

@@ -496,6 +496,44 @@ int tkspmv_enqueue_score_rows(tkspmv_t *e, const float *dev_xs, int32_t count, c
  * 64 MiB of vectors and 16384 list entries per query on engine-owned scratch. */
 int tkspmv_score_rows(tkspmv_t *e, const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride,
                       float *host_scores);
+/* Row statistics ("how long is every row?": the norms cosine similarity and length normalisation divide by), taken from the matrix
+ * the engine already holds -- what host.cosine_weights of the Python package computes from the COO on the host, for engines that no
+ * longer have a COO (tkspmv_create_packed, a shard that dropped its slice). dev_out[r] receives one float32 for LOCAL row r
+ * (indexed like masks, group labels, weight and bias); exactly desc.rows floats are written:
+ *   TKSPMV_ROW_NNZ     the row's stored entries as the packer stored them (explicit zeros and repeated columns count), exact below
+ *                      2^24 entries per row: what tkspmv_enqueue_row_vectors reports in dev_len and tkspmv_packed_get_row in *n
+ *   TKSPMV_ROW_L1      the sum of |v| over the row's entries
+ *   TKSPMV_ROW_L2SQ    the sum of v * v, each product one separately rounded fp32 multiplication
+ *   TKSPMV_ROW_INV_L2  the cosine weight 1.0f / sqrt(L2SQ): two separately rounded IEEE fp32 operations, subnormals kept; +0.0f where
+ *                      L2SQ is 0, +inf or NaN, so every weight is finite
+ * The sums are formed in the order every streaming path sums a row's score in (in-lane segmented sums, the clipped scan over the 64
+ * lanes, the packet carry): a statistic is, bit for bit, the score the row would get if every product were |v| or v * v, so it is
+ * reproducible and tkspmv_packed_row_stats restates it on the host. A row without entries gives +0.0f for every kind.
+ * desc.min_score, the installed filter and the installed query play no part. One pass over stream copy 0 of the matrix
+ * (row_stats_kernel), with one 4-byte store per row behind a memset of dev_out on the same stream. Asynchronous, complete in stream
+ * order on any stream (NULL: the engine's); reads and writes no engine state, so it may be mixed freely with the other calls, as
+ * tkspmv_enqueue_range may. With desc.rows = 0 the call succeeds and writes nothing.
+ * Per-query or combined weights: take TKSPMV_ROW_INV_L2 or TKSPMV_ROW_NNZ into a device array of your own, compute what you need
+ * there and pass it as dev_weight to tkspmv_enqueue_boosted -- pivoted length normalisation, for one, is
+ * weight[r] = 1 / (1 - b + b * nnz[r] / avg) with avg the mean of nnz.
+ * Errors: TKSPMV_ERR_INVALID (checked before any device call) for a NULL engine, a NULL dev_out or a kind outside 0 .. 3;
+ * TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_row_vectors reports it (a packet stream that is not fp32, an engine that does
+ * not hold the packets). The approximate per-partition engines ARE served. */
+#define TKSPMV_ROW_NNZ 0
+#define TKSPMV_ROW_L1 1
+#define TKSPMV_ROW_L2SQ 2
+#define TKSPMV_ROW_INV_L2 3
+int tkspmv_enqueue_row_stats(tkspmv_t *e, int32_t kind, float *dev_out /* [rows] */, void *stream);
+/* The same into a host array of desc.rows floats, on engine-owned scratch of that size (allocated by the first call); waits for its
+ * own launch only. */
+int tkspmv_row_stats(tkspmv_t *e, int32_t kind, float *host_out /* [rows] */);
+/* Cosine instead of the dot product without the COO: installs weight = TKSPMV_ROW_INV_L2 as the engine's boost and removes any
+ * installed bias -- the state tkspmv_set_boost(e, w, NULL) leaves, with w computed on the device (it never visits the host; every
+ * entry is finite by construction, so nothing is checked). With a query of norm 1, tkspmv_run_boosted / tkspmv_enqueue_boosted with
+ * both arrays NULL then return cosines. Like tkspmv_set_boost the call waits for the engine's stream first, allocates the weight
+ * array on first use, and the boost counts as installed only once the launch has completed without error. Errors:
+ * TKSPMV_ERR_INVALID for a NULL engine; TKSPMV_ERR_UNSUPPORTED where tkspmv_enqueue_row_stats reports it. */
+int tkspmv_set_boost_cosine(tkspmv_t *e);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
@@ -710,6 +748,11 @@ int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, f
  * without entries scores +0.0f. No GPU needed. TKSPMV_ERR_INVALID for a NULL argument, n_rows < 1 or a row >= rows (nothing is
  * written then), TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32. */
 int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint32_t *rows, int32_t n_rows, float *scores);
+/* One statistic (TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2) of EVERY row of a packed matrix: out[r], rows floats, with the bits an engine
+ * created from this packed matrix reports (tkspmv_enqueue_row_stats): the lookup and the restated arithmetic of
+ * tkspmv_packed_score_rows, with each product replaced by 1, |v| or v * v. No GPU needed. TKSPMV_ERR_INVALID for a NULL argument or
+ * a kind outside 0 .. 3, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
+int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out /* [rows] */);
 void tkspmv_packed_free(tkspmv_packed *p);
 /* The DEVICE packer (what tkspmv_create uses by default): packs desc's COO with HIP kernels on desc->device
  * and copies the result back into a tkspmv_packed, so that it can be compared byte for byte with tkspmv_pack's
