@@ -1,4 +1,5 @@
 // c_api.cpp -- extern "C" surface declared in include/tkspmv.h (plain pointers and sizes only).
+#include <algorithm>
 #include <cstdlib>
 #include <chrono>
 #include <cmath>
@@ -6,6 +7,7 @@
 #include <limits>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/tkspmv.h"
 #include "device_pack.hpp"
@@ -229,6 +231,11 @@ int tkspmv_score_rows(tkspmv_t *h, const float *host_xs, int32_t count, const ui
 int tkspmv_enqueue_row_stats(tkspmv_t *h, int32_t kind, float *dev_out, void *stream) { ENGINE_CALL(enqueue_row_stats(kind, dev_out, stream, err)) }
 int tkspmv_row_stats(tkspmv_t *h, int32_t kind, float *host_out) { ENGINE_CALL(row_stats(kind, host_out, err)) }
 int tkspmv_set_boost_cosine(tkspmv_t *h) { ENGINE_CALL(set_boost_cosine(err)) }
+int tkspmv_enqueue_col_stats(tkspmv_t *h, int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
+                             void *stream) {
+    ENGINE_CALL(enqueue_col_stats(kind, count, dev_mask, mask_stride_words, dev_out, out_stride_words, stream, err))
+}
+int tkspmv_col_stats(tkspmv_t *h, int32_t kind, int32_t use_filter, void *host_out) { ENGINE_CALL(col_stats(kind, use_filter, host_out, err)) }
 int tkspmv_synchronize(tkspmv_t *h) { ENGINE_CALL(synchronize(err)) }
 int tkspmv_read(tkspmv_t *h, uint32_t *idx, float *val, int32_t *n) { ENGINE_CALL(read(idx, val, n, err)) }
 int tkspmv_result_device(tkspmv_t *h, const uint32_t **dev_idx, const float **dev_val) {
@@ -540,6 +547,64 @@ int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
             case TKSPMV_ROW_L1: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return std::fabs(v); }); break;
             case TKSPMV_ROW_L2SQ: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return v * v; }); break;
             default: out[r] = inv_l2_of(reduce_located_row(V, run, [](float v, uint16_t) { return v * v; })); break;
+        }
+    }
+    return TKSPMV_OK;
+}
+
+// col_stats_kernel (kernels/col_stats.hpp) restated as a walk over the stream, from what the device has: the packets, pkt_row and the
+// partition table. Per partition: its last row end is looked for from its last packet backwards; the slots up to it, in stream order,
+// are its entries -- what lies behind is padding --, a SKIP slot is the placeholder of an empty row, and the row of a slot is the row of
+// the partition's first packet plus the row ends in front of it. MAX / MIN compare order keys (order_key, kernels/common.hpp).
+int tkspmv_packed_col_stats(const tkspmv_packed *p, int32_t kind, const uint32_t *mask, void *out) {
+    if (!p || !out || kind < TKSPMV_COL_NNZ || kind > TKSPMV_COL_MIN)
+        return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix and output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)");
+    const PackedMatrix &pm = p->pm;
+    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
+        return fail(TKSPMV_ERR_UNSUPPORTED, "column statistics are taken from fp32 packet streams only (TKSPMV_F32)");
+    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
+    const uint32_t PE = pm.packet_entries;
+    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
+                        pm.precision == Precision::F32C12};
+    const auto order_key = [](uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
+    const uint32_t negate = kind == TKSPMV_COL_MIN ? 0x80000000u : 0u;
+    std::vector<uint32_t> acc(pm.cols, 0u);  // counts, or order keys (0: no counted entry)
+    for (size_t q = 0; q < pm.part_first.size(); ++q) {
+        const uint32_t f0 = pm.part_first[q];
+        uint32_t n = 0u, last_slot = 0u;
+        for (uint32_t k = pm.part_count[q]; k > 0u; --k)
+            if (V.last_end(f0 + k - 1u, last_slot)) {
+                n = k;
+                break;
+            }
+        uint32_t r = n ? pm.pkt_row[f0] : 0u;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t lim = k + 1u == n ? last_slot : PE - 1u;
+            for (uint32_t ss = 0; ss <= lim; ++ss) {
+                const uint16_t w = V.word(f0 + k, ss);
+                const uint32_t c = (uint32_t)(w >> COLW_COL_SHIFT);
+                const bool allowed = !mask || (r < pm.rows && ((mask[r >> 5] >> (r & 31u)) & 1u));
+                if (!(w & COLW_SKIP) && allowed && c < pm.cols) {
+                    if (kind == TKSPMV_COL_NNZ) {
+                        ++acc[c];
+                    } else {
+                        uint32_t bits;
+                        const float v = V.value(f0 + k, ss);
+                        std::memcpy(&bits, &v, 4);
+                        acc[c] = std::max(acc[c], order_key(bits ^ negate));
+                    }
+                }
+                if (w & COLW_ROW_END) ++r;
+            }
+        }
+    }
+    uint32_t *const o = static_cast<uint32_t *>(out);
+    for (uint32_t c = 0; c < pm.cols; ++c) {
+        if (kind == TKSPMV_COL_NNZ) {
+            o[c] = acc[c];
+        } else {  // key_to_float; key 0: -inf; then the negation of MIN undone
+            const uint32_t k = acc[c];
+            o[c] = (k == 0u ? 0xFF800000u : ((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k)) ^ negate;
         }
     }
     return TKSPMV_OK;

@@ -54,6 +54,7 @@
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
 #include "kernels/row_stats.hpp"
+#include "kernels/col_stats.hpp"
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
 #include "kernels/boost_cut.hpp"
@@ -111,6 +112,7 @@ typedef void (*match_fn)(const StreamParams, const MatchParams);
 typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*row_stats_fn)(const StreamParams, const RowStatsParams);
+typedef void (*col_stats_fn)(const StreamParams, const ColStatsParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
 typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
@@ -123,6 +125,7 @@ struct Kernels {
     row_vectors_fn row_vectors = nullptr;
     score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
     row_stats_fn row_stats[4] = {};      // [kind: TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2] (no x at all: likewise)
+    col_stats_fn col_stats[2][2] = {};   // [EXT: TKSPMV_COL_MAX / _MIN][FILT]
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
@@ -156,6 +159,10 @@ static Kernels kernels_of(bool dbg) {
         K.row_stats[TKSPMV_ROW_L1] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L1>;
         K.row_stats[TKSPMV_ROW_L2SQ] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L2SQ>;
         K.row_stats[TKSPMV_ROW_INV_L2] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_INV_L2>;
+        K.col_stats[0][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, false>;
+        K.col_stats[0][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, true>;
+        K.col_stats[1][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, false>;
+        K.col_stats[1][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, true>;
     }
     if constexpr (is_batchable(F)) {
         K.batch[0] = &batch_kernel<C, XCOLS, QM, false, false>;
@@ -499,6 +506,13 @@ struct EngineImpl {
     struct RowStats {
         float *d_rs_out = nullptr;  // [rows]
     } stats;
+
+    // Column statistics (tkspmv_enqueue_col_stats, col_stats_kernel) likewise. The scratch of tkspmv_col_stats -- cols words --, which
+    // allocates it on its first call.
+    struct ColStats {
+        static constexpr int COL_STATS_MAX = 32;  // sets per launch
+        uint32_t *d_cs_out = nullptr;  // [cols]
+    } cstats;
 
     // The device words of a path with an array select of its own (d_gwords, d_awords): [4][256] histogram, zeroed per query | word 1024:
     // the path's own counter | the candidate counter | what the selection kernel zeroes behind itself (threshold word, nine tickets)
@@ -1093,6 +1107,39 @@ struct EngineImpl {
         if (pm.n_packets == 0u) return;
         const RowStatsParams R{mat.d_packets, out, desc.rows};
         hipLaunchKernelGGL(kern.row_stats[kind], dim3(grid), dim3(512), 0, s, stream_params(nullptr), R);
+    }
+    // Why column statistics are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask). Served where
+    // row statistics are; among the rows of a mask, where filtered queries are (match_unsupported's rule).
+    const char *col_stats_unsupported(bool with_mask) const {
+        if (const char *why = row_vectors_unsupported()) return why;
+        return with_mask ? filter_unsupported() : nullptr;
+    }
+    // One statistic of every column over n sets of rows (set i: the rows of mask + i * mstride words, or all rows without a mask; result
+    // at out + i * ostride words, cols of them), complete in stream order when this returns: the outputs are zeroed in front -- the sets'
+    // own words only --, then launches of up to COL_STATS_MAX sets whose workgroups add to / raise the words, then for MAX / MIN one
+    // closing launch that turns order keys into floats. No engine state is read or written besides the matrix: the stream copies
+    // rotate with the set's number in THIS call.
+    void launch_col_stats(int kind, int n, const uint32_t *mask, size_t mstride, uint32_t *out, size_t ostride, hipStream_t s) const {
+        const size_t cols = desc.cols;
+        if (cols == 0u) return;
+        if (n == 1 || ostride == cols) (void)hipMemsetAsync(out, 0, (size_t)n * cols * 4, s);
+        else (void)hipMemset2DAsync(out, ostride * 4, 0, cols * 4, (size_t)n, s);
+        const bool ext = kind != TKSPMV_COL_NNZ;
+        const uint32_t negate = kind == TKSPMV_COL_MIN ? 0x80000000u : 0u;
+        if (pm.n_packets != 0u) {
+            ColStatsParams R{};
+            R.out_stride = ostride;
+            R.negate = negate;
+            R.args_tag = COL_STATS_ARGS_TAG;
+            launch_scan(R, kern.col_stats[ext][mask != nullptr], stream_params(nullptr), n, ColStats::COL_STATS_MAX, mstride, s, [&](int i, int) {
+                R.mask = mask ? mask + (size_t)i * mstride : nullptr;
+                R.out = out + (size_t)i * ostride;
+            });
+        }
+        if (ext) {
+            const uint32_t cgrid = (uint32_t)std::min<size_t>(((size_t)n * cols + 255u) / 256u, 16384u);
+            hipLaunchKernelGGL(col_stats_close_kernel, dim3(cgrid), dim3(256), 0, s, out, (uint64_t)ostride, (uint32_t)cols, (uint32_t)n, negate);
+        }
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -3060,6 +3107,37 @@ int Engine::row_stats(int32_t kind, float *host_out, std::string &err) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(hipMemcpy(host_out, m.stats.d_rs_out, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_col_stats(int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
+                              void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_out || kind < TKSPMV_COL_NNZ || kind > TKSPMV_COL_MIN || count < 1 || (!dev_mask && count != 1) || mask_stride_words < 0 || out_stride_words < 0 ||
+        (count > 1 && out_stride_words < (int64_t)m.desc.cols))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_col_stats (output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN, count >= 1, count = 1 without "
+                                             "masks, strides >= 0, out_stride_words >= cols with count > 1)");
+    if (const char *why = m.col_stats_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("column statistics: ") + why);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_col_stats(kind, count, dev_mask, m.stride_of(dev_mask, mask_stride_words), static_cast<uint32_t *>(dev_out), (size_t)out_stride_words, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::col_stats(int32_t kind, int32_t use_filter, void *host_out, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_out || kind < TKSPMV_COL_NNZ || kind > TKSPMV_COL_MIN)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to col_stats (output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)");
+    if (const char *why = m.col_stats_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("column statistics: ") + why);
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_STATE, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    if (m.desc.cols == 0u) return TKSPMV_OK;
+    HIP_TRY(hipSetDevice(m.device));
+    if (!m.cstats.d_cs_out) HIP_TRY(m.alloc(m.cstats.d_cs_out, (size_t)m.desc.cols * 4));
+    // No result is read and no result buffer written, so the engine need not be settled: the wait is for this call's own launch.
+    m.launch_col_stats(kind, 1, use_filter ? m.filter.d_filter : nullptr, 0u, m.cstats.d_cs_out, 0u, m.stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(hipMemcpy(host_out, m.cstats.d_cs_out, (size_t)m.desc.cols * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 

@@ -91,6 +91,12 @@ class Engine {
     int enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::string &err);
     int row_stats(int32_t kind, float *host_out, std::string &err);
     int set_boost_cosine(std::string &err);
+    // Column statistics (col_stats_kernel): one word per column and set of rows -- the number of stored entries (uint32) or the largest /
+    // smallest stored value (float32) --, a set being all rows or the rows of an allow-mask; exact whatever the order of the atomics.
+    // col_stats is the host-side counterpart (engine-owned scratch, waits; use_filter: among the rows of the installed mask).
+    int enqueue_col_stats(int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
+                          void *stream, std::string &err);
+    int col_stats(int32_t kind, int32_t use_filter, void *host_out, std::string &err);
     // enqueue_list through the multi-query path when the engine has one (desc.multi_q), else the ordinary sequence
     int enqueue_multi_list(const float *const *dev_xs, uint32_t *const *dev_idx, float *const *dev_val, int32_t count,
                            void *stream, std::string &err);

@@ -519,6 +519,25 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:self.num_rows]
 
+    def enqueue_col_stats(self, kind, out, masks=None, mask_stride=0, out_stride=0, stream=None, count=1):
+        """Column statistics: one 4-byte word per column and set of rows into device memory at `out` -- kind = _lib.COL_NNZ (uint32:
+        the stored entries of the column; explicit zeros and a column repeated within a row count), COL_MAX / COL_MIN (float32: the
+        largest / smallest stored value, -inf / +inf for a column without an entry). masks = None: one set, all rows. Else `count`
+        sets, set i the rows of the allow-mask at masks + i*mask_stride words (row_mask() words by LOCAL row; stride 0: the same mask),
+        written at out + i*out_stride words (>= cols when count > 1). Exact and bit-reproducible; one pass over the matrix per set.
+        No host sync, no engine state touched."""
+        p = lambda a: C.c_void_p(int(a)) if a else None
+        _lib.check(_lib.lib().tkspmv_enqueue_col_stats(self._h, int(kind), int(count), p(masks), int(mask_stride), p(out), int(out_stride),
+                                                       C.c_void_p(int(stream or 0))))
+
+    def col_stats(self, kind, use_filter=False):
+        """enqueue_col_stats with a host array: uint32[cols] (COL_NNZ) or float32[cols] (COL_MAX, COL_MIN) over all rows, or with
+        use_filter among the rows of the mask set_filter() installed. Waits."""
+        out = np.empty(max(self.num_cols, 1), dtype=np.uint32)
+        _lib.check(_lib.lib().tkspmv_col_stats(self._h, int(kind), int(bool(use_filter)), out.ctypes.data_as(C.c_void_p)))
+        out = out[:self.num_cols]
+        return out if int(kind) == _lib.COL_NNZ else out.view(np.float32)
+
     def rerank(self, rows, vec=None, k=None):
         """The given global row ids re-scored for one query (vec; None: the vector installed by reset()) and ordered like
         read_result -- score descending, then row descending: (values, indices). Ids outside the engine's rows are dropped; at most

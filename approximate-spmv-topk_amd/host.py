@@ -337,6 +337,61 @@ def match_rows(row, col, rows, clauses, pred, allow=None):
     return ok
 
 
+def col_stats(m, kind, allow=None):
+    """The contract of column statistics (SpMV.enqueue_col_stats) restated in numpy from the COO alone, for CPU-side users and as
+    the tests' expectation: for CooMatrix m one word per column over the entries whose row allow[rows] (bool, if given) allows --
+    kind _lib.COL_NNZ: uint32, the number of entries stored in the column (explicit zeros, negative values and a column repeated
+    within a row all count; 0 for a column without one); COL_MAX / COL_MIN: float32, the largest / smallest value in the engine's
+    total order of floats (order_key: -0.0 < +0.0), -inf / +inf for a column without an entry."""
+    kind, cols, rows = int(kind), int(m.cols), int(m.rows)
+    if kind not in (_lib.COL_NNZ, _lib.COL_MAX, _lib.COL_MIN):
+        raise ValueError("kind must be COL_NNZ, COL_MAX or COL_MIN")
+    c = np.asarray(m.col).astype(np.int64).ravel()
+    v = np.ascontiguousarray(m.val, dtype=np.float32).ravel()
+    if allow is not None:
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.shape != (rows,):
+            raise ValueError(f"allow must be a bool array of shape ({rows},)")
+        keep = a[np.asarray(m.row).astype(np.int64).ravel()]
+        c, v = c[keep], v[keep]
+    if kind == _lib.COL_NNZ:
+        return np.bincount(c, minlength=cols).astype(np.uint32)
+    negate = np.uint32(0x80000000 if kind == _lib.COL_MIN else 0)  # the smallest value is the largest of the negated ones
+    u = v.view(np.uint32) ^ negate
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)  # the engine's order_key
+    best = np.zeros(cols, dtype=np.uint32)  # (0: no entry -- the key of no finite or infinite float)
+    np.maximum.at(best, c, key)
+    bits = np.where(best & np.uint32(0x80000000), best & np.uint32(0x7FFFFFFF), ~best).astype(np.uint32)  # order_key's inverse
+    bits = np.where(best == 0, np.uint32(0xFF800000), bits) ^ negate
+    return bits.astype(np.uint32).view(np.float32)
+
+
+def idf_weights(df, n_rows, scheme="bm25"):
+    """Inverse document frequency weights from document frequencies df[cols] (col_stats(COL_NNZ) of a matrix without repeated
+    columns) and the number of rows n: scheme "bm25" is log(1 + (n - df + 0.5) / (df + 0.5)), "smooth" is log((1 + n) / (1 + df)) + 1;
+    computed in float64, returned as float32, finite for df = 0."""
+    d = np.asarray(df, dtype=np.float64)
+    n = float(n_rows)
+    if scheme == "bm25":
+        w = np.log1p((n - d + 0.5) / (d + 0.5))
+    elif scheme == "smooth":
+        w = np.log((1.0 + n) / (1.0 + d)) + 1.0
+    else:
+        raise ValueError('scheme must be "bm25" or "smooth"')
+    return w.astype(np.float32)
+
+
+def score_bound(x, cmax, cmin):
+    """An upper bound of every row's score x . row from the columns' extremes (col_stats COL_MAX / COL_MIN): the sum over the
+    columns of max(0, x[c] * cmax[c], x[c] * cmin[c]) in float64; a column without entries (cmax = -inf) contributes 0. Holds for
+    matrices whose rows do not repeat a column."""
+    xv = np.asarray(x, dtype=np.float64)
+    hi, lo = np.asarray(cmax, dtype=np.float64), np.asarray(cmin, dtype=np.float64)
+    used = np.isfinite(hi) & np.isfinite(lo)
+    hi, lo = np.where(used, hi, 0.0), np.where(used, lo, 0.0)
+    return float(np.sum(np.maximum(0.0, np.maximum(xv * hi, xv * lo))))
+
+
 def generate_matrix(rows, cols, avg_nnz, distribution="gamma", seed=1):
     dist = {"uniform": 0, "gamma": 1}[distribution]
     c = _lib.Coo()
@@ -536,6 +591,24 @@ class Packed:
         out = np.empty(max(int(self.info()["rows"]), 1), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_packed_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:int(self.info()["rows"])]
+
+    def col_stats(self, kind, allow=None):
+        """uint32[cols] (kind _lib.COL_NNZ) or float32[cols] (COL_MAX, COL_MIN): one statistic of every column over all rows, or over
+        the rows allow (a bool array of length rows, or row_mask() words) allows, with the bits an engine created from this packed
+        matrix reports (SpMV.col_stats): a walk over the packet stream, placeholders and padding dropped. fp32 values only
+        (TkspmvError ERR_UNSUPPORTED otherwise); ERR_INVALID for a kind outside 0..2."""
+        rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
+        words = None
+        if allow is not None:
+            a = np.asarray(allow)
+            words = np.ascontiguousarray(row_mask(rows, a) if a.dtype == np.bool_ else a, dtype=np.uint32)
+            if words.shape != (max(1, (rows + 31) // 32),):
+                raise ValueError("allow must be bool[rows] or ceil(rows / 32) mask words")
+        out = np.empty(max(cols, 1), dtype=np.uint32)
+        _lib.check(_lib.lib().tkspmv_packed_col_stats(self._h, int(kind), words.ctypes.data_as(C.POINTER(C.c_uint32)) if words is not None else None,
+                                                      out.ctypes.data_as(C.c_void_p)))
+        out = out[:cols]
+        return out if int(kind) == _lib.COL_NNZ else out.view(np.float32)
 
     def raw(self):
         """(packets bytes, packet_bytes, pkt_row, part_first, part_count) as numpy views/copies."""

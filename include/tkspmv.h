@@ -534,6 +534,42 @@ int tkspmv_row_stats(tkspmv_t *e, int32_t kind, float *host_out /* [rows] */);
  * array on first use, and the boost counts as installed only once the launch has completed without error. Errors:
  * TKSPMV_ERR_INVALID for a NULL engine; TKSPMV_ERR_UNSUPPORTED where tkspmv_enqueue_row_stats reports it. */
 int tkspmv_set_boost_cosine(tkspmv_t *e);
+/* Column statistics ("how many rows carry this term, how large do its values get?": what IDF / BM25 query weights, score upper
+ * bounds -- the sum over c of max(0, x[c] * max[c], x[c] * min[c]) bounds every row's score -- and significant-terms counts are made
+ * of), taken from the matrix the engine already holds: np.bincount(col) without a COO, and in ONE pass what tkspmv_enqueue_match
+ * answers with one pass per single-column predicate. One 4-byte word per column, desc.cols of them per SET; a set is all rows
+ * (dev_mask = NULL, count must be 1) or the rows of one allow-mask (set i: dev_mask + i * mask_stride_words, indexed by LOCAL row like
+ * every mask; stride 0: one mask for all sets). Set i's words are written at dev_out + i * out_stride_words words (out_stride_words
+ * >= cols when count > 1; the words between the sets are not touched):
+ *   TKSPMV_COL_NNZ  uint32   the number of counted entries stored in column c; 0 for a column without one
+ *   TKSPMV_COL_MAX  float32  the largest counted value; -inf for a column without a counted entry
+ *   TKSPMV_COL_MIN  float32  the smallest counted value; +inf for a column without a counted entry
+ * An entry is COUNTED when it is an entry of the COO as the packer stored it -- explicit zeros, negative values and a column repeated
+ * within a row all count, the convention of TKSPMV_ROW_NNZ --, that is: not the placeholder of an empty row and not the padding behind
+ * a partition's last row, and when its row is allowed by the set's mask, if the set has one.
+ * Document frequency: COL_NNZ[c] equals the number of rows that carry column c -- the count tkspmv_enqueue_match reports for the
+ * single-column clause {c} -- exactly when no row repeats column c; otherwise it is larger by the repeats.
+ * Values compare in the engine's total order of scores (-0.0 < +0.0), so MAX / MIN are functions of the multiset of counted values;
+ * NaNs compare wherever that order puts them. Integer add and max are associative and commutative: all three kinds are exact and
+ * bit-reproducible whatever the launch geometry and the order of the atomics, and tkspmv_packed_col_stats restates them on the host.
+ * desc.min_score, the installed query, the boost and the engine's result pair play no part. One pass over the matrix per set
+ * (col_stats_kernel; up to 32 sets per launch, set i on stream copy i % stream_replicas; NNZ reads the column plane only) behind a
+ * memset of the sets' words on the same stream, and for MAX / MIN one small closing launch. Asynchronous, complete in stream order on
+ * any stream (NULL: the engine's); reads and writes no engine state, so it may be mixed freely with the other calls, as
+ * tkspmv_enqueue_range may. Column SUMS are not offered: a float sum through atomics depends on their order.
+ * Errors: TKSPMV_ERR_INVALID (checked first, before any device call) for a NULL engine, a NULL dev_out, a kind outside 0 .. 2,
+ * count < 1, a NULL mask with count != 1, a negative stride, out_stride_words < cols with count > 1; TKSPMV_ERR_UNSUPPORTED where
+ * tkspmv_enqueue_row_stats reports it (a packet stream that is not fp32), and with a mask where tkspmv_enqueue_filtered reports it
+ * (the approximate per-partition engines are served without a mask only). */
+#define TKSPMV_COL_NNZ 0
+#define TKSPMV_COL_MAX 1
+#define TKSPMV_COL_MIN 2
+int tkspmv_enqueue_col_stats(tkspmv_t *e, int32_t kind, int32_t count, const uint32_t *dev_mask /* NULL: all rows, count must be 1 */,
+                             int64_t mask_stride_words, void *dev_out /* [count] sets of cols words */, int64_t out_stride_words, void *stream);
+/* One set into a host array of desc.cols words, on engine-owned scratch of that size (allocated by the first call), launched on the
+ * engine's stream; waits for its own launch only. use_filter != 0: among the rows of the mask tkspmv_set_filter installed
+ * (TKSPMV_ERR_STATE if none is installed). */
+int tkspmv_col_stats(tkspmv_t *e, int32_t kind, int32_t use_filter, void *host_out /* [cols] */);
 /* Several queries per pass over the matrix (an extension: the reference streams its matrix once per
  * query vector, host_spmv_bscsr.cpp:602-622). Same arguments and result contract as tkspmv_enqueue_batch. Needs
  * desc.multi_q != 0 at create time: info.multi_q queries share every chunk of the wave-sliced ELL copy of the matrix that
@@ -753,6 +789,12 @@ int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint3
  * tkspmv_packed_score_rows, with each product replaced by 1, |v| or v * v. No GPU needed. TKSPMV_ERR_INVALID for a NULL argument or
  * a kind outside 0 .. 3, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
 int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out /* [rows] */);
+/* One column statistic (TKSPMV_COL_NNZ .. TKSPMV_COL_MIN) of a packed matrix over all rows (mask = NULL) or the rows of an allow-mask
+ * of ceil(rows / 32) words: out[c], cols words, with the bits an engine created from this packed matrix reports
+ * (tkspmv_enqueue_col_stats): a plain walk over the packet stream, so it works on a loaded .tkspmv file with no COO. No GPU needed.
+ * TKSPMV_ERR_INVALID for a NULL matrix or output or a kind outside 0 .. 2, TKSPMV_ERR_UNSUPPORTED for value types other than
+ * TKSPMV_F32; a rejected call writes nothing. */
+int tkspmv_packed_col_stats(const tkspmv_packed *p, int32_t kind, const uint32_t *mask /* NULL: all rows */, void *out /* [cols] */);
 void tkspmv_packed_free(tkspmv_packed *p);
 /* The DEVICE packer (what tkspmv_create uses by default): packs desc's COO with HIP kernels on desc->device
  * and copies the result back into a tkspmv_packed, so that it can be compared byte for byte with tkspmv_pack's
