@@ -234,6 +234,21 @@ def check(status):
         raise TkspmvError(status, lib().tkspmv_last_error().decode("utf-8", "replace"))
 
 
+def ptr(a):
+    """A device address or a raw handle (a hipStream_t) as the c_void_p the prototypes take; 0 / None: NULL."""
+    return C.c_void_p(int(a)) if a else None
+
+
+def u32p(arr):
+    """A contiguous uint32 numpy array as the typed pointer the prototypes take; None: NULL."""
+    return None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def f32p(arr):
+    """A contiguous float32 numpy array as the typed pointer the prototypes take; None: NULL."""
+    return None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_float))
+
+
 def set_option(name, value):
     """tkspmv_set_option: an engine option (include/tkspmv.h; `options()` lists them) for the engines created after this call.
     value None: back to unset. Raises TkspmvError for a name that is not in the library's table."""

@@ -2,9 +2,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <chrono>
-#include <cmath>
 #include <cstring>
-#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -14,7 +12,7 @@
 #include "engine.hpp"
 #include "host_utils.hpp"
 #include "options.hpp"
-#include "row_lookup.hpp"
+#include "packed_host.hpp"
 #include "wbscsr.hpp"
 #include "wsell.hpp"
 
@@ -32,75 +30,30 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
-// The score of one located row from its own packets: reduce_core (kernels/packet_math.hpp) restated lane by lane, what
-// score_rows_kernel (kernels/score_rows.hpp) runs on the device. Per packet of the run: products inside the run, +0.0f outside; every
-// slot's own ROW_END mask; the carry +0.0f in front of the first packet. Every sum and product is a separately rounded fp32 operation
-// (-ffp-contract=off), in the kernel's order. product(value, column word) is the product of one slot inside the run: v * x[col] for a
-// score, a function of v alone for a row statistic (row_stats_kernel, kernels/row_stats.hpp).
-template <class Product>
-static float reduce_located_row(const HostRowView &V, const RowRun &run, Product product) {
-    const uint32_t C = V.C;
-    float carry = 0.0f, score = 0.0f;
-    for (uint32_t pk = run.first_pkt; pk <= run.last_pkt; ++pk) {
-        float s[64][8], head[64], tail[64], vv[64], t[64];
-        bool end[64][8];
-        uint64_t H = 0;  // lanes that hold a row end
-        for (uint32_t l = 0; l < 64u; ++l) {
-            float p[8];
-            for (uint32_t j = 0; j < C; ++j) {
-                const uint32_t ss = l * C + j;
-                const uint16_t w = V.word(pk, ss);
-                const bool inside = (pk > run.first_pkt || ss >= run.first_slot) && (pk < run.last_pkt || ss <= run.last_slot);
-                p[j] = inside ? product(V.value(pk, ss), w) : 0.0f;
-                end[l][j] = (w & COLW_ROW_END) != 0;
-                if (end[l][j]) H |= 1ull << l;
-            }
-            if (l == 0u) p[0] = p[0] + carry;
-            s[l][0] = p[0];
-            for (uint32_t j = 1; j < C; ++j) s[l][j] = (end[l][j - 1] ? 0.0f : s[l][j - 1]) + p[j];
-            head[l] = s[l][C - 1];
-            for (uint32_t j = C - 1; j-- > 0u;)
-                if (end[l][j]) head[l] = s[l][j];
-            tail[l] = end[l][C - 1] ? 0.0f : s[l][C - 1];
-        }
-        // the clipped scan: the lane masks of reduce_core, bit for bit
-        const uint64_t M1 = ~H, M2 = M1 & (M1 << 1), M4 = M2 & (M2 << 2), M8 = M4 & (M4 << 4);
-        const uint64_t X16 = M1 & 0xFFFF0000FFFF0000ull, P16 = X16 & ~(X16 + 0x0001000000010000ull);
-        const uint32_t Z32 = (uint32_t)(M1 >> 32);
-        const uint64_t P32 = (uint64_t)(Z32 & ~(Z32 + 1u)) << 32;
-        for (uint32_t l = 0; l < 64u; ++l) vv[l] = tail[l];
-        const uint64_t masks[4] = {M1, M2, M4, M8};
-        for (uint32_t step = 0; step < 4u; ++step) {  // row_shr:1, 2, 4, 8 inside each row of 16 lanes; a lane without a source adds +0.0f
-            const uint32_t d = 1u << step;
-            for (uint32_t l = 0; l < 64u; ++l) t[l] = vv[l] + ((l & 15u) >= d ? vv[l - d] : 0.0f);
-            for (uint32_t l = 0; l < 64u; ++l)
-                if ((masks[step] >> l) & 1u) vv[l] = t[l];
-        }
-        for (uint32_t l = 0; l < 64u; ++l) t[l] = ((l >> 4) & 1u) ? vv[(l & ~15u) - 1u] + vv[l] : vv[l];  // row_bcast:15: lane 15 -> row 1, lane 47 -> row 3
-        for (uint32_t l = 0; l < 64u; ++l)
-            if ((P16 >> l) & 1u) vv[l] = t[l];
-        for (uint32_t l = 32; l < 64u; ++l) t[l] = vv[31] + vv[l];  // row_bcast:31: lane 31 -> rows 2 and 3
-        for (uint32_t l = 32; l < 64u; ++l)
-            if ((P32 >> l) & 1u) vv[l] = t[l];
-        carry = vv[63];
-        if (pk == run.last_pkt) {  // expand(): the first row end of a lane yields S, later ones their own s[j]
-            const uint32_t l = run.last_slot / C, j = run.last_slot % C;
-            bool earlier = false;
-            for (uint32_t i = 0; i < j; ++i) earlier = earlier || end[l][i];
-            const float S = (l == 0u ? 0.0f : vv[l - 1u]) + head[l];
-            score = earlier ? s[l][j] : S;
-        }
+// Engine::create behind tkspmv_create and tkspmv_create_packed: the handle, or the engine's status and message.
+static int create_engine(tkspmv_t **out, const tkspmv_desc &d, const PackedMatrix *prepacked, const char *nomem) {
+    std::string err;
+    int status = TKSPMV_OK;
+    Engine *e = nullptr;
+    try {
+        e = Engine::create(d, err, status, prepacked);
+    } catch (const std::bad_alloc &) {
+        return fail(TKSPMV_ERR_NOMEM, nomem);
     }
-    return score;
+    if (!e) return fail(status, err);
+    *out = new tkspmv_engine{e};
+    return TKSPMV_OK;
 }
-static float score_located_row(const HostRowView &V, const RowRun &run, const float *x) {
-    return reduce_located_row(V, run, [x](float v, uint16_t w) { return v * x[w >> COLW_COL_SHIFT]; });
-}
-// The cosine weight of a row whose squares sum to l2sq (inv_l2_of, kernels/row_stats.hpp): two separately rounded fp32 operations;
-// +0.0f where the sum is 0, +inf or NaN.
-static float inv_l2_of(float l2sq) {
-    const float w = 1.0f / std::sqrt(l2sq);
-    return (l2sq > 0.0f && l2sq < std::numeric_limits<float>::infinity()) ? w : 0.0f;
+
+// stream_precision (wbscsr.hpp) backwards: the tkspmv_precision that names a stream's value type. fp32 travels with column words of
+// either width, fixed point at any of three widths; truncated Q1.7 has two arithmetic modes and comes back as the narrow one.
+static bool is_f32(Precision p) { return p == Precision::F32 || p == Precision::F32C12; }
+static bool is_fixed(Precision p) { return p == Precision::FIXED || p == Precision::FIXED20 || p == Precision::FIXED26; }
+static int32_t api_precision_of(Precision p) {
+    if (is_f32(p)) return TKSPMV_F32;
+    if (p == Precision::F16) return TKSPMV_F16;
+    if (is_fixed(p)) return TKSPMV_FIXED;
+    return p == Precision::Q1_7_RND ? TKSPMV_Q1_7_F32 : TKSPMV_Q1_7;
 }
 
 extern "C" {
@@ -112,17 +65,7 @@ int tkspmv_device_count(void) { return device_count(); }
 int tkspmv_create(tkspmv_t **out, const tkspmv_desc *desc) {
     if (!out || !desc) return fail(TKSPMV_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    std::string err;
-    int status = TKSPMV_OK;
-    Engine *e = nullptr;
-    try {
-        e = Engine::create(*desc, err, status);
-    } catch (const std::bad_alloc &) {
-        return fail(TKSPMV_ERR_NOMEM, "out of host memory while packing");
-    }
-    if (!e) return fail(status, err);
-    *out = new tkspmv_engine{e};
-    return TKSPMV_OK;
+    return create_engine(out, *desc, nullptr, "out of host memory while packing");
 }
 
 void tkspmv_destroy(tkspmv_t *h) {
@@ -135,6 +78,14 @@ void tkspmv_destroy(tkspmv_t *h) {
     if (!h) return fail(TKSPMV_ERR_INVALID, "NULL engine");      \
     std::string err;                                             \
     int st = h->e->call;                                         \
+    if (st != TKSPMV_OK) g_err = err;                            \
+    return st;
+
+// The host twins (packed_host.hpp) behind a packed handle: the argument check with its message, then the twin's status and message.
+#define PACKED_CALL(args_ok, bad_args, call)                     \
+    if (!(args_ok)) return fail(TKSPMV_ERR_INVALID, bad_args);   \
+    std::string err;                                             \
+    int st = call;                                               \
     if (st != TKSPMV_OK) g_err = err;                            \
     return st;
 
@@ -353,9 +304,14 @@ int tkspmv_sample_vector(float *vec, int32_t size, int32_t random, int32_t sum_t
     return TKSPMV_OK;
 }
 
+static int check_dist(int32_t dist) {
+    if (dist != DIST_UNIFORM && dist != DIST_GAMMA) return fail(TKSPMV_ERR_INVALID, "dist must be 0 (uniform) or 1 (gamma)");
+    return TKSPMV_OK;
+}
+
 int tkspmv_generate(uint32_t rows, uint32_t cols, uint32_t avg_nnz, int32_t dist, uint64_t seed, tkspmv_coo *out) {
     if (!out || cols == 0 || avg_nnz == 0) return fail(TKSPMV_ERR_INVALID, "bad arguments");
-    if (dist != DIST_UNIFORM && dist != DIST_GAMMA) return fail(TKSPMV_ERR_INVALID, "dist must be 0 (uniform) or 1 (gamma)");
+    if (const int st = check_dist(dist); st != TKSPMV_OK) return st;
     CooMatrix m;
     try {
         generate_matrix(rows, cols, avg_nnz, dist, seed, m);
@@ -368,7 +324,7 @@ int tkspmv_generate(uint32_t rows, uint32_t cols, uint32_t avg_nnz, int32_t dist
 int tkspmv_generate_rows(uint32_t row_begin, uint32_t row_end, uint32_t cols, uint32_t avg_nnz, int32_t dist, uint64_t seed,
                          tkspmv_coo *out) {
     if (!out || cols == 0 || avg_nnz == 0 || row_end < row_begin) return fail(TKSPMV_ERR_INVALID, "bad arguments");
-    if (dist != DIST_UNIFORM && dist != DIST_GAMMA) return fail(TKSPMV_ERR_INVALID, "dist must be 0 (uniform) or 1 (gamma)");
+    if (const int st = check_dist(dist); st != TKSPMV_OK) return st;
     CooMatrix m;
     try {
         generate_matrix_rows(row_begin, row_end, cols, avg_nnz, dist, seed, m);
@@ -381,7 +337,7 @@ int tkspmv_generate_rows(uint32_t row_begin, uint32_t row_end, uint32_t cols, ui
 int tkspmv_generate_degrees(uint32_t row_begin, uint32_t row_end, uint32_t avg_nnz, int32_t dist, uint64_t seed,
                             uint32_t *deg) {
     if (!deg || avg_nnz == 0 || row_end < row_begin) return fail(TKSPMV_ERR_INVALID, "bad arguments");
-    if (dist != DIST_UNIFORM && dist != DIST_GAMMA) return fail(TKSPMV_ERR_INVALID, "dist must be 0 (uniform) or 1 (gamma)");
+    if (const int st = check_dist(dist); st != TKSPMV_OK) return st;
     generate_degrees(row_begin, row_end, avg_nnz, dist, seed, deg);
     return TKSPMV_OK;
 }
@@ -457,15 +413,21 @@ int tkspmv_packed_info(const tkspmv_packed *p, tkspmv_info *info) {
     return TKSPMV_OK;
 }
 
+// A decoded matrix into the caller's arrays (each optional) and its number of entries into *n.
+static void copy_out_coo(const std::vector<uint32_t> &r, const std::vector<uint32_t> &c, const std::vector<float> &v, uint32_t *row, uint32_t *col,
+                         float *val, uint64_t *n) {
+    *n = r.size();
+    if (row) std::memcpy(row, r.data(), r.size() * 4);
+    if (col) std::memcpy(col, c.data(), c.size() * 4);
+    if (val) std::memcpy(val, v.data(), v.size() * 4);
+}
+
 int tkspmv_packed_decode(const tkspmv_packed *p, uint32_t *row, uint32_t *col, float *val, uint64_t *n) {
     if (!p || !n) return fail(TKSPMV_ERR_INVALID, "NULL argument");
     std::vector<uint32_t> r, c;
     std::vector<float> v;
     decode_wbscsr(p->pm, r, c, v);
-    *n = r.size();
-    if (row) std::memcpy(row, r.data(), r.size() * 4);
-    if (col) std::memcpy(col, c.data(), c.size() * 4);
-    if (val) std::memcpy(val, v.data(), v.size() * 4);
+    copy_out_coo(r, c, v, row, col, val, n);
     return TKSPMV_OK;
 }
 
@@ -482,132 +444,19 @@ int tkspmv_packed_raw(const tkspmv_packed *p, const void **packets, uint64_t *pa
 }
 
 int tkspmv_packed_get_row(const tkspmv_packed *p, uint32_t row, uint32_t *col, float *val, uint32_t capacity, uint32_t *n) {
-    if (!p || !n || (capacity > 0u && (!col || !val))) return fail(TKSPMV_ERR_INVALID, "NULL argument");
-    const PackedMatrix &pm = p->pm;
-    if (row >= pm.rows) return fail(TKSPMV_ERR_INVALID, "row out of range (>= rows)");
-    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
-        return fail(TKSPMV_ERR_UNSUPPORTED, "rows are looked up in fp32 packet streams only (TKSPMV_F32)");
-    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
-    const uint32_t PE = pm.packet_entries;
-    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
-                        pm.precision == Precision::F32C12};
-    RowRun run{0u, 0u, 0u, 0u};
-    *n = 0u;
-    if (!locate_row(V, row, pm.n_packets, (uint32_t)pm.part_first.size(), PE, run)) return TKSPMV_OK;  // beyond the last stored row
-    *n = row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot));
-    if (*n == 0u) return TKSPMV_OK;
-    uint32_t out = 0u;
-    for (uint32_t pk = run.first_pkt; pk <= run.last_pkt && out < capacity; ++pk) {
-        const uint32_t s0 = pk == run.first_pkt ? run.first_slot : 0u, s1 = pk == run.last_pkt ? run.last_slot : PE - 1u;
-        for (uint32_t ss = s0; ss <= s1 && out < capacity; ++ss, ++out) {
-            col[out] = (uint32_t)(V.word(pk, ss) >> COLW_COL_SHIFT);
-            val[out] = V.value(pk, ss);
-        }
-    }
-    return TKSPMV_OK;
+    PACKED_CALL(p && n && (capacity == 0u || (col && val)), "NULL argument", packed_get_row(p->pm, row, col, val, capacity, n, err))
 }
-
 int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint32_t *rows, int32_t n_rows, float *scores) {
-    if (!p || !x || !rows || !scores || n_rows < 1) return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix, vector, rows and scores given, n_rows >= 1)");
-    const PackedMatrix &pm = p->pm;
-    for (int32_t i = 0; i < n_rows; ++i)
-        if (rows[i] >= pm.rows) return fail(TKSPMV_ERR_INVALID, "row out of range (>= rows)");
-    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
-        return fail(TKSPMV_ERR_UNSUPPORTED, "rows are scored in fp32 packet streams only (TKSPMV_F32)");
-    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
-    const uint32_t PE = pm.packet_entries;
-    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
-                        pm.precision == Precision::F32C12};
-    for (int32_t i = 0; i < n_rows; ++i) {
-        RowRun run{0u, 0u, 0u, 0u};
-        scores[i] = 0.0f;  // a row without entries: a placeholder, or no packets at all
-        if (locate_row(V, rows[i], pm.n_packets, (uint32_t)pm.part_first.size(), PE, run) && row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot)) != 0u)
-            scores[i] = score_located_row(V, run, x);
-    }
-    return TKSPMV_OK;
+    PACKED_CALL(p && x && rows && scores && n_rows >= 1, "bad arguments (packed matrix, vector, rows and scores given, n_rows >= 1)",
+                packed_score_rows(p->pm, x, rows, n_rows, scores, err))
 }
-
 int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
-    if (!p || !out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
-        return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix and output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
-    const PackedMatrix &pm = p->pm;
-    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
-        return fail(TKSPMV_ERR_UNSUPPORTED, "row statistics are taken from fp32 packet streams only (TKSPMV_F32)");
-    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
-    const uint32_t PE = pm.packet_entries;
-    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
-                        pm.precision == Precision::F32C12};
-    for (uint32_t r = 0; r < pm.rows; ++r) {
-        RowRun run{0u, 0u, 0u, 0u};
-        out[r] = 0.0f;  // a row without entries: a placeholder, or no packets at all
-        if (!locate_row(V, r, pm.n_packets, (uint32_t)pm.part_first.size(), PE, run) || row_run_entries(run, PE, V.word(run.first_pkt, run.first_slot)) == 0u)
-            continue;
-        switch (kind) {
-            case TKSPMV_ROW_NNZ: out[r] = reduce_located_row(V, run, [](float, uint16_t) { return 1.0f; }); break;
-            case TKSPMV_ROW_L1: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return std::fabs(v); }); break;
-            case TKSPMV_ROW_L2SQ: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return v * v; }); break;
-            default: out[r] = inv_l2_of(reduce_located_row(V, run, [](float v, uint16_t) { return v * v; })); break;
-        }
-    }
-    return TKSPMV_OK;
+    PACKED_CALL(p && out && kind >= TKSPMV_ROW_NNZ && kind <= TKSPMV_ROW_INV_L2,
+                "bad arguments (packed matrix and output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)", packed_row_stats(p->pm, kind, out, err))
 }
-
-// col_stats_kernel (kernels/col_stats.hpp) restated as a walk over the stream, from what the device has: the packets, pkt_row and the
-// partition table. Per partition: its last row end is looked for from its last packet backwards; the slots up to it, in stream order,
-// are its entries -- what lies behind is padding --, a SKIP slot is the placeholder of an empty row, and the row of a slot is the row of
-// the partition's first packet plus the row ends in front of it. MAX / MIN compare order keys (order_key, kernels/common.hpp).
 int tkspmv_packed_col_stats(const tkspmv_packed *p, int32_t kind, const uint32_t *mask, void *out) {
-    if (!p || !out || kind < TKSPMV_COL_NNZ || kind > TKSPMV_COL_MIN)
-        return fail(TKSPMV_ERR_INVALID, "bad arguments (packed matrix and output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)");
-    const PackedMatrix &pm = p->pm;
-    if (pm.precision != Precision::F32 && pm.precision != Precision::F32C12)
-        return fail(TKSPMV_ERR_UNSUPPORTED, "column statistics are taken from fp32 packet streams only (TKSPMV_F32)");
-    if (pm.packets.size() != pm.stream_bytes() || pm.pkt_row.size() != pm.n_packets) return fail(TKSPMV_ERR_INVALID, "the packed matrix is incomplete");
-    const uint32_t PE = pm.packet_entries;
-    const HostRowView V{pm.packets.data(), pm.pkt_row.data(), pm.part_first.data(), pm.part_count.data(), pm.packet_bytes, PE, pm.C,
-                        pm.precision == Precision::F32C12};
-    const auto order_key = [](uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
-    const uint32_t negate = kind == TKSPMV_COL_MIN ? 0x80000000u : 0u;
-    std::vector<uint32_t> acc(pm.cols, 0u);  // counts, or order keys (0: no counted entry)
-    for (size_t q = 0; q < pm.part_first.size(); ++q) {
-        const uint32_t f0 = pm.part_first[q];
-        uint32_t n = 0u, last_slot = 0u;
-        for (uint32_t k = pm.part_count[q]; k > 0u; --k)
-            if (V.last_end(f0 + k - 1u, last_slot)) {
-                n = k;
-                break;
-            }
-        uint32_t r = n ? pm.pkt_row[f0] : 0u;
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t lim = k + 1u == n ? last_slot : PE - 1u;
-            for (uint32_t ss = 0; ss <= lim; ++ss) {
-                const uint16_t w = V.word(f0 + k, ss);
-                const uint32_t c = (uint32_t)(w >> COLW_COL_SHIFT);
-                const bool allowed = !mask || (r < pm.rows && ((mask[r >> 5] >> (r & 31u)) & 1u));
-                if (!(w & COLW_SKIP) && allowed && c < pm.cols) {
-                    if (kind == TKSPMV_COL_NNZ) {
-                        ++acc[c];
-                    } else {
-                        uint32_t bits;
-                        const float v = V.value(f0 + k, ss);
-                        std::memcpy(&bits, &v, 4);
-                        acc[c] = std::max(acc[c], order_key(bits ^ negate));
-                    }
-                }
-                if (w & COLW_ROW_END) ++r;
-            }
-        }
-    }
-    uint32_t *const o = static_cast<uint32_t *>(out);
-    for (uint32_t c = 0; c < pm.cols; ++c) {
-        if (kind == TKSPMV_COL_NNZ) {
-            o[c] = acc[c];
-        } else {  // key_to_float; key 0: -inf; then the negation of MIN undone
-            const uint32_t k = acc[c];
-            o[c] = (k == 0u ? 0xFF800000u : ((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k)) ^ negate;
-        }
-    }
-    return TKSPMV_OK;
+    PACKED_CALL(p && out && kind >= TKSPMV_COL_NNZ && kind <= TKSPMV_COL_MIN,
+                "bad arguments (packed matrix and output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)", packed_col_stats(p->pm, kind, mask, out, err))
 }
 
 void tkspmv_packed_free(tkspmv_packed *p) { delete p; }
@@ -623,10 +472,7 @@ int tkspmv_sell_roundtrip(const tkspmv_desc *d, uint32_t n_wave_partitions_hint,
     std::vector<uint32_t> r, c;
     std::vector<float> v;
     decode_wsell(sm, r, c, v);
-    *n = r.size();
-    if (row) std::memcpy(row, r.data(), r.size() * 4);
-    if (col) std::memcpy(col, c.data(), c.size() * 4);
-    if (val) std::memcpy(val, v.data(), v.size() * 4);
+    copy_out_coo(r, c, v, row, col, val, n);
     if (info) {
         uint32_t most = 0;
         for (uint32_t pc : sm.part_count) most = std::max(most, pc);
@@ -714,29 +560,12 @@ int tkspmv_create_packed(tkspmv_t **out, const tkspmv_packed *p, const tkspmv_de
     d.cols = p->pm.cols;
     d.nnz = p->pm.nnz;
     // desc.precision chooses among the arithmetic modes of the packed value type (only Q1.7 has two)
-    const bool fixed_either = desc->precision == TKSPMV_FIXED && (p->pm.precision == Precision::FIXED || p->pm.precision == Precision::FIXED20 || p->pm.precision == Precision::FIXED26);
-    const bool f32_either = desc->precision == TKSPMV_F32 && (p->pm.precision == Precision::F32 || p->pm.precision == Precision::F32C12);
-    if (!fixed_either && !f32_either && stream_precision(desc->precision) != p->pm.precision)
-        d.precision = (p->pm.precision == Precision::F32 || p->pm.precision == Precision::F32C12)
-                          ? TKSPMV_F32
-                          : (p->pm.precision == Precision::F16
-                                 ? TKSPMV_F16
-                                 : ((p->pm.precision == Precision::FIXED || p->pm.precision == Precision::FIXED20 || p->pm.precision == Precision::FIXED26)
-                                        ? TKSPMV_FIXED
-                                        : (p->pm.precision == Precision::Q1_7_RND ? TKSPMV_Q1_7_F32 : TKSPMV_Q1_7)));
+    const bool fixed_either = desc->precision == TKSPMV_FIXED && is_fixed(p->pm.precision);
+    const bool f32_either = desc->precision == TKSPMV_F32 && is_f32(p->pm.precision);
+    if (!fixed_either && !f32_either && stream_precision(desc->precision) != p->pm.precision) d.precision = api_precision_of(p->pm.precision);
     d.fixed_width = (int32_t)p->pm.fixed_width;  // a property of the packed values
     d.nnz_per_lane = (int32_t)p->pm.C;
-    std::string err;
-    int status = TKSPMV_OK;
-    Engine *e = nullptr;
-    try {
-        e = Engine::create(d, err, status, &p->pm);
-    } catch (const std::bad_alloc &) {
-        return fail(TKSPMV_ERR_NOMEM, "out of host memory");
-    }
-    if (!e) return fail(status, err);
-    *out = new tkspmv_engine{e};
-    return TKSPMV_OK;
+    return create_engine(out, d, &p->pm, "out of host memory");
 }
 
 }  // extern "C"

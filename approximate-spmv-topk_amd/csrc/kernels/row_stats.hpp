@@ -33,7 +33,7 @@ struct RowStatsParams {
 // The cosine weight of a row whose squares sum to l2sq: two separately rounded IEEE operations, subnormals kept; +0.0f where the sum
 // is 0, +inf or NaN, so every weight is finite (the largest: 1 / sqrt(2^-149) < 2^75). Spelled as the language's own sqrt and
 // division, which hipcc rounds correctly by default: the header's __fsqrt_rn is the hardware's approximation (one ulp off for
-// some arguments) unless OCML_BASIC_ROUNDED_OPERATIONS is defined, and the host restatements (c_api.cpp, host.inv_l2) are IEEE.
+// some arguments) unless OCML_BASIC_ROUNDED_OPERATIONS is defined, and the host restatements (packed_host.cpp, host.inv_l2) are IEEE.
 __device__ __forceinline__ float inv_l2_of(float l2sq) {
     const float w = 1.0f / __builtin_sqrtf(l2sq);
     return (l2sq > 0.0f && l2sq < __builtin_huge_valf()) ? w : 0.0f;

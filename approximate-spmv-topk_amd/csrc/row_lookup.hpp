@@ -1,5 +1,5 @@
 // row_lookup.hpp -- where one row lives in the wave-BSCSR packet stream (wbscsr.hpp): the lookup behind
-// tkspmv_packed_get_row (host, c_api.cpp) and row_vectors_kernel (device, kernels/row_vectors.hpp). One definition for both,
+// tkspmv_packed_get_row (host, packed_host.cpp) and row_vectors_kernel (device, kernels/row_vectors.hpp). One definition for both,
 // as slot_to_index is for the packers: the host decoder and the kernel cannot drift apart.
 //
 // The stream stores no row ids per entry and no row pointers; what it has is pkt_row[p], the row of packet p's FIRST entry.
@@ -107,34 +107,5 @@ TKSPMV_HD inline uint32_t row_run_entries(const RowRun &run, uint32_t PE, uint16
     if (first_word & COLW_SKIP) return 0u;
     return (run.last_pkt - run.first_pkt) * PE + run.last_slot + 1u - run.first_slot;
 }
-
-// The host's view of a packed fp32 stream: plain loops over the slots of a packet.
-struct HostRowView {
-    const uint8_t *packets;
-    const uint32_t *pkt_row_, *part_first_, *part_count_;
-    uint32_t packet_bytes, PE, C;
-    bool c12;
-    uint32_t pkt_row(uint32_t p) const { return pkt_row_[p]; }
-    uint32_t part_first(uint32_t q) const { return part_first_[q]; }
-    uint32_t part_count(uint32_t q) const { return part_count_[q]; }
-    uint16_t word(uint32_t p, uint32_t ss) const { return f32_colword_at(packets + (size_t)p * packet_bytes, PE, C, c12, ss); }
-    float value(uint32_t p, uint32_t ss) const { return f32_value_at(packets + (size_t)p * packet_bytes, C, ss); }
-    bool kth_end(uint32_t p, uint32_t k, uint32_t &slot) const {
-        for (uint32_t ss = 0; ss < PE; ++ss)
-            if ((word(p, ss) & COLW_ROW_END) && --k == 0u) {
-                slot = ss;
-                return true;
-            }
-        return false;
-    }
-    bool last_end(uint32_t p, uint32_t &slot) const {
-        for (uint32_t ss = PE; ss-- > 0u;)
-            if (word(p, ss) & COLW_ROW_END) {
-                slot = ss;
-                return true;
-            }
-        return false;
-    }
-};
 
 }  // namespace tkspmv

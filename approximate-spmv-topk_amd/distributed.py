@@ -215,10 +215,10 @@ class NativeShardedSpMV:
         self._lib.check_dist(self._lib.lib().tkspmv_dist_set_batch(self._h, int(batch)))
 
     def enqueue(self, dev_x_ptr):
-        self._lib.check_dist(self._lib.lib().tkspmv_dist_enqueue(self._h, self._C.c_void_p(int(dev_x_ptr))))
+        self._lib.check_dist(self._lib.lib().tkspmv_dist_enqueue(self._h, self._lib.ptr(dev_x_ptr)))
 
     def run_many(self, dev_xs_ptr, n_x, count):
-        self._lib.check_dist(self._lib.lib().tkspmv_dist_run_many(self._h, self._C.c_void_p(int(dev_xs_ptr)), n_x, count))
+        self._lib.check_dist(self._lib.lib().tkspmv_dist_run_many(self._h, self._lib.ptr(dev_xs_ptr), n_x, count))
 
     def synchronize(self):
         self._lib.check_dist(self._lib.lib().tkspmv_dist_synchronize(self._h))
@@ -234,8 +234,7 @@ class NativeShardedSpMV:
         idx = np.empty(self.k, dtype=np.uint32)
         val = np.empty(self.k, dtype=np.float32)
         n = C.c_int32()
-        self._lib.check_dist(self._lib.lib().tkspmv_dist_read(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                             val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        self._lib.check_dist(self._lib.lib().tkspmv_dist_read(self._h, self._lib.u32p(idx), self._lib.f32p(val), C.byref(n)))
         return val, idx
 
     def read_batch(self):
@@ -244,8 +243,7 @@ class NativeShardedSpMV:
         idx = np.empty((32, self.k), dtype=np.uint32)
         val = np.empty((32, self.k), dtype=np.float32)
         n = C.c_int32()
-        self._lib.check_dist(self._lib.lib().tkspmv_dist_read_batch(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                                   val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        self._lib.check_dist(self._lib.lib().tkspmv_dist_read_batch(self._h, self._lib.u32p(idx), self._lib.f32p(val), C.byref(n)))
         return val[:n.value], idx[:n.value]
 
     def close(self):
@@ -263,23 +261,19 @@ class NativeShardedSpMV:
 def merge_topk_batch_device(gathered_i32, world, n_q, k, stream=0):
     """The native merge kernel as the pipelined step launches it: gathered_i32 is a [world][n_q][2][k] int32 CUDA tensor (what
     the all-gather of an exchange batch leaves behind); returns (idx int32[n_q][k], val float32[n_q][k])."""
-    import ctypes as C
     from . import _lib
     out_idx = torch.zeros((n_q, k), dtype=torch.int32, device=gathered_i32.device)
     out_val = torch.zeros((n_q, k), dtype=torch.float32, device=gathered_i32.device)
-    _lib.check_dist(_lib.lib().tkspmv_merge_topk_batch(C.c_void_p(gathered_i32.data_ptr()), world, n_q, k,
-                                                       C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()),
-                                                       C.c_void_p(int(stream))))
+    _lib.check_dist(_lib.lib().tkspmv_merge_topk_batch(_lib.ptr(gathered_i32.data_ptr()), world, n_q, k, _lib.ptr(out_idx.data_ptr()),
+                                                       _lib.ptr(out_val.data_ptr()), _lib.ptr(stream)))
     return out_idx, out_val
 
 
 def merge_topk_device(gathered_i32, world, k, stream=0):
     """The native merge kernel on a [world][2][k] int32 CUDA tensor; returns (idx int32[k], val float32[k]) tensors."""
-    import ctypes as C
     from . import _lib
     out_idx = torch.zeros(k, dtype=torch.int32, device=gathered_i32.device)
     out_val = torch.zeros(k, dtype=torch.float32, device=gathered_i32.device)
-    _lib.check_dist(_lib.lib().tkspmv_merge_topk(C.c_void_p(gathered_i32.data_ptr()), world, k,
-                                                 C.c_void_p(out_idx.data_ptr()), C.c_void_p(out_val.data_ptr()),
-                                                 C.c_void_p(int(stream))))
+    _lib.check_dist(_lib.lib().tkspmv_merge_topk(_lib.ptr(gathered_i32.data_ptr()), world, k, _lib.ptr(out_idx.data_ptr()), _lib.ptr(out_val.data_ptr()),
+                                                 _lib.ptr(stream)))
     return out_idx, out_val

@@ -9,11 +9,13 @@ reset(vec) -> operator()() -> read_result()), bound to the HIP engine through th
 The compute path is the HIP library only; constructing an engine without a GPU raises TkspmvError(ERR_DEVICE).
 """
 import ctypes as C
+from contextlib import contextmanager
 
 import numpy as np
 
 from . import _lib
-from .host import row_mask
+from ._lib import f32p, ptr, u32p
+from .host import _allow_words
 
 MAX_PAGE = 1000  # ranked_spmv's default page: every page takes the scores + radix-select route whatever k is, so a large page is cheapest
 
@@ -34,9 +36,7 @@ class SpMV:
         nnz = int(row.shape[0]) if num_nnz is None else int(num_nnz)
         d = _lib.Desc()
         d.rows, d.cols, d.nnz = int(num_rows), int(num_cols), nnz
-        d.row = row.ctypes.data_as(C.POINTER(C.c_uint32))
-        d.col = col.ctypes.data_as(C.POINTER(C.c_uint32))
-        d.val = v.ctypes.data_as(C.POINTER(C.c_float)) if v is not None else None
+        d.row, d.col, d.val = u32p(row), u32p(col), f32p(v)
         d.k, d.partitions, d.k_per_partition, d.precision = int(k), int(partitions), int(k_per_partition), precision
         d.device, d.first_row, d.min_score = int(device), int(first_row), float(min_score)
         d.waves_per_cu, d.threads_per_wg, d.nnz_per_lane = int(waves_per_cu), int(threads_per_wg), int(nnz_per_lane)
@@ -45,8 +45,12 @@ class SpMV:
         d.multi_q = int(multi_q)
         d.impl = int(impl)
         _lib.check(_lib.lib().tkspmv_create(C.byref(self._h), C.byref(d)))
+        self._created(k, int(num_rows), int(num_cols), nnz, first_row, debug, vec)
+
+    def _created(self, k, num_rows, num_cols, num_nnz, first_row, debug, vec):
+        """What __init__ and from_packed share once the handle exists: the engine's sizes as attributes, then the first vector."""
         self.k = int(k)
-        self.num_rows, self.num_cols, self.num_nnz = int(num_rows), int(num_cols), nnz
+        self.num_rows, self.num_cols, self.num_nnz = num_rows, num_cols, num_nnz
         self.first_row = int(first_row)
         self.debug = debug
         if vec is not None:
@@ -68,12 +72,7 @@ class SpMV:
         d.stream_replicas = int(stream_replicas)
         d.multi_q = int(multi_q)
         _lib.check(_lib.lib().tkspmv_create_packed(C.byref(self._h), packed._h, C.byref(d)))
-        self.k = int(k)
-        self.num_rows, self.num_cols, self.num_nnz = info["rows"], info["cols"], info["nnz"]
-        self.first_row = int(first_row)
-        self.debug = debug
-        if vec is not None:
-            self.reset(vec)
+        self._created(k, info["rows"], info["cols"], info["nnz"], first_row, debug, vec)
         return self
 
     # -- the four verbs ---------------------------------------------------------------------------------
@@ -82,7 +81,7 @@ class SpMV:
         if v.shape[0] != self.num_cols:
             raise ValueError(f"query vector has {v.shape[0]} entries, expected {self.num_cols}")
         ns = C.c_double()
-        _lib.check(_lib.lib().tkspmv_set_query(self._h, v.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ns)))
+        _lib.check(_lib.lib().tkspmv_set_query(self._h, f32p(v), C.byref(ns)))
         return int(ns.value)
 
     def __call__(self, debug=0):
@@ -94,46 +93,41 @@ class SpMV:
         idx = np.empty(self.k, dtype=np.uint32)
         val = np.empty(self.k, dtype=np.float32)
         n = C.c_int32()
-        _lib.check(_lib.lib().tkspmv_read(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                          val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        _lib.check(_lib.lib().tkspmv_read(self._h, u32p(idx), f32p(val), C.byref(n)))
         return val[:n.value], idx[:n.value]
 
     # -- extras -----------------------------------------------------------------------------------------
     def reset_device(self, dev_ptr):
         """Query vector already resident in HBM (raw device pointer, e.g. torch tensor.data_ptr())."""
-        _lib.check(_lib.lib().tkspmv_set_query_device(self._h, C.c_void_p(int(dev_ptr))))
+        _lib.check(_lib.lib().tkspmv_set_query_device(self._h, ptr(dev_ptr)))
 
     def enqueue(self, dev_x=0, dev_idx=0, dev_val=0, stream=0):
         """Asynchronous launch of one query on `stream` (raw hipStream_t handle; 0 = engine stream)."""
-        _lib.check(_lib.lib().tkspmv_enqueue(self._h, C.c_void_p(int(dev_x)), C.c_void_p(int(dev_idx)),
-                                             C.c_void_p(int(dev_val)), C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue(self._h, ptr(dev_x), ptr(dev_idx), ptr(dev_val), ptr(stream)))
 
     def enqueue_many(self, dev_xs, n_x, count, stream=0):
         """`count` queries back to back from a device array of n_x query vectors (no host sync)."""
-        _lib.check(_lib.lib().tkspmv_enqueue_many(self._h, C.c_void_p(int(dev_xs)), int(n_x), int(count),
-                                                  C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_many(self._h, ptr(dev_xs), int(n_x), int(count), ptr(stream)))
 
     def time_queries(self, dev_xs, n_x, iters):
         """ns per query of `iters` back-to-back queries (one hipEvent pair around the batch; nothing else launched)."""
         ns = C.c_double()
-        _lib.check(_lib.lib().tkspmv_time_queries(self._h, C.c_void_p(int(dev_xs)), int(n_x), int(iters), C.byref(ns)))
+        _lib.check(_lib.lib().tkspmv_time_queries(self._h, ptr(dev_xs), int(n_x), int(iters), C.byref(ns)))
         return ns.value
 
     def time_host_loop(self, host_xs, iters):
         """The reference's reset / operator() / read_result loop run natively `iters` times over the rows of host_xs (float32,
         [n_x, cols]): (loop_us[iters], kernel_us[iters]) -- the host clock around the three calls, and tkspmv_run's own figure."""
         xs = np.ascontiguousarray(host_xs, dtype=np.float32)
-        loop = np.zeros(int(iters), dtype=np.float64)
-        kern = np.zeros(int(iters), dtype=np.float64)
-        _lib.check(_lib.lib().tkspmv_time_host_loop(self._h, xs.ctypes.data_as(C.POINTER(C.c_float)), int(xs.shape[0]), int(iters),
-                                                    loop.ctypes.data_as(C.POINTER(C.c_double)), kern.ctypes.data_as(C.POINTER(C.c_double))))
-        return loop / 1e3, kern / 1e3
+        loop, kern = (C.c_double * int(iters))(), (C.c_double * int(iters))()
+        _lib.check(_lib.lib().tkspmv_time_host_loop(self._h, f32p(xs), int(xs.shape[0]), int(iters), loop, kern))
+        return np.array(loop, dtype=np.float64) / 1e3, np.array(kern, dtype=np.float64) / 1e3
 
     def time_query_batches(self, dev_xs, n_x, iters, reps):
         """`reps` batches of `iters` back-to-back queries, all enqueued before the first wait: ns per query of every batch (the GPU
         never idles between them: the kernel under sustained load)."""
         out = (C.c_double * int(reps))()
-        _lib.check(_lib.lib().tkspmv_time_query_batches(self._h, C.c_void_p(int(dev_xs)), int(n_x), int(iters), int(reps), out))
+        _lib.check(_lib.lib().tkspmv_time_query_batches(self._h, ptr(dev_xs), int(n_x), int(iters), int(reps), out))
         return [float(v) for v in out]
 
     def time_stream_read(self, passes):
@@ -146,21 +140,15 @@ class SpMV:
     def enqueue_batch(self, dev_xs, count, dev_idx=0, dev_val=0, stream=0):
         """A batch of `count` queries (rows of a device array, stride cols floats); query i's k results go to
         dev_idx + i*k / dev_val + i*k (device pointers; 0 => engine buffers, last query wins). No host sync."""
-        _lib.check(_lib.lib().tkspmv_enqueue_batch(self._h, C.c_void_p(int(dev_xs)), int(count),
-                                                   C.c_void_p(int(dev_idx)) if dev_idx else None,
-                                                   C.c_void_p(int(dev_val)) if dev_val else None,
-                                                   C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_batch(self._h, ptr(dev_xs), int(count), ptr(dev_idx), ptr(dev_val), ptr(stream)))
 
     def enqueue_filtered(self, dev_xs, count, dev_mask, mask_stride=0, dev_idx=0, dev_val=0, stream=0):
         """Filtered top-k of `count` queries: query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset())
         restricted to the rows set in the allow-mask dev_mask + i*mask_stride words (mask_stride = 0: one mask for every query;
         dev_mask = 0: the mask installed by set_filter). Masks are uint32 words as row_mask() builds them. Results as in
         enqueue_batch. No host sync."""
-        _lib.check(_lib.lib().tkspmv_enqueue_filtered(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
-                                                      C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
-                                                      C.c_void_p(int(dev_idx)) if dev_idx else None,
-                                                      C.c_void_p(int(dev_val)) if dev_val else None,
-                                                      C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_filtered(self._h, ptr(dev_xs), int(count), ptr(dev_mask), int(mask_stride), ptr(dev_idx), ptr(dev_val),
+                                                      ptr(stream)))
 
     def set_filter(self, mask_words):
         """Installs an allow-mask (row_mask() words, ceil(rows/32) of them) for enqueue_filtered(dev_mask=0); None removes it."""
@@ -170,16 +158,22 @@ class SpMV:
         w = np.ascontiguousarray(mask_words, dtype=np.uint32)
         if w.shape != ((self.num_rows + 31) // 32,):
             raise ValueError(f"allow-mask has {w.size} words, expected {(self.num_rows + 31) // 32} for {self.num_rows} rows")
-        _lib.check(_lib.lib().tkspmv_set_filter(self._h, w.ctypes.data_as(C.POINTER(C.c_uint32))))
+        _lib.check(_lib.lib().tkspmv_set_filter(self._h, u32p(w)))
+
+    def _install(self, vec=None, allow=None, groups=None):
+        """The prologue of the host-array query forms, each step only if its argument is given: reset(vec), then set_filter(allow)
+        (a bool array of length rows, or row_mask() words), then set_groups(groups)."""
+        if vec is not None:
+            self.reset(vec)
+        if allow is not None:
+            self.set_filter(_allow_words(self.num_rows, allow))
+        if groups is not None:
+            self.set_groups(groups)
 
     def run_filtered(self, vec=None, allow=None):
         """One filtered query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
         row_mask() words), then the query restricted to the installed mask. Returns (values, indices) like read_result."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self._install(vec, allow)
         self.enqueue_filtered(0, 1, 0)
         self.synchronize()
         return self.read_result()
@@ -199,7 +193,7 @@ class SpMV:
         g = np.ascontiguousarray(g, dtype=np.uint32)
         if n_groups is None:
             n_groups = int(g.max()) + 1 if g.size else 1
-        _lib.check(_lib.lib().tkspmv_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_groups)))
+        _lib.check(_lib.lib().tkspmv_set_groups(self._h, u32p(g), int(n_groups)))
         self._n_groups = int(n_groups)  # (run_facets sizes its arrays by it)
 
     def enqueue_grouped(self, dev_xs, count, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_grp=0, dev_n=0, stream=0):
@@ -207,30 +201,19 @@ class SpMV:
         groups of set_groups(), each by its best row. dev_mask: allow-mask(s) as in enqueue_filtered, 0 = unfiltered. dev_idx /
         dev_val / dev_grp: [count][k] device buffers, all three or none (engine buffers, last query wins); dev_n: [count] real
         entries per list (optional). Pads are (0, 0.0) with group id 0xFFFFFFFF. No host sync; one grouped call in flight at a time."""
-        _lib.check(_lib.lib().tkspmv_enqueue_grouped(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
-                                                     C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
-                                                     C.c_void_p(int(dev_idx)) if dev_idx else None,
-                                                     C.c_void_p(int(dev_val)) if dev_val else None,
-                                                     C.c_void_p(int(dev_grp)) if dev_grp else None,
-                                                     C.c_void_p(int(dev_n)) if dev_n else None, C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_grouped(self._h, ptr(dev_xs), int(count), ptr(dev_mask), int(mask_stride), ptr(dev_idx), ptr(dev_val),
+                                                     ptr(dev_grp), ptr(dev_n), ptr(stream)))
 
     def run_grouped(self, vec=None, allow=None, groups=None):
         """One grouped query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
         row_mask() words; the query is then restricted to it), set_groups(groups) if given. Returns (values, indices, groups) of
         the groups that exist for the query, at most k, ordered like read_result."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
-        if groups is not None:
-            self.set_groups(groups)
+        self._install(vec, allow, groups)
         idx = np.zeros(self.k, dtype=np.uint32)
         val = np.zeros(self.k, dtype=np.float32)
         grp = np.zeros(self.k, dtype=np.uint32)
         n = C.c_int32(0)
-        _lib.check(_lib.lib().tkspmv_run_grouped(self._h, int(allow is not None), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                 val.ctypes.data_as(C.POINTER(C.c_float)), grp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+        _lib.check(_lib.lib().tkspmv_run_grouped(self._h, int(allow is not None), u32p(idx), f32p(val), u32p(grp), C.byref(n)))
         return val[:n.value], idx[:n.value], grp[:n.value]
 
     def enqueue_after(self, dev_xs, count, dev_cursors=0, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_n=0, dev_total=0, dev_next=0,
@@ -242,9 +225,8 @@ class SpMV:
         page and eligible rows behind the cursor, the page included (optional); dev_next: [count] cursors of the following pages
         (optional; may be dev_cursors itself: the same call again then walks on). Pads are (0, 0.0). No host sync; one such call
         in flight at a time; the first call allocates about 12 bytes per row."""
-        p = lambda a: C.c_void_p(int(a)) if a else None
-        _lib.check(_lib.lib().tkspmv_enqueue_after(self._h, p(dev_xs), int(count), p(dev_cursors), p(dev_mask), int(mask_stride), p(dev_idx),
-                                                   p(dev_val), p(dev_n), p(dev_total), p(dev_next), C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_after(self._h, ptr(dev_xs), int(count), ptr(dev_cursors), ptr(dev_mask), int(mask_stride), ptr(dev_idx),
+                                                   ptr(dev_val), ptr(dev_n), ptr(dev_total), ptr(dev_next), ptr(stream)))
 
     def run_after(self, cursor=None, vec=None, allow=None):
         """One page with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or row_mask()
@@ -252,11 +234,7 @@ class SpMV:
         (row, score_bits, state), as the call before returned it. Returns (idx, val, n, total, next): idx / val of k entries, the
         first n real, the rest pads; total = the eligible rows behind the cursor, this page included; next = the cursor of the
         following page, state CURSOR_END when this page was the last."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self._install(vec, allow)
         return self._run_after(cursor, allow is not None)
 
     def _run_after(self, cursor, use_filter, boosted=False):
@@ -268,8 +246,7 @@ class SpMV:
         val = np.zeros(self.k, dtype=np.float32)
         n, total, nxt = C.c_int32(0), C.c_uint32(0), _lib.Cursor()
         run = _lib.lib().tkspmv_run_boosted if boosted else _lib.lib().tkspmv_run_after
-        _lib.check(run(self._h, cur, int(use_filter), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), C.byref(total), C.byref(nxt)))
+        _lib.check(run(self._h, cur, int(use_filter), u32p(idx), f32p(val), C.byref(n), C.byref(total), C.byref(nxt)))
         return idx, val, int(n.value), int(total.value), (int(nxt.row), int(nxt.score_bits), int(nxt.state))
 
     def pages(self, vec=None, allow=None):
@@ -277,12 +254,16 @@ class SpMV:
         run_after): yields (values, indices) of each page's real entries, ordered like read_result, until the cursor says END --
         no empty trailing page, and no page at all when no row is eligible. The query vector and the mask must stay installed
         while the generator is in use."""
-        idx, val, n, _, cursor = self.run_after(None, vec, allow)
+        yield from self._pages(self.run_after(None, vec, allow), allow is not None, False)
+
+    def _pages(self, page, use_filter, boosted):
+        """The walk behind pages() and boosted_pages(): from the first page (run_after's tuple) on until the cursor says END."""
+        idx, val, n, _, cursor = page
         while n:
             yield val[:n], idx[:n]
             if cursor[2] == _lib.CURSOR_END:
                 return
-            idx, val, n, _, cursor = self._run_after(cursor, allow is not None)
+            idx, val, n, _, cursor = self._run_after(cursor, use_filter, boosted)
 
     def set_boost(self, weight=None, bias=None):
         """Installs the boost of boosted queries: float32 weight[r] and bias[r] for every local row r, either may be None (no
@@ -296,7 +277,7 @@ class SpMV:
                     raise ValueError(f"{name} has shape {np.shape(a)}, expected ({self.num_rows},)")
                 a = np.ascontiguousarray(a, dtype=np.float32)
             arrays.append(a)
-        _lib.check(_lib.lib().tkspmv_set_boost(self._h, *(a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None for a in arrays)))
+        _lib.check(_lib.lib().tkspmv_set_boost(self._h, *(f32p(a) for a in arrays)))
 
     def set_cosine(self):
         """Installs the cosine weights 1 / ||row r||_2 (row_stats(ROW_INV_L2)) as the boost and removes any installed bias: the state
@@ -312,20 +293,15 @@ class SpMV:
         multiply / no add; both 0: the boost installed by set_boost). Every other argument and the outputs are enqueue_after's,
         read on the boosted score: the cursors' score_bits are boosted scores, and min_score applies to them. No host sync; one
         enqueue_after or enqueue_boosted call in flight at a time (they share their scratch)."""
-        p = lambda a: C.c_void_p(int(a)) if a else None
-        _lib.check(_lib.lib().tkspmv_enqueue_boosted(self._h, p(dev_xs), int(count), p(dev_weight), p(dev_bias), int(boost_stride), p(dev_cursors),
-                                                     p(dev_mask), int(mask_stride), p(dev_idx), p(dev_val), p(dev_n), p(dev_total), p(dev_next),
-                                                     C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_boosted(self._h, ptr(dev_xs), int(count), ptr(dev_weight), ptr(dev_bias), int(boost_stride),
+                                                     ptr(dev_cursors), ptr(dev_mask), int(mask_stride), ptr(dev_idx), ptr(dev_val), ptr(dev_n),
+                                                     ptr(dev_total), ptr(dev_next), ptr(stream)))
 
     def run_boosted(self, cursor=None, vec=None, allow=None, weight=None, bias=None):
         """run_after over boosted scores: reset(vec) / set_filter(allow) if given, set_boost(weight, bias) if either is given
         (else the boost installed before), then the k eligible rows behind `cursor` in the order of the boosted scores. Returns
         run_after's tuple (idx, val, n, total, next); val holds boosted scores."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self._install(vec, allow)
         if weight is not None or bias is not None:
             self.set_boost(weight, bias)
         return self._run_after(cursor, allow is not None, True)
@@ -333,33 +309,22 @@ class SpMV:
     def boosted_pages(self, vec=None, allow=None, weight=None, bias=None):
         """pages() over boosted scores (arguments as in run_boosted): yields (values, indices) of each page's real entries until the
         cursor says END. The query vector, the mask and the boost must stay installed while the generator is in use."""
-        idx, val, n, _, cursor = self.run_boosted(None, vec, allow, weight, bias)
-        while n:
-            yield val[:n], idx[:n]
-            if cursor[2] == _lib.CURSOR_END:
-                return
-            idx, val, n, _, cursor = self._run_after(cursor, allow is not None, True)
+        yield from self._pages(self.run_boosted(None, vec, allow, weight, bias), allow is not None, True)
 
     def enqueue_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_idx=0, dev_val=0, capacity=0, dev_mask=0, mask_stride=0, stream=0):
         """Range queries: for query i (dev_xs + i*cols; dev_xs = 0 with count = 1: the vector installed by reset()) every row that
         has entries, is allowed by dev_mask + i*mask_stride words (0: unfiltered) and scores >= dev_thresholds[i]. dev_counts[i]
         receives the number of matches; dev_idx / dev_val + i*capacity the first min(count, capacity) of them, in no particular
         order (capacity = 0 with no outputs: count only). No host sync, no engine state touched."""
-        _lib.check(_lib.lib().tkspmv_enqueue_range(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
-                                                   C.c_void_p(int(dev_thresholds)) if dev_thresholds else None,
-                                                   C.c_void_p(int(dev_mask)) if dev_mask else None, int(mask_stride),
-                                                   C.c_void_p(int(dev_idx)) if dev_idx else None,
-                                                   C.c_void_p(int(dev_val)) if dev_val else None, int(capacity),
-                                                   C.c_void_p(int(dev_counts)) if dev_counts else None,
-                                                   C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_range(self._h, ptr(dev_xs), int(count), ptr(dev_thresholds), ptr(dev_mask), int(mask_stride),
+                                                   ptr(dev_idx), ptr(dev_val), int(capacity), ptr(dev_counts), ptr(stream)))
 
     def _run_range(self, threshold, use_filter, capacity):
         idx = np.zeros(max(capacity, 1), dtype=np.uint32)
         val = np.zeros(max(capacity, 1), dtype=np.float32)
         count = C.c_uint64(0)
-        _lib.check(_lib.lib().tkspmv_run_range(self._h, float(threshold), int(use_filter),
-                                               idx.ctypes.data_as(C.POINTER(C.c_uint32)) if capacity else None,
-                                               val.ctypes.data_as(C.POINTER(C.c_float)) if capacity else None, int(capacity), C.byref(count)))
+        _lib.check(_lib.lib().tkspmv_run_range(self._h, float(threshold), int(use_filter), u32p(idx) if capacity else None,
+                                               f32p(val) if capacity else None, int(capacity), C.byref(count)))
         n = min(int(count.value), capacity)
         return val[:n], idx[:n], int(count.value)
 
@@ -368,11 +333,7 @@ class SpMV:
         row_mask() words; the query is then restricted to it), then every row scoring >= threshold. Returns (values, indices)
         sorted like read_result. capacity=None: the count is asked for first, then exactly that many (the set is deterministic);
         else at most `capacity` matches are returned and last_range_count holds the true number."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self._install(vec, allow)
         use_filter = allow is not None
         if capacity is None:
             _, _, capacity = self._run_range(threshold, use_filter, 0)
@@ -385,9 +346,8 @@ class SpMV:
         every query), restricted to dev_mask + i*mask_stride words (0: unfiltered). dev_out + i*out_stride receives the mask's
         ceil(rows/32) words (out_stride = 0 with count = 1), valid wherever a mask is accepted; dev_counts[i] (optional) the number of
         matching rows. No host sync, no engine state touched."""
-        p = lambda a: C.c_void_p(int(a)) if a else None
-        _lib.check(_lib.lib().tkspmv_enqueue_match(self._h, p(dev_clauses), int(clause_stride), p(dev_preds), int(count), p(dev_mask), int(mask_stride),
-                                                   p(dev_out), int(out_stride), p(dev_counts), C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_match(self._h, ptr(dev_clauses), int(clause_stride), ptr(dev_preds), int(count), ptr(dev_mask),
+                                                   int(mask_stride), ptr(dev_out), int(out_stride), ptr(dev_counts), ptr(stream)))
 
     def match(self, clauses, pred, allow=None, install=False):
         """One term predicate with host arrays: clauses (uint32[cols]) and pred (must, must_not, should, min_should) as bool_query()
@@ -397,14 +357,12 @@ class SpMV:
         t = np.ascontiguousarray(clauses, dtype=np.uint32)
         if t.shape != (self.num_cols,):
             raise ValueError(f"clause table has shape {t.shape}, expected ({self.num_cols},)")
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
+        self._install(allow=allow)
         rec = _lib.Match(*(int(v) & 0xFFFFFFFF for v in pred))
         words = np.zeros(max(1, (self.num_rows + 31) // 32), dtype=np.uint32)
         count = C.c_uint64(0)
-        _lib.check(_lib.lib().tkspmv_run_match(self._h, t.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(rec), int(allow is not None), int(bool(install)),
-                                               words.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        _lib.check(_lib.lib().tkspmv_run_match(self._h, u32p(t), C.byref(rec), int(allow is not None), int(bool(install)), u32p(words),
+                                               C.byref(count)))
         return words, int(count.value)
 
     def enqueue_facets(self, dev_xs, count, dev_thresholds, dev_counts, n_bins=0, dev_labels=0, dev_best=0, dev_totals=0, dev_mask=0, mask_stride=0,
@@ -414,28 +372,21 @@ class SpMV:
         labels of set_groups(). dev_counts[i*n_bins + b] receives the matches with label b; dev_best (optional, _lib.FacetBest
         records) each bin's match that comes first in the result order, (0, 0) for an empty bin; dev_totals[i] (optional) all
         matches. No host sync, no engine state touched."""
-        p = lambda a: C.c_void_p(int(a)) if a else None
-        _lib.check(_lib.lib().tkspmv_enqueue_facets(self._h, p(dev_xs), int(count), p(dev_thresholds), p(dev_mask), int(mask_stride), p(dev_labels),
-                                                    int(n_bins), p(dev_counts), p(dev_best), p(dev_totals), C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_facets(self._h, ptr(dev_xs), int(count), ptr(dev_thresholds), ptr(dev_mask), int(mask_stride),
+                                                    ptr(dev_labels), int(n_bins), ptr(dev_counts), ptr(dev_best), ptr(dev_totals), ptr(stream)))
 
     def run_facets(self, threshold, vec=None, allow=None, groups=None):
         """One facet query with host arrays: reset(vec) if given, set_filter(allow) if given (a bool array of length rows, or
         row_mask() words; the query is then restricted to it), set_groups(groups) if given, then the rows scoring >= threshold
         counted per installed label. Returns (counts, best_idx, best_val, total): per group its matches and the row id and score
         of its best match ((0, 0.0) for a group without one), and the number of all matches."""
-        if vec is not None:
-            self.reset(vec)
-        if allow is not None:
-            a = np.asarray(allow)
-            self.set_filter(row_mask(self.num_rows, a) if a.dtype == np.bool_ else a)
-        if groups is not None:
-            self.set_groups(groups)
+        self._install(vec, allow, groups)
         n = max(1, self._n_groups)  # (none installed: the library says so and writes nothing)
         counts = np.zeros(n, dtype=np.uint32)
-        best = np.zeros((n, 2), dtype=np.uint32)
+        records = (_lib.FacetBest * n)()
         total = C.c_uint64(0)
-        _lib.check(_lib.lib().tkspmv_run_facets(self._h, float(threshold), int(allow is not None), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                best.ctypes.data_as(C.POINTER(_lib.FacetBest)), C.byref(total)))
+        _lib.check(_lib.lib().tkspmv_run_facets(self._h, float(threshold), int(allow is not None), u32p(counts), records, C.byref(total)))
+        best = np.frombuffer(records, dtype=np.uint32).reshape(n, 2)
         n = self._n_groups
         return counts[:n], best[:n, 0].copy(), best[:n, 1].copy().view(np.float32), int(total.value)
 
@@ -445,9 +396,7 @@ class SpMV:
         in order). dev_len[i] (optional) receives the row's number of entries, 0xFFFFFFFF for an id outside the engine's rows (a
         zero vector). The output feeds enqueue_batch / enqueue_filtered / enqueue_range / enqueue_multi unchanged. No host sync, no
         engine state touched."""
-        _lib.check(_lib.lib().tkspmv_enqueue_row_vectors(self._h, C.c_void_p(int(dev_rows)) if dev_rows else None, int(count),
-                                                         C.c_void_p(int(dev_xs)) if dev_xs else None,
-                                                         C.c_void_p(int(dev_len)) if dev_len else None, C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_row_vectors(self._h, ptr(dev_rows), int(count), ptr(dev_xs), ptr(dev_len), ptr(stream)))
 
     def row_vectors(self, rows):
         """enqueue_row_vectors with host arrays: (xs[n, cols] float32, lengths[n] uint32) of the given global row ids. Waits."""
@@ -455,8 +404,7 @@ class SpMV:
         xs = np.empty((ids.size, self.num_cols), dtype=np.float32)
         ln = np.empty(ids.size, dtype=np.uint32)
         if ids.size:
-            _lib.check(_lib.lib().tkspmv_row_vectors(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size),
-                                                     xs.ctypes.data_as(C.POINTER(C.c_float)), ln.ctypes.data_as(C.POINTER(C.c_uint32))))
+            _lib.check(_lib.lib().tkspmv_row_vectors(self._h, u32p(ids), int(ids.size), f32p(xs), u32p(ln)))
         return xs, ln
 
     def similar(self, rows, exclude_self=False):
@@ -467,8 +415,7 @@ class SpMV:
         idx = np.zeros((ids.size, self.k), dtype=np.uint32)
         val = np.zeros((ids.size, self.k), dtype=np.float32)
         if ids.size:
-            _lib.check(_lib.lib().tkspmv_run_similar(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size), int(bool(exclude_self)),
-                                                     idx.ctypes.data_as(C.POINTER(C.c_uint32)), val.ctypes.data_as(C.POINTER(C.c_float))))
+            _lib.check(_lib.lib().tkspmv_run_similar(self._h, u32p(ids), int(ids.size), int(bool(exclude_self)), u32p(idx), f32p(val)))
         return val, idx
 
     def enqueue_score_rows(self, dev_xs, count, dev_rows, n_rows, dev_scores, rows_stride=0, stream=0):
@@ -477,9 +424,8 @@ class SpMV:
         count = 1: the vector installed by reset()), bit for bit the value every other path reports. Computed from the rows' own
         packets: the matrix is not streamed. A row without entries scores +0.0, an id outside the engine's rows -inf. No host sync,
         no engine state touched."""
-        _lib.check(_lib.lib().tkspmv_enqueue_score_rows(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
-                                                        C.c_void_p(int(dev_rows)) if dev_rows else None, int(n_rows), int(rows_stride),
-                                                        C.c_void_p(int(dev_scores)) if dev_scores else None, C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_score_rows(self._h, ptr(dev_xs), int(count), ptr(dev_rows), int(n_rows), int(rows_stride),
+                                                        ptr(dev_scores), ptr(stream)))
 
     def score_rows(self, rows, vecs=None):
         """enqueue_score_rows with host arrays: float32[count, n_rows] scores of the given global row ids. rows: 1-D (one list for
@@ -500,9 +446,7 @@ class SpMV:
         n_rows = int(ids.shape[-1])
         out = np.empty((count, n_rows), dtype=np.float32)
         if count and n_rows:
-            _lib.check(_lib.lib().tkspmv_score_rows(self._h, xs.ctypes.data_as(C.POINTER(C.c_float)) if xs is not None else None, count,
-                                                    ids.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, n_rows if ids.ndim == 2 else 0,
-                                                    out.ctypes.data_as(C.POINTER(C.c_float))))
+            _lib.check(_lib.lib().tkspmv_score_rows(self._h, f32p(xs), count, u32p(ids), n_rows, n_rows if ids.ndim == 2 else 0, f32p(out)))
         return out
 
     def enqueue_row_stats(self, kind, dev_out, stream=0):
@@ -511,12 +455,12 @@ class SpMV:
         inf or NaN). The sums are float32 in the order every streaming path sums a row's score in; a row without entries gives
         +0.0. One pass over the matrix. No host sync, no engine state touched. ROW_INV_L2 or ROW_NNZ in a device array of the
         caller's is what per-query or combined weights for enqueue_boosted(dev_weight=...) are made from."""
-        _lib.check(_lib.lib().tkspmv_enqueue_row_stats(self._h, int(kind), C.c_void_p(int(dev_out)) if dev_out else None, C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_row_stats(self._h, int(kind), ptr(dev_out), ptr(stream)))
 
     def row_stats(self, kind):
         """enqueue_row_stats with a host array: float32[rows] of the given kind. Waits."""
         out = np.empty(max(self.num_rows, 1), dtype=np.float32)
-        _lib.check(_lib.lib().tkspmv_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
+        _lib.check(_lib.lib().tkspmv_row_stats(self._h, int(kind), f32p(out)))
         return out[:self.num_rows]
 
     def enqueue_col_stats(self, kind, out, masks=None, mask_stride=0, out_stride=0, stream=None, count=1):
@@ -526,15 +470,14 @@ class SpMV:
         sets, set i the rows of the allow-mask at masks + i*mask_stride words (row_mask() words by LOCAL row; stride 0: the same mask),
         written at out + i*out_stride words (>= cols when count > 1). Exact and bit-reproducible; one pass over the matrix per set.
         No host sync, no engine state touched."""
-        p = lambda a: C.c_void_p(int(a)) if a else None
-        _lib.check(_lib.lib().tkspmv_enqueue_col_stats(self._h, int(kind), int(count), p(masks), int(mask_stride), p(out), int(out_stride),
-                                                       C.c_void_p(int(stream or 0))))
+        _lib.check(_lib.lib().tkspmv_enqueue_col_stats(self._h, int(kind), int(count), ptr(masks), int(mask_stride), ptr(out), int(out_stride),
+                                                       ptr(stream)))
 
     def col_stats(self, kind, use_filter=False):
         """enqueue_col_stats with a host array: uint32[cols] (COL_NNZ) or float32[cols] (COL_MAX, COL_MIN) over all rows, or with
         use_filter among the rows of the mask set_filter() installed. Waits."""
         out = np.empty(max(self.num_cols, 1), dtype=np.uint32)
-        _lib.check(_lib.lib().tkspmv_col_stats(self._h, int(kind), int(bool(use_filter)), out.ctypes.data_as(C.c_void_p)))
+        _lib.check(_lib.lib().tkspmv_col_stats(self._h, int(kind), int(bool(use_filter)), ptr(out.ctypes.data)))
         out = out[:self.num_cols]
         return out if int(kind) == _lib.COL_NNZ else out.view(np.float32)
 
@@ -554,15 +497,12 @@ class SpMV:
         """enqueue_batch with several queries per pass over the matrix (info()["multi_q"] of them share every chunk that
         is loaded; engine created with multi_q > 0). Same arguments; dev_xs = 0 with count = 1: the vector installed by
         reset(). No host sync."""
-        _lib.check(_lib.lib().tkspmv_enqueue_multi(self._h, C.c_void_p(int(dev_xs)) if dev_xs else None, int(count),
-                                                   C.c_void_p(int(dev_idx)) if dev_idx else None,
-                                                   C.c_void_p(int(dev_val)) if dev_val else None,
-                                                   C.c_void_p(int(stream))))
+        _lib.check(_lib.lib().tkspmv_enqueue_multi(self._h, ptr(dev_xs), int(count), ptr(dev_idx), ptr(dev_val), ptr(stream)))
 
     def time_multi(self, dev_xs, n_x, iters):
         """ns per query of `iters` queries through the multi-query path (one hipEvent pair around the sequence)."""
         ns = C.c_double()
-        _lib.check(_lib.lib().tkspmv_time_multi(self._h, C.c_void_p(int(dev_xs)), int(n_x), int(iters), C.byref(ns)))
+        _lib.check(_lib.lib().tkspmv_time_multi(self._h, ptr(dev_xs), int(n_x), int(iters), C.byref(ns)))
         return ns.value
 
     def debug_counters(self):
@@ -594,12 +534,12 @@ class SpMV:
     def scores(self):
         """Full y = A.x of the current query (verification aid; the hot path never materialises it)."""
         y = np.empty(max(self.num_rows, 1), dtype=np.float32)
-        _lib.check(_lib.lib().tkspmv_scores(self._h, y.ctypes.data_as(C.POINTER(C.c_float))))
+        _lib.check(_lib.lib().tkspmv_scores(self._h, f32p(y)))
         return y[:self.num_rows]
 
     def profile(self, dev_xs, n_x, iters):
         t = _lib.Timing()
-        _lib.check(_lib.lib().tkspmv_profile(self._h, C.c_void_p(int(dev_xs)), int(n_x), int(iters), C.byref(t)))
+        _lib.check(_lib.lib().tkspmv_profile(self._h, ptr(dev_xs), int(n_x), int(iters), C.byref(t)))
         return {n: getattr(t, n) for n, _ in t._fields_ if n != "reserved"}
 
     def result_device(self):
@@ -627,28 +567,32 @@ class SpMV:
             pass
 
 
+@contextmanager
+def _one_shot(m, **kw):
+    """The engine of a one-shot helper: built for CooMatrix m with the helper's keywords, closed when the helper is done with it."""
+    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, **kw)
+    try:
+        yield e
+    finally:
+        e.close()
+
+
 def topk_spmv(m, vec, k=100, allow=None, **kw):
     """One-shot helper: build the engine for CooMatrix m, run one query, return (values, indices). allow: a bool array of
     length m.rows (or row_mask() words): the top-k among those rows only (filtered query)."""
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
-    try:
+    with _one_shot(m, vec=vec, k=k, **kw) as e:
         if allow is not None:
             return e.run_filtered(allow=allow)
         e()
         return e.read_result()
-    finally:
-        e.close()
 
 
 def range_spmv(m, vec, threshold, allow=None, **kw):
     """One-shot helper: build the engine for CooMatrix m, return (values, indices) of every row scoring >= threshold (among the
     rows of `allow`, if given), sorted like topk_spmv's result."""
     kw.setdefault("k", 8)
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
-    try:
+    with _one_shot(m, vec=vec, **kw) as e:
         return e.run_range(threshold, allow=allow)
-    finally:
-        e.close()
 
 
 def facet_spmv(m, vec, threshold, groups, n_groups=None, allow=None, **kw):
@@ -656,30 +600,23 @@ def facet_spmv(m, vec, threshold, groups, n_groups=None, allow=None, **kw):
     threshold (among the rows of `allow`, if given) per label groups[r] < n_groups (None: the largest label + 1): each label's
     matches, the row id and score of its best match ((0, 0.0) where it has none), and the number of all matches."""
     kw.setdefault("k", 8)
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, **kw)
-    try:
+    with _one_shot(m, vec=vec, **kw) as e:
         e.set_groups(groups, n_groups)
         return e.run_facets(threshold, allow=allow)
-    finally:
-        e.close()
 
 
 def grouped_spmv(m, vec, groups, k=100, allow=None, **kw):
     """One-shot helper: build the engine for CooMatrix m, return (values, indices, groups) of the k best groups of rows (labels
     groups[r], one per row), each by its best row (among the rows of `allow`, if given), ordered like topk_spmv's result."""
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
-    try:
+    with _one_shot(m, vec=vec, k=k, **kw) as e:
         return e.run_grouped(allow=allow, groups=groups)
-    finally:
-        e.close()
 
 
 def ranked_spmv(m, vec, n, k=MAX_PAGE, allow=None, **kw):
     """One-shot helper: build the engine for CooMatrix m with pages of k rows, return (values, indices) of the n best rows (among
     the rows of `allow`, if given) for ANY n, by search-after paging: ordered like topk_spmv's result, fewer than n when fewer
     rows are eligible."""
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
-    try:
+    with _one_shot(m, vec=vec, k=k, **kw) as e:
         vals, idxs, have = [], [], 0
         for v, i in e.pages(allow=allow):
             vals.append(v)
@@ -690,20 +627,15 @@ def ranked_spmv(m, vec, n, k=MAX_PAGE, allow=None, **kw):
         if not vals:
             return np.empty(0, dtype=np.float32), np.empty(0, dtype=np.uint32)
         return np.concatenate(vals)[:int(n)], np.concatenate(idxs)[:int(n)]
-    finally:
-        e.close()
 
 
 def boosted_spmv(m, vec, k, weight=None, bias=None, allow=None, **kw):
     """One-shot helper: build the engine for CooMatrix m, return (values, indices) of the k rows (among the rows of `allow`, if
     given) with the best boosted scores weight[r] * score + bias[r] (either array may be None, not both), ordered like
     topk_spmv's result; values are boosted scores."""
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=vec, k=k, **kw)
-    try:
+    with _one_shot(m, vec=vec, k=k, **kw) as e:
         idx, val, n, _, _ = e.run_boosted(allow=allow, weight=weight, bias=bias)
         return val[:n], idx[:n]
-    finally:
-        e.close()
 
 
 def cosine_spmv(m, vec, k, allow=None, **kw):
@@ -713,13 +645,10 @@ def cosine_spmv(m, vec, k, allow=None, **kw):
     v = np.asarray(vec, dtype=np.float64)
     norm = float(np.sqrt(np.sum(v * v)))
     x = (v / norm if norm > 0 else v).astype(np.float32)
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, vec=x, k=k, **kw)
-    try:
+    with _one_shot(m, vec=x, k=k, **kw) as e:
         e.set_cosine()
         idx, val, n, _, _ = e.run_boosted(allow=allow)
         return val[:n], idx[:n]
-    finally:
-        e.close()
 
 
 def knn_graph(m, k, rows=None, **kw):
@@ -731,9 +660,6 @@ def knn_graph(m, k, rows=None, **kw):
         raise ValueError(f"k + 1 must be in [2, {_lib.MAX_K}]")
     first_row = int(kw.get("first_row", 0))
     ids = np.arange(first_row, first_row + m.rows, dtype=np.uint32) if rows is None else np.asarray(rows, dtype=np.uint32)
-    e = SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k + 1, **kw)
-    try:
+    with _one_shot(m, k=k + 1, **kw) as e:
         val, idx = e.similar(ids, exclude_self=True)
         return val[:, :k].copy(), idx[:, :k].copy()
-    finally:
-        e.close()

@@ -58,16 +58,14 @@ def write_mtx(path, m, index_base=1, precision=10):
     row = np.ascontiguousarray(m.row, dtype=np.uint32)
     col = np.ascontiguousarray(m.col, dtype=np.uint32)
     val = np.ascontiguousarray(m.val, dtype=np.float32)
-    _lib.check(_lib.lib().tkspmv_mtx_write(
-        str(path).encode(), m.rows, m.cols, row.shape[0], row.ctypes.data_as(C.POINTER(C.c_uint32)),
-        col.ctypes.data_as(C.POINTER(C.c_uint32)), val.ctypes.data_as(C.POINTER(C.c_float)), index_base, precision))
+    _lib.check(_lib.lib().tkspmv_mtx_write(str(path).encode(), m.rows, m.cols, row.shape[0], _lib.u32p(row), _lib.u32p(col), _lib.f32p(val),
+                                           index_base, precision))
 
 
 def create_sample_vector(size, random=False, sum_to_one=True, norm_one=False, seed=0):
     """Same argument order and defaults as the reference; seed == 0 draws from std::random_device."""
     vec = np.empty(size, dtype=np.float32)
-    _lib.check(_lib.lib().tkspmv_sample_vector(vec.ctypes.data_as(C.POINTER(C.c_float)), size, int(random),
-                                               int(sum_to_one), int(norm_one), int(seed)))
+    _lib.check(_lib.lib().tkspmv_sample_vector(_lib.f32p(vec), size, int(random), int(sum_to_one), int(norm_one), int(seed)))
     return vec
 
 
@@ -98,6 +96,19 @@ def row_mask(rows, allow=None, exclude=None):
     return np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32)
 
 
+def _allow_words(rows, allow):
+    """The `allow` argument of the host-array calls (SpMV.run_filtered and the like, Packed.col_stats) as contiguous uint32 mask
+    words: a bool array of length rows goes through row_mask(), anything else is taken as mask words. The callers check the length."""
+    a = np.asarray(allow)
+    return np.ascontiguousarray(row_mask(rows, a) if a.dtype == np.bool_ else a, dtype=np.uint32)
+
+
+def _order_key(f):
+    """Monotone float32 -> uint32, the engine's order_key."""
+    u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
 def collapse_topk(scores, present, groups, k, min_score=0.0, first_row=0):
     """The contract of grouped top-k (SpMV.enqueue_grouped) restated in numpy, for CPU-side users and as the tests' expectation:
     from float32 scores[rows], present[rows] (the row is eligible apart from its score: it has entries and is allowed) and
@@ -110,13 +121,8 @@ def collapse_topk(scores, present, groups, k, min_score=0.0, first_row=0):
     ok = np.asarray(present).astype(bool)
     if y.ndim != 1 or g.shape != y.shape or ok.shape != y.shape:
         raise ValueError("scores, present and groups must be 1-D arrays of one length")
-
-    def order_key(f):  # monotone float32 -> uint32, the engine's order_key
-        u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
-        return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
-
-    key = order_key(y)
-    ok = ok & (key >= order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
+    key = _order_key(y)
+    ok = ok & (key >= _order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
     rows = np.flatnonzero(ok)
     ckey = (key[rows].astype(np.uint64) << np.uint64(32)) | rows.astype(np.uint64)
     order = np.argsort(ckey, kind="stable")[::-1]  # (keys are unique: they carry the row)
@@ -153,19 +159,14 @@ def page_after(y, present, k, cursor=None, min_score=0.0, first_row=0, allow=Non
             raise ValueError("allow must be a bool array of y's length")
         ok = ok & a
     k = int(k)
-
-    def order_key(f):  # monotone float32 -> uint32, the engine's order_key
-        u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
-        return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
-
-    key = order_key(y)
-    ok = ok & (key >= order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
+    key = _order_key(y)
+    ok = ok & (key >= _order_key(np.array([min_score], dtype=np.float32))[0]) & (y > -np.inf)
     rows = np.flatnonzero(ok)
     ckey = (key[rows].astype(np.uint64) << np.uint64(32)) | (rows.astype(np.uint64) + np.uint64(int(first_row)))
     if cursor is not None:
         c_row, c_bits, c_state = (int(v) for v in cursor)
         if c_state == 1:
-            c_key = order_key(np.array([c_bits], dtype=np.uint32).view(np.float32))[0]
+            c_key = _order_key(np.array([c_bits], dtype=np.uint32).view(np.float32))[0]
             behind = ckey < ((np.uint64(c_key) << np.uint64(32)) | np.uint64(c_row & 0xFFFFFFFF))
         else:
             behind = np.full(rows.shape, c_state == 0)
@@ -412,8 +413,7 @@ def generate_degrees(row_begin, row_end, avg_nnz, distribution="gamma", seed=1):
     """Row lengths of rows [row_begin, row_end) of the generated matrix (uint32 array)."""
     dist = {"uniform": 0, "gamma": 1}[distribution]
     deg = np.empty(max(row_end - row_begin, 1), dtype=np.uint32)
-    _lib.check(_lib.lib().tkspmv_generate_degrees(row_begin, row_end, avg_nnz, dist, seed,
-                                                  deg.ctypes.data_as(C.POINTER(C.c_uint32))))
+    _lib.check(_lib.lib().tkspmv_generate_degrees(row_begin, row_end, avg_nnz, dist, seed, _lib.u32p(deg)))
     return deg[:row_end - row_begin]
 
 
@@ -453,16 +453,12 @@ def sell_roundtrip(m, n_wave_partitions=4088, precision=_lib.F32):
     d = _lib.Desc()
     d.rows, d.cols, d.nnz = m.rows, m.cols, row.shape[0]
     d.precision = int(precision)  # Q1_7_F32: byte chunks (Q1.7 rounded to nearest; decoded values are the rounded ones)
-    d.row = row.ctypes.data_as(C.POINTER(C.c_uint32))
-    d.col = col.ctypes.data_as(C.POINTER(C.c_uint32))
-    d.val = val.ctypes.data_as(C.POINTER(C.c_float))
+    d.row, d.col, d.val = _lib.u32p(row), _lib.u32p(col), _lib.f32p(val)
     nn = max(int(d.nnz), 1)
     orow, ocol, oval = np.empty(nn, np.uint32), np.empty(nn, np.uint32), np.empty(nn, np.float32)
     n = C.c_uint64()
     info = (C.c_uint64 * 6)()
-    _lib.check(_lib.lib().tkspmv_sell_roundtrip(
-        C.byref(d), int(n_wave_partitions), orow.ctypes.data_as(C.POINTER(C.c_uint32)), ocol.ctypes.data_as(C.POINTER(C.c_uint32)),
-        oval.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), info))
+    _lib.check(_lib.lib().tkspmv_sell_roundtrip(C.byref(d), int(n_wave_partitions), _lib.u32p(orow), _lib.u32p(ocol), _lib.f32p(oval), C.byref(n), info))
     n = int(n.value)
     keys = ("slices", "chunks", "padded_entries", "partitions", "stream_bytes", "most_chunks_per_partition")
     return orow[:n], ocol[:n], oval[:n], dict(zip(keys, (int(v) for v in info)))
@@ -477,9 +473,7 @@ def sell_pack_device_check(m, n_wave_partitions=4088, precision=_lib.F32, device
     d = _lib.Desc()
     d.rows, d.cols, d.nnz = m.rows, m.cols, row.shape[0]
     d.precision, d.device = int(precision), int(device)
-    d.row = row.ctypes.data_as(C.POINTER(C.c_uint32))
-    d.col = col.ctypes.data_as(C.POINTER(C.c_uint32))
-    d.val = val.ctypes.data_as(C.POINTER(C.c_float))
+    d.row, d.col, d.val = _lib.u32p(row), _lib.u32p(col), _lib.f32p(val)
     info = (C.c_uint64 * 3)()
     ms = (C.c_double * 4)()
     _lib.check(_lib.lib().tkspmv_sell_pack_device_check(C.byref(d), int(n_wave_partitions), info, ms))
@@ -500,9 +494,7 @@ class Packed:
         self._val = np.ascontiguousarray(m.val, dtype=np.float32)
         d = _lib.Desc()
         d.rows, d.cols, d.nnz = m.rows, m.cols, self._row.shape[0]
-        d.row = self._row.ctypes.data_as(C.POINTER(C.c_uint32))
-        d.col = self._col.ctypes.data_as(C.POINTER(C.c_uint32))
-        d.val = self._val.ctypes.data_as(C.POINTER(C.c_float))
+        d.row, d.col, d.val = _lib.u32p(self._row), _lib.u32p(self._col), _lib.f32p(self._val)
         d.k, d.precision, d.nnz_per_lane, d.fixed_width = k, precision, nnz_per_lane, fixed_width
         d.device = device
         self.pack_ms = None
@@ -549,9 +541,7 @@ class Packed:
         col = np.empty(max(self.nnz, 1), dtype=np.uint32)
         val = np.empty(max(self.nnz, 1), dtype=np.float32)
         n = C.c_uint64()
-        _lib.check(_lib.lib().tkspmv_packed_decode(
-            self._h, row.ctypes.data_as(C.POINTER(C.c_uint32)), col.ctypes.data_as(C.POINTER(C.c_uint32)),
-            val.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        _lib.check(_lib.lib().tkspmv_packed_decode(self._h, _lib.u32p(row), _lib.u32p(col), _lib.f32p(val), C.byref(n)))
         n = int(n.value)
         return row[:n], col[:n], val[:n]
 
@@ -564,8 +554,7 @@ class Packed:
         col = np.empty(max(n.value, 1), dtype=np.uint32)
         val = np.empty(max(n.value, 1), dtype=np.float32)
         if n.value:
-            _lib.check(L.tkspmv_packed_get_row(self._h, int(row), col.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                               val.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+            _lib.check(L.tkspmv_packed_get_row(self._h, int(row), _lib.u32p(col), _lib.f32p(val), n.value, C.byref(n)))
         return col[:n.value], val[:n.value]
 
     def score_rows(self, x, rows):
@@ -578,9 +567,7 @@ class Packed:
             raise ValueError(f"vector has shape {xv.shape}, expected ({self.info()['cols']},)")
         out = np.empty(ids.size, dtype=np.float32)
         if ids.size:
-            _lib.check(_lib.lib().tkspmv_packed_score_rows(self._h, xv.ctypes.data_as(C.POINTER(C.c_float)),
-                                                           ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(ids.size),
-                                                           out.ctypes.data_as(C.POINTER(C.c_float))))
+            _lib.check(_lib.lib().tkspmv_packed_score_rows(self._h, _lib.f32p(xv), _lib.u32p(ids), int(ids.size), _lib.f32p(out)))
         return out
 
     def row_stats(self, kind):
@@ -589,7 +576,7 @@ class Packed:
         matrix reports (SpMV.row_stats): the sums are formed in the streaming kernels' order, on the host. A row without entries
         gives +0.0. fp32 values only (TkspmvError ERR_UNSUPPORTED otherwise); ERR_INVALID for a kind outside 0..3."""
         out = np.empty(max(int(self.info()["rows"]), 1), dtype=np.float32)
-        _lib.check(_lib.lib().tkspmv_packed_row_stats(self._h, int(kind), out.ctypes.data_as(C.POINTER(C.c_float))))
+        _lib.check(_lib.lib().tkspmv_packed_row_stats(self._h, int(kind), _lib.f32p(out)))
         return out[:int(self.info()["rows"])]
 
     def col_stats(self, kind, allow=None):
@@ -600,13 +587,11 @@ class Packed:
         rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
         words = None
         if allow is not None:
-            a = np.asarray(allow)
-            words = np.ascontiguousarray(row_mask(rows, a) if a.dtype == np.bool_ else a, dtype=np.uint32)
+            words = _allow_words(rows, allow)
             if words.shape != (max(1, (rows + 31) // 32),):
                 raise ValueError("allow must be bool[rows] or ceil(rows / 32) mask words")
         out = np.empty(max(cols, 1), dtype=np.uint32)
-        _lib.check(_lib.lib().tkspmv_packed_col_stats(self._h, int(kind), words.ctypes.data_as(C.POINTER(C.c_uint32)) if words is not None else None,
-                                                      out.ctypes.data_as(C.c_void_p)))
+        _lib.check(_lib.lib().tkspmv_packed_col_stats(self._h, int(kind), _lib.u32p(words), _lib.ptr(out.ctypes.data)))
         out = out[:cols]
         return out if int(kind) == _lib.COL_NNZ else out.view(np.float32)
 
