@@ -1,6 +1,5 @@
 """Search-after paging without a GPU: the symbols of every layer, the cursor's size on both sides, argument checks that come before
-any device call, the numpy restatement of the contract (page_after) pinned to the oracle's selection and to a plain loop, and the
-resource report of the new kernels."""
+any device call, the numpy restatement of the contract (page_after) pinned to the oracle's selection and to a plain loop."""
 import ctypes as C
 import os
 import re
@@ -8,14 +7,11 @@ import re
 import numpy as np
 import pytest
 
+from support import bits_of, order_key
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
 CSRC = os.path.join(ROOT, "approximate-spmv-topk_amd", "csrc")
 NAMES = ("tkspmv_enqueue_after", "tkspmv_run_after")
-# what the existing report tests pick their kernel families by: the new kernels' names must match none of them
-FAMILY_SUBSTRINGS = ("stream_kernel", "batch_kernel", "multi_kernel", "range_kernel", "row_vectors_kernel", "score_rows_kernel", "stream_filter_kernel",
-                     "group_best_kernel", "group_split_kernel", "group_ids_kernel")
-NEW_KERNELS = ("after_cut_kernel", "after_finish_kernel")
 START, AFTER, END = 0, 1, 2
 
 
@@ -56,27 +52,18 @@ def test_null_engine_fails_before_any_device_call(pkg):
     assert n.value == 7 and total.value == 9 and (nxt.row, nxt.score_bits, nxt.state, nxt.reserved) == (11, 12, 13, 14)
 
 
-def _order_key(f):
-    u = int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
-
-
-def _bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
 def _loop(y, present, k, cursor, min_score, first_row):
     """The contract as a plain loop: every eligible row behind the cursor by its key, descending; the first k; what is left."""
-    kmin = _order_key(min_score)
-    keyed = [(_order_key(y[r]) << 32) | (r + first_row) for r in range(len(y)) if present[r] and _order_key(y[r]) >= kmin and y[r] > -np.inf]
+    kmin = order_key(min_score)
+    keyed = [(order_key(y[r]) << 32) | (r + first_row) for r in range(len(y)) if present[r] and order_key(y[r]) >= kmin and y[r] > -np.inf]
     if cursor is not None and cursor[2] == AFTER:
-        ceiling = (_order_key(np.array([cursor[1]], dtype=np.uint32).view(np.float32)[0]) << 32) | cursor[0]
+        ceiling = (order_key(np.array([cursor[1]], dtype=np.uint32).view(np.float32)[0]) << 32) | cursor[0]
         keyed = [c for c in keyed if c < ceiling]
     elif cursor is not None and cursor[2] != START:
         keyed = []
     keyed.sort(reverse=True)
     page = [c & 0xFFFFFFFF for c in keyed[:k]]
-    nxt = (page[-1], _bits(y[page[-1] - first_row]), AFTER) if len(keyed) > k else (0, 0, END)
+    nxt = (page[-1], bits_of(y[page[-1] - first_row]), AFTER) if len(keyed) > k else (0, 0, END)
     return page, len(keyed), nxt
 
 
@@ -140,16 +127,16 @@ def test_cursors_that_name_no_row_of_the_engine(pkg):
     absent = int(np.flatnonzero(~present & (y == 0.5))[0])
     masked = int(np.flatnonzero(present & ~allow & (y == 0.5))[0])
     cursors = [
-        (absent + first_row, _bits(0.5), AFTER),        # a row without entries
-        (masked + first_row, _bits(0.5), AFTER),        # a masked row
-        (5, _bits(0.5), AFTER),                         # below first_row: another shard's row
-        (first_row + rows + 77, _bits(0.5), AFTER),     # above the last row
-        (0xFFFFFFFF, _bits(0.5), AFTER),                # in front of every row with that score
-        (0, _bits(0.5), AFTER),                         # behind every row with that score
-        (first_row + 1500, _bits(0.3), AFTER),          # a score between two values
-        (first_row + 1500, _bits(7.0), AFTER),          # above every score: the whole ranking
-        (first_row + 1500, _bits(-3.0), AFTER),         # below min_score: nothing
-        (first_row + 1500, _bits(0.5), END), (1, 2, 3), (1, 2, 0xFFFFFFFF),  # END, and the states that act as END
+        (absent + first_row, bits_of(0.5), AFTER),        # a row without entries
+        (masked + first_row, bits_of(0.5), AFTER),        # a masked row
+        (5, bits_of(0.5), AFTER),                         # below first_row: another shard's row
+        (first_row + rows + 77, bits_of(0.5), AFTER),     # above the last row
+        (0xFFFFFFFF, bits_of(0.5), AFTER),                # in front of every row with that score
+        (0, bits_of(0.5), AFTER),                         # behind every row with that score
+        (first_row + 1500, bits_of(0.3), AFTER),          # a score between two values
+        (first_row + 1500, bits_of(7.0), AFTER),          # above every score: the whole ranking
+        (first_row + 1500, bits_of(-3.0), AFTER),         # below min_score: nothing
+        (first_row + 1500, bits_of(0.5), END), (1, 2, 3), (1, 2, 0xFFFFFFFF),  # END, and the states that act as END
     ]
     for cursor in cursors:
         for a in (None, allow):
@@ -165,20 +152,20 @@ def test_total_and_next(pkg):
     y = np.arange(1, 21, dtype=np.float32)  # rows 0..19, the best is row 19
     present = np.ones(20, dtype=bool)
     idx, val, n, total, nxt = pkg.page_after(y, present, 5)
-    assert (n, total, nxt) == (5, 20, (15, _bits(16.0), AFTER)) and idx.tolist() == [19, 18, 17, 16, 15]
-    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (5, _bits(6.0), AFTER))
+    assert (n, total, nxt) == (5, 20, (15, bits_of(16.0), AFTER)) and idx.tolist() == [19, 18, 17, 16, 15]
+    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (5, bits_of(6.0), AFTER))
     assert (n, total) == (5, 5) and idx.tolist() == [4, 3, 2, 1, 0] and nxt == (0, 0, END)  # total == k exactly: no page follows
-    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (6, _bits(7.0), AFTER))
-    assert (n, total, nxt) == (5, 6, (1, _bits(2.0), AFTER))  # one more row than a page: AFTER(the last real entry)
+    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (6, bits_of(7.0), AFTER))
+    assert (n, total, nxt) == (5, 6, (1, bits_of(2.0), AFTER))  # one more row than a page: AFTER(the last real entry)
     idx, val, n, total, nxt = pkg.page_after(y, present, 5, nxt)
     assert (n, total, nxt) == (1, 1, (0, 0, END)) and idx.tolist() == [0, 0, 0, 0, 0] and val[0] == 1.0 and np.all(val[1:] == 0)
-    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (0, _bits(1.0), AFTER))
+    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (0, bits_of(1.0), AFTER))
     assert (n, total, nxt) == (0, 0, (0, 0, END))  # nothing behind the last row
     idx, val, n, total, nxt = pkg.page_after(y, np.zeros(20, dtype=bool), 5)
     assert (n, total, nxt) == (0, 0, (0, 0, END)) and np.all(idx == 0)  # START over nothing
-    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (111, _bits(11.0), AFTER), first_row=100)
+    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (111, bits_of(11.0), AFTER), first_row=100)
     assert (n, total) == (5, 11) and idx.tolist() == [110, 109, 108, 107, 106]  # global ids: row 110 scores 11.0 and 110 < 111
-    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (10, _bits(11.0), AFTER), first_row=100)
+    idx, val, n, total, nxt = pkg.page_after(y, present, 5, (10, bits_of(11.0), AFTER), first_row=100)
     assert (n, total) == (5, 10) and idx.tolist() == [109, 108, 107, 106, 105]  # ... and 110 is not below 10
 
 
@@ -197,31 +184,3 @@ def test_signed_zeros_and_minus_infinity_like_the_device(pkg):
     assert n == total == 0 and nxt == (0, 0, END)  # ... and not behind itself
     idx, val, n, total, nxt = pkg.page_after(y, present, 5, (9, 0xFF800000, AFTER), -np.inf)
     assert n == total == 0  # a cursor at -inf: nothing is eligible behind it
-
-
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        m = re.match(r"\s*Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return kernels
-
-
-def test_after_kernels_in_resource_report():
-    k = _report()
-    for kernel in NEW_KERNELS:
-        found = {n: v for n, v in k.items() if kernel in n}
-        assert len(found) == 1, (kernel, sorted(found))
-        (name, v), = found.items()
-        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (name, v)
-        assert not any(s in name for s in FAMILY_SUBSTRINGS), name
-    cut = next(v for n, v in k.items() if "after_cut_kernel" in n)
-    assert cut["LDS Size [bytes/block]"] == 0, cut
-    assert cut["VGPRs"] <= 64, cut  # 256-thread workgroups at full occupancy

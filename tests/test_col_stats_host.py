@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import coo, signed
 from test_gpu_match import _edges
 from test_score_rows_host import _hand_made, _words
 
@@ -14,16 +15,6 @@ KINDS = (0, 1, 2)
 
 def _u32(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.ascontiguousarray(row, np.uint32), col=np.ascontiguousarray(col, np.uint32),
-                         val=np.ascontiguousarray(val, np.float32))
-
-
-def _signed(pkg, m, seed):
-    sign = np.where(np.random.default_rng(seed).random(m.val.size) < 0.5, -1.0, 1.0).astype(np.float32)
-    return _coo(pkg, m.rows, m.cols, m.row, m.col, m.val * sign)
 
 
 def padding_leak_matrix(pkg):
@@ -39,7 +30,7 @@ def padding_leak_matrix(pkg):
         row += [r] * 7
         col += [0 if r % 3 == 0 else int(c[0]), 1] + [int(x) for x in c]
         val += [0.25 + rng.random() if r % 3 == 0 else float(v[0]), -0.1 - rng.random()] + [float(x) for x in v]
-    return _coo(pkg, 300, 64, row, col, val)
+    return coo(pkg, 300, 64, row, col, val)
 
 
 def every_row_matrix(pkg, rows=3000, cols=1024):
@@ -47,7 +38,7 @@ def every_row_matrix(pkg, rows=3000, cols=1024):
     rng = np.random.default_rng(11)
     col = rng.integers(0, cols, (rows, 10))
     col[:, 3] = 7
-    return _coo(pkg, rows, cols, np.repeat(np.arange(rows), 10), col.ravel(), rng.standard_normal(rows * 10))
+    return coo(pkg, rows, cols, np.repeat(np.arange(rows), 10), col.ravel(), rng.standard_normal(rows * 10))
 
 
 def _ends_in_padding(packed, c_lane):
@@ -90,7 +81,7 @@ def _matrices(pkg):
     yield "padding leak", padding_leak_matrix(pkg), None
     yield "every row", every_row_matrix(pkg), None
     for rows, cols in ((2500, 300), (2500, 1024), (2500, 4096), (3000, 16384)):
-        yield f"{rows}x{cols}", _signed(pkg, pkg.generate_matrix(rows, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols), None
+        yield f"{rows}x{cols}", signed(pkg, pkg.generate_matrix(rows, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols), None
 
 
 def test_twin_matches_the_coo(pkg):
@@ -115,7 +106,7 @@ def test_twin_matches_the_coo(pkg):
 
 
 def test_eight_long_partitions(pkg):
-    m = _signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
+    m = signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
     packed = pkg.Packed(m, k=16, n_wave_partitions=8)
     assert packed.info()["n_wave_partitions"] == 8 and packed.info()["packets_per_partition"] >= 300
     _compare(pkg, m, packed, None, "8 long partitions")
@@ -137,7 +128,7 @@ def test_padding_does_not_leak(pkg):
 
 def test_repeats_zeros_and_signed_zero(pkg):
     # a repeated column counts twice, an explicit 0.0 counts, and -0.0 < +0.0 in the order of values
-    m = _coo(pkg, 4, 8, [0, 0, 1, 2, 2, 3], [3, 3, 5, 6, 6, 5], [1.0, 2.0, 0.0, 0.0, -0.0, -3.0])
+    m = coo(pkg, 4, 8, [0, 0, 1, 2, 2, 3], [3, 3, 5, 6, 6, 5], [1.0, 2.0, 0.0, 0.0, -0.0, -3.0])
     packed = pkg.Packed(m, k=2, n_wave_partitions=1)
     nnz, cmax, cmin = _compare(pkg, m, packed, None, "tiny")
     assert nnz.tolist() == [0, 0, 0, 2, 0, 2, 2, 0]
@@ -158,10 +149,10 @@ def test_idf_weights(pkg):
 
 
 def test_score_bound(pkg):
-    m = _signed(pkg, pkg.generate_matrix(2500, 300, 20, "uniform", 9), 9)
+    m = signed(pkg, pkg.generate_matrix(2500, 300, 20, "uniform", 9), 9)
     key = m.row.astype(np.uint64) * np.uint64(1 << 20) + m.col.astype(np.uint64)
     keep = np.sort(np.unique(key, return_index=True)[1])  # (one entry per (row, column): a bound per column knows nothing of repeats)
-    m = _coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep])
+    m = coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep])
     cmax, cmin = pkg.col_stats(m, 1), pkg.col_stats(m, 2)
     rng = np.random.default_rng(3)
     for _ in range(5):
@@ -171,7 +162,7 @@ def test_score_bound(pkg):
         bound = pkg.score_bound(x, cmax, cmin)
         assert np.isfinite(bound) and np.all(y <= bound)
     # a column without entries contributes 0
-    e = _coo(pkg, 2, 3, [0, 1], [0, 0], [2.0, -1.0])
+    e = coo(pkg, 2, 3, [0, 1], [0, 0], [2.0, -1.0])
     assert pkg.score_bound(np.array([1.0, 5.0, -5.0]), pkg.col_stats(e, 1), pkg.col_stats(e, 2)) == 2.0
     assert pkg.score_bound(np.array([-1.0, 5.0, -5.0]), pkg.col_stats(e, 1), pkg.col_stats(e, 2)) == 1.0
 

@@ -7,6 +7,8 @@ import struct
 
 import numpy as np
 
+from support import bits_of, order_key
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -45,15 +47,6 @@ def test_null_engine_fails_before_any_device_call(pkg):
     assert total.value == 7 and list(counts) == [5, 5]
 
 
-def _bits(f):
-    return struct.unpack("<I", struct.pack("<f", f))[0]
-
-
-def _key(f):
-    u = _bits(f)
-    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
-
-
 def _loop(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
     """The contract, row by row in plain Python: fp32 >=, the best by (order key << 32 | global row)."""
     counts, best, total = [0] * n_bins, [0] * n_bins, 0
@@ -67,7 +60,7 @@ def _loop(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
         if b >= n_bins:
             continue
         counts[b] += 1
-        best[b] = max(best[b], (_key(s) << 32) | (first_row + r))
+        best[b] = max(best[b], (order_key(s) << 32) | (first_row + r))
     bi = [k & 0xFFFFFFFF if c else 0 for k, c in zip(best, counts)]
     bv = []
     for k, c in zip(best, counts):
@@ -104,7 +97,7 @@ def test_facet_counts_small_cases(pkg):
         assert bv.view(np.uint32).tolist() == [0, 0, 0x80000000, 0x80000000]
     # labels >= n_bins belong to no bin and count in the total; an empty bin gives (0, 0.0)
     c, bi, bv, t = _same(pkg, [0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3, 0.2], ones, [0, NF, 5, 3, 0, NF, 2, 0], 3, 0.25)
-    assert c.tolist() == [2, 0, 1] and bi.tolist() == [0, 0, 6] and bv.view(np.uint32).tolist() == [_bits(np.float32(0.9)), 0, _bits(np.float32(0.3))] and t == 7
+    assert c.tolist() == [2, 0, 1] and bi.tolist() == [0, 0, 6] and bv.view(np.uint32).tolist() == [bits_of(np.float32(0.9)), 0, bits_of(np.float32(0.3))] and t == 7
     # -inf matches every present row (also one that scores -inf), NaN nothing; a NaN score never matches
     present = np.array([1, 1, 0, 1, 1, 1, 0, 1], dtype=bool)
     sc = [0.1, -np.inf, 0.9, np.nan, -3.0, 2.0, 0.2, 0.0]

@@ -1,16 +1,14 @@
-"""Filtered top-k without a GPU: the allow-mask packing of row_mask(), the resource report of stream_filter_kernel, and its ISA
+"""Filtered top-k without a GPU: the allow-mask packing of row_mask(), and the ISA of stream_filter_kernel
 (the streaming loop touches no scratch and waits for no chain of single loads; the mask words travel on the scalar unit)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from support import INCLUDE, compile_device_only
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
-CSRC = os.path.join(ROOT, "approximate-spmv-topk_amd", "csrc")
 
 
 def _mask_loop(rows, allow):
@@ -72,42 +70,8 @@ def test_filter_symbols_exported(pkg):
         assert callable(getattr(pkg.SpMV, name))
 
 
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        m = re.match(r"\s*Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return kernels
-
-
-def test_filter_kernels_in_resource_report():
-    k = _report()
-    filt = {n: v for n, v in k.items() if "tkspmv20stream_filter_kernel" in n}
-    # fp32 only: the 12-bit column layout, plain fp32 at 1024 / 4096 / 16384 columns, 8 entries per lane; each with and without SCORES
-    assert len(filt) == 10, sorted(filt)
-    for n, v in filt.items():
-        assert v["AGPRs"] == 0, (n, v)
-        # (the opt-in 8-entries-per-lane top-k variant sits at the register limit and spills, like its unfiltered twin: the exemption
-        #  test_kernel_resources.py grants stream_kernel<8, false>)
-        if "stream_filter_kernelILi8ELb0E" not in n:
-            assert v["VGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (n, v)
-        if "stream_filter_kernelILi4ELb0E" in n or "stream_filter_kernelILi8ELb0E" in n:
-            assert v["VGPRs"] <= 80, (n, v)  # two 576-thread workgroups per CU, like stream_kernel
-
-
 def _compile_filter_kernels(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    tu = tmp_path / "tu.hip"
-    tu.write_text("""#include <hip/hip_runtime.h>
+    return compile_device_only(tmp_path, """#include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kernels/common.hpp"
 #include "kernels/select.hpp"
@@ -119,11 +83,7 @@ template __global__ void stream_filter_kernel<4, false, 1024, 0, 3>(const Stream
 template __global__ void stream_filter_kernel<4, false, 16384, 0, 3>(const StreamParams, const SelectParams, const FilterParams);
 template __global__ void stream_filter_kernel<8, false, 1024, 0, 2>(const StreamParams, const SelectParams, const FilterParams);
 }
-""")
-    asm = tmp_path / "tu.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S",
-                           "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", str(asm), str(tu)], stderr=subprocess.DEVNULL)
-    return asm.read_text().split("\n")
+""", (INCLUDE,)).split("\n")
 
 
 def test_filter_kernel_isa(tmp_path):

@@ -12,70 +12,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support
+from support import GUARD, EngineSetup, PageOut, bits_of, status_of
+
 pytestmark = pytest.mark.gpu
 
-GUARD = 64  # guard words around every device output
 START, AFTER, END = 0, 1, 2
-
-
-class _Scores:
-    """The order-matched oracle's scores of the engine's layout (the matrix re-packed once by the product's host packer)."""
-    def __init__(self, pkg, eng, m):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def __call__(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-
-def _present(m):
-    return np.bincount(m.row, minlength=m.rows)[:m.rows] > 0
-
-
-def _bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
-def _cursors(torch, cursors):
-    """[count] tkspmv_cursor records in device memory from (row, score_bits, state) tuples (None: START)."""
-    a = np.zeros((len(cursors), 4), dtype=np.uint32)
-    for i, c in enumerate(cursors):
-        if c is not None:
-            a[i, :3] = c
-    return torch.from_numpy(a.view(np.int32)).cuda()
-
-
-class _Out:
-    """[count][k] device outputs for idx / val, [count] for n and total and [count] cursors for next, each between two guard zones."""
-    def __init__(self, torch, count, k):
-        self.count, self.k = count, k
-        self.i = torch.full((2 * GUARD + count * k,), -7, dtype=torch.int32, device="cuda")
-        self.v = torch.full((2 * GUARD + count * k,), -7.0, dtype=torch.float32, device="cuda")
-        self.n = torch.full((2 * GUARD + count,), -7, dtype=torch.int32, device="cuda")
-        self.t = torch.full((2 * GUARD + count,), -7, dtype=torch.int32, device="cuda")
-        self.c = torch.full((2 * GUARD + count * 4,), -7, dtype=torch.int32, device="cuda")
-
-    def ptrs(self, q=0):
-        """The output pointers of a call whose first query is this buffer's query q."""
-        return dict(dev_idx=self.i.data_ptr() + 4 * (GUARD + q * self.k), dev_val=self.v.data_ptr() + 4 * (GUARD + q * self.k),
-                    dev_n=self.n.data_ptr() + 4 * (GUARD + q), dev_total=self.t.data_ptr() + 4 * (GUARD + q),
-                    dev_next=self.c.data_ptr() + 4 * (GUARD + 4 * q))
-
-    def read(self):
-        """[(idx[k] uint32, val[k] float32, n, total, next)] per query; the guard zones must be untouched."""
-        res = []
-        for t, per in ((self.i, self.k), (self.v, self.k), (self.n, 1), (self.t, 1), (self.c, 4)):
-            a = t.cpu().numpy()
-            assert np.all(a[:GUARD] == -7) and np.all(a[GUARD + self.count * per:] == -7), "a guard zone was written"
-            res.append(a[GUARD:GUARD + self.count * per].reshape(self.count, per))
-        idx, val, n, total, nxt = res[0].view(np.uint32), res[1], res[2].view(np.uint32), res[3].view(np.uint32), res[4].view(np.uint32)
-        assert np.all(nxt[:, 3] == 0), "the reserved word of a next cursor must be 0"
-        return [(idx[q], val[q], int(n[q, 0]), int(total[q, 0]), tuple(int(w) for w in nxt[q, :3])) for q in range(self.count)]
 
 
 def _same(got, want, what=""):
@@ -90,8 +32,8 @@ def _same(got, want, what=""):
 
 def _query(eng, torch, dxs, count, cursors=None, stream=0, **kw):
     """enqueue_after into fresh guarded buffers; waits; [(idx, val, n, total, next)] per query."""
-    out = _Out(torch, count, eng.k)
-    dcur = _cursors(torch, cursors) if cursors is not None else None
+    out = PageOut(torch, count, eng.k)
+    dcur = support.cursors(torch, cursors) if cursors is not None else None
     torch.cuda.synchronize()
     eng.enqueue_after(dxs.data_ptr() if dxs is not None else 0, count, dev_cursors=dcur.data_ptr() if dcur is not None else 0,
                       stream=stream.cuda_stream if stream else 0, **out.ptrs(), **kw)
@@ -123,31 +65,10 @@ def _drop_rows(m, every, which):
     return m
 
 
-class _Setup:
-    """One engine of a configuration with its query installed, and the scores and presence flags the expectation pages over."""
-    def __init__(self, pkg, oracle, torch, name):
-        c = CONFIGS[name]
-        rows, cols, nnz = c["shape"]
-        kw = dict(c["kw"])
-        self.fp32 = "precision" not in kw
-        if not self.fp32:
-            kw["precision"] = getattr(pkg, kw["precision"])
-        self.m = _drop_rows(pkg.generate_matrix(rows, cols, nnz, "gamma", rows % 97 + 5), 7, 3)
-        self.x = pkg.create_sample_vector(cols, True, False, True, 19)
-        self.k, self.first_row, self.min_score = c["k"], kw.get("first_row", 0), 0.0
-        self.eng = pkg.SpMV(self.m.row, self.m.col, self.m.val, rows, cols, k=self.k, device=0, **kw)
-        if self.fp32:
-            self.scores = _Scores(pkg, self.eng, self.m)
-            self.y, self.present = self.scores(oracle, self.x)
-        else:
-            self.eng.reset(self.x)
-            self.y, self.present = self.eng.scores().copy(), _present(self.m)
-        if "min_rank" in c:  # min_score at about the 30th best score: the engine is created again with it
-            self.min_score = float(np.sort(self.y[self.present])[::-1][c["min_rank"] - 1])
-            self.eng.close()
-            self.eng = pkg.SpMV(self.m.row, self.m.col, self.m.val, rows, cols, k=self.k, device=0, min_score=self.min_score, **kw)
-        self.eng.reset(self.x)
-        self.dx = torch.from_numpy(self.x).cuda()
+class _Setup(EngineSetup):
+    """The engine and scores of one of CONFIGS, over a matrix with empty rows in its middle; the expectation pages over the scores."""
+    def matrix(self, m):
+        return _drop_rows(m, 7, 3)
 
     def expect(self, pkg, cursor=None, allow=None, y=None, present=None, k=None):
         y = self.y if y is None else y
@@ -158,7 +79,7 @@ class _Setup:
 @pytest.fixture(scope="module", params=[c for c in CONFIGS if c != "walk"])
 def setup(request, pkg, oracle):
     import torch
-    s = _Setup(pkg, oracle, torch, request.param)
+    s = _Setup(pkg, oracle, torch, CONFIGS[request.param])
     yield s
     s.eng.close()
 
@@ -194,13 +115,13 @@ def test_mid_order_cursors(pkg, setup):
     mid = ranking[1][min(eligible, 2000) // 2]  # a score of the ranking's middle
     cursors = []
     for r in sorted({0, 1, eligible // 3, eligible // 2, eligible - 2, eligible - 1} & set(range(eligible))):
-        cursors.append((int(ranking[0][r]), _bits(ranking[1][r]), AFTER))               # an entry of the ranking itself
-    cursors += [(empty + s.first_row, _bits(mid), AFTER),                                # a row without entries
-                (masked + s.first_row, _bits(s.y[masked]), AFTER),                       # a masked row (for the masked queries below)
-                (s.first_row + rows + 1000, _bits(mid), AFTER), (0xFFFFFFFF, _bits(mid), AFTER), (0, _bits(mid), AFTER),  # rows in no shard
-                (17, _bits(np.nextafter(np.float32(mid), np.float32(np.inf))), AFTER),   # a score (most likely) no row has
-                (17, _bits(1e30), AFTER), (17, _bits(-1.0), AFTER),                      # above every score, below every eligible one
-                (17, _bits(mid), END), (17, _bits(mid), 0xFFFFFFFF)]                     # END and a state that acts as END
+        cursors.append((int(ranking[0][r]), bits_of(ranking[1][r]), AFTER))               # an entry of the ranking itself
+    cursors += [(empty + s.first_row, bits_of(mid), AFTER),                                # a row without entries
+                (masked + s.first_row, bits_of(s.y[masked]), AFTER),                       # a masked row (for the masked queries below)
+                (s.first_row + rows + 1000, bits_of(mid), AFTER), (0xFFFFFFFF, bits_of(mid), AFTER), (0, bits_of(mid), AFTER),  # rows in no shard
+                (17, bits_of(np.nextafter(np.float32(mid), np.float32(np.inf))), AFTER),   # a score (most likely) no row has
+                (17, bits_of(1e30), AFTER), (17, bits_of(-1.0), AFTER),                      # above every score, below every eligible one
+                (17, bits_of(mid), END), (17, bits_of(mid), 0xFFFFFFFF)]                     # END and a state that acts as END
     xs = torch.from_numpy(np.tile(s.x, (len(cursors), 1))).cuda()
     got = _query(eng, torch, xs, len(cursors), cursors)
     for c, g in zip(cursors, got):
@@ -218,15 +139,15 @@ def _walk(pkg, torch, eng, dx, want_ranking, eligible):
     """ceil(eligible / k) calls with ONE cursor buffer advanced in place, all enqueued before the first wait."""
     k = eng.k
     pages = -(-eligible // k)
-    out = _Out(torch, pages, k)
-    cur = _cursors(torch, [None])
+    out = PageOut(torch, pages, k)
+    cur = support.cursors(torch, [None])
     torch.cuda.synchronize()
     for p in range(pages):
         ptrs = out.ptrs(p)
         ptrs["dev_next"] = cur.data_ptr()
         eng.enqueue_after(dx.data_ptr(), 1, dev_cursors=cur.data_ptr(), **ptrs)
     eng.synchronize()
-    out.c[GUARD:GUARD + 4 * pages] = 0  # (next went to the cursor buffer instead: read() checks the reserved words)
+    out.dev["dev_next"][GUARD:GUARD + 4 * pages] = 0  # (next went to the cursor buffer instead: read() checks the reserved words)
     got = out.read()
     left = eligible
     for p, (idx, val, n, total, _) in enumerate(got):
@@ -243,7 +164,7 @@ def _walk(pkg, torch, eng, dx, want_ranking, eligible):
 
 def test_full_walk_with_one_cursor_buffer(pkg, oracle):
     import torch
-    s = _Setup(pkg, oracle, torch, "walk")
+    s = _Setup(pkg, oracle, torch, CONFIGS["walk"])
     ranking = s.expect(pkg, k=s.m.rows)
     eligible = ranking[2]
     assert eligible % s.k != 0 and eligible > 100 * s.k
@@ -264,7 +185,7 @@ class _Ties:
         self.x = (np.random.default_rng(2).random(self.cols) < 0.04).astype(np.float32)
         self.y = np.zeros(self.rows, dtype=np.float32)
         np.add.at(self.y, self.m.row, self.x[self.m.col])  # (sums of at most a few dozen ones: exact)
-        self.present = _present(self.m)
+        self.present = support.present(self.m)
         _, counts = np.unique(self.y[self.present], return_counts=True)
         assert np.sort(counts)[-2] > 2048, "two tie classes must be larger than the selection's LDS list"
 
@@ -316,7 +237,7 @@ def test_row_sharded_pages_merge_to_the_single_engines(pkg, ties):
 @pytest.fixture(scope="module")
 def plain(pkg, oracle):
     import torch
-    s = _Setup(pkg, oracle, torch, "default12bit")
+    s = _Setup(pkg, oracle, torch, CONFIGS["default12bit"])
     yield s
     s.eng.close()
 
@@ -329,7 +250,7 @@ def test_masks_and_cursors_per_query(pkg, oracle, plain):
         allow = rng.random(rows) < density
         dmask = torch.from_numpy(pkg.row_mask(rows, allow).view(np.int32)).cuda()
         top = s.expect(pkg, None, allow)
-        cursor = (int(top[0][min(top[2], 7) - 1]), _bits(top[1][min(top[2], 7) - 1]), AFTER)  # behind the 7th allowed row
+        cursor = (int(top[0][min(top[2], 7) - 1]), bits_of(top[1][min(top[2], 7) - 1]), AFTER)  # behind the 7th allowed row
         got = _query(eng, torch, torch.from_numpy(np.tile(s.x, (2, 1))).cuda(), 2, [None, cursor], dev_mask=dmask.data_ptr())
         _same(got[0], top, f"mask {density}")
         _same(got[1], s.expect(pkg, cursor, allow), f"mask {density}, cursor")
@@ -365,8 +286,8 @@ def test_no_cross_talk_with_the_batch_path_and_read(pkg, oracle, plain):
     scores = [s.scores(oracle, xs[q]) for q in range(nq)]
     tops = {q: s.expect(pkg, None, None, *scores[q]) for q in (2, 7, 8, 11)}
     cursors = [tops[7][4], tops[8][4]]  # page 2 of queries 7 and 8
-    dcur = _cursors(torch, cursors)
-    out = _Out(torch, 2, k)
+    dcur = support.cursors(torch, cursors)
+    out = PageOut(torch, 2, k)
     torch.cuda.synchronize()
     # an unwaited batch sequence, the after call right behind it, another batch sequence right behind that: one stream, one wait
     eng.enqueue_batch(dxs.data_ptr(), nq, b_i[0].data_ptr(), b_v[0].data_ptr())
@@ -382,7 +303,7 @@ def test_no_cross_talk_with_the_batch_path_and_read(pkg, oracle, plain):
         _same(out.read()[j], s.expect(pkg, cursors[j], None, *scores[q]), f"after query {q}")
     before = eng.debug_counters()
     # engine-owned outputs: tkspmv_read returns the page (the last query wins), pads included
-    dcur3 = _cursors(torch, [None, None, tops[2][4]])
+    dcur3 = support.cursors(torch, [None, None, tops[2][4]])
     torch.cuda.synchronize()
     eng.enqueue_after(dxs.data_ptr(), 3, dev_cursors=dcur3.data_ptr())
     eng.synchronize()
@@ -435,12 +356,6 @@ def test_run_after_pages_and_ranked_spmv(pkg, ties):
     assert idx.size == ranking[2] and np.array_equal(idx, ranking[0][:ranking[2]])
 
 
-def _status(pkg, fn, *a, **kw):
-    with pytest.raises(pkg.TkspmvError) as e:
-        fn(*a, **kw)
-    return e.value.status
-
-
 def test_errors(pkg):
     import torch
     L = pkg._lib
@@ -451,17 +366,17 @@ def test_errors(pkg):
     buf = torch.zeros(k, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0)
-    assert _status(pkg, eng.enqueue_after, 0, 1) == L.ERR_STATE    # no query vector installed
-    assert _status(pkg, eng.run_after) == L.ERR_STATE
-    assert _status(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID  # NULL dev_xs takes the installed vector: count must be 1
+    assert status_of(pkg, eng.enqueue_after, 0, 1) == L.ERR_STATE    # no query vector installed
+    assert status_of(pkg, eng.run_after) == L.ERR_STATE
+    assert status_of(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID  # NULL dev_xs takes the installed vector: count must be 1
     eng.reset(x)
-    assert _status(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_after, 0, 0) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_after, 0, -3) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_after, 0, 1, 0, dmask.data_ptr(), -1) == L.ERR_INVALID  # a negative stride
+    assert status_of(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_after, 0, 0) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_after, 0, -3) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_after, 0, 1, 0, dmask.data_ptr(), -1) == L.ERR_INVALID  # a negative stride
     for given in ((1, 0), (0, 1)):  # output pointers partly given
         p = [buf.data_ptr() if g else 0 for g in given]
-        assert _status(pkg, eng.enqueue_after, 0, 1, 0, 0, 0, *p) == L.ERR_INVALID
+        assert status_of(pkg, eng.enqueue_after, 0, 1, 0, 0, 0, *p) == L.ERR_INVALID
     n = C.c_int32(5)
     assert L.lib().tkspmv_run_after(eng._h, None, 1, None, None, C.byref(n), None, None) == L.ERR_INVALID  # use_filter, none installed
     assert n.value == 5
@@ -470,13 +385,13 @@ def test_errors(pkg):
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0, partitions=4, k_per_partition=8)  # the approximate per-partition path
     eng.reset(x)
-    assert _status(pkg, eng.run_after) == L.ERR_UNSUPPORTED
-    assert _status(pkg, eng.enqueue_after, 0, 1) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.run_after) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.enqueue_after, 0, 1) == L.ERR_UNSUPPORTED
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0, precision=pkg.F16)
     eng.reset(x)
     eng.run_after()  # served without a mask ...
-    assert _status(pkg, eng.enqueue_after, 0, 1, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels
+    assert status_of(pkg, eng.enqueue_after, 0, 1, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels
     with pytest.raises(pkg.TkspmvError) as e:
         eng.enqueue_after(0, 1, 0, dmask.data_ptr())
     assert "filtered queries need fp32 values" in str(e.value)

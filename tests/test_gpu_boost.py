@@ -11,59 +11,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support
+from support import GUARD, PageOut, bits_of, status_of
+
 pytestmark = pytest.mark.gpu
 
-GUARD = 64  # guard words around every device output
 START, AFTER, END = 0, 1, 2
 NINF = float("-inf")
 
 
-def _present(m):
-    return np.bincount(m.row, minlength=m.rows)[:m.rows] > 0
-
-
-def _bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
-
-
-def _cursors(torch, cursors):
-    """[count] tkspmv_cursor records in device memory from (row, score_bits, state) tuples (None: START)."""
-    a = np.zeros((len(cursors), 4), dtype=np.uint32)
-    for i, c in enumerate(cursors):
-        if c is not None:
-            a[i, :3] = c
-    return torch.from_numpy(a.view(np.int32)).cuda()
-
-
-class _Out:
-    """[count][k] device outputs for idx / val, [count] for n and total and [count] cursors for next, each between two guard zones."""
-    def __init__(self, torch, count, k):
-        self.count, self.k = count, k
-        self.i = torch.full((2 * GUARD + count * k,), -7, dtype=torch.int32, device="cuda")
-        self.v = torch.full((2 * GUARD + count * k,), -7.0, dtype=torch.float32, device="cuda")
-        self.n = torch.full((2 * GUARD + count,), -7, dtype=torch.int32, device="cuda")
-        self.t = torch.full((2 * GUARD + count,), -7, dtype=torch.int32, device="cuda")
-        self.c = torch.full((2 * GUARD + count * 4,), -7, dtype=torch.int32, device="cuda")
-
-    def ptrs(self, q=0):
-        return dict(dev_idx=self.i.data_ptr() + 4 * (GUARD + q * self.k), dev_val=self.v.data_ptr() + 4 * (GUARD + q * self.k),
-                    dev_n=self.n.data_ptr() + 4 * (GUARD + q), dev_total=self.t.data_ptr() + 4 * (GUARD + q),
-                    dev_next=self.c.data_ptr() + 4 * (GUARD + 4 * q))
-
-    def read(self):
-        """[(idx[k] uint32, val[k] float32, n, total, next)] per query; the guard zones must be untouched."""
-        res = []
-        for t, per in ((self.i, self.k), (self.v, self.k), (self.n, 1), (self.t, 1), (self.c, 4)):
-            a = t.cpu().numpy()
-            assert np.all(a[:GUARD] == -7) and np.all(a[GUARD + self.count * per:] == -7), "a guard zone was written"
-            res.append(a[GUARD:GUARD + self.count * per].reshape(self.count, per))
-        idx, val, n, total, nxt = res[0].view(np.uint32), res[1], res[2].view(np.uint32), res[3].view(np.uint32), res[4].view(np.uint32)
-        assert np.all(nxt[:, 3] == 0), "the reserved word of a next cursor must be 0"
-        return [(idx[q], val[q], int(n[q, 0]), int(total[q, 0]), tuple(int(w) for w in nxt[q, :3])) for q in range(self.count)]
 
 
 def _same(got, want, what=""):
@@ -84,8 +42,8 @@ def _dev(torch, a):
 def _query(eng, torch, dxs, count, w=None, b=None, stride=0, cursors=None, stream=0, after=False, **kw):
     """enqueue_boosted (w / b: device tensors or None; after: enqueue_after instead) into fresh guarded buffers; waits;
     [(idx, val, n, total, next)] per query."""
-    out = _Out(torch, count, eng.k)
-    dcur = _cursors(torch, cursors) if cursors is not None else None
+    out = PageOut(torch, count, eng.k)
+    dcur = support.cursors(torch, cursors) if cursors is not None else None
     torch.cuda.synchronize()
     common = dict(dev_cursors=dcur.data_ptr() if dcur is not None else 0, stream=stream.cuda_stream if stream else 0, **out.ptrs(), **kw)
     if after:
@@ -120,7 +78,7 @@ class _Setup:
         self.fp32 = "precision" not in kw
         self.eng = pkg.SpMV(self.m.row, self.m.col, self.m.val, rows, cols, k=k, device=0, **kw)
         self.eng.reset(self.x)
-        self.y, self.present = self.eng.scores().copy(), _present(self.m)
+        self.y, self.present = self.eng.scores().copy(), support.present(self.m)
         self.dx = torch.from_numpy(self.x).cuda()
 
     def scores_of(self, x):
@@ -180,7 +138,7 @@ def test_random_weight_and_bias(pkg, setup):
         # ... and the page behind it, and a page from the ranking's middle: the cursor's score_bits are boosted scores
         ranking = s.expect(pkg, hw, hb, k=s.rows)
         mid = ranking[2] // 2
-        cursors = [top[4], (int(ranking[0][mid]), _bits(ranking[1][mid]), AFTER), (17, _bits(1e30), AFTER), (17, _bits(1.0), END)]
+        cursors = [top[4], (int(ranking[0][mid]), bits_of(ranking[1][mid]), AFTER), (17, bits_of(1e30), AFTER), (17, bits_of(1.0), END)]
         xs = torch.from_numpy(np.tile(s.x, (len(cursors), 1))).cuda()
         for c, g in zip(cursors, _query(eng, torch, xs, len(cursors), tw, tb, cursors=cursors)):
             _same(g, s.expect(pkg, hw, hb, c), (name, c))
@@ -190,7 +148,7 @@ def test_identities_are_enqueue_after_bit_for_bit(pkg, setup):
     import torch
     s, eng = setup, setup.eng
     plain = s.expect(pkg)
-    cursors = [None, plain[4], (s.first_row + s.rows // 2, _bits(np.median(s.y[s.present])), AFTER)]
+    cursors = [None, plain[4], (s.first_row + s.rows // 2, bits_of(np.median(s.y[s.present])), AFTER)]
     xs = torch.from_numpy(np.tile(s.x, (len(cursors), 1))).cuda()
     after = _query(eng, torch, xs, len(cursors), cursors=cursors, after=True)
     ones = _dev(torch, np.ones(s.rows, dtype=np.float32))
@@ -215,7 +173,7 @@ def test_ties(pkg, setup):
     three = np.random.default_rng(6).choice(np.array([0.25, 0.5, 0.75], dtype=np.float32), s.rows)
     ranking = s.expect(pkg, zero, three, k=s.rows)
     cut = int((three[s.present] == 0.75).sum())  # the first row of the second tie class
-    cursors = [None, (int(ranking[0][cut - 1]), _bits(0.75), AFTER), (int(ranking[0][cut + 5]), _bits(0.5), AFTER)]
+    cursors = [None, (int(ranking[0][cut - 1]), bits_of(0.75), AFTER), (int(ranking[0][cut + 5]), bits_of(0.5), AFTER)]
     xs = torch.from_numpy(np.tile(s.x, (len(cursors), 1))).cuda()
     for c, g in zip(cursors, _query(eng, torch, xs, len(cursors), _dev(torch, zero), _dev(torch, three), cursors=cursors)):
         _same(g, s.expect(pkg, zero, three, c), ("three values", c))
@@ -316,15 +274,15 @@ def test_full_walk_with_one_cursor_buffer(pkg, tail):
     eligible = ranking[2]
     assert eligible % k != 0 and eligible > 20 * k
     pages = -(-eligible // k)
-    out = _Out(torch, pages, k)
-    cur = _cursors(torch, [None])
+    out = PageOut(torch, pages, k)
+    cur = support.cursors(torch, [None])
     torch.cuda.synchronize()
     for p in range(pages):  # all enqueued before the first wait, dev_next == dev_cursors
         ptrs = out.ptrs(p)
         ptrs["dev_next"] = cur.data_ptr()
         eng.enqueue_boosted(s.dx.data_ptr(), 1, dw.data_ptr(), db.data_ptr(), 0, dev_cursors=cur.data_ptr(), **ptrs)
     eng.synchronize()
-    out.c[GUARD:GUARD + 4 * pages] = 0  # (next went to the cursor buffer instead: read() checks the reserved words)
+    out.dev["dev_next"][GUARD:GUARD + 4 * pages] = 0  # (next went to the cursor buffer instead: read() checks the reserved words)
     got = out.read()
     left = eligible
     for p, (idx, val, n, total, _) in enumerate(got):
@@ -370,17 +328,11 @@ def test_four_queries_with_per_query_bias_and_unaligned_stride(pkg, tail):
         _same(got[q], s.expect(pkg, w[0, :rows], b[0, :rows], cursors[q], y=ys[q]), f"stride 0, query {q}")
     # arrays that start off a multiple of 16 bytes
     off_w, off_b = _dev(torch, np.concatenate([[np.nan], w[2, :rows]])), _dev(torch, np.concatenate([[np.nan] * 3, b[2, :rows]]))
-    out = _Out(torch, 1, s.k)
+    out = PageOut(torch, 1, s.k)
     torch.cuda.synchronize()
     eng.enqueue_boosted(dxs.data_ptr(), 1, off_w.data_ptr() + 4, off_b.data_ptr() + 12, 0, **out.ptrs())
     eng.synchronize()
     _same(out.read()[0], s.expect(pkg, w[2, :rows], b[2, :rows], y=ys[0]), "unaligned pointers")
-
-
-def _status(pkg, fn, *a, **kw):
-    with pytest.raises(pkg.TkspmvError) as e:
-        fn(*a, **kw)
-    return e.value.status
 
 
 def test_installed_boost_run_boosted_and_a_callers_stream(pkg, tail):
@@ -388,8 +340,8 @@ def test_installed_boost_run_boosted_and_a_callers_stream(pkg, tail):
     s, eng, L = tail, tail.eng, pkg._lib
     w, b = s.random_boost(5)
     eng.set_boost(None, None)
-    assert _status(pkg, eng.enqueue_boosted, s.dx.data_ptr(), 1) == L.ERR_STATE  # both NULL, none installed
-    assert _status(pkg, eng.run_boosted) == L.ERR_STATE
+    assert status_of(pkg, eng.enqueue_boosted, s.dx.data_ptr(), 1) == L.ERR_STATE  # both NULL, none installed
+    assert status_of(pkg, eng.run_boosted) == L.ERR_STATE
     eng.set_boost(w, b)
     want = s.expect(pkg, w, b)
     _same(_query(eng, torch, s.dx, 1)[0], want, "both NULL: the installed boost")
@@ -400,10 +352,10 @@ def test_installed_boost_run_boosted_and_a_callers_stream(pkg, tail):
     _same(eng.run_boosted(want[4]), s.expect(pkg, w, b, want[4]), "run_boosted, page 2")
     bad = w.copy()
     bad[100] = np.inf
-    assert _status(pkg, eng.set_boost, bad, b) == L.ERR_INVALID
+    assert status_of(pkg, eng.set_boost, bad, b) == L.ERR_INVALID
     bad = b.copy()
     bad[s.rows - 1] = np.nan
-    assert _status(pkg, eng.set_boost, None, bad) == L.ERR_INVALID
+    assert status_of(pkg, eng.set_boost, None, bad) == L.ERR_INVALID
     _same(eng.run_boosted(), want, "the boost installed before stays in force")
     with pytest.raises(ValueError):
         eng.set_boost(w[:-1])
@@ -420,7 +372,7 @@ def test_installed_boost_run_boosted_and_a_callers_stream(pkg, tail):
     _same(_query(eng, torch, s.dx, 1, dw, db, stream=side)[0], want, "a caller's stream")
     _same(_query(eng, torch, s.dx, 1, stream=side)[0], want, "a caller's stream, installed boost")
     eng.set_boost(None, None)
-    assert _status(pkg, eng.run_boosted) == L.ERR_STATE
+    assert status_of(pkg, eng.run_boosted) == L.ERR_STATE
     val, idx = pkg.boosted_spmv(s.m, s.x, s.k, weight=w, bias=b)  # the one-shot helper
     assert np.array_equal(idx, want[0]) and np.array_equal(val.view(np.uint32), want[1].view(np.uint32))
 
@@ -437,20 +389,20 @@ def test_errors_in_the_stated_order(pkg):
     torch.cuda.synchronize()
     W = dw.data_ptr()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 512, k=k, device=0)
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, W) == L.ERR_STATE     # no query vector installed
-    assert _status(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_STATE        # ... and no boost either
-    assert _status(pkg, eng.run_boosted) == L.ERR_STATE
-    assert _status(pkg, eng.enqueue_boosted, 0, 2, W) == L.ERR_INVALID   # NULL dev_xs takes the installed vector: count must be 1
-    assert _status(pkg, eng.enqueue_boosted, 0, 2) == L.ERR_INVALID      # INVALID comes before STATE
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, W) == L.ERR_STATE     # no query vector installed
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_STATE        # ... and no boost either
+    assert status_of(pkg, eng.run_boosted) == L.ERR_STATE
+    assert status_of(pkg, eng.enqueue_boosted, 0, 2, W) == L.ERR_INVALID   # NULL dev_xs takes the installed vector: count must be 1
+    assert status_of(pkg, eng.enqueue_boosted, 0, 2) == L.ERR_INVALID      # INVALID comes before STATE
     eng.reset(x)
-    assert _status(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_STATE        # a vector, but no boost installed
-    assert _status(pkg, eng.enqueue_boosted, 0, 0, W) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_boosted, 0, -3, W) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, W, 0, -1) == L.ERR_INVALID  # a negative boost stride
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, dmask.data_ptr(), -1) == L.ERR_INVALID  # a negative mask stride
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_STATE        # a vector, but no boost installed
+    assert status_of(pkg, eng.enqueue_boosted, 0, 0, W) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_boosted, 0, -3, W) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, W, 0, -1) == L.ERR_INVALID  # a negative boost stride
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, dmask.data_ptr(), -1) == L.ERR_INVALID  # a negative mask stride
     for given in ((1, 0), (0, 1)):  # output pointers partly given
         p = [buf.data_ptr() if g else 0 for g in given]
-        assert _status(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, 0, 0, *p) == L.ERR_INVALID
+        assert status_of(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, 0, 0, *p) == L.ERR_INVALID
     n = C.c_int32(5)
     assert L.lib().tkspmv_run_boosted(eng._h, None, 1, None, None, C.byref(n), None, None) == L.ERR_INVALID  # use_filter, none installed
     assert n.value == 5
@@ -458,18 +410,18 @@ def test_errors_in_the_stated_order(pkg):
     assert cnt == k and total > k and nxt[2] == AFTER
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 512, k=k, device=0, partitions=4, k_per_partition=8)  # the approximate per-partition path
-    assert _status(pkg, eng.enqueue_boosted, 0, 0, W) == L.ERR_INVALID      # INVALID comes first ...
-    assert _status(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_UNSUPPORTED     # ... UNSUPPORTED before STATE (no vector, no boost)
+    assert status_of(pkg, eng.enqueue_boosted, 0, 0, W) == L.ERR_INVALID      # INVALID comes first ...
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1) == L.ERR_UNSUPPORTED     # ... UNSUPPORTED before STATE (no vector, no boost)
     eng.reset(x)
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, W) == L.ERR_UNSUPPORTED
-    assert _status(pkg, eng.run_boosted) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, W) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.run_boosted) == L.ERR_UNSUPPORTED
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 512, k=k, device=0, precision=pkg.F16)
     eng.reset(x)
     eng.run_boosted(weight=np.ones(rows, dtype=np.float32))  # served without a mask ...
     eng.set_boost(None, None)
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, 0, 0, 0, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels (before STATE)
-    assert _status(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, 0, 0, 0, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels (before STATE)
+    assert status_of(pkg, eng.enqueue_boosted, 0, 1, W, 0, 0, 0, dmask.data_ptr()) == L.ERR_UNSUPPORTED
     eng.close()
 
 

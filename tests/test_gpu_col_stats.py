@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_col_stats_host import _coo, _signed, _u32, every_row_matrix, padding_leak_matrix
+from support import coo, signed
+from test_col_stats_host import _u32, every_row_matrix, padding_leak_matrix
 from test_gpu_match import _edges
 
 pytestmark = pytest.mark.gpu
@@ -82,7 +83,7 @@ GENERATED = [(2500, 300, 4), (2500, 1024, 4), (2500, 1024, 8), (20000, 4096, 4),
 @pytest.mark.parametrize("rows,cols,c_lane", GENERATED)
 def test_generated_matrices(pkg, rows, cols, c_lane):
     import torch
-    m = _signed(pkg, pkg.generate_matrix(rows, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols)
+    m = signed(pkg, pkg.generate_matrix(rows, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0, nnz_per_lane=c_lane)
     assert eng.info()["packet_entries"] == 64 * c_lane
     _check_engine(pkg, eng, m, f"{rows}x{cols} C={c_lane}")
@@ -97,8 +98,8 @@ def test_generated_matrices(pkg, rows, cols, c_lane):
 def test_partition_shapes(pkg):
     rng = np.random.default_rng(7)
     rows, per = 128, 8  # 1024 entries: the last row ends on the last slot of a packet, no padding at 4 entries per lane
-    fit = _coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
-    few = _signed(pkg, pkg.generate_matrix(1000, 512, 20, "uniform", 13), 13)  # fewer partitions than waves
+    fit = coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
+    few = signed(pkg, pkg.generate_matrix(1000, 512, 20, "uniform", 13), 13)  # fewer partitions than waves
     leak = padding_leak_matrix(pkg)
     for label, m in (("exact fit", fit), ("1000x512", few), ("padding leak", leak)):
         for c_lane in (4, 8):
@@ -112,7 +113,7 @@ def test_partition_shapes(pkg):
 
 def test_long_partitions_and_geometry(pkg):
     import torch
-    m = _signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
+    m = signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
     packed = pkg.Packed(m, k=16, n_wave_partitions=8)
     assert packed.info()["packets_per_partition"] >= 300
     eng = pkg.SpMV.from_packed(packed, k=16, device=0)
@@ -121,7 +122,7 @@ def test_long_partitions_and_geometry(pkg):
     half = np.random.default_rng(2).random(m.rows) < 0.5
     assert np.array_equal(_masked(pkg, torch, eng, 0, [half], m.cols)[0], pkg.col_stats(m, 0, half))
     eng.close()
-    m = _signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
+    m = signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
     for kw in (dict(threads_per_wg=256, waves_per_cu=4), dict(threads_per_wg=64, waves_per_cu=4), dict(waves_per_cu=1)):
         eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=16, device=0, **kw)
         _check_engine(pkg, eng, m, f"geometry {kw}")
@@ -139,7 +140,7 @@ def test_lds_contention_and_long_rows(pkg):
     rng = np.random.default_rng(19)
     lens = np.where(np.arange(600) % 50 == 10, 700, rng.integers(0, 12, 600))
     row = np.repeat(np.arange(600), lens)
-    m = _coo(pkg, 600, 1024, row, rng.integers(0, 1024, row.size), rng.standard_normal(row.size))
+    m = coo(pkg, 600, 1024, row, rng.integers(0, 1024, row.size), rng.standard_normal(row.size))
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0)
     _check_engine(pkg, eng, m, "rows of 700 entries")
     only = np.arange(m.rows) == 310  # the only allowed row crosses packet boundaries
@@ -172,7 +173,7 @@ def test_masks_shared_per_set_and_strided(pkg):
 
 def test_forty_sets_cross_the_launch_boundary(pkg):
     import torch
-    m = _signed(pkg, pkg.generate_matrix(2500, 300, 20, "uniform", 3), 3)
+    m = signed(pkg, pkg.generate_matrix(2500, 300, 20, "uniform", 3), 3)
     rng = np.random.default_rng(40)
     masks = [rng.random(m.rows) < (i + 1) / 41 for i in range(40)]
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0)
@@ -185,7 +186,7 @@ def test_forty_sets_cross_the_launch_boundary(pkg):
 
 def test_installed_filter_and_state(pkg):
     L = pkg._lib
-    m = _signed(pkg, pkg.generate_matrix(5000, 512, 20, "uniform", 61), 61)
+    m = signed(pkg, pkg.generate_matrix(5000, 512, 20, "uniform", 61), 61)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0)
     with pytest.raises(pkg.TkspmvError) as e:
         eng.col_stats(0, use_filter=True)
@@ -244,12 +245,12 @@ def test_composition_with_match(pkg):
     # with the repeated entry removed, COL_NNZ is the document frequency
     keep = np.ones(m.row.size, dtype=bool)
     keep[np.flatnonzero((m.row == 202) & (m.col == 950))[1]] = False
-    df, nnz, _ = run(_coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep]))
+    df, nnz, _ = run(coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep]))
     assert np.array_equal(nnz[cols32], df)
 
 
 def test_scope(pkg, tmp_path):
-    m = _signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
+    m = signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
     # an engine made from a saved and loaded file: no COO anywhere near it
     packed = pkg.Packed(m, k=16, n_wave_partitions=pkg.Packed.wave_partitions(device=0, m=m))
     packed.save(tmp_path / "m.tkspmv")

@@ -11,41 +11,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support
+from support import Scores, bits
+
 pytestmark = pytest.mark.gpu
 
 NO_FACET = 0xFFFFFFFF
 FILL32, FILL64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A
 BINS = (1, 7, 64, 1000, 200_000)
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-class _Scores:
-    """The order-matched oracle's scores of the engine's layout, as test_gpu_range.py builds them."""
-    def __init__(self, pkg, eng, m):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def __call__(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-
-def _masks(rows, unfiltered_idx, first_row, seed):
-    """The four masks of test_gpu_filter.py."""
-    rng = np.random.default_rng(seed)
-    out = {f"random{d}": rng.random(rows) < d for d in (0.5, 0.05, 0.001)}
-    top = unfiltered_idx.astype(np.int64) - first_row
-    ex = np.ones(rows, dtype=bool)
-    ex[top[top >= 0]] = False  # the unfiltered top-k excluded
-    out["no_topk"] = ex
-    return out
 
 
 def _labels(kind, rows, n_bins, seed=0):
@@ -125,7 +98,7 @@ def _expect(pkg, scores, labels, n_bins, tv, first_row=0, allows=None):
         allow = None if allows is None else allows[i if len(allows) > 1 else 0]
         c, bi, bv, tot = pkg.facet_counts(yp, present, labels, n_bins, t, first_row=first_row, allow=allow)
         cs.append(c)
-        bs.append(np.stack([bi, _bits(bv)], axis=1))
+        bs.append(np.stack([bi, bits(bv)], axis=1))
         ts.append(tot)
     return np.stack(cs), np.stack(bs), np.array(ts, dtype=np.uint32)
 
@@ -159,7 +132,7 @@ class _Case:
         self.x = np.ascontiguousarray(pkg.create_sample_vector(cols, True, False, True, 17), dtype=np.float32)
         self.engines = _engines(pkg, self.m, 100, **kw)
         eng = self.engines["default"]
-        self.yp, self.present = _Scores(pkg, eng, self.m)(oracle, self.x)
+        self.yp, self.present = Scores(pkg, eng, self.m)(oracle, self.x)
         s = np.sort(self.yp[self.present])[::-1]
         ranks = [r for r in (1, 100, 1000) if r <= s.size]
         self.tv = np.array([-np.inf, 0.0] + [s[r - 1] for r in ranks] + [np.nextafter(np.float32(s[0]), np.float32(np.inf)), np.nan], dtype=np.float32)
@@ -231,7 +204,7 @@ def test_masks(pkg, cases, shape):
     """The four masks of test_gpu_filter.py, one for every query (stride 0) and one per query (stride)."""
     import torch
     c = cases(shape)
-    masks = _masks(c.rows, c.topk, c.first_row, c.rows)
+    masks = support.masks(c.rows, c.topk, c.first_row, c.rows)
     for n_bins in (7, 1000):
         lab = _labels("no_facet", c.rows, n_bins, seed=5)
         dlab = torch.from_numpy(lab.view(np.int32)).cuda()
@@ -285,7 +258,7 @@ def seq(pkg, oracle):
     engines = _engines(pkg, m, 100, stream_replicas=4)
     engines.pop("lds64").close()
     xs = np.stack([pkg.create_sample_vector(cols, True, False, True, 300 + i) for i in range(nq)]).astype(np.float32)
-    sc = _Scores(pkg, engines["default"], m)
+    sc = Scores(pkg, engines["default"], m)
     scores = [sc(oracle, xs[i]) for i in range(nq)]
     yield m, engines, xs, scores
     for e in engines.values():
@@ -357,7 +330,7 @@ def test_no_cross_talk(pkg, oracle):
     lab = _labels("uniform", rows, n_bins, seed=4)
     dlab = torch.from_numpy(lab.view(np.int32)).cuda()
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0)
-    sc = _Scores(pkg, eng, m)
+    sc = Scores(pkg, eng, m)
     scores = [sc(oracle, xs[i]) for i in range(nq)]
     tv = np.array([np.sort(scores[q][0][scores[q][1]])[::-1][499] for q in range(nq)], dtype=np.float32)
     dthr = torch.from_numpy(tv).cuda()
@@ -379,11 +352,11 @@ def test_no_cross_talk(pkg, oracle):
     ref()
     fv, fi = ref.read_result()
     ref.close()
-    assert np.array_equal(bi, ei) and np.array_equal(_bits(bv), _bits(ev))
-    assert np.array_equal(ri, fi) and np.array_equal(_bits(rv), _bits(fv))
+    assert np.array_equal(bi, ei) and np.array_equal(bits(bv), bits(ev))
+    assert np.array_equal(ri, fi) and np.array_equal(bits(rv), bits(fv))
     for q in range(nq):
         oi, ov = oracle.select_topk(*scores[q], k)
-        assert np.array_equal(bi[q], oi) and np.array_equal(_bits(bv[q]), _bits(ov))
+        assert np.array_equal(bi[q], oi) and np.array_equal(bits(bv[q]), bits(ov))
     exp = _expect(pkg, scores, lab, n_bins, tv)
     for name, read in zip(("engine_stream", "callers_stream"), reads):
         _same(read(), exp, f"cross_talk/{name}")
@@ -410,14 +383,14 @@ def test_installed_labels(pkg, oracle, cases):
            dt.cpu().numpy().view(np.uint32)), exp, "installed/enqueue")
     t = float(c.tv[3])
     counts, bi, bv, total = eng.run_facets(t, vec=c.x)
-    assert np.array_equal(counts, exp[0][3]) and np.array_equal(bi, exp[1][3][:, 0]) and np.array_equal(_bits(bv), exp[1][3][:, 1]) and total == exp[2][3]
+    assert np.array_equal(counts, exp[0][3]) and np.array_equal(bi, exp[1][3][:, 0]) and np.array_equal(bits(bv), exp[1][3][:, 1]) and total == exp[2][3]
     allow = np.random.default_rng(21).random(c.rows) < 0.3
     ec, ei, ev, et = pkg.facet_counts(c.yp, c.present, lab, n_groups, -np.inf, first_row=c.first_row, allow=allow)
     counts, bi, bv, total = eng.run_facets(-np.inf, allow=allow)
-    assert np.array_equal(counts, ec) and np.array_equal(bi, ei) and np.array_equal(_bits(bv), _bits(ev)) and total == et
+    assert np.array_equal(counts, ec) and np.array_equal(bi, ei) and np.array_equal(bits(bv), bits(ev)) and total == et
     eng.set_filter(None)
     gv1, gi1, gg1 = eng.run_grouped()
-    assert np.array_equal(gi0, gi1) and np.array_equal(_bits(gv0), _bits(gv1)) and np.array_equal(gg0, gg1)
+    assert np.array_equal(gi0, gi1) and np.array_equal(bits(gv0), bits(gv1)) and np.array_equal(gg0, gg1)
     eng.set_groups(None)
     # the one-shot helper
     small = pkg.generate_matrix(1000, 512, 20, "gamma", 5)

@@ -7,6 +7,9 @@ The conftest syncs torch only for the existing enqueue names: these tests call t
 import numpy as np
 import pytest
 
+import support
+from support import Scores
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4
@@ -16,23 +19,8 @@ def _engine(pkg, m, k, **kw):
     return pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, **kw)
 
 
-class _Scores:
-    """The order-matched oracle's scores of the engine's layout (the matrix re-packed once by the product's host packer)."""
-    def __init__(self, pkg, eng, m):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def __call__(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-
 def _packed_scores(pkg, oracle, eng, m, x):
-    return _Scores(pkg, eng, m)(oracle, x)
+    return Scores(pkg, eng, m)(oracle, x)
 
 
 def _expect(oracle, yp, present, allow, k, min_score=0.0, first_row=0):
@@ -60,16 +48,6 @@ def _check(oracle, m, x, k, allow, idx, val, ei, ev, min_score=0.0, first_row=0)
     assert np.allclose(np.sort(val[:n])[::-1], np.sort(y64[gold])[::-1], rtol=RTOL, atol=0)
 
 
-def _masks(rows, unfiltered_idx, first_row, seed):
-    rng = np.random.default_rng(seed)
-    out = {f"random{d}": rng.random(rows) < d for d in (0.5, 0.05, 0.001)}
-    top = unfiltered_idx.astype(np.int64) - first_row
-    ex = np.ones(rows, dtype=bool)
-    ex[top[top >= 0]] = False  # the unfiltered top-k excluded: the answer is the next k
-    out["no_topk"] = ex
-    return out
-
-
 @pytest.mark.parametrize("rows,cols,nnz,k,kw", [
     (1_000_000, 1024, 20, 100, {}),                 # deferred selection chain
     (200_000, 4096, 20, 100, {}),
@@ -92,7 +70,7 @@ def test_filtered_matches_oracle(pkg, oracle, rows, cols, nnz, k, kw):
     assert np.array_equal(fi, ui) and np.array_equal(fv.view(np.uint32), uv.view(np.uint32))
     ei, ev = _expect(oracle, yp, present, np.ones(rows, dtype=bool), k, 0.0, first_row)
     _check(oracle, m, x, k, np.ones(rows, dtype=bool), fi, fv, ei, ev, 0.0, first_row)
-    masks = _masks(rows, ui, first_row, rows)
+    masks = support.masks(rows, ui, first_row, rows)
     for name, allow in masks.items():
         val, idx = eng.run_filtered(allow=allow)
         ei, ev = _expect(oracle, yp, present, allow, k, 0.0, first_row)
@@ -161,7 +139,7 @@ def test_per_query_masks(pkg, oracle):
     eng.synchronize()
     gi, gv = out_i.cpu().numpy().view(np.uint32), out_v.cpu().numpy()
     expected = []
-    sc = _Scores(pkg, eng, m)
+    sc = Scores(pkg, eng, m)
     for i in range(nq):
         yp, present = sc(oracle, xs[i])
         expected.append((yp, present))
@@ -248,7 +226,7 @@ def test_no_cross_talk(pkg, oracle):
     _sequence(pkg, ref, xs, dxs, None, torch)
     ref_counters = ref.debug_counters()
     # every result oracle-exact
-    scores, sc = {}, _Scores(pkg, ref, m)
+    scores, sc = {}, Scores(pkg, ref, m)
 
     def yp_of(i):
         if i not in scores:

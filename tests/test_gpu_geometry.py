@@ -23,7 +23,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_range import _Dev, _bits, _check_query, _expected
+from support import bits
+from test_gpu_range import _Dev, _check_query, _expected
 from test_gpu_single import _exact, _packed_raw
 
 pytestmark = pytest.mark.gpu
@@ -130,7 +131,7 @@ def _every_entry_point(pkg, oracle, s, eng):
     eng.synchronize()
     ei, ev = oracle.select_topk(yp, (present & s.allow).astype(np.uint8), k)
     assert np.array_equal(out_i.cpu().numpy().view(np.uint32), ei), "filtered: index list differs from the order-matched oracle"
-    assert np.array_equal(_bits(out_v.cpu().numpy()), _bits(ev)), "filtered: scores are not bit-identical"
+    assert np.array_equal(bits(out_v.cpu().numpy()), bits(ev)), "filtered: scores are not bit-identical"
     # range queries at the rank-10 and rank-1000 thresholds
     srt = np.sort(yp[present])[::-1]
     tv = np.array([srt[9], srt[999]], dtype=np.float32)
@@ -149,9 +150,9 @@ def _every_entry_point(pkg, oracle, s, eng):
     # facet counts per label row % 37, score_rows of 64 rows
     fc, fbi, fbv, total = eng.run_facets(float(tv[1]), vec=s.xs[0], groups=s.labels)
     ec, ebi, ebv, et = pkg.facet_counts(yp, present, s.labels, 37, float(tv[1]))
-    assert total == et and np.array_equal(fc, ec) and np.array_equal(fbi, ebi) and np.array_equal(_bits(fbv), _bits(ebv)), "facet counts differ"
+    assert total == et and np.array_equal(fc, ec) and np.array_equal(fbi, ebi) and np.array_equal(bits(fbv), bits(ebv)), "facet counts differ"
     sc = eng.score_rows(s.ids, s.xs[0])
-    assert np.array_equal(_bits(sc[0]), _bits(yp[s.ids])), "score_rows differs from the order-matched oracle"
+    assert np.array_equal(bits(sc[0]), bits(yp[s.ids])), "score_rows differs from the order-matched oracle"
     return ("single" if d == 4 else ("radix" if _radix(eng) else "stream")), c2  # ("radix": inferred, see the module's note)
 
 

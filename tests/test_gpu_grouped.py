@@ -9,52 +9,21 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import EngineSetup, GuardedOut, Scores, status_of
+
 pytestmark = pytest.mark.gpu
 
-GUARD = 64          # guard words around every device output
 PAD_GROUP = 0xFFFFFFFF
 
 
-class _Scores:
-    """The order-matched oracle's scores of the engine's layout (the matrix re-packed once by the product's host packer)."""
-    def __init__(self, pkg, eng, m):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def __call__(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-
-def _present(m):
-    return np.bincount(m.row, minlength=m.rows)[:m.rows] > 0
-
-
-class _Out:
+class _Out(GuardedOut):
     """[count][k] device outputs for idx / val / grp and [count] for n, each between two guard zones."""
-    def __init__(self, torch, count, k):
-        self.torch, self.count, self.k = torch, count, k
-        self.i = torch.full((2 * GUARD + count * k,), -7, dtype=torch.int32, device="cuda")
-        self.v = torch.full((2 * GUARD + count * k,), -7.0, dtype=torch.float32, device="cuda")
-        self.g = torch.full((2 * GUARD + count * k,), -7, dtype=torch.int32, device="cuda")
-        self.n = torch.full((2 * GUARD + count,), -7, dtype=torch.int32, device="cuda")
-
-    def ptrs(self):
-        return dict(dev_idx=self.i.data_ptr() + 4 * GUARD, dev_val=self.v.data_ptr() + 4 * GUARD, dev_grp=self.g.data_ptr() + 4 * GUARD,
-                    dev_n=self.n.data_ptr() + 4 * GUARD)
+    COLUMNS = (("dev_idx", "k", "int32"), ("dev_val", "k", "float32"), ("dev_grp", "k", "int32"), ("dev_n", 1, "int32"))
 
     def read(self):
         """(idx[count, k] uint32, val[count, k] float32, grp[count, k] uint32, n[count]); the guard zones must be untouched."""
-        res = []
-        for t, per in ((self.i, self.k), (self.v, self.k), (self.g, self.k), (self.n, 1)):
-            a = t.cpu().numpy()
-            assert np.all(a[:GUARD] == -7) and np.all(a[GUARD + self.count * per:] == -7), "a guard zone was written"
-            res.append(a[GUARD:GUARD + self.count * per].reshape(self.count, per))
-        return res[0].view(np.uint32), res[1], res[2].view(np.uint32), res[3][:, 0]
+        res = super().read()
+        return res["dev_idx"].view(np.uint32), res["dev_val"], res["dev_grp"].view(np.uint32), res["dev_n"][:, 0]
 
 
 def _same(got, want, what=""):
@@ -109,31 +78,11 @@ CONFIGS = {
 }
 
 
-class _Setup:
-    """One engine of a configuration with its query installed, and the scores and presence flags the expectation collapses."""
+class _Setup(EngineSetup):
+    """The engine and scores of one of CONFIGS, and the labelings of its rows; the expectation collapses the scores."""
     def __init__(self, pkg, oracle, torch, name):
-        c = CONFIGS[name]
-        rows, cols, nnz = c["shape"]
-        kw = dict(c["kw"])
-        self.fp32 = "precision" not in kw
-        if not self.fp32:
-            kw["precision"] = getattr(pkg, kw["precision"])
-        self.m = pkg.generate_matrix(rows, cols, nnz, "gamma", rows % 97 + 5)
-        self.x = pkg.create_sample_vector(cols, True, False, True, 19)
-        self.k, self.first_row, self.min_score = c["k"], kw.get("first_row", 0), 0.0
-        self.eng = pkg.SpMV(self.m.row, self.m.col, self.m.val, rows, cols, k=self.k, device=0, **kw)
-        if self.fp32:
-            self.y, self.present = _Scores(pkg, self.eng, self.m)(oracle, self.x)
-        else:
-            self.eng.reset(self.x)
-            self.y, self.present = self.eng.scores().copy(), _present(self.m)
-        if "min_rank" in c:  # min_score at about the 30th best score: the engine is created again with it
-            self.min_score = float(np.sort(self.y[self.present])[::-1][c["min_rank"] - 1])
-            self.eng.close()
-            self.eng = pkg.SpMV(self.m.row, self.m.col, self.m.val, rows, cols, k=self.k, device=0, min_score=self.min_score, **kw)
-        self.eng.reset(self.x)
-        self.labelings = _labelings(rows, rows + 1)
-        self.dx = torch.from_numpy(self.x).cuda()
+        super().__init__(pkg, oracle, torch, CONFIGS[name])
+        self.labelings = _labelings(self.m.rows, self.m.rows + 1)
 
     def expect(self, pkg, labels, allow=None, y=None, present=None):
         y = self.y if y is None else y
@@ -179,7 +128,6 @@ def test_grouped_matches_collapse_topk(pkg, setup, labeling):
 def plain(pkg, oracle):
     import torch
     s = _Setup(pkg, oracle, torch, "default12bit")
-    s.scores = _Scores(pkg, s.eng, s.m)
     yield s
     s.eng.close()
 
@@ -191,7 +139,7 @@ def test_ties_within_groups_and_across_the_cut(pkg, oracle):
     m.val = np.ones_like(m.val)  # all ones and a vector of small integers: integer scores, exact in any order, tied everywhere
     x = np.random.default_rng(2).integers(0, 3, cols).astype(np.float32)
     eng = pkg.SpMV(m.row, m.col, m.val, rows, cols, k=k, device=0)
-    y, present = _Scores(pkg, eng, m)(oracle, x)
+    y, present = Scores(pkg, eng, m)(oracle, x)
     assert np.unique(y[present]).size < 200
     labels = np.arange(rows) // 7
     eng.set_groups(labels)
@@ -309,12 +257,6 @@ def test_no_cross_talk_with_the_batch_path(pkg, oracle, plain):
     eng.reset(s.x)
 
 
-def _status(pkg, fn, *a, **kw):
-    with pytest.raises(pkg.TkspmvError) as e:
-        fn(*a, **kw)
-    return e.value.status
-
-
 def test_errors(pkg, oracle):
     import torch
     L = pkg._lib
@@ -327,41 +269,41 @@ def test_errors(pkg, oracle):
     torch.cuda.synchronize()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0)
     eng.reset(x)
-    assert _status(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE  # before set_groups
-    assert _status(pkg, eng.run_grouped) == L.ERR_STATE
-    assert _status(pkg, eng.set_groups, labels, int(labels.max())) == L.ERR_INVALID  # a label == n_groups ...
-    assert _status(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE                     # ... installs nothing
-    assert _status(pkg, eng.set_groups, labels, 0) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE  # before set_groups
+    assert status_of(pkg, eng.run_grouped) == L.ERR_STATE
+    assert status_of(pkg, eng.set_groups, labels, int(labels.max())) == L.ERR_INVALID  # a label == n_groups ...
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE                     # ... installs nothing
+    assert status_of(pkg, eng.set_groups, labels, 0) == L.ERR_INVALID
     eng.set_groups(labels)
     val, idx, grp = eng.run_grouped()
-    assert _status(pkg, eng.set_groups, labels + 1, int(labels.max()) + 1) == L.ERR_INVALID  # the labels installed before stay
+    assert status_of(pkg, eng.set_groups, labels + 1, int(labels.max()) + 1) == L.ERR_INVALID  # the labels installed before stay
     v2, i2, g2 = eng.run_grouped()
     assert np.array_equal(i2, idx) and np.array_equal(g2, grp) and np.array_equal(v2.view(np.uint32), val.view(np.uint32))
-    assert _status(pkg, eng.enqueue_grouped, 0, 0) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_grouped, 0, 1, dmask.data_ptr(), -1) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_grouped, 0, 0) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1, dmask.data_ptr(), -1) == L.ERR_INVALID
     for given in ((1, 0, 0), (1, 1, 0), (0, 1, 1), (0, 0, 1)):  # output pointers partly given
         p = [buf.data_ptr() if g else 0 for g in given]
-        assert _status(pkg, eng.enqueue_grouped, 0, 1, 0, 0, *p) == L.ERR_INVALID
+        assert status_of(pkg, eng.enqueue_grouped, 0, 1, 0, 0, *p) == L.ERR_INVALID
     n = C.c_int32(0)
     assert L.lib().tkspmv_run_grouped(eng._h, 1, None, None, None, C.byref(n)) == L.ERR_INVALID  # use_filter, none installed
     eng.set_groups(None)
-    assert _status(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE  # removed
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE  # removed
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0)
     eng.set_groups(labels)
-    assert _status(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE    # no query vector installed
-    assert _status(pkg, eng.enqueue_grouped, 0, 2) == L.ERR_INVALID  # NULL dev_xs takes the installed vector: count must be 1
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1) == L.ERR_STATE    # no query vector installed
+    assert status_of(pkg, eng.enqueue_grouped, 0, 2) == L.ERR_INVALID  # NULL dev_xs takes the installed vector: count must be 1
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0, partitions=4, k_per_partition=8)  # the approximate per-partition path
     eng.reset(x)
     eng.set_groups(labels)
-    assert _status(pkg, eng.run_grouped) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, eng.run_grouped) == L.ERR_UNSUPPORTED
     eng.close()
     eng = pkg.SpMV(m.row, m.col, m.val, rows, 1024, k=k, device=0, precision=pkg.F16)
     eng.reset(x)
     eng.set_groups(labels)
     eng.run_grouped()  # served without a mask ...
-    assert _status(pkg, eng.enqueue_grouped, 0, 1, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels
+    assert status_of(pkg, eng.enqueue_grouped, 0, 1, dmask.data_ptr()) == L.ERR_UNSUPPORTED  # ... a mask needs the filter kernels
     with pytest.raises(pkg.TkspmvError) as e:
         eng.enqueue_grouped(0, 1, dmask.data_ptr())
     assert "filtered queries need fp32 values" in str(e.value)

@@ -12,7 +12,9 @@ The conftest syncs torch only for the existing enqueue names: these tests call t
 import numpy as np
 import pytest
 
-from test_gpu_range import _Dev, _bits, _check_query, _expected, _masks, _thresholds
+import support
+from support import bits
+from test_gpu_range import _Dev, _check_query, _expected, _thresholds
 from test_gpu_single import _exact
 
 pytestmark = pytest.mark.gpu
@@ -171,7 +173,7 @@ def test_very_long_partitions_every_query_form(pkg, oracle, first, P):
     _exact(pkg, oracle, m, eng, x, k, idx, val, raw, C)
     c1 = eng.debug_counters()
     served = _served(c0, c1, 1)
-    assert np.array_equal(_bits(eng.scores()), _bits(yp)), "tkspmv_scores differs from the order-matched oracle"
+    assert np.array_equal(bits(eng.scores()), bits(yp)), "tkspmv_scores differs from the order-matched oracle"
     bi, bv = _batch_lists(eng, xs[1:6], k)
     for q in range(5):
         _exact(pkg, oracle, m, eng, xs[1 + q], k, bi[q], bv[q], raw, C)
@@ -197,10 +199,10 @@ def test_very_long_partitions_every_query_form(pkg, oracle, first, P):
         rv, ri = eng.run_range(thr[name])
         exp = exps[names.index(name)]
         ei, ev = oracle.sort_tuples(np.array([r for r, _ in exp], dtype=np.uint32), np.array([b for _, b in exp], dtype=np.uint32).view(np.float32))
-        assert eng.last_range_count == len(exp) and np.array_equal(ri, ei) and np.array_equal(_bits(rv), _bits(ev)), f"P={P}/run_range/{name}"
+        assert eng.last_range_count == len(exp) and np.array_equal(ri, ei) and np.array_equal(bits(rv), bits(ev)), f"P={P}/run_range/{name}"
 
     # filtered top-k under a dense and a very sparse mask
-    masks = _masks(rows, idx, 0, rows)
+    masks = support.masks(rows, idx, 0, rows)
     dx = torch.from_numpy(x).cuda()
     for name in ("random0.5", "random0.001"):
         allow = masks[name]
@@ -212,20 +214,20 @@ def test_very_long_partitions_every_query_form(pkg, oracle, first, P):
         eng.synchronize()
         ei, ev = oracle.select_topk(yp, (present & allow).astype(np.uint8), k)
         assert np.array_equal(out_i.cpu().numpy().view(np.uint32), ei), f"P={P}/filtered/{name}: index list differs from the order-matched oracle"
-        assert np.array_equal(_bits(out_v.cpu().numpy()), _bits(ev)), f"P={P}/filtered/{name}: scores are not bit-identical"
+        assert np.array_equal(bits(out_v.cpu().numpy()), bits(ev)), f"P={P}/filtered/{name}: scores are not bit-identical"
 
     # facet counts per label row % 37
     labels = np.arange(rows) % 37
     for name in ("rank1000", "zero"):
         fc, fbi, fbv, total = eng.run_facets(thr[name], vec=x, groups=labels)
         ec, ebi, ebv, et = pkg.facet_counts(yp, present, labels, 37, thr[name])
-        assert total == et and np.array_equal(fc, ec) and np.array_equal(fbi, ebi) and np.array_equal(_bits(fbv), _bits(ebv)), f"P={P}/facets/{name}"
+        assert total == et and np.array_equal(fc, ec) and np.array_equal(fbi, ebi) and np.array_equal(bits(fbv), bits(ebv)), f"P={P}/facets/{name}"
 
     # grouped top-k: groups of 7 consecutive rows
     groups = np.arange(rows) // 7
     gval, gidx, ggrp = eng.run_grouped(vec=x, groups=groups)
     ei, ev, eg, en = pkg.collapse_topk(yp, present, groups, k)
-    assert gidx.size == en == k and np.array_equal(gidx, ei[:en]) and np.array_equal(_bits(gval), _bits(ev[:en])) and np.array_equal(ggrp, eg[:en]), f"P={P}/grouped"
+    assert gidx.size == en == k and np.array_equal(gidx, ei[:en]) and np.array_equal(bits(gval), bits(ev[:en])) and np.array_equal(ggrp, eg[:en]), f"P={P}/grouped"
 
     # search-after: three pages
     cursor = None
@@ -233,7 +235,7 @@ def test_very_long_partitions_every_query_form(pkg, oracle, first, P):
         got = eng.run_after(cursor, vec=x)
         want = pkg.page_after(yp, present, k, cursor)
         assert (got[2], got[3], got[4]) == (want[2], want[3], want[4]), (f"P={P}/after/page {page}", got[2:], want[2:])
-        assert np.array_equal(got[0], want[0]) and np.array_equal(_bits(got[1]), _bits(want[1])), f"P={P}/after/page {page}"
+        assert np.array_equal(got[0], want[0]) and np.array_equal(bits(got[1]), bits(want[1])), f"P={P}/after/page {page}"
         cursor = got[4]
     assert cursor[2] == pkg.CURSOR_AFTER
 
@@ -251,13 +253,13 @@ def test_very_long_partitions_every_query_form(pkg, oracle, first, P):
     lasts = np.concatenate([firsts[1:] - 1, [int(np.flatnonzero(present)[-1]), rows - 1]])
     ids = np.concatenate([np.random.default_rng(P).choice(rows, 64, replace=False), firsts, lasts]).astype(np.uint32)
     sc = eng.score_rows(ids, x)
-    assert np.array_equal(_bits(sc[0]), _bits(yp[ids])), f"P={P}/score_rows"
+    assert np.array_equal(bits(sc[0]), bits(yp[ids])), f"P={P}/score_rows"
     rx, rl = eng.row_vectors(ids)
     for i, r in enumerate(ids):
         sel = m.row == r
         want = np.zeros(m.cols, dtype=np.float32)
         np.add.at(want, m.col[sel], m.val[sel])
-        assert rl[i] == np.count_nonzero(sel) and np.array_equal(_bits(rx[i]), _bits(want)), f"P={P}/row_vectors/row {r}"
+        assert rl[i] == np.count_nonzero(sel) and np.array_equal(bits(rx[i]), bits(want)), f"P={P}/row_vectors/row {r}"
 
     print(f"\n[P={P}: {FIRST[P]} packets per partition, k={k}] tkspmv_run served by {served}; grid {info['grid']} x {info['block']}, n_groups {info['n_groups']}, "
           f"batch_mode {info['batch_mode']:#x}; after the run {_some(c1)}; after the batch of 5 {_some(c2)}; at the end {_some(eng.debug_counters())}")
@@ -296,13 +298,13 @@ def test_other_value_types_at_65_packets_per_partition(pkg, oracle, second, prec
     for q in range(2):
         val, idx = _run(eng, xs[q])
         assert np.array_equal(idx, want[q][0]), f"{precision}/{width}: tkspmv_run {q}: index list differs from the model"
-        assert np.array_equal(_bits(val), _bits(want[q][1])), f"{precision}/{width}: tkspmv_run {q}: scores are not bit-identical"
+        assert np.array_equal(bits(val), bits(want[q][1])), f"{precision}/{width}: tkspmv_run {q}: scores are not bit-identical"
     y, _ = model(xs[1])
-    assert np.array_equal(_bits(eng.scores()), _bits(y)), f"{precision}/{width}: tkspmv_scores differs from the model"
+    assert np.array_equal(bits(eng.scores()), bits(y)), f"{precision}/{width}: tkspmv_scores differs from the model"
     bi, bv = _batch_lists(eng, xs, k)
     for q in range(8):
         assert np.array_equal(bi[q], want[q][0]), f"{precision}/{width}: batch query {q}: index list differs from the model"
-        assert np.array_equal(_bits(bv[q]), _bits(want[q][1])), f"{precision}/{width}: batch query {q}: scores are not bit-identical"
+        assert np.array_equal(bits(bv[q]), bits(want[q][1])), f"{precision}/{width}: batch query {q}: scores are not bit-identical"
     c1 = eng.debug_counters()
     assert info["batch_mode"] & 0xFF and c1["batch_launches"] > c0["batch_launches"] and c1["single_launches"] == 0, (info, c1)
     print(f"\n[{precision} width {width}, 65 packets per partition] batch_mode {info['batch_mode']:#x}; {_some(c0)} -> {_some(c1)}")
@@ -328,6 +330,6 @@ def test_compact_stream_on_a_prepacked_engine(pkg, oracle, monkeypatch, first):
         lists[compact] = _batch_lists(eng, xs[:12], k)
         print(f"\n[P=47, 2 replicas, F32_COMPACT={compact}] batch_packet_bytes {info['batch_packet_bytes']}; {_some(eng.debug_counters())}")
         eng.close()
-    assert np.array_equal(lists["1"][0], lists["0"][0]) and np.array_equal(_bits(lists["1"][1]), _bits(lists["0"][1])), "the two streams' lists differ"
+    assert np.array_equal(lists["1"][0], lists["0"][0]) and np.array_equal(bits(lists["1"][1]), bits(lists["0"][1])), "the two streams' lists differ"
     for q in range(12):
         _exact(pkg, oracle, m, None, xs[q], k, lists["1"][0][q], lists["1"][1][q], raw, info["packet_entries"] // 64)

@@ -9,13 +9,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import bits
+
 pytestmark = pytest.mark.gpu
 
 FILL = 0x5A5A5A5A
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
 
 
 def _dev(torch, a):
@@ -334,9 +332,9 @@ def test_feeds_filtered_range_and_facets_unwaited(pkg, cases):
         eng.synchronize()
         torch.cuda.synchronize()
         n = int(rc.cpu().numpy().view(np.uint32)[0])
-        hi, hv = ri.cpu().numpy().view(np.uint32)[:n], _bits(rv.cpu().numpy()[:n])
+        hi, hv = ri.cpu().numpy().view(np.uint32)[:n], bits(rv.cpu().numpy()[:n])
         o = np.lexsort((hv, hi))  # (range results come in no particular order)
-        return (oi.cpu().numpy().view(np.uint32), _bits(ov.cpu().numpy()), n, hi[o], hv[o], fc.cpu().numpy().view(np.uint32),
+        return (oi.cpu().numpy().view(np.uint32), bits(ov.cpu().numpy()), n, hi[o], hv[o], fc.cpu().numpy().view(np.uint32),
                 fb.cpu().numpy(), ft.cpu().numpy().view(np.uint32))
 
     dhost = _dev(torch, host_words)
@@ -365,7 +363,7 @@ def test_run_match_installs_the_filter(pkg, cases):
         eng.enqueue_filtered(0, 1, 0)
         eng.synchronize()
         gv, gi = eng.read_result()
-        assert np.array_equal(gi, ei) and np.array_equal(_bits(gv), _bits(ev))
+        assert np.array_equal(gi, ei) and np.array_equal(bits(gv), bits(ev))
         # AND with the installed filter
         allow = np.random.default_rng(8).random(m.rows) < 0.5
         both = ok & allow
@@ -375,7 +373,7 @@ def test_run_match_installs_the_filter(pkg, cases):
         eng.enqueue_filtered(0, 1, 0)
         eng.synchronize()
         gv, gi = eng.read_result()
-        assert np.array_equal(gi, ei) and np.array_equal(_bits(gv), _bits(ev))
+        assert np.array_equal(gi, ei) and np.array_equal(bits(gv), bits(ev))
         # host_mask and count may each be NULL; use_filter with none installed is an error
         lib = pkg._lib.lib()
         rec = pkg._lib.Match(*c.preds[5])
@@ -407,7 +405,7 @@ def test_no_cross_talk_with_the_batch(pkg, cases):
             read = then(eng)  # (not waited for: right behind the batch launch)
             eng.synchronize()
             torch.cuda.synchronize()
-            return oi.cpu().numpy().view(np.uint32).copy(), _bits(ov.cpu().numpy()).copy(), read() if read else None
+            return oi.cpu().numpy().view(np.uint32).copy(), bits(ov.cpu().numpy()).copy(), read() if read else None
         finally:
             eng.close()
     ei, ev, _ = batch(lambda eng: None)

@@ -15,6 +15,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import status_of
+
 pytestmark = pytest.mark.gpu
 
 ROWS, COLS, PER_ROW, K = 64, 32, 5, 4
@@ -44,37 +46,31 @@ def dev():
     return t
 
 
-def _status(pkg, fn, *a, **kw):
-    with pytest.raises(pkg.TkspmvError) as e:
-        fn(*a, **kw)
-    return e.value.status
-
-
 def test_enqueue_forms_outside_their_scope(pkg, engines, dev):
     L = pkg._lib
     P = dev.data_ptr()
     for name in ("f16", "parts"):  # both outside filter_unsupported / range_unsupported
         eng = engines[name]
-        assert _status(pkg, eng.enqueue_filtered, P, 0, P) == L.ERR_UNSUPPORTED, name
-        assert _status(pkg, eng.enqueue_range, P, 0, P, P) == L.ERR_UNSUPPORTED, name
-        assert _status(pkg, eng.enqueue_facets, P, 0, P, P) == L.ERR_INVALID, name
-        assert _status(pkg, eng.enqueue_facets, 0, 2, P, P) == L.ERR_INVALID, name
+        assert status_of(pkg, eng.enqueue_filtered, P, 0, P) == L.ERR_UNSUPPORTED, name
+        assert status_of(pkg, eng.enqueue_range, P, 0, P, P) == L.ERR_UNSUPPORTED, name
+        assert status_of(pkg, eng.enqueue_facets, P, 0, P, P) == L.ERR_INVALID, name
+        assert status_of(pkg, eng.enqueue_facets, 0, 2, P, P) == L.ERR_INVALID, name
     eng = engines["parts"]  # outside grouped_unsupported
-    assert _status(pkg, eng.enqueue_grouped, P, 0) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_after, P, 0) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_grouped, P, 0) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_after, P, 0) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_after, 0, 2) == L.ERR_INVALID
     eng = engines["f16"]  # outside row_vectors_unsupported / match_unsupported
-    assert _status(pkg, eng.enqueue_score_rows, 0, 2, P, 4, P) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_score_rows, P, 0, P, 4, P) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_row_vectors, P, 0, P) == L.ERR_INVALID
-    assert _status(pkg, eng.enqueue_match, P, P, 0, P) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_score_rows, 0, 2, P, 4, P) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_score_rows, P, 0, P, 4, P) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_row_vectors, P, 0, P) == L.ERR_INVALID
+    assert status_of(pkg, eng.enqueue_match, P, P, 0, P) == L.ERR_INVALID
     # ... and the same calls with valid arguments say UNSUPPORTED
-    assert _status(pkg, engines["parts"].enqueue_grouped, P, 1) == L.ERR_UNSUPPORTED
-    assert _status(pkg, engines["parts"].enqueue_after, P, 1) == L.ERR_UNSUPPORTED
-    assert _status(pkg, engines["f16"].enqueue_facets, P, 1, P, P) == L.ERR_UNSUPPORTED
-    assert _status(pkg, engines["f16"].enqueue_score_rows, P, 1, P, 4, P) == L.ERR_UNSUPPORTED
-    assert _status(pkg, engines["f16"].enqueue_row_vectors, P, 1, P) == L.ERR_UNSUPPORTED
-    assert _status(pkg, engines["f16"].enqueue_match, P, P, 1, P) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["parts"].enqueue_grouped, P, 1) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["parts"].enqueue_after, P, 1) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["f16"].enqueue_facets, P, 1, P, P) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["f16"].enqueue_score_rows, P, 1, P, 4, P) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["f16"].enqueue_row_vectors, P, 1, P) == L.ERR_UNSUPPORTED
+    assert status_of(pkg, engines["f16"].enqueue_match, P, P, 1, P) == L.ERR_UNSUPPORTED
 
 
 def test_host_forms_outside_their_scope(pkg, engines):

@@ -10,6 +10,9 @@ import dataclasses
 import numpy as np
 import pytest
 
+import support
+from support import Scores, bits
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4   # the project's north-star tolerance
@@ -21,43 +24,12 @@ def _engine(pkg, m, k, **kw):
     return pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, **kw)
 
 
-class _Scores:
-    """The order-matched oracle's scores of the engine's layout (the matrix re-packed once by the product's host packer, with the
-    engine's own partition count), as test_gpu_filter.py builds them."""
-    def __init__(self, pkg, eng, m):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def __call__(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-
-def _masks(rows, unfiltered_idx, first_row, seed):
-    """The four masks of test_gpu_filter.py."""
-    rng = np.random.default_rng(seed)
-    out = {f"random{d}": rng.random(rows) < d for d in (0.5, 0.05, 0.001)}
-    top = unfiltered_idx.astype(np.int64) - first_row
-    ex = np.ones(rows, dtype=bool)
-    ex[top[top >= 0]] = False  # the unfiltered top-k excluded
-    out["no_topk"] = ex
-    return out
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
 def _expected(yp, present, allow, t, first_row=0):
     """{(first_row + r, bits(yp[r]))} of the rows that have entries, are allowed and score >= t, compared in fp32."""
     with np.errstate(invalid="ignore"):
         hit = present & allow & (yp.astype(np.float32) >= np.float32(t))
     rows = np.flatnonzero(hit)
-    return set(zip((rows + first_row).tolist(), _bits(yp[rows]).tolist()))
+    return set(zip((rows + first_row).tolist(), bits(yp[rows]).tolist()))
 
 
 def _thresholds(yp, present, extra=()):
@@ -89,13 +61,13 @@ def _check_query(count, idx, val, capacity, exp, label):
     """count: dev_counts[i]; idx / val: the query's capacity output entries."""
     assert int(count) == len(exp), f"{label}: dev_counts = {int(count)}, expected {len(exp)} matches"
     n = min(len(exp), capacity)
-    got = list(zip(idx[:n].tolist(), _bits(val[:n]).tolist()))
+    got = list(zip(idx[:n].tolist(), bits(val[:n]).tolist()))
     assert len(set(r for r, _ in got)) == n, f"{label}: a row was returned twice"
     if len(exp) <= capacity:
         assert set(got) == exp, f"{label}: the match set differs from the order-matched oracle ({len(set(got) ^ exp)} pairs)"
     else:
         assert set(got) <= exp, f"{label}: a stored pair is no member of the expected set"
-    assert np.all(idx[n:] == FILL_I) and np.all(_bits(val[n:]) == _bits(np.float32(FILL_V))), f"{label}: entries beyond min(count, capacity) were written"
+    assert np.all(idx[n:] == FILL_I) and np.all(bits(val[n:]) == bits(np.float32(FILL_V))), f"{label}: entries beyond min(count, capacity) were written"
 
 
 def _gold_leg(oracle, m, x, t, got_rows, got_vals, first_row, label, y64_cache):
@@ -135,14 +107,14 @@ def test_range_matches_oracle(pkg, oracle, request, rows, cols, nnz, k, kw):
     x = pkg.create_sample_vector(cols, True, False, True, 17)
     first_row = kw.get("first_row", 0)
     eng = _engine(pkg, m, k, **kw)
-    yp, present = _Scores(pkg, eng, m)(oracle, x)
+    yp, present = Scores(pkg, eng, m)(oracle, x)
     extra = [("zero", 0.0), ("minus_one", -1.0), ("minus_inf", float("-inf"))] if rows == 1000 else []
     thr = _thresholds(yp, present, extra)
     eng.reset(x)
     eng()
     _, ui = eng.read_result()
     masks = {"unfiltered": None}
-    masks.update(_masks(rows, ui, first_row, rows))
+    masks.update(support.masks(rows, ui, first_row, rows))
     names = list(thr)
     nq = len(names)
     tv = np.array([thr[n] for n in names], dtype=np.float32)
@@ -192,7 +164,7 @@ def test_signed_data(pkg, oracle):
     m = dataclasses.replace(m, val=(m.val * rng.choice(np.float32([-1.0, 1.0]), m.val.shape[0])).astype(np.float32))
     x = (pkg.create_sample_vector(cols, True, False, True, 19) * rng.choice(np.float32([-1.0, 1.0]), cols)).astype(np.float32)
     eng = _engine(pkg, m, k)
-    yp, present = _Scores(pkg, eng, m)(oracle, x)
+    yp, present = Scores(pkg, eng, m)(oracle, x)
     assert (yp[present] < 0).sum() > rows // 10
     s = np.sort(yp[present])[::-1]
     tv = np.array([s[9], s[999], s[s.size * 3 // 4]], dtype=np.float32)
@@ -218,7 +190,7 @@ def mid(pkg, oracle):
     m = pkg.generate_matrix(rows, cols, 20, "gamma", 12)
     eng = _engine(pkg, m, k)
     xs = np.stack([pkg.create_sample_vector(cols, True, False, True, 300 + i) for i in range(nq)]).astype(np.float32)
-    sc = _Scores(pkg, eng, m)
+    sc = Scores(pkg, eng, m)
     scores = [sc(oracle, xs[i]) for i in range(nq)]
     yield m, eng, xs, scores
     eng.close()
@@ -303,24 +275,24 @@ def test_run_range(pkg, oracle, mid):
         # capacity=None: count first, then exactly that many
         val, idx = eng.run_range(t, vec=xs[5])
         ei, ev = sorted_pairs(_expected(yp, present, ones, t))
-        assert np.array_equal(idx, ei) and np.array_equal(_bits(val), _bits(ev))
+        assert np.array_equal(idx, ei) and np.array_equal(bits(val), bits(ev))
         assert eng.last_range_count == ei.size
         val, idx = eng.run_range(t, allow=allow)
         ei, ev = sorted_pairs(_expected(yp, present, allow, t))
-        assert np.array_equal(idx, ei) and np.array_equal(_bits(val), _bits(ev))
+        assert np.array_equal(idx, ei) and np.array_equal(bits(val), bits(ev))
     # a capacity that is too small: the true count, and `capacity` distinct members of the expected set, sorted among themselves
     t = float(s[4999])
     exp = _expected(yp, present, allow, t)
     val, idx = eng.run_range(t, allow=allow, capacity=50)
     assert eng.last_range_count == len(exp) and len(exp) > 50 and idx.size == 50
-    got = set(zip(idx.tolist(), _bits(val).tolist()))
+    got = set(zip(idx.tolist(), bits(val).tolist()))
     assert len(got) == 50 and got <= exp
     si, sv = oracle.sort_tuples(idx, val)
-    assert np.array_equal(idx, si) and np.array_equal(_bits(val), _bits(sv))
+    assert np.array_equal(idx, si) and np.array_equal(bits(val), bits(sv))
     # a capacity larger than the count: all of them
     val, idx = eng.run_range(float(s[9]), allow=allow, capacity=50)
     ei, ev = sorted_pairs(_expected(yp, present, allow, float(s[9])))
-    assert np.array_equal(idx, ei) and np.array_equal(_bits(val), _bits(ev)) and eng.last_range_count == ei.size
+    assert np.array_equal(idx, ei) and np.array_equal(bits(val), bits(ev)) and eng.last_range_count == ei.size
     eng.set_filter(None)
     # the one-shot helper
     small = pkg.generate_matrix(1000, 512, 20, "gamma", 5)
@@ -376,7 +348,7 @@ def test_no_cross_talk(pkg, oracle):
     words = np.stack([pkg.row_mask(rows, a) for a in allows])
     dmask = torch.from_numpy(words.view(np.int32)).cuda()
     eng = _engine(pkg, m, k, multi_q=4)
-    scores, sc = {}, _Scores(pkg, eng, m)
+    scores, sc = {}, Scores(pkg, eng, m)
 
     def yp_of(i):
         if i not in scores:
@@ -396,15 +368,15 @@ def test_no_cross_talk(pkg, oracle):
     for q in range(8):
         _check_query(counts[q], gi[q], gv[q], 256, _expected(*yp_of(q), allows[q], tv[q]), f"cross_talk/{q}")
         ei, ev = oracle.select_topk(*yp_of(q), k)
-        assert np.array_equal(got["batch1"][0][q], ei) and np.array_equal(_bits(got["batch1"][1][q]), _bits(ev))
+        assert np.array_equal(got["batch1"][0][q], ei) and np.array_equal(bits(got["batch1"][1][q]), bits(ev))
         ei, ev = oracle.select_topk(*yp_of(4 + q), k)
-        assert np.array_equal(got["batch2"][0][q], ei) and np.array_equal(_bits(got["batch2"][1][q]), _bits(ev))
+        assert np.array_equal(got["batch2"][0][q], ei) and np.array_equal(bits(got["batch2"][1][q]), bits(ev))
     ei, ev = oracle.select_topk(*yp_of(3), k)
-    assert np.array_equal(got["run"][0], ei) and np.array_equal(_bits(got["run"][1]), _bits(ev))
+    assert np.array_equal(got["run"][0], ei) and np.array_equal(bits(got["run"][1]), bits(ev))
     # the multi-query pass sums in its own order (row per lane): the oracle's segmented scores, as smoke() checks it
     y, present = oracle.scores_f32_segmented(m.row, m.col, m.val, xs[5], m.rows)
     ei, ev = oracle.select_topk(y, present, k)
-    assert np.array_equal(got["multi"][0], ei) and np.array_equal(_bits(got["multi"][1]), _bits(ev))
+    assert np.array_equal(got["multi"][0], ei) and np.array_equal(bits(got["multi"][1]), bits(ev))
     # no repair the sequence without the range queries would not have run
     for key in ("checks_failed", "late_repairs", "single_repairs"):
         assert counters[key] <= ref_counters[key], (key, counters, ref_counters)

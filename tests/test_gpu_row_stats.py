@@ -11,26 +11,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import bits, coo, signed
 from test_score_rows_host import _hand_made
 
 pytestmark = pytest.mark.gpu
 
 FILL, GUARD = -7.0, 64
 KINDS = (0, 1, 2, 3)
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.ascontiguousarray(row, np.uint32), col=np.ascontiguousarray(col, np.uint32),
-                         val=np.ascontiguousarray(val, np.float32))
-
-
-def _signed(pkg, m, seed):
-    sign = np.where(np.random.default_rng(seed).random(m.val.size) < 0.5, -1.0, 1.0).astype(np.float32)
-    return _coo(pkg, m.rows, m.cols, m.row, m.col, m.val * sign)
 
 
 def _twin(pkg, eng, m, packed=None):
@@ -47,7 +34,7 @@ def _check_engine(pkg, eng, m, label, packed=None):
     for kind in KINDS:
         got = eng.row_stats(kind)
         assert got.shape == (m.rows,) and got.dtype == np.float32
-        bad = np.flatnonzero(_bits(got) != _bits(want[kind]))
+        bad = np.flatnonzero(bits(got) != bits(want[kind]))
         assert bad.size == 0, f"{label} kind {kind}: {bad.size} rows differ from the host twin, first {bad[:8]}: {got[bad[:8]]} != {want[kind][bad[:8]]}"
     assert np.array_equal(want[0], np.bincount(m.row, minlength=m.rows).astype(np.float32)), label
     return want
@@ -58,7 +45,7 @@ GENERATED = [(cols, c_lane) for cols in (300, 1024, 4096) for c_lane in (4, 8) i
 
 @pytest.mark.parametrize("cols,c_lane", GENERATED + [(4096, 8)])
 def test_generated_matrices(pkg, cols, c_lane):
-    m = _signed(pkg, pkg.generate_matrix(2500, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols)
+    m = signed(pkg, pkg.generate_matrix(2500, cols, 20, "gamma" if cols == 1024 else "uniform", 5 + cols), cols)
     if c_lane == 8 and cols > 1024:  # (8 entries per lane exist up to 1024 columns: creation refuses, nothing to compare)
         with pytest.raises(pkg.TkspmvError):
             pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0, nnz_per_lane=c_lane).close()
@@ -77,7 +64,7 @@ def _hand_made_general(pkg):
     row = np.concatenate([base.row, np.full(8, 12), np.full(8, 13)])
     col = np.concatenate([base.col, rng.integers(0, 1024, 16)])
     val = np.concatenate([base.val, (1.0 + rng.random(8)) * 1e-20 * np.array([1, -1] * 4), (1.0 + rng.random(8)) * 1e25 * np.array([-1, 1] * 4)])
-    return _coo(pkg, base.rows, 1024, row, col, val)
+    return coo(pkg, base.rows, 1024, row, col, val)
 
 
 @pytest.mark.parametrize("c_lane", [4, 8])
@@ -86,18 +73,18 @@ def test_hand_made_rows(pkg, c_lane):
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=4, device=0, nnz_per_lane=c_lane)
     nnz, l1, l2sq, inv = _check_engine(pkg, eng, m, f"hand-made C={c_lane}")
     for a in (nnz, l1, l2sq, inv):
-        assert np.all(_bits(a[[0, 1, 4, 9, 14]]) == 0)
+        assert np.all(bits(a[[0, 1, 4, 9, 14]]) == 0)
     assert nnz[3] == 256 and nnz[5] == 512 and nnz[6] == 1500
     assert 0 < l2sq[12] < np.finfo(np.float32).tiny and np.isfinite(inv[12]) and inv[12] > 1e19
-    assert np.isposinf(l2sq[13]) and _bits(inv[13:14])[0] == 0
-    assert np.array_equal(_bits(inv), _bits(pkg.inv_l2(l2sq))) and np.all(np.isfinite(eng.row_stats(pkg._lib.ROW_INV_L2)))
+    assert np.isposinf(l2sq[13]) and bits(inv[13:14])[0] == 0
+    assert np.array_equal(bits(inv), bits(pkg.inv_l2(l2sq))) and np.all(np.isfinite(eng.row_stats(pkg._lib.ROW_INV_L2)))
     eng.close()
 
 
 def test_partition_tails(pkg):
     rng = np.random.default_rng(7)
     rows, per = 128, 8  # 1024 entries: rows end on the last slot of a packet
-    m = _coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
+    m = coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
     for c_lane in (4, 8):
         eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=4, device=0, nnz_per_lane=c_lane)
         _check_engine(pkg, eng, m, f"exact fit C={c_lane}")
@@ -105,7 +92,7 @@ def test_partition_tails(pkg):
 
 
 def test_from_packed_first_row_approximate_and_geometry(pkg, tmp_path):
-    m = _signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
+    m = signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 9), 9)
     # an engine made from a saved and loaded file: no COO anywhere near it
     hint = pkg.Packed.wave_partitions(device=0, m=m)
     packed = pkg.Packed(m, k=16, n_wave_partitions=hint)
@@ -130,7 +117,7 @@ def test_from_packed_first_row_approximate_and_geometry(pkg, tmp_path):
 
 def test_long_partitions(pkg):
     """8 partitions of several hundred packets each (the shape of test_gpu_long_partitions.py): a wave walks them all."""
-    m = _signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
+    m = signed(pkg, pkg.generate_matrix(40000, 1024, 20, "gamma", 41), 41)
     packed = pkg.Packed(m, k=16, n_wave_partitions=8)
     assert packed.info()["packets_per_partition"] >= 300
     eng = pkg.SpMV.from_packed(packed, k=16, device=0)
@@ -143,7 +130,7 @@ def test_enqueue_into_a_guarded_buffer(pkg):
     """Exactly rows floats change: guard zones of 64 floats on both sides keep their sentinel; on the engine's stream and on a
     caller's stream with the caller's event waited for."""
     import torch
-    m = _signed(pkg, pkg.generate_matrix(2500, 1024, 20, "gamma", 31), 31)
+    m = signed(pkg, pkg.generate_matrix(2500, 1024, 20, "gamma", 31), 31)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0, first_row=77)
     want = _twin(pkg, eng, m)
     side = torch.cuda.Stream()
@@ -163,36 +150,36 @@ def test_enqueue_into_a_guarded_buffer(pkg):
                 done.record(side)
                 done.synchronize()
             out = buf.cpu().numpy()
-            assert np.all(_bits(out[:GUARD]) == _bits(np.float32(FILL))) and np.all(_bits(out[GUARD + m.rows:]) == _bits(np.float32(FILL))), "written outside [0, rows)"
-            assert np.array_equal(_bits(out[GUARD:GUARD + m.rows]), _bits(want[kind])), (stream is not None, kind)
+            assert np.all(bits(out[:GUARD]) == bits(np.float32(FILL))) and np.all(bits(out[GUARD + m.rows:]) == bits(np.float32(FILL))), "written outside [0, rows)"
+            assert np.array_equal(bits(out[GUARD:GUARD + m.rows]), bits(want[kind])), (stream is not None, kind)
     eng.close()
 
 
 def test_identity_with_the_scoring_paths(pkg):
     """L2SQ of row r == score_rows([r], vecs=row_vectors([r])): the row scored against itself, on matrices without repeated columns."""
     L = pkg._lib
-    m = _signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 17), 17)
+    m = signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 17), 17)
     key = m.row.astype(np.uint64) * np.uint64(1 << 20) + m.col.astype(np.uint64)
     keep = np.unique(key, return_index=True)[1]  # (the first entry of every (row, column))
-    m = _coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep])
+    m = coo(pkg, m.rows, m.cols, m.row[keep], m.col[keep], m.val[keep])
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0)
     l2sq = eng.row_stats(L.ROW_L2SQ)
     ids = np.random.default_rng(3).choice(m.rows, 200, replace=False).astype(np.uint32)
     rv, _ = eng.row_vectors(ids)
     got = np.array([eng.score_rows(ids[i:i + 1], rv[i])[0, 0] for i in range(ids.size)], dtype=np.float32)
-    assert np.array_equal(_bits(got), _bits(l2sq[ids]))
+    assert np.array_equal(bits(got), bits(l2sq[ids]))
     assert np.count_nonzero(l2sq[ids]) >= 190
     eng.close()
     base, _ = _hand_made(pkg, 1024)
     key = base.row.astype(np.uint64) * np.uint64(1 << 20) + base.col.astype(np.uint64)
     keep = np.sort(np.unique(key, return_index=True)[1])
-    m = _coo(pkg, base.rows, 1024, base.row[keep], base.col[keep], base.val[keep])
+    m = coo(pkg, base.rows, 1024, base.row[keep], base.col[keep], base.val[keep])
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=4, device=0)
     l2sq = eng.row_stats(L.ROW_L2SQ)
     ids = np.arange(m.rows, dtype=np.uint32)
     rv, _ = eng.row_vectors(ids)
     got = np.array([eng.score_rows(ids[i:i + 1], rv[i])[0, 0] for i in range(ids.size)], dtype=np.float32)
-    assert np.array_equal(_bits(got), _bits(l2sq))
+    assert np.array_equal(bits(got), bits(l2sq))
     eng.close()
 
 
@@ -203,7 +190,7 @@ def _unit(x):
 
 def test_cosine_boost(pkg, tmp_path):
     L = pkg._lib
-    m = _signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 23), 23)
+    m = signed(pkg, pkg.generate_matrix(20000, 1024, 20, "gamma", 23), 23)
     k = 20
     x = _unit(np.random.default_rng(4).standard_normal(m.cols))
     a = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, vec=x, min_score=-np.inf)
@@ -215,7 +202,7 @@ def test_cosine_boost(pkg, tmp_path):
         out, cursor = [], None
         for _ in range(n_pages):
             idx, val, n, total, cursor = eng.run_boosted(cursor, allow=allow, **boost)
-            out.append((idx.copy(), _bits(val).copy(), n, total, tuple(cursor)))
+            out.append((idx.copy(), bits(val).copy(), n, total, tuple(cursor)))
             boost = {}
         return out
 
@@ -245,7 +232,7 @@ def test_cosine_boost(pkg, tmp_path):
 
 
 def test_cosine_spmv(pkg):
-    m = _signed(pkg, pkg.generate_matrix(5000, 1024, 20, "gamma", 29), 29)
+    m = signed(pkg, pkg.generate_matrix(5000, 1024, 20, "gamma", 29), 29)
     q = np.zeros(m.cols, dtype=np.float32)
     np.add.at(q, m.col[m.row == 7], m.val[m.row == 7])
     assert np.count_nonzero(m.row == 7) >= 2
@@ -275,7 +262,7 @@ def test_engine_state_is_untouched(pkg):
     eng.enqueue_batch(d_q.data_ptr(), 8, d_idx[0].data_ptr(), d_val[0].data_ptr())
     eng.synchronize()
     torch.cuda.synchronize()
-    want_idx, want_val = d_idx[0].cpu().numpy().copy(), _bits(d_val[0].cpu().numpy()).copy()
+    want_idx, want_val = d_idx[0].cpu().numpy().copy(), bits(d_val[0].cpu().numpy()).copy()
     eng.enqueue_batch(d_q.data_ptr(), 8)  # (engine-owned result pair: the last query wins)
     eng.synchronize()
     res0, counters0 = eng.read_result(), eng.debug_counters()
@@ -284,7 +271,7 @@ def test_engine_state_is_untouched(pkg):
     eng.synchronize()
     res1, counters1 = eng.read_result(), eng.debug_counters()
     assert counters1 == counters0, "enqueue_row_stats moved a counter"
-    assert np.array_equal(res0[1], res1[1]) and np.array_equal(_bits(res0[0]), _bits(res1[0])), "enqueue_row_stats changed the result pair"
+    assert np.array_equal(res0[1], res1[1]) and np.array_equal(bits(res0[0]), bits(res1[0])), "enqueue_row_stats changed the result pair"
     # a batch call right behind an unwaited pass returns the same lists
     d_idx[1].zero_(), d_val[1].zero_()
     torch.cuda.synchronize()
@@ -292,7 +279,7 @@ def test_engine_state_is_untouched(pkg):
     eng.enqueue_batch(d_q.data_ptr(), 8, d_idx[1].data_ptr(), d_val[1].data_ptr())
     eng.synchronize()
     torch.cuda.synchronize()
-    assert np.array_equal(d_idx[1].cpu().numpy(), want_idx) and np.array_equal(_bits(d_val[1].cpu().numpy()), want_val)
+    assert np.array_equal(d_idx[1].cpu().numpy(), want_idx) and np.array_equal(bits(d_val[1].cpu().numpy()), want_val)
     eng.close()
 
 
@@ -328,7 +315,7 @@ def test_status_codes(pkg):
     assert lib.tkspmv_row_stats(eng._h, 0, None) == INVALID
     eng.synchronize()
     torch.cuda.synchronize()
-    assert np.all(h_out == FILL) and np.all(_bits(d_out.cpu().numpy()) == _bits(np.float32(FILL))), "a rejected call wrote its output"
+    assert np.all(h_out == FILL) and np.all(bits(d_out.cpu().numpy()) == bits(np.float32(FILL))), "a rejected call wrote its output"
     eng.enqueue_row_stats(0, O)
     eng.synchronize()
     torch.cuda.synchronize()

@@ -11,6 +11,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support
+from support import Layout, bits, coo
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-4   # the project's north-star tolerance (test_gpu_range.py)
@@ -18,15 +21,6 @@ FILL, GUARD = -7.0, 1024
 OUTSIDE = 0xFFFFFFFF
 NEG_INF_BITS = 0xFF800000
 GAP = 0xABCD1234  # what lies between the lists of a strided id buffer
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.ascontiguousarray(row, np.uint32), col=np.ascontiguousarray(col, np.uint32),
-                         val=np.ascontiguousarray(val, np.float32))
 
 
 LONG = {100: 256, 101: 512, 102: 1500}  # rows rewritten with exactly this many entries
@@ -52,7 +46,7 @@ def _matrix(pkg, rows, cols, seed, dist="gamma"):
     val.append(np.array([0.1, 0.3, 1e-8, 0.7, 0.2, 0.5, 0.05, 1e-9, 0.6], dtype=np.float32))  # (sums whose order shows in the bits)
     row, col, val = np.concatenate(row), np.concatenate(col), np.concatenate(val)
     order = np.argsort(row, kind="stable")
-    return _coo(pkg, rows, cols, row[order], col[order], val[order]), sorted(empty)
+    return coo(pkg, rows, cols, row[order], col[order], val[order]), sorted(empty)
 
 
 def _rows_with_repeats(m, want=5):
@@ -61,33 +55,6 @@ def _rows_with_repeats(m, want=5):
     u, cnt = np.unique(key, return_counts=True)
     rr = np.unique((u[cnt > 1] >> np.uint64(20)).astype(np.int64))
     return [int(r) for r in rr if r not in LONG and r != TRIPLE][:want]
-
-
-class _Layout:
-    """The engine's own layout, re-packed by the host packer with the engine's partition count (as test_gpu_range.py's _Scores)."""
-    def __init__(self, pkg, eng, m, packed=None):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        if packed is None:  # (else: the packed matrix the engine was created from)
-            packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def scores(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-    def partition_rows(self, n=6):
-        """First and last row of several partitions (spread over the stream)."""
-        _, _, pkt_row, part_first, _ = self.raw
-        firsts = pkt_row[part_first].astype(np.int64)
-        qs = sorted(set(np.linspace(0, firsts.size - 1, n).astype(int).tolist()))
-        out = []
-        for q in qs:
-            out.append(int(firsts[q]))
-            out.append(int(firsts[q + 1]) - 1 if q + 1 < firsts.size else int(pkt_row.max()))
-        return out
 
 
 def _special_ids(m, empties, layout, first_row):
@@ -127,7 +94,7 @@ class _Expect:
             r = lst - self.first_row
             inside = (r >= 0) & (r < self.rows)
             rc = np.where(inside, r, 0)
-            out[q] = np.where(inside, np.where(present[rc], _bits(yp)[rc], 0), NEG_INF_BITS)
+            out[q] = np.where(inside, np.where(present[rc], bits(yp)[rc], 0), NEG_INF_BITS)
         return out
 
 
@@ -155,12 +122,12 @@ def _run(torch, eng, xs, ids, stride=0, stream=None):
     torch.cuda.synchronize()
     assert np.array_equal(d_ids.cpu().numpy().view(np.uint32), buf), "the id buffer changed"
     out = d_out.cpu().numpy()
-    assert np.all(_bits(out[count * n_rows:]) == _bits(np.float32(FILL))), "written beyond count x n_rows"
+    assert np.all(bits(out[count * n_rows:]) == bits(np.float32(FILL))), "written beyond count x n_rows"
     return out[:count * n_rows].reshape(count, n_rows)
 
 
 def _check(torch, eng, expect, xs, ids, label, stride=0, stream=None):
-    got = _bits(_run(torch, eng, xs, ids, stride, stream))
+    got = bits(_run(torch, eng, xs, ids, stride, stream))
     want = expect.bits(xs, ids)
     bad = np.argwhere(got != want)
     assert bad.size == 0, f"{label}: {bad.shape[0]} scores differ, first (query, position) {bad[:6].tolist()}: got {got[tuple(bad[0])]:#x}, expected {want[tuple(bad[0])]:#x}"
@@ -196,7 +163,7 @@ def test_score_rows(pkg, oracle, tmp_path, name, mk, kw):
     else:
         eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=16, device=0, **kw)
     assert eng.info()["packet_entries"] == (512 if name == "c8_1024" else 256)
-    layout = _Layout(pkg, eng, m, packed)
+    layout = Layout(pkg, eng, m, packed)
     expect = _Expect(oracle, layout, m.rows, first_row)
     special = _special_ids(m, empties, layout, first_row)
     assert len(special) >= 33
@@ -227,25 +194,13 @@ def test_score_rows(pkg, oracle, tmp_path, name, mk, kw):
     got = _run(torch, eng, xg[None, :], inside)[0]
     y64, _ = oracle.scores_f64(m.row, m.col, m.val, xg, m.rows)
     assert np.allclose(got.astype(np.float64), y64[inside.astype(np.int64) - first_row], rtol=RTOL, atol=0), f"{name}: scores differ from fp64"
-    assert np.array_equal(_bits(got), expect.bits(xg[None, :], inside)[0]), f"{name}: gold-leg scores differ from the order-matched oracle"
+    assert np.array_equal(bits(got), expect.bits(xg[None, :], inside)[0]), f"{name}: gold-leg scores differ from the order-matched oracle"
     # the host-array call: one list, a list per query, the installed vector
-    assert np.array_equal(_bits(eng.score_rows(special, xs[:3])), expect.bits(xs[:3], special)), name
-    assert np.array_equal(_bits(eng.score_rows(per_query[:4], xs[:4])), expect.bits(xs[:4], per_query[:4])), name
+    assert np.array_equal(bits(eng.score_rows(special, xs[:3])), expect.bits(xs[:3], special)), name
+    assert np.array_equal(bits(eng.score_rows(per_query[:4], xs[:4])), expect.bits(xs[:4], per_query[:4])), name
     eng.reset(xs[7])
-    assert np.array_equal(_bits(eng.score_rows(many)), expect.bits(xs[7:8], many)), name
+    assert np.array_equal(bits(eng.score_rows(many)), expect.bits(xs[7:8], many)), name
     eng.close()
-
-
-def _batch(torch, eng, xs_host, k):
-    """enqueue_batch on host vectors uploaded here; waits. (values[n, k], indices[n, k])"""
-    n = xs_host.shape[0]
-    d_xs = torch.from_numpy(np.ascontiguousarray(xs_host, dtype=np.float32)).cuda()
-    d_idx = torch.zeros((n, k), dtype=torch.int32, device="cuda")
-    d_val = torch.zeros((n, k), dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    eng.enqueue_batch(d_xs.data_ptr(), n, d_idx.data_ptr(), d_val.data_ptr())
-    eng.synchronize()
-    return d_val.cpu().numpy(), d_idx.cpu().numpy().view(np.uint32)
 
 
 def test_cross_path_identities(pkg):
@@ -260,20 +215,20 @@ def test_cross_path_identities(pkg):
     for q in range(2):
         eng.reset(xs[q])
         y = eng.scores()
-        assert np.array_equal(_bits(eng.score_rows(all_ids)[0]), _bits(y)), "score_rows of all rows differs from scores()"
-        assert np.array_equal(_bits(eng.score_rows(all_ids[::-1].copy(), xs[q])[0]), _bits(y[::-1]))
+        assert np.array_equal(bits(eng.score_rows(all_ids)[0]), bits(y)), "score_rows of all rows differs from scores()"
+        assert np.array_equal(bits(eng.score_rows(all_ids[::-1].copy(), xs[q])[0]), bits(y[::-1]))
     # the top-k lists fed back (non-negative queries: the lists are full of rows with positive scores)
     xq = np.stack([pkg.create_sample_vector(m.cols, True, False, True, 80 + i) for i in range(4)])
-    val, idx = _batch(torch, eng, xq, k)
+    val, idx = support.batch(torch, eng, xq, k)
     assert np.all(val > 0)
-    assert np.array_equal(_bits(eng.score_rows(idx, xq)), _bits(val)), "the scores of the rows enqueue_batch returned differ from its scores"
+    assert np.array_equal(bits(eng.score_rows(idx, xq)), bits(val)), "the scores of the rows enqueue_batch returned differ from its scores"
     # rows as queries: score_rows(ids, row_vectors(ids)) against scores() with each row vector installed
     ids = (first_row + np.array([100, 101, 102, TRIPLE, 0, 2, 29999, 4711])).astype(np.uint32)
     rv, _ = eng.row_vectors(ids)
     got = eng.score_rows(ids, rv)
     for i in range(ids.size):
         eng.reset(rv[i])
-        assert np.array_equal(_bits(got[i]), _bits(eng.scores()[ids.astype(np.int64) - first_row])), f"row vector {int(ids[i])} as the query"
+        assert np.array_equal(bits(got[i]), bits(eng.scores()[ids.astype(np.int64) - first_row])), f"row vector {int(ids[i])} as the query"
     eng.close()
 
 
@@ -282,8 +237,8 @@ def test_approximate_partition_engines_are_served(pkg, oracle):
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=32, partitions=8, k_per_partition=8, device=0)
     ids = np.array([0, 100, 101, 102, TRIPLE, 1, 19999, 20000], dtype=np.uint32)
     xs = _signed_queries(2, m.cols, 72)
-    expect = _Expect(oracle, _Layout(pkg, eng, m), m.rows, 0)
-    assert np.array_equal(_bits(eng.score_rows(ids, xs)), expect.bits(xs, ids))
+    expect = _Expect(oracle, Layout(pkg, eng, m), m.rows, 0)
+    assert np.array_equal(bits(eng.score_rows(ids, xs)), expect.bits(xs, ids))
     eng.close()
 
 
@@ -297,7 +252,7 @@ def test_no_cross_talk(pkg):
     ids = np.concatenate([[100, 101, 102, TRIPLE, 0, m.rows - 3, m.rows + 5], rng.integers(0, m.rows, 505)]).astype(np.uint32)
     xq = np.stack([pkg.create_sample_vector(m.cols, True, False, True, 60 + i) for i in range(8)])
     # the solo runs
-    want_q = _batch(torch, eng, xq, k)
+    want_q = support.batch(torch, eng, xq, k)
     want_s = eng.score_rows(ids, xq)
     n = ids.size
     d_q = torch.from_numpy(xq).cuda()
@@ -322,12 +277,12 @@ def test_no_cross_talk(pkg):
         label = "engine's stream" if stream is None else "caller's stream"
         launches = eng.debug_counters()["batch_launches"] - before
         solo = eng.debug_counters()["batch_launches"]
-        _batch(torch, eng, xq, k)
+        support.batch(torch, eng, xq, k)
         per_call = eng.debug_counters()["batch_launches"] - solo
         assert launches == 2 * per_call, f"{label}: batch_launches advanced by {launches} for two batch calls of {per_call} each"
-        assert np.array_equal(_bits(d_sc.cpu().numpy()), _bits(want_s)), label
+        assert np.array_equal(bits(d_sc.cpu().numpy()), bits(want_s)), label
         for d_idx, d_val in ((d_idx0, d_val0), (d_idx1, d_val1)):
-            assert np.array_equal(d_idx.cpu().numpy().view(np.uint32), want_q[1]) and np.array_equal(_bits(d_val.cpu().numpy()), _bits(want_q[0])), label
+            assert np.array_equal(d_idx.cpu().numpy().view(np.uint32), want_q[1]) and np.array_equal(bits(d_val.cpu().numpy()), bits(want_q[0])), label
     eng.close()
 
 
@@ -335,7 +290,7 @@ def test_score_rows_and_rerank(pkg, oracle):
     m, empties = _matrix(pkg, 20000, 1024, 14)
     first_row = 300
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=10, device=0, first_row=first_row)
-    expect = _Expect(oracle, _Layout(pkg, eng, m), m.rows, first_row)
+    expect = _Expect(oracle, Layout(pkg, eng, m), m.rows, first_row)
     x = _signed_queries(1, m.cols, 73)[0]
     rng = np.random.default_rng(3)
     cand = np.concatenate([first_row + rng.integers(0, m.rows, 300), [first_row + r for r in empties], [first_row - 1, 0, first_row + m.rows, OUTSIDE],
@@ -354,15 +309,15 @@ def test_score_rows_and_rerank(pkg, oracle):
     w_ids, w_val = cand[keep], want_bits[keep].view(np.float32)
     order = sorted(range(w_ids.size), key=lambda i: (-float(w_val[i]), -int(w_ids[i])))
     val, idx = eng.rerank(cand, x)
-    assert np.array_equal(idx, w_ids[order]) and np.array_equal(_bits(val), _bits(w_val[order]))
+    assert np.array_equal(idx, w_ids[order]) and np.array_equal(bits(val), bits(w_val[order]))
     assert np.all(np.diff(val) <= 0) and np.count_nonzero(val == 0) >= len(empties)
     ties = np.flatnonzero(np.diff(val) == 0)
     assert ties.size >= len(empties) and np.all(idx[ties] >= idx[ties + 1]), "equal scores are ordered by row, descending"
     val5, idx5 = eng.rerank(cand, x, k=5)
-    assert np.array_equal(idx5, idx[:5]) and np.array_equal(_bits(val5), _bits(val[:5]))
+    assert np.array_equal(idx5, idx[:5]) and np.array_equal(bits(val5), bits(val[:5]))
     eng.reset(x)
     val_i, idx_i = eng.rerank(cand)  # the installed vector
-    assert np.array_equal(idx_i, idx) and np.array_equal(_bits(val_i), _bits(val))
+    assert np.array_equal(idx_i, idx) and np.array_equal(bits(val_i), bits(val))
     v0, i0 = eng.rerank([OUTSIDE, 0], x)
     assert v0.shape == (0,) and i0.shape == (0,)
     eng.close()
@@ -409,7 +364,7 @@ def test_errors(pkg):
     assert np.all(h_out == FILL)
     eng.synchronize()
     torch.cuda.synchronize()
-    assert np.all(_bits(d_out.cpu().numpy()) == _bits(np.float32(FILL))), "a rejected call wrote its output"
+    assert np.all(bits(d_out.cpu().numpy()) == bits(np.float32(FILL))), "a rejected call wrote its output"
     # accepted: stride equal to n_rows, and the installed vector once there is one
     eng.reset(np.ones(512, np.float32))
     eng.enqueue_score_rows(0, 1, I, 4, O)
@@ -418,5 +373,5 @@ def test_errors(pkg):
     torch.cuda.synchronize()
     out = d_out.cpu().numpy()
     y0 = eng.scores()[0]
-    assert np.all(_bits(out[:4]) == _bits(y0)) and np.all(_bits(out[64:72]) == _bits(y0)) and np.all(out[4:64] == FILL) and np.all(out[72:] == FILL)
+    assert np.all(bits(out[:4]) == bits(y0)) and np.all(bits(out[64:72]) == bits(y0)) and np.all(out[4:64] == FILL) and np.all(out[72:] == FILL)
     eng.close()

@@ -11,19 +11,13 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import support
+from support import Layout, bits, coo
+
 pytestmark = pytest.mark.gpu
 
 FILL_X, FILL_LEN, GUARD = -7.0, 12345, 1024
 OUTSIDE = 0xFFFFFFFF
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.ascontiguousarray(row, np.uint32), col=np.ascontiguousarray(col, np.uint32),
-                         val=np.ascontiguousarray(val, np.float32))
 
 
 LONG = {100: 256, 101: 512, 102: 1500}  # rows rewritten with exactly this many entries
@@ -49,7 +43,7 @@ def _matrix(pkg, rows, cols, seed, dist="gamma"):
     val.append(np.array([0.1, 0.3, 1e-8, 0.7, 0.2, 0.5, 0.05, 1e-9, 0.6], dtype=np.float32))  # (sums whose order shows in the bits)
     row, col, val = np.concatenate(row), np.concatenate(col), np.concatenate(val)
     order = np.argsort(row, kind="stable")
-    return _coo(pkg, rows, cols, row[order], col[order], val[order]), sorted(empty)
+    return coo(pkg, rows, cols, row[order], col[order], val[order]), sorted(empty)
 
 
 class _Rows:
@@ -89,33 +83,6 @@ class _Rows:
         return rr[:want]
 
 
-class _Layout:
-    """The engine's own layout, re-packed by the host packer with the engine's partition count (as test_gpu_range.py's _Scores)."""
-    def __init__(self, pkg, eng, m, packed=None):
-        info = eng.info()
-        self.C = info["packet_entries"] // 64
-        if packed is None:  # (else: the packed matrix the engine was created from)
-            packed = pkg.Packed(m, k=eng.k, nnz_per_lane=self.C, n_wave_partitions=(info["batch_mode"] >> 16) or info["n_wave_partitions"])
-        assert packed.info()["n_wave_partitions"] == info["n_wave_partitions"]
-        self.raw, self.rows = packed.raw(), m.rows
-        self._keep = packed
-
-    def scores(self, oracle, x):
-        yp, present = oracle.packed_scores(self.raw, x, self.rows, self.C)
-        return yp, present.astype(bool)
-
-    def partition_rows(self, n=6):
-        """First and last row of several partitions (spread over the stream)."""
-        _, _, pkt_row, part_first, _ = self.raw
-        firsts = pkt_row[part_first].astype(np.int64)
-        qs = sorted(set(np.linspace(0, firsts.size - 1, n).astype(int).tolist()))
-        out = []
-        for q in qs:
-            out.append(int(firsts[q]))
-            out.append(int(firsts[q + 1]) - 1 if q + 1 < firsts.size else int(pkt_row.max()))
-        return out
-
-
 def _special_ids(m, empties, rows_helper, layout, first_row):
     rep = rows_helper.rows_with_repeats()
     assert len(rep) >= 3, "the input has no rows with a repeated column: the case shows nothing"
@@ -151,11 +118,11 @@ def _check_row_vectors(torch, eng, helper, ids, cols, label, stream=None):
     xs, ln = _run_row_vectors(torch, eng, ids, cols, stream)
     n = len(ids)
     exp_xs, exp_ln = helper.vectors(ids)
-    assert np.all(_bits(xs[n * cols:]) == _bits(np.float32(FILL_X))), f"{label}: written beyond count x cols"
+    assert np.all(bits(xs[n * cols:]) == bits(np.float32(FILL_X))), f"{label}: written beyond count x cols"
     assert np.all(ln[n:] == FILL_LEN), f"{label}: lengths written beyond count"
     assert np.array_equal(ln[:n], exp_ln), f"{label}: lengths differ at {np.flatnonzero(ln[:n] != exp_ln)[:8]}"
-    got = _bits(xs[:n * cols]).reshape(n, cols)
-    bad = np.flatnonzero(np.any(got != _bits(exp_xs), axis=1))
+    got = bits(xs[:n * cols]).reshape(n, cols)
+    bad = np.flatnonzero(np.any(got != bits(exp_xs), axis=1))
     assert bad.size == 0, f"{label}: vectors differ for ids {[int(ids[i]) for i in bad[:8]]} (positions {bad[:8]})"
 
 
@@ -185,7 +152,7 @@ def test_row_vectors(pkg, tmp_path, name, mk, kw):
         eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=16, device=0, **kw)
     info = eng.info()
     assert info["packet_entries"] == (512 if name == "c8_1024" else 256)
-    helper, layout = _Rows(m, first_row), _Layout(pkg, eng, m, packed)
+    helper, layout = _Rows(m, first_row), Layout(pkg, eng, m, packed)
     special = _special_ids(m, empties, helper, layout, first_row)
     assert len(special) >= 33
     rng = np.random.default_rng(1)
@@ -201,7 +168,7 @@ def test_row_vectors(pkg, tmp_path, name, mk, kw):
     # the host-array call
     xs, ln = eng.row_vectors(special)
     exp_xs, exp_ln = helper.vectors(special)
-    assert np.array_equal(ln, exp_ln) and np.array_equal(_bits(xs), _bits(exp_xs)), name
+    assert np.array_equal(ln, exp_ln) and np.array_equal(bits(xs), bits(exp_xs)), name
     eng.close()
 
 
@@ -211,20 +178,8 @@ def test_approximate_partition_engines_are_served(pkg):
     ids = [0, 100, 101, 102, TRIPLE, 19999, 20000]
     xs, ln = eng.row_vectors(ids)
     exp_xs, exp_ln = _Rows(m).vectors(ids)
-    assert np.array_equal(ln, exp_ln) and np.array_equal(_bits(xs), _bits(exp_xs))
+    assert np.array_equal(ln, exp_ln) and np.array_equal(bits(xs), bits(exp_xs))
     eng.close()
-
-
-def _batch(torch, eng, xs_host, k):
-    """enqueue_batch on host vectors uploaded here; waits. (values[n, k], indices[n, k])"""
-    n = xs_host.shape[0]
-    d_xs = torch.from_numpy(np.ascontiguousarray(xs_host, dtype=np.float32)).cuda()
-    d_idx = torch.zeros((n, k), dtype=torch.int32, device="cuda")
-    d_val = torch.zeros((n, k), dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    eng.enqueue_batch(d_xs.data_ptr(), n, d_idx.data_ptr(), d_val.data_ptr())
-    eng.synchronize()
-    return d_val.cpu().numpy(), d_idx.cpu().numpy().view(np.uint32)
 
 
 def test_no_cross_talk(pkg):
@@ -237,9 +192,9 @@ def test_no_cross_talk(pkg):
     ids = np.concatenate([[100, 101, 102, TRIPLE, 0, m.rows - 3], rng.integers(0, m.rows, 42)]).astype(np.uint32)
     xq = np.stack([pkg.create_sample_vector(m.cols, True, False, True, 60 + i) for i in range(8)])
     # the waited run
-    want_q = _batch(torch, eng, xq, k)
+    want_q = support.batch(torch, eng, xq, k)
     rv, _ = eng.row_vectors(ids)
-    want_r = _batch(torch, eng, rv, k)
+    want_r = support.batch(torch, eng, rv, k)
     # the unwaited sequence
     n = ids.size
     d_q = torch.from_numpy(xq).cuda()
@@ -260,9 +215,9 @@ def test_no_cross_talk(pkg):
         else:
             stream.synchronize()
         label = "engine's stream" if stream is None else "caller's stream"
-        assert np.array_equal(_bits(d_rv.cpu().numpy()), _bits(rv)), label
-        assert np.array_equal(d_idx0.cpu().numpy().view(np.uint32), want_q[1]) and np.array_equal(_bits(d_val0.cpu().numpy()), _bits(want_q[0])), label
-        assert np.array_equal(d_idx1.cpu().numpy().view(np.uint32), want_r[1]) and np.array_equal(_bits(d_val1.cpu().numpy()), _bits(want_r[0])), label
+        assert np.array_equal(bits(d_rv.cpu().numpy()), bits(rv)), label
+        assert np.array_equal(d_idx0.cpu().numpy().view(np.uint32), want_q[1]) and np.array_equal(bits(d_val0.cpu().numpy()), bits(want_q[0])), label
+        assert np.array_equal(d_idx1.cpu().numpy().view(np.uint32), want_r[1]) and np.array_equal(bits(d_val1.cpu().numpy()), bits(want_r[0])), label
     eng.close()
 
 
@@ -299,7 +254,7 @@ def test_similar(pkg, oracle, rows, k, n_ids, first_row):
     import torch
     m, empties = _matrix(pkg, rows, 1024, 31)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0, first_row=first_row)
-    helper, layout = _Rows(m, first_row), _Layout(pkg, eng, m)
+    helper, layout = _Rows(m, first_row), Layout(pkg, eng, m)
     rng = np.random.default_rng(5)
     special = [100, 101, 102, TRIPLE, 0, empties[0], rows // 2, rows - 1, rows - 3]
     ids = (first_row + np.concatenate([special, rng.integers(0, rows, n_ids - len(special))])).astype(np.uint32)
@@ -310,13 +265,13 @@ def test_similar(pkg, oracle, rows, k, n_ids, first_row):
     #  lists are compared only now that the call has returned)
     assert after["checks_failed"] >= before["checks_failed"] and after["batch_launches"] >= before["batch_launches"]
     xs, _ = helper.vectors(ids)
-    bval, bidx = _batch(torch, eng, xs, k)
-    assert np.array_equal(idx, bidx) and np.array_equal(_bits(val), _bits(bval)), "similar differs from enqueue_batch on host-densified vectors"
+    bval, bidx = support.batch(torch, eng, xs, k)
+    assert np.array_equal(idx, bidx) and np.array_equal(bits(val), bits(bval)), "similar differs from enqueue_batch on host-densified vectors"
     oval, oidx = _oracle_lists(oracle, layout, xs, k, first_row)
-    assert np.array_equal(idx, oidx) and np.array_equal(_bits(val), _bits(oval)), "similar differs from the order-matched oracle"
+    assert np.array_equal(idx, oidx) and np.array_equal(bits(val), bits(oval)), "similar differs from the order-matched oracle"
     xval, xidx = eng.similar(ids, exclude_self=True)
     eval_, eidx = _without_self(val, idx, ids)
-    assert np.array_equal(xidx, eidx) and np.array_equal(_bits(xval), _bits(eval_))
+    assert np.array_equal(xidx, eidx) and np.array_equal(bits(xval), bits(eval_))
     # (the generator's rows have norm 1: a row with entries is its own best match, so the removal above did happen)
     assert np.count_nonzero(np.any(idx == ids[:, None], axis=1)) > n_ids // 2
     eng.close()
@@ -333,7 +288,7 @@ def test_exclude_self_keeps_a_list_without_the_row(pkg, oracle):
     col = np.concatenate([g.col[keep], np.array([17, 400], np.uint32)])
     val = np.concatenate([g.val[keep] * scale[g.row[keep]], np.array([1e-3, 1e-3], np.float32)])
     order = np.argsort(row, kind="stable")
-    m = _coo(pkg, g.rows, g.cols, row[order], col[order], val[order])
+    m = coo(pkg, g.rows, g.cols, row[order], col[order], val[order])
     k = 20
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k, device=0)
     ids = np.array([R, 5, R, 19000], dtype=np.uint32)
@@ -341,16 +296,16 @@ def test_exclude_self_keeps_a_list_without_the_row(pkg, oracle):
     assert R not in idx_p[0].tolist(), "the constructed row is in its own top-k: the case shows nothing"
     assert 5 in idx_p[1].tolist() and 19000 in idx_p[3].tolist()
     val_x, idx_x = eng.similar(ids, exclude_self=True)
-    assert np.array_equal(idx_x[0], idx_p[0]) and np.array_equal(_bits(val_x[0]), _bits(val_p[0]))
-    assert np.array_equal(idx_x[2], idx_p[2]) and np.array_equal(_bits(val_x[2]), _bits(val_p[2]))
+    assert np.array_equal(idx_x[0], idx_p[0]) and np.array_equal(bits(val_x[0]), bits(val_p[0]))
+    assert np.array_equal(idx_x[2], idx_p[2]) and np.array_equal(bits(val_x[2]), bits(val_p[2]))
     e_val, e_idx = _without_self(val_p, idx_p, ids)
-    assert np.array_equal(idx_x, e_idx) and np.array_equal(_bits(val_x), _bits(e_val))
+    assert np.array_equal(idx_x, e_idx) and np.array_equal(bits(val_x), bits(e_val))
     assert idx_x[1, k - 1] == 0 and val_x[1, k - 1] == 0.0 and 5 not in idx_x[1, :k - 1].tolist()
     # the plain lists are the oracle's
-    layout = _Layout(pkg, eng, m)
+    layout = Layout(pkg, eng, m)
     xs, _ = _Rows(m).vectors(ids)
     oval, oidx = _oracle_lists(oracle, layout, xs, k)
-    assert np.array_equal(idx_p, oidx) and np.array_equal(_bits(val_p), _bits(oval))
+    assert np.array_equal(idx_p, oidx) and np.array_equal(bits(val_p), bits(oval))
     eng.close()
 
 
@@ -360,18 +315,18 @@ def test_knn_graph(pkg, oracle):
     val, idx = pkg.knn_graph(m, k, device=0)
     assert val.shape == (m.rows, k) and idx.shape == (m.rows, k)
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=k + 1, device=0)  # (the engine knn_graph builds: the same layout)
-    layout = _Layout(pkg, eng, m)
+    layout = Layout(pkg, eng, m)
     eng.close()
     ids = np.arange(m.rows, dtype=np.uint32)
     xs, _ = _Rows(m).vectors(ids)
     oval, oidx = _oracle_lists(oracle, layout, xs, k + 1)
     e_val, e_idx = _without_self(oval, oidx, ids)
-    bad = np.flatnonzero(np.any(idx != e_idx[:, :k], axis=1) | np.any(_bits(val) != _bits(e_val[:, :k]), axis=1))
+    bad = np.flatnonzero(np.any(idx != e_idx[:, :k], axis=1) | np.any(bits(val) != bits(e_val[:, :k]), axis=1))
     assert bad.size == 0, f"knn_graph differs from the oracle's top-{k + 1} without the row itself for rows {bad[:8]}"
     # a subset of rows
     sub = np.array([102, 5, TRIPLE, 19999, 5], dtype=np.uint32)
     sval, sidx = pkg.knn_graph(m, k, rows=sub, device=0)
-    assert np.array_equal(sidx, e_idx[sub, :k]) and np.array_equal(_bits(sval), _bits(e_val[sub, :k]))
+    assert np.array_equal(sidx, e_idx[sub, :k]) and np.array_equal(bits(sval), bits(e_val[sub, :k]))
 
 
 def test_errors(pkg):
@@ -405,7 +360,7 @@ def test_errors(pkg):
     assert lib.tkspmv_run_similar(eng._h, None, 2, 0, None, None) == INVALID
     eng.synchronize()
     torch.cuda.synchronize()
-    assert np.all(_bits(d_xs.cpu().numpy()) == _bits(np.float32(FILL_X))), "a rejected call wrote its output"
+    assert np.all(bits(d_xs.cpu().numpy()) == bits(np.float32(FILL_X))), "a rejected call wrote its output"
     # empty requests of the Python layer are answered without a call
     xs, ln = eng.row_vectors([])
     assert xs.shape == (0, 512) and ln.shape == (0,)

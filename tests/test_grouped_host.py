@@ -1,20 +1,16 @@
 """Grouped top-k without a GPU: the symbols of every layer, argument checks that come before any device call, the numpy
-restatement of the contract (collapse_topk) pinned to the oracle's selection and to a plain loop, and the resource report of the
-new kernels."""
+restatement of the contract (collapse_topk) pinned to the oracle's selection and to a plain loop."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+from support import order_key
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
 CSRC = os.path.join(ROOT, "approximate-spmv-topk_amd", "csrc")
 NAMES = ("tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped")
-# what the existing report tests pick their kernel families by: the new kernels' names must match none of them
-FAMILY_SUBSTRINGS = ("stream_kernel", "batch_kernel", "multi_kernel", "range_kernel", "row_vectors_kernel", "score_rows_kernel", "stream_filter_kernel")
-NEW_KERNELS = ("group_best_kernel", "group_split_kernel", "group_ids_kernel")
 
 
 def test_grouped_symbols_in_every_layer(pkg):
@@ -56,15 +52,10 @@ def test_collapse_with_one_row_per_group_is_the_oracles_selection(pkg, oracle):
     assert n < k  # (the last case: fewer than k rows above 2.5 -- the pad of the oracle is the pad of collapse_topk)
 
 
-def _order_key(f):
-    u = int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
-
-
 def _loop(y, present, groups, k, min_score, first_row):
     """The contract as a plain loop: every eligible row by its key, descending; the first row of each group; cut at k."""
-    kmin = _order_key(min_score)
-    keyed = sorted(((_order_key(y[r]) << 32) | r for r in range(len(y)) if present[r] and _order_key(y[r]) >= kmin and y[r] > -np.inf), reverse=True)
+    kmin = order_key(min_score)
+    keyed = sorted(((order_key(y[r]) << 32) | r for r in range(len(y)) if present[r] and order_key(y[r]) >= kmin and y[r] > -np.inf), reverse=True)
     seen, out = set(), []
     for key in keyed:
         r = key & 0xFFFFFFFF
@@ -116,31 +107,3 @@ def test_collapse_treats_signed_zeros_and_minus_infinity_like_the_device(pkg):
     assert n == 2 and idx[:2].tolist() == [3, 1]  # -0.0 sorts below +0.0 = min_score by the order key
     idx, val, grp, n = pkg.collapse_topk(y, present, np.arange(5), 5, -np.inf)
     assert n == 3 and idx[:3].tolist() == [3, 1, 0] and val[2].view(np.uint32) == 0x80000000  # -inf is never eligible
-
-
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        m = re.match(r"\s*Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return kernels
-
-
-def test_grouped_kernels_in_resource_report():
-    k = _report()
-    for kernel in NEW_KERNELS:
-        found = {n: v for n, v in k.items() if kernel in n}
-        assert len(found) == 1, (kernel, sorted(found))
-        (name, v), = found.items()
-        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (name, v)
-        assert not any(s in name for s in FAMILY_SUBSTRINGS), name
-    best = next(v for n, v in k.items() if "group_best_kernel" in n)
-    assert best["LDS Size [bytes/block]"] == 0, best  # the run reduction stays in registers
-    assert best["VGPRs"] <= 64, best  # 256-thread workgroups at full occupancy

@@ -1,17 +1,13 @@
 """Range queries without a GPU: the symbols of every layer, the RANGE_PERIOD option, argument checks that come before any device
-call, the resource report of range_kernel, and its ISA (the streaming loop touches no scratch, waits for no chain of single loads,
+call, and the ISA of range_kernel (the streaming loop touches no scratch, waits for no chain of single loads,
 makes no flat access; the mask words travel on the scalar unit)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
-import pytest
+from support import INCLUDE, compile_device_only
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
-CSRC = os.path.join(ROOT, "approximate-spmv-topk_amd", "csrc")
 
 
 def test_range_symbols_in_every_layer(pkg):
@@ -42,40 +38,8 @@ def test_null_engine_fails_before_any_device_call(pkg):
     assert count.value == 7
 
 
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        m = re.match(r"\s*Function Name: (\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return kernels
-
-
-def test_range_kernels_in_resource_report():
-    k = _report()
-    rng = {n: v for n, v in k.items() if "tkspmv12range_kernel" in n}
-    # fp32 only: the 12-bit column layout, plain fp32 at 1024 / 4096 / 16384 columns, 8 entries per lane; each with and without FILT
-    assert len(rng) == 10, sorted(rng)
-    for n, v in rng.items():
-        assert v["AGPRs"] == 0, (n, v)
-        if "range_kernelILi4E" in n:
-            assert v["VGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (n, v)
-        # 512-thread workgroups (8 streaming waves, no server wave), two per CU: 16 waves per CU, 4 per SIMD, 128 registers each
-        assert v["VGPRs"] <= 128, (n, v)
-
-
 def _compile_range_kernels(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    tu = tmp_path / "tu.hip"
-    tu.write_text("""#include <hip/hip_runtime.h>
+    return compile_device_only(tmp_path, """#include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kernels/common.hpp"
 #include "kernels/select.hpp"
@@ -90,11 +54,7 @@ template __global__ void range_kernel<4, 1024, 7, true, 3>(const StreamParams, c
 template __global__ void range_kernel<4, 16384, 0, true, 3>(const StreamParams, const RangeParams);
 template __global__ void range_kernel<8, 1024, 0, true, 2>(const StreamParams, const RangeParams);
 }
-""")
-    asm = tmp_path / "tu.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S",
-                           "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", str(asm), str(tu)], stderr=subprocess.DEVNULL)
-    return asm.read_text().split("\n")
+""", (INCLUDE,)).split("\n")
 
 
 def test_range_kernel_isa(tmp_path):

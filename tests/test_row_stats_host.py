@@ -4,8 +4,7 @@ order every streaming path sums in. The existing order-matched oracle pins that 
 function of the column, val[i] = g[col[i]], the query x = g makes every product g*g = v*v bit for bit, and x = sign(g) makes it
 |v|, so Packed.row_stats (tkspmv_packed_row_stats) must equal oracle_lib.packed_scores over the whole stream as bits, for EVERY
 row. The matrices and packings are those of test_score_rows_host.py. Every such test asserts that some L2SQ differs from the plain
-left-to-right fp32 sum of the row's squares: otherwise the inputs would show nothing about the order. And the resource report of
-row_stats_kernel."""
+left-to-right fp32 sum of the row's squares: otherwise the inputs would show nothing about the order."""
 import ctypes as C
 import os
 import re
@@ -13,7 +12,8 @@ import re
 import numpy as np
 import pytest
 
-from test_score_rows_host import HINTS, ROW_END, SKIP, _bits, _coo, _every_packing, _hand_made, _report, _words
+from support import bits, coo
+from test_score_rows_host import HINTS, ROW_END, SKIP, _every_packing, _hand_made, _words
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -24  # unit roundoff of float32
@@ -29,7 +29,7 @@ def _g(cols, seed):
 
 
 def _by_column(pkg, m, g):
-    return _coo(pkg, m.rows, m.cols, m.row, m.col, g[m.col])
+    return coo(pkg, m.rows, m.cols, m.row, m.col, g[m.col])
 
 
 def _sequential_squares(m):
@@ -58,15 +58,15 @@ def _check_all_kinds(pkg, oracle, m, g, packed, c_lane, label):
         with np.errstate(over="ignore", under="ignore"):
             want, present = oracle.packed_scores(raw, x, m.rows, c_lane)
         assert np.array_equal(present.astype(bool), has), label
-        bad = np.flatnonzero(_bits(got[kind]) != _bits(want))
+        bad = np.flatnonzero(bits(got[kind]) != bits(want))
         assert bad.size == 0, f"{label} kind {kind}: {bad.size} rows differ from the full-stream sums, first {bad[:8]}: {got[kind][bad[:8]]} != {want[bad[:8]]}"
     nnz = packed.row_stats(L.ROW_NNZ)
     assert np.array_equal(nnz, np.bincount(m.row, minlength=m.rows).astype(np.float32)), label
     inv = packed.row_stats(L.ROW_INV_L2)
-    assert np.array_equal(_bits(inv), _bits(pkg.inv_l2(got[L.ROW_L2SQ]))), label
+    assert np.array_equal(bits(inv), bits(pkg.inv_l2(got[L.ROW_L2SQ]))), label
     assert np.all(np.isfinite(inv)), label
     for a in (got[L.ROW_L2SQ], got[L.ROW_L1], nnz, inv):
-        assert a.shape == (m.rows,) and a.dtype == np.float32 and np.all(_bits(a[~has]) == 0), f"{label}: a row without entries is not +0.0"
+        assert a.shape == (m.rows,) and a.dtype == np.float32 and np.all(bits(a[~has]) == 0), f"{label}: a row without entries is not +0.0"
     return got[L.ROW_L2SQ]
 
 
@@ -127,8 +127,8 @@ def test_inv_l2_finish(pkg):
     s = np.array([0.0, -0.0, np.inf, np.nan, 4.0, 2.0, 1e-40, 1.4e-45, 3.0e38, -1.0], dtype=np.float32)
     w = pkg.inv_l2(s)
     assert w.dtype == np.float32 and np.all(np.isfinite(w))
-    assert np.all(_bits(w[[0, 1, 2, 3, 9]]) == 0)
-    assert w[4] == np.float32(0.5) and _bits(w[5:6])[0] == _bits(np.float32(1) / np.sqrt(np.float32(2)))[0]
+    assert np.all(bits(w[[0, 1, 2, 3, 9]]) == 0)
+    assert w[4] == np.float32(0.5) and bits(w[5:6])[0] == bits(np.float32(1) / np.sqrt(np.float32(2)))[0]
     assert w[6] > 0 and w[7] > 0 and w[8] > 0
 
 
@@ -142,7 +142,7 @@ def test_every_row_of_generated_matrices(pkg, oracle, dist, cols):
     for packed, c_lane, label in _every_packing(pkg, m, f"{dist} 2500x{cols}", HINTS):
         l2sq = _check_all_kinds(pkg, oracle, m, g, packed, c_lane, label)
         layouts.add(packed.raw()[1] * 2 // (64 * c_lane))  # half bytes per entry
-        order_shows += int(np.count_nonzero(_bits(l2sq) != _bits(seq)))
+        order_shows += int(np.count_nonzero(bits(l2sq) != bits(seq)))
     # both fp32 layouts are met: 6 bytes per entry (16-bit column words) and, at C = 4 up to 1024 columns, 5.5 (12-bit words)
     assert 12 in layouts and ((11 in layouts) == (cols <= 1024))
     assert order_shows > 0, "every L2SQ equals the left-to-right fp32 sum of its row's squares: the inputs show nothing about the order"
@@ -162,7 +162,7 @@ def _hand_made_by_column(pkg, cols):
     col = np.concatenate([col, np.array(TINY_COLS), np.array(HUGE_COLS)])
     lens = dict(lens)
     lens[TINY_ROW], lens[HUGE_ROW] = len(TINY_COLS), len(HUGE_COLS)
-    return _coo(pkg, base.rows, cols, row, col, g[col]), g, lens
+    return coo(pkg, base.rows, cols, row, col, g[col]), g, lens
 
 
 @pytest.mark.parametrize("cols", [1024, 4096])
@@ -177,7 +177,7 @@ def test_hand_made_rows(pkg, oracle, cols):
         # the empty rows inside [0, last stored row] are placeholders in the stream; the trailing one has no packet at all
         assert int(np.count_nonzero(w & SKIP)) == 4 and int(pkt_row.max()) <= HUGE_ROW, label
         for kind in range(4):
-            assert np.all(_bits(packed.row_stats(kind)[[0, 1, 4, 9, 14]]) == 0), (label, kind)
+            assert np.all(bits(packed.row_stats(kind)[[0, 1, 4, 9, 14]]) == 0), (label, kind)
         nnz = packed.row_stats(L.ROW_NNZ)
         assert all(nnz[r] == n for r, n in lens.items()) and nnz[3] == 256 and nnz[5] == 512 and nnz[6] == 1500, label
         # the 1500-entry row spans three or more packets, one in the middle whole (no row end in it)
@@ -186,9 +186,9 @@ def test_hand_made_rows(pkg, oracle, cols):
         # a subnormal sum of squares gives a finite weight, an overflowing one the weight 0
         inv = packed.row_stats(L.ROW_INV_L2)
         assert 0 < l2sq[TINY_ROW] < np.finfo(np.float32).tiny and np.isfinite(inv[TINY_ROW]) and inv[TINY_ROW] > 1e19, (label, l2sq[TINY_ROW], inv[TINY_ROW])
-        assert np.isposinf(l2sq[HUGE_ROW]) and _bits(inv[HUGE_ROW:HUGE_ROW + 1])[0] == 0, (label, l2sq[HUGE_ROW], inv[HUGE_ROW])
+        assert np.isposinf(l2sq[HUGE_ROW]) and bits(inv[HUGE_ROW:HUGE_ROW + 1])[0] == 0, (label, l2sq[HUGE_ROW], inv[HUGE_ROW])
         # the long rows' sums are not the left-to-right ones: the wave's order of summation is what was compared
-        assert any(_bits(l2sq[r:r + 1])[0] != _bits(seq[r:r + 1])[0] for r in (3, 5, 6)), label
+        assert any(bits(l2sq[r:r + 1])[0] != bits(seq[r:r + 1])[0] for r in (3, 5, 6)), label
 
 
 def test_partition_tails(pkg, oracle):
@@ -197,12 +197,12 @@ def test_partition_tails(pkg, oracle):
     rng = np.random.default_rng(7)
     g = _g(512, 70)
     col = rng.integers(0, 512, rows * per)
-    m = _coo(pkg, rows, 512, np.repeat(np.arange(rows), per), col, g[col])
+    m = coo(pkg, rows, 512, np.repeat(np.arange(rows), per), col, g[col])
     seen_full_tail = order_shows = 0
     seq = _sequential_squares(m)
     for packed, c_lane, label in _every_packing(pkg, m, "exact fit", hints=(1, 2, 4)):
         l2sq = _check_all_kinds(pkg, oracle, m, g, packed, c_lane, label)
-        order_shows += int(np.count_nonzero(_bits(l2sq) != _bits(seq)))
+        order_shows += int(np.count_nonzero(bits(l2sq) != bits(seq)))
         raw = packed.raw()
         w, pf, pc = _words(raw, c_lane), raw[3], raw[4]
         seen_full_tail += sum(1 for q in range(pf.size) if w[int(pf[q] + pc[q] - 1), 64 * c_lane - 1] & ROW_END)
@@ -210,7 +210,7 @@ def test_partition_tails(pkg, oracle):
     rows, per = 600, 7  # rows of 7 entries never fill a packet exactly; many partitions
     g = _g(300, 71)
     col = rng.integers(0, 300, rows * per)
-    m = _coo(pkg, rows, 300, np.repeat(np.arange(rows), per), col, g[col])
+    m = coo(pkg, rows, 300, np.repeat(np.arange(rows), per), col, g[col])
     seq = _sequential_squares(m)
     for packed, c_lane, label in _every_packing(pkg, m, "padded tails", hints=(64,)):
         PE = 64 * c_lane
@@ -222,7 +222,7 @@ def test_partition_tails(pkg, oracle):
             padded += int(ends.size and ends[-1] < PE - 1)
         assert pf.size >= 4 and padded >= 2, "no padded partition tail: the case shows nothing"
         l2sq = _check_all_kinds(pkg, oracle, m, g, packed, c_lane, label)
-        order_shows += int(np.count_nonzero(_bits(l2sq) != _bits(seq)))
+        order_shows += int(np.count_nonzero(bits(l2sq) != bits(seq)))
     assert order_shows > 0, "every L2SQ equals the left-to-right fp32 sum of its row's squares: the inputs show nothing about the order"
 
 
@@ -235,8 +235,8 @@ def test_rows_of_a_loaded_file(pkg, oracle, tmp_path):
     loaded = pkg.Packed.load(path)
     l2sq = _check_all_kinds(pkg, oracle, m, g, loaded, 4, "loaded file")
     for kind in range(4):
-        assert np.array_equal(_bits(loaded.row_stats(kind)), _bits(packed.row_stats(kind))), kind
-    assert np.count_nonzero(_bits(l2sq) != _bits(_sequential_squares(m))) > 0
+        assert np.array_equal(bits(loaded.row_stats(kind)), bits(packed.row_stats(kind))), kind
+    assert np.count_nonzero(bits(l2sq) != bits(_sequential_squares(m))) > 0
 
 
 @pytest.mark.parametrize("c_lane", [4, 8])
@@ -247,7 +247,7 @@ def test_general_matrices_against_float64(pkg, c_lane):
     L = pkg._lib
     g = pkg.generate_matrix(2500, 1024, 20, "gamma", 21)
     sign = np.where(np.random.default_rng(22).random(g.val.size) < 0.5, -1.0, 1.0).astype(np.float32)
-    m = _coo(pkg, g.rows, g.cols, g.row, g.col, g.val * sign)
+    m = coo(pkg, g.rows, g.cols, g.row, g.col, g.val * sign)
     packed = pkg.Packed(m, k=8, nnz_per_lane=c_lane, n_wave_partitions=64)
     n = np.bincount(m.row, minlength=m.rows).astype(np.float64)
     assert np.array_equal(packed.row_stats(L.ROW_NNZ), n.astype(np.float32))
@@ -259,20 +259,7 @@ def test_general_matrices_against_float64(pkg, c_lane):
     assert np.all(np.abs(got_l1 - l1) <= bound * l1), float(np.max(np.abs(got_l1 - l1) / np.maximum(l1, 1e-300) - bound))
     assert np.all(np.abs(got_l2 - l2) <= bound * l2), float(np.max(np.abs(got_l2 - l2) / np.maximum(l2, 1e-300) - bound))
     w, want = pkg.inv_l2(packed.row_stats(L.ROW_L2SQ)).astype(np.float64), pkg.cosine_weights(m).astype(np.float64)
-    assert np.array_equal(_bits(packed.row_stats(L.ROW_INV_L2)), _bits(w.astype(np.float32)))
+    assert np.array_equal(bits(packed.row_stats(L.ROW_INV_L2)), bits(w.astype(np.float32)))
     assert np.all(np.abs(w - want) <= (n / 2 + 3) * EPS * want), float(np.max(np.abs(w - want) / np.maximum(want, 1e-300)) / EPS)
     assert np.all((want == 0) == (n == 0))
     packed.close()
-
-
-def test_row_stats_kernels_in_resource_report():
-    k = _report()
-    rs = {n: v for n, v in k.items() if "row_stats_kernel" in n}
-    # the 12-bit column layout, plain fp32 at 4 entries per lane (every column tier: no x), 8 entries per lane; four kinds each
-    found = sorted(re.search(r"row_stats_kernelILi(\d)ELb([01])ELi(\d)E", n).groups() for n in rs)
-    assert found == sorted((c, b, str(kind)) for c, b in (("4", "0"), ("4", "1"), ("8", "0")) for kind in range(4)), sorted(rs)
-    for n, v in rs.items():
-        # (the substrings by which the other resource tests pick their kernels out of the report)
-        assert not any(t in n for t in ("row_vectors_kernel", "score_rows_kernel", "stream_kernel", "batch_kernel", "multi_kernel", "range_kernel",
-                                        "facet_kernel", "match_kernel")), n
-        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (n, v)

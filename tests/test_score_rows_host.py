@@ -3,33 +3,18 @@ the feature rests on -- a row's score, bit for bit as every streaming path repor
 alone -- for EVERY row: Packed.score_rows (tkspmv_packed_score_rows: the shared row lookup + the kernels' reduction restated for
 the host) against the order-matched oracle over the whole stream (oracle_lib.packed_scores), on the generated and hand-made
 matrices of test_similar_host.py, both entries-per-lane settings and several partition counts. Values and x are signed, so the
-order of the sums shows in the bits; every test asserts that it does. And the resource report of score_rows_kernel."""
+order of the sums shows in the bits; every test asserts that it does."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+from support import bits, coo, signed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
 HINTS = (1, 7, 64, 4096)
 ROW_END, SKIP = 1, 2
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.asarray(row, np.uint32), col=np.asarray(col, np.uint32),
-                         val=np.asarray(val, np.float32))
-
-
-def _signed(pkg, m, seed):
-    """The same matrix with random signs on its values."""
-    sign = np.where(np.random.default_rng(seed).random(m.val.size) < 0.5, -1.0, 1.0).astype(np.float32)
-    return _coo(pkg, m.rows, m.cols, m.row, m.col, m.val * sign)
 
 
 def _x(cols, seed):
@@ -61,9 +46,9 @@ def _check_all_rows(oracle, m, packed, c_lane, x, label):
     """Packed.score_rows(x, every row) == the oracle over the whole stream, as bits; +0.0 where the oracle saw no entries."""
     got = packed.score_rows(x, np.arange(m.rows, dtype=np.uint32))
     want, present = oracle.packed_scores(packed.raw(), x, m.rows, c_lane)
-    bad = np.flatnonzero(_bits(got) != _bits(want))
+    bad = np.flatnonzero(bits(got) != bits(want))
     assert bad.size == 0, f"{label}: {bad.size} rows differ from the full-stream scores, first {bad[:8]}: {got[bad[:8]]} != {want[bad[:8]]}"
-    assert np.all(_bits(got[present == 0]) == 0), f"{label}: a row without entries does not score +0.0"
+    assert np.all(bits(got[present == 0]) == 0), f"{label}: a row without entries does not score +0.0"
     has = np.zeros(m.rows, dtype=bool)
     has[m.row] = True
     assert np.array_equal(present.astype(bool), has), label
@@ -97,14 +82,14 @@ def test_null_arguments_fail_before_any_device_call(pkg):
 @pytest.mark.parametrize("dist", ["uniform", "gamma"])
 @pytest.mark.parametrize("cols", [300, 1024, 4096])
 def test_every_row_of_generated_matrices(pkg, oracle, dist, cols):
-    m = _signed(pkg, pkg.generate_matrix(2500, cols, 20, dist, 5 + cols), cols)
+    m = signed(pkg, pkg.generate_matrix(2500, cols, 20, dist, 5 + cols), cols)
     x = _x(cols, 100 + cols)
     seq = _sequential(m, x)
     layouts, order_shows = set(), 0
     for packed, c_lane, label in _every_packing(pkg, m, f"{dist} 2500x{cols}"):
         got = _check_all_rows(oracle, m, packed, c_lane, x, label)
         layouts.add(packed.raw()[1] * 2 // (64 * c_lane))  # half bytes per entry
-        order_shows += int(np.count_nonzero(_bits(got) != _bits(seq)))
+        order_shows += int(np.count_nonzero(bits(got) != bits(seq)))
     # both fp32 layouts are met: 6 bytes per entry (16-bit column words) and, at C = 4 up to 1024 columns, 5.5 (12-bit words)
     assert 12 in layouts and ((11 in layouts) == (cols <= 1024))
     assert order_shows > 0, "every score equals the left-to-right fp32 sum of its row: the inputs show nothing about the order"
@@ -120,7 +105,7 @@ def _hand_made(pkg, cols=1024):
         row.append(np.full(lens[r], r, np.uint32))
         col.append(rng.integers(0, cols, lens[r]).astype(np.uint32))
         val.append(rng.standard_normal(lens[r]).astype(np.float32))
-    return _coo(pkg, rows, cols, np.concatenate(row), np.concatenate(col), np.concatenate(val)), lens
+    return coo(pkg, rows, cols, np.concatenate(row), np.concatenate(col), np.concatenate(val)), lens
 
 
 def _words(raw, c_lane):
@@ -158,22 +143,22 @@ def test_hand_made_rows(pkg, oracle, cols):
         w, pkt_row = _words(raw, c_lane), raw[2]
         # the empty rows inside [0, last stored row] are placeholders in the stream; the trailing ones have no packet at all
         assert int(np.count_nonzero(w & SKIP)) == 4 and int(pkt_row.max()) <= 11, label
-        assert np.all(_bits(got[[0, 1, 4, 9, 12, 13, 14]]) == 0), label
+        assert np.all(bits(got[[0, 1, 4, 9, 12, 13, 14]]) == 0), label
         # the 1500-entry row spans three or more packets, one in the middle whole (no row end in it)
         mine = np.flatnonzero(pkt_row == 6)
         assert any(not np.any(w[p] & ROW_END) for p in mine), label
         # the long rows' sums are not the left-to-right ones: the wave's order of summation is what was compared
-        assert _bits(got[6]) != _bits(seq[6]) or _bits(got[5]) != _bits(seq[5]) or _bits(got[3]) != _bits(seq[3]), label
+        assert bits(got[6]) != bits(seq[6]) or bits(got[5]) != bits(seq[5]) or bits(got[3]) != bits(seq[3]), label
         # any order of the ids, repeated ids
         ids = np.array([6, 0, 14, 6, 3, 8, 5, 5, 2], dtype=np.uint32)
-        assert np.array_equal(_bits(packed.score_rows(x, ids)), _bits(got[ids])), label
+        assert np.array_equal(bits(packed.score_rows(x, ids)), bits(got[ids])), label
 
 
 def test_partition_tails(pkg, oracle):
     """Rows that end on the last slot of a partition's last packet, and the rows right behind a padded partition tail."""
     rows, per = 128, 8  # 1024 entries: four full packets at C = 4, two at C = 8
     rng = np.random.default_rng(7)
-    m = _coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
+    m = coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
     x = _x(512, 8)
     seen_full_tail = 0
     for packed, c_lane, label in _every_packing(pkg, m, "exact fit", hints=(1, 2, 4)):
@@ -183,7 +168,7 @@ def test_partition_tails(pkg, oracle):
         seen_full_tail += sum(1 for q in range(pf.size) if w[int(pf[q] + pc[q] - 1), 64 * c_lane - 1] & ROW_END)
     assert seen_full_tail >= 6, "no partition ended on the last slot of its last packet: the case shows nothing"
     rows, per = 600, 7  # rows of 7 entries never fill a packet exactly; many partitions
-    m = _coo(pkg, rows, 300, np.repeat(np.arange(rows), per), rng.integers(0, 300, rows * per), rng.standard_normal(rows * per))
+    m = coo(pkg, rows, 300, np.repeat(np.arange(rows), per), rng.integers(0, 300, rows * per), rng.standard_normal(rows * per))
     x = _x(300, 9)
     for packed, c_lane, label in _every_packing(pkg, m, "padded tails", hints=(64,)):
         PE = 64 * c_lane
@@ -198,15 +183,15 @@ def test_partition_tails(pkg, oracle):
 
 
 def test_rows_of_a_loaded_file(pkg, oracle, tmp_path):
-    m = _signed(pkg, pkg.generate_matrix(1500, 1024, 20, "gamma", 9), 9)
+    m = signed(pkg, pkg.generate_matrix(1500, 1024, 20, "gamma", 9), 9)
     packed = pkg.Packed(m, k=8, n_wave_partitions=64)
     path = tmp_path / "m.tkspmv"
     packed.save(path)
     loaded = pkg.Packed.load(path)
     x = _x(1024, 10)
     got = _check_all_rows(oracle, m, loaded, 4, x, "loaded file")
-    assert np.array_equal(_bits(got), _bits(packed.score_rows(x, np.arange(m.rows))))
-    assert np.count_nonzero(_bits(got) != _bits(_sequential(m, x))) > 0
+    assert np.array_equal(bits(got), bits(packed.score_rows(x, np.arange(m.rows))))
+    assert np.count_nonzero(bits(got) != bits(_sequential(m, x))) > 0
 
 
 def test_errors(pkg):
@@ -242,31 +227,3 @@ def test_errors(pkg):
             p.score_rows(x, [0])
         assert e.value.status == UNSUPPORTED
         p.close()
-
-
-# ---- the kernel's resource report --------------------------------------------------------------------------------------------
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        mt = re.match(r"\s*Function Name: (\S+)", ln)
-        if mt:
-            cur = kernels.setdefault(mt.group(1), {})
-            continue
-        mt = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\d+)", ln)
-        if mt and cur is not None:
-            cur[mt.group(1)] = int(mt.group(2))
-    return kernels
-
-
-def test_score_rows_kernels_in_resource_report():
-    k = _report()
-    sr = {n: v for n, v in k.items() if "score_rows_kernel" in n}
-    # the 12-bit column layout, plain fp32 at 4 entries per lane (every column tier: x is not staged in LDS), 8 entries per lane
-    assert len(sr) == 3, sorted(sr)
-    assert sorted(re.search(r"score_rows_kernelILi(\d)ELb([01])E", n).groups() for n in sr) == [("4", "0"), ("4", "1"), ("8", "0")], sorted(sr)
-    for n, v in sr.items():
-        # (the substrings by which the other tests pick their kernels out of the report)
-        assert not any(t in n for t in ("row_vectors_kernel", "stream_kernel", "batch_kernel", "multi_kernel", "range_kernel")), n
-        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (n, v)

@@ -1,20 +1,20 @@
 """Queries by stored row without a GPU: the symbols of every layer, argument checks that come before any device call, the shared
 row lookup (csrc/row_lookup.hpp) through tkspmv_packed_get_row -- every row of every fixture and of generated and hand-made
 matrices, for both entries-per-lane settings and several partition counts, compared with the COO's row entry for entry, value bits
-included -- and the resource report of row_vectors_kernel.
+included.
 
 The hand-made cases assert from Packed.raw() that the situation they are made for really occurs in the packed stream."""
 import ctypes as C
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
 
+from support import coo
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REPORT = os.path.join(ROOT, "approximate-spmv-topk_amd", "kernel_resources.txt")
 HINTS = (1, 7, 64, 4064)
 ROW_END, SKIP = 1, 2
 
@@ -58,11 +58,6 @@ def test_knn_graph_checks_k_before_building(pkg):
 
 
 # ---- the lookup ------------------------------------------------------------------------------------------------------------
-def _coo(pkg, rows, cols, row, col, val):
-    return pkg.CooMatrix(rows=int(rows), cols=int(cols), row=np.asarray(row, np.uint32), col=np.asarray(col, np.uint32),
-                         val=np.asarray(val, np.float32))
-
-
 def _words(raw, C_lane):
     """Column words of the stream, [n_packets, PE] in stream-slot order, decoded here from the raw bytes (16-bit words behind the
     values; the split 12-bit plane where a packet has 5.5 bytes per entry)."""
@@ -114,7 +109,7 @@ def _fixtures(pkg):
     for f in sorted(glob.glob(os.path.join(GOLD, "gold_*.npz"))):
         z = np.load(f)
         if "row" in z.files and "col" in z.files and "rows" in z.files:
-            out[os.path.basename(f)] = _coo(pkg, z["rows"], z["cols"], z["row"], z["col"], z["val"])
+            out[os.path.basename(f)] = coo(pkg, z["rows"], z["cols"], z["row"], z["col"], z["val"])
     out["small_0indexed.mtx"] = pkg.read_mtx(os.path.join(GOLD, "small_0indexed.mtx"), index_base=0, sort=True)
     out["small_1indexed.mtx"] = pkg.read_mtx(os.path.join(GOLD, "small_1indexed.mtx"), index_base=1, sort=True)
     return out
@@ -166,7 +161,7 @@ def _hand_made(pkg, cols=1024):
         row.append(np.full(lens[r], r, np.uint32))
         col.append(rng.integers(0, cols, lens[r]).astype(np.uint32))
         val.append(rng.standard_normal(lens[r]).astype(np.float32))
-    return _coo(pkg, rows, cols, np.concatenate(row), np.concatenate(col), np.concatenate(val)), lens
+    return coo(pkg, rows, cols, np.concatenate(row), np.concatenate(col), np.concatenate(val)), lens
 
 
 @pytest.mark.parametrize("cols", [1024, 4096])
@@ -194,7 +189,7 @@ def test_partition_tails(pkg):
     # 128 rows of 8 entries: 1024 entries, four full packets at C = 4, two at C = 8
     rows, per = 128, 8
     rng = np.random.default_rng(7)
-    m = _coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
+    m = coo(pkg, rows, 512, np.repeat(np.arange(rows), per), rng.integers(0, 512, rows * per), rng.standard_normal(rows * per))
     seen_full_tail = 0
     for c_lane in (4, 8):
         PE = 64 * c_lane
@@ -212,7 +207,7 @@ def test_partition_tails(pkg):
     assert seen_full_tail >= 6, "no partition ended on the last slot of its last packet: the case shows nothing"
     # padded tails: rows of 7 entries never fill a packet exactly; many partitions
     rows, per = 600, 7
-    m = _coo(pkg, rows, 300, np.repeat(np.arange(rows), per), rng.integers(0, 300, rows * per), rng.standard_normal(rows * per))
+    m = coo(pkg, rows, 300, np.repeat(np.arange(rows), per), rng.integers(0, 300, rows * per), rng.standard_normal(rows * per))
     for c_lane in (4, 8):
         PE = 64 * c_lane
         packed = pkg.Packed(m, k=8, nnz_per_lane=c_lane, n_wave_partitions=64)
@@ -262,29 +257,3 @@ def test_get_row_of_a_loaded_file(pkg, tmp_path):
     packed.save(path)
     loaded = pkg.Packed.load(path)
     _check_all_rows(pkg, m, loaded, "loaded file")
-
-
-# ---- the kernel's resource report --------------------------------------------------------------------------------------------
-def _report():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report (the library was not built by this Makefile)")
-    kernels, cur = {}, None
-    for ln in open(REPORT):
-        mt = re.match(r"\s*Function Name: (\S+)", ln)
-        if mt:
-            cur = kernels.setdefault(mt.group(1), {})
-            continue
-        mt = re.match(r"\s*(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\d+)", ln)
-        if mt and cur is not None:
-            cur[mt.group(1)] = int(mt.group(2))
-    return kernels
-
-
-def test_row_vectors_kernels_in_resource_report():
-    k = _report()
-    rv = {n: v for n, v in k.items() if "row_vectors_kernel" in n}
-    # the 12-bit column layout, plain fp32 at 1024 / 4096 / 16384 columns, 8 entries per lane
-    assert len(rv) == 5, sorted(rv)
-    for n, v in rv.items():
-        assert not any(t in n for t in ("stream_kernel", "batch_kernel", "multi_kernel", "range_kernel")), n
-        assert v["AGPRs"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (n, v)
