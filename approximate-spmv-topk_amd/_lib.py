@@ -101,10 +101,10 @@ class Match(C.Structure):
 # Every symbol include/tkspmv.h declares; tests check the library exports all of them.
 EXPORTED_SYMBOLS = [
     "tkspmv_create", "tkspmv_destroy", "tkspmv_get_info", "tkspmv_set_query", "tkspmv_set_query_device",
-    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_set_boost", "tkspmv_enqueue_boosted", "tkspmv_run_boosted", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_match", "tkspmv_run_match", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_enqueue_row_stats", "tkspmv_row_stats", "tkspmv_set_boost_cosine", "tkspmv_enqueue_col_stats", "tkspmv_col_stats", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
+    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_set_boost", "tkspmv_enqueue_boosted", "tkspmv_run_boosted", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_match", "tkspmv_run_match", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_enqueue_row_stats", "tkspmv_row_stats", "tkspmv_set_boost_cosine", "tkspmv_enqueue_assign", "tkspmv_assign", "tkspmv_enqueue_col_stats", "tkspmv_col_stats", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
     "tkspmv_time_queries", "tkspmv_time_host_loop", "tkspmv_time_query_batches", "tkspmv_time_stream_read", "tkspmv_enqueue_multi", "tkspmv_time_multi", "tkspmv_profile", "tkspmv_last_error", "tkspmv_device_count", "tkspmv_mtx_read", "tkspmv_mtx_free",
     "tkspmv_mtx_write", "tkspmv_sample_vector", "tkspmv_generate", "tkspmv_generate_rows", "tkspmv_generate_degrees", "tkspmv_options_parse", "tkspmv_pack", "tkspmv_pack_device",
-    "tkspmv_sell_roundtrip", "tkspmv_sell_pack_device_check", "tkspmv_packed_info", "tkspmv_packed_decode", "tkspmv_packed_raw", "tkspmv_packed_get_row", "tkspmv_packed_score_rows", "tkspmv_packed_row_stats", "tkspmv_packed_col_stats", "tkspmv_packed_free", "tkspmv_wave_partitions", "tkspmv_packed_save", "tkspmv_packed_load",
+    "tkspmv_sell_roundtrip", "tkspmv_sell_pack_device_check", "tkspmv_packed_info", "tkspmv_packed_decode", "tkspmv_packed_raw", "tkspmv_packed_get_row", "tkspmv_packed_score_rows", "tkspmv_packed_row_stats", "tkspmv_packed_assign", "tkspmv_packed_col_stats", "tkspmv_packed_free", "tkspmv_wave_partitions", "tkspmv_packed_save", "tkspmv_packed_load",
     "tkspmv_create_packed",
     "tkspmv_dist_unique_id", "tkspmv_dist_create", "tkspmv_dist_set_batch", "tkspmv_dist_enqueue", "tkspmv_dist_run_many",
     "tkspmv_dist_synchronize", "tkspmv_dist_time_exchange", "tkspmv_dist_read", "tkspmv_dist_destroy", "tkspmv_dist_last_error",
@@ -165,6 +165,8 @@ def lib():
     L.tkspmv_enqueue_row_stats.argtypes = [vp, C.c_int32, vp, vp]
     L.tkspmv_row_stats.argtypes = [vp, C.c_int32, f32p]
     L.tkspmv_set_boost_cosine.argtypes = [vp]
+    L.tkspmv_enqueue_assign.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+    L.tkspmv_assign.argtypes = [vp, f32p, C.c_int32, u32p, f32p]
     L.tkspmv_enqueue_col_stats.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp]
     L.tkspmv_col_stats.argtypes = [vp, C.c_int32, C.c_int32, vp]
     L.tkspmv_synchronize.argtypes = [vp]
@@ -199,6 +201,7 @@ def lib():
     L.tkspmv_packed_get_row.argtypes = [vp, C.c_uint32, u32p, f32p, C.c_uint32, u32p]
     L.tkspmv_packed_score_rows.argtypes = [vp, f32p, u32p, C.c_int32, f32p]
     L.tkspmv_packed_row_stats.argtypes = [vp, C.c_int32, f32p]
+    L.tkspmv_packed_assign.argtypes = [vp, f32p, C.c_int32, u32p, f32p]
     L.tkspmv_packed_col_stats.argtypes = [vp, C.c_int32, u32p, vp]
     L.tkspmv_wave_partitions.argtypes = [C.POINTER(Desc), C.POINTER(C.c_uint32)]
     L.tkspmv_packed_save.argtypes = [vp, C.c_char_p]

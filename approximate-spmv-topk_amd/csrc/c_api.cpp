@@ -182,6 +182,12 @@ int tkspmv_score_rows(tkspmv_t *h, const float *host_xs, int32_t count, const ui
 int tkspmv_enqueue_row_stats(tkspmv_t *h, int32_t kind, float *dev_out, void *stream) { ENGINE_CALL(enqueue_row_stats(kind, dev_out, stream, err)) }
 int tkspmv_row_stats(tkspmv_t *h, int32_t kind, float *host_out) { ENGINE_CALL(row_stats(kind, host_out, err)) }
 int tkspmv_set_boost_cosine(tkspmv_t *h) { ENGINE_CALL(set_boost_cosine(err)) }
+int tkspmv_enqueue_assign(tkspmv_t *h, const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream) {
+    ENGINE_CALL(enqueue_assign(dev_xs, count, dev_labels, dev_best, stream, err))
+}
+int tkspmv_assign(tkspmv_t *h, const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best) {
+    ENGINE_CALL(assign(host_xs, count, host_labels, host_best, err))
+}
 int tkspmv_enqueue_col_stats(tkspmv_t *h, int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
                              void *stream) {
     ENGINE_CALL(enqueue_col_stats(kind, count, dev_mask, mask_stride_words, dev_out, out_stride_words, stream, err))
@@ -453,6 +459,9 @@ int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint3
 int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
     PACKED_CALL(p && out && kind >= TKSPMV_ROW_NNZ && kind <= TKSPMV_ROW_INV_L2,
                 "bad arguments (packed matrix and output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)", packed_row_stats(p->pm, kind, out, err))
+}
+int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels, float *best) {
+    PACKED_CALL(p && xs && labels && count >= 1, "bad arguments (packed matrix, vectors and labels given, count >= 1)", packed_assign(p->pm, xs, count, labels, best, err))
 }
 int tkspmv_packed_col_stats(const tkspmv_packed *p, int32_t kind, const uint32_t *mask, void *out) {
     PACKED_CALL(p && out && kind >= TKSPMV_COL_NNZ && kind <= TKSPMV_COL_MIN,

@@ -54,6 +54,7 @@
 #include "kernels/row_vectors.hpp"
 #include "kernels/score_rows.hpp"
 #include "kernels/row_stats.hpp"
+#include "kernels/assign.hpp"
 #include "kernels/col_stats.hpp"
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
@@ -113,6 +114,7 @@ typedef void (*row_vectors_fn)(const RowVecParams);
 typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*row_stats_fn)(const StreamParams, const RowStatsParams);
 typedef void (*col_stats_fn)(const StreamParams, const ColStatsParams);
+typedef void (*assign_fn)(const StreamParams, const AssignParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
 typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
@@ -126,6 +128,7 @@ struct Kernels {
     score_rows_fn score_rows = nullptr;  // (no x in LDS: one instantiation serves every column tier)
     row_stats_fn row_stats[4] = {};      // [kind: TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2] (no x at all: likewise)
     col_stats_fn col_stats[2][2] = {};   // [EXT: TKSPMV_COL_MAX / _MIN][FILT]
+    assign_fn assign = nullptr;          // (16384 / XCOLS vectors in LDS per pass)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
@@ -159,6 +162,7 @@ static Kernels kernels_of(bool dbg) {
         K.row_stats[TKSPMV_ROW_L1] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L1>;
         K.row_stats[TKSPMV_ROW_L2SQ] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L2SQ>;
         K.row_stats[TKSPMV_ROW_INV_L2] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_INV_L2>;
+        K.assign = &assign_kernel<C, XCOLS, QM>;
         K.col_stats[0][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, false>;
         K.col_stats[0][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, true>;
         K.col_stats[1][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, false>;
@@ -506,6 +510,16 @@ struct EngineImpl {
     struct RowStats {
         float *d_rs_out = nullptr;  // [rows]
     } stats;
+
+    // Assignment (tkspmv_enqueue_assign, assign_kernel) likewise. The scratch of tkspmv_assign, which allocates it on its first call:
+    // rows labels and rows scores, and a chunk of vectors that grows to the largest chunk asked for (at most ASSIGN_MAX_BYTES).
+    struct Assign {
+        static constexpr size_t ASSIGN_MAX_BYTES = (size_t)64 << 20;
+        uint32_t *d_as_labels = nullptr;  // [rows]
+        float *d_as_best = nullptr;       // [rows]
+        float *d_as_xs = nullptr;         // [as_cap][cols]
+        uint32_t as_cap = 0;              // vectors the scratch holds
+    } assign;
 
     // Column statistics (tkspmv_enqueue_col_stats, col_stats_kernel) likewise. The scratch of tkspmv_col_stats -- cols words --, which
     // allocates it on its first call.
@@ -1107,6 +1121,28 @@ struct EngineImpl {
         if (pm.n_packets == 0u) return;
         const RowStatsParams R{mat.d_packets, out, desc.rows};
         hipLaunchKernelGGL(kern.row_stats[kind], dim3(grid), dim3(512), 0, s, stream_params(nullptr), R);
+    }
+    // Vectors one assign_kernel launch serves: as many as fit the kernel's 64 KiB of LDS at the engine's column tier (16 / 4 / 1).
+    int assign_pass() const { return assign_vectors_per_pass(fmt.xcols); }
+    // Labels and best scores of every local row for the vectors xs[0 .. n), which are the vectors q_base .. q_base + n of their call,
+    // complete in stream order when this returns. q_base = 0: both outputs are zeroed in front (rows without entries are never written
+    // by the kernel) and the first launch stores unconditionally; every later launch -- of this call or, q_base != 0, of the call's
+    // later chunks -- merges with the stored pair and needs best. One pass over stream copy 0 per assign_pass() vectors, with the
+    // scan kernels' geometry. Not a launch_scan call: AssignParams has no stream-copy table and no mask geometry to fill. No engine
+    // state is read or written besides the matrix.
+    void launch_assign(const float *xs, int n, uint32_t q_base, uint32_t *labels, float *best, hipStream_t s) const {
+        if (desc.rows == 0u) return;
+        if (q_base == 0u) {
+            (void)hipMemsetAsync(labels, 0, (size_t)desc.rows * 4, s);
+            if (best) (void)hipMemsetAsync(best, 0, (size_t)desc.rows * 4, s);
+        }
+        if (pm.n_packets == 0u) return;
+        const StreamParams P = stream_params(nullptr);
+        const int qp = assign_pass();
+        for (int i = 0; i < n; i += qp) {
+            const AssignParams R{mat.d_packets, xs + (size_t)i * desc.cols, labels, best, desc.rows, (uint32_t)std::min(qp, n - i), q_base + (uint32_t)i};
+            hipLaunchKernelGGL(kern.assign, dim3(grid), dim3(512), 0, s, P, R);
+        }
     }
     // Why column statistics are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask). Served where
     // row statistics are; among the rows of a mask, where filtered queries are (match_unsupported's rule).
@@ -3107,6 +3143,49 @@ int Engine::row_stats(int32_t kind, float *host_out, std::string &err) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m.stream));
     HIP_TRY(hipMemcpy(host_out, m.stats.d_rs_out, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_xs || !dev_labels || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_assign (vectors and labels given, count >= 1)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
+    // (the launches behind the first merge with the scores of the ones before: without dev_best there is nowhere to keep them -- the
+    //  engine owns no scratch that a call on a caller's stream could use without a wait)
+    if (!dev_best && count > m.assign_pass())
+        return fail(err, TKSPMV_ERR_INVALID, "dev_best = NULL takes one pass: count must not exceed the vectors of one pass (16384 / the column tier: 16, 4 or 1)");
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_assign(dev_xs, count, 0u, dev_labels, dev_best, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::assign(const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_xs || !host_labels || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to assign (vectors and labels given, count >= 1)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
+    if (m.desc.rows == 0u) return TKSPMV_OK;
+    HIP_TRY(hipSetDevice(m.device));
+    EngineImpl::Assign &A = m.assign;
+    const size_t cols = m.desc.cols, rows = m.desc.rows;
+    if (!A.d_as_labels) HIP_TRY(m.alloc(A.d_as_labels, rows * 4));
+    if (!A.d_as_best) HIP_TRY(m.alloc(A.d_as_best, rows * 4));
+    const uint32_t want = (uint32_t)std::min<size_t>((size_t)count, std::max<size_t>(1, EngineImpl::Assign::ASSIGN_MAX_BYTES / (std::max<size_t>(cols, 1) * 4)));
+    if (want > A.as_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: assign waits itself)
+        HIP_TRY(m.grow_scratch(A.as_cap, want, {{(void **)&A.d_as_xs, (size_t)want * std::max<size_t>(cols, 1) * 4}}));
+    }
+    // chunks of vectors: up, the chunk's launches, wait (the next chunk overwrites the vectors). No result is read and no result buffer
+    // written, so the engine need not be settled: the waits are for this call's own launches.
+    for (int32_t q0 = 0; q0 < count; q0 += (int32_t)A.as_cap) {
+        const int32_t qc = std::min<int32_t>((int32_t)A.as_cap, count - q0);
+        HIP_TRY(hipMemcpy(A.d_as_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
+        m.launch_assign(A.d_as_xs, qc, (uint32_t)q0, A.d_as_labels, A.d_as_best, m.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m.stream));
+    }
+    HIP_TRY(hipMemcpy(host_labels, A.d_as_labels, rows * 4, hipMemcpyDeviceToHost));
+    if (host_best) HIP_TRY(hipMemcpy(host_best, A.d_as_best, rows * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 

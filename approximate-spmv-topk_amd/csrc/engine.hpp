@@ -91,6 +91,11 @@ class Engine {
     int enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::string &err);
     int row_stats(int32_t kind, float *host_out, std::string &err);
     int set_boost_cosine(std::string &err);
+    // Assignment (assign_kernel): for every local row the index of the best-scoring of `count` vectors (ties: the smallest) and that
+    // score, the bits every scoring path reports; one pass over the packet stream per 16384 / column tier vectors. dev_best = NULL:
+    // one pass only. assign is the host-side counterpart (engine-owned scratch, chunks of vectors, waits for its own launches).
+    int enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream, std::string &err);
+    int assign(const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best, std::string &err);
     // Column statistics (col_stats_kernel): one word per column and set of rows -- the number of stored entries (uint32) or the largest /
     // smallest stored value (float32) --, a set being all rows or the rows of an allow-mask; exact whatever the order of the atomics.
     // col_stats is the host-side counterpart (engine-owned scratch, waits; use_filter: among the rows of the installed mask).

@@ -1,4 +1,4 @@
-// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel and col_stats_kernel (packed_host.hpp).
+// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel, col_stats_kernel and assign_kernel (packed_host.hpp).
 #include "packed_host.hpp"
 
 #include <algorithm>
@@ -157,6 +157,31 @@ int packed_row_stats(const PackedMatrix &pm, int32_t kind, float *out, std::stri
             case TKSPMV_ROW_L2SQ: out[r] = reduce_located_row(V, run, [](float v, uint16_t) { return v * v; }); break;
             default: out[r] = inv_l2_of(reduce_located_row(V, run, [](float v, uint16_t) { return v * v; })); break;
         }
+    }
+    return TKSPMV_OK;
+}
+
+// assign_kernel (kernels/assign.hpp) restated row by row: the row's score against every vector in turn -- packed_score_rows' value --,
+// the first kept, a later one only where it is strictly greater (ties go to the smallest index). A row without entries: label 0, +0.0f.
+int packed_assign(const PackedMatrix &pm, const float *xs, int32_t count, uint32_t *labels, float *best, std::string &err) {
+    HostRowView V;
+    if (const int st = open_f32_stream(pm, "rows are assigned in", V, err); st != TKSPMV_OK) return st;
+    for (uint32_t r = 0; r < pm.rows; ++r) {
+        RowRun run{0u, 0u, 0u, 0u};
+        uint32_t label = 0u;
+        float b = 0.0f;
+        if (locate_entries(pm, V, r, run) != 0u) {
+            b = score_located_row(V, run, xs);
+            for (int32_t q = 1; q < count; ++q) {
+                const float s = score_located_row(V, run, xs + (size_t)q * pm.cols);
+                if (s > b) {
+                    b = s;
+                    label = (uint32_t)q;
+                }
+            }
+        }
+        labels[r] = label;
+        if (best) best[r] = b;
     }
     return TKSPMV_OK;
 }

@@ -1,5 +1,5 @@
-// packed_host.hpp -- the host twins of four kernels over a packed fp32 stream (wbscsr.hpp), behind tkspmv_packed_get_row,
-// tkspmv_packed_score_rows, tkspmv_packed_row_stats and tkspmv_packed_col_stats (c_api.cpp). Plain C++ over a PackedMatrix, no GPU:
+// packed_host.hpp -- the host twins of five kernels over a packed fp32 stream (wbscsr.hpp), behind tkspmv_packed_get_row,
+// tkspmv_packed_score_rows, tkspmv_packed_row_stats, tkspmv_packed_col_stats and tkspmv_packed_assign (c_api.cpp). Plain C++ over a PackedMatrix, no GPU:
 // what they return agrees with the device bit for bit, and the host tests compare them with models that share nothing with them.
 #pragma once
 #include <cstdint>
@@ -45,5 +45,6 @@ int packed_get_row(const PackedMatrix &pm, uint32_t row, uint32_t *col, float *v
 int packed_score_rows(const PackedMatrix &pm, const float *x, const uint32_t *rows, int32_t n_rows, float *scores, std::string &err);
 int packed_row_stats(const PackedMatrix &pm, int32_t kind, float *out, std::string &err);
 int packed_col_stats(const PackedMatrix &pm, int32_t kind, const uint32_t *mask, void *out, std::string &err);
+int packed_assign(const PackedMatrix &pm, const float *xs, int32_t count, uint32_t *labels, float *best, std::string &err);
 
 }  // namespace tkspmv

@@ -463,6 +463,31 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_row_stats(self._h, int(kind), f32p(out)))
         return out[:self.num_rows]
 
+    def enqueue_assign(self, dev_xs, count, dev_labels, dev_best=0, stream=0):
+        """Assignment: for every LOCAL row r the best-scoring of the `count` vectors at dev_xs (float32, cols each, back to back):
+        dev_labels[r] (uint32) = its index, ties to the smallest, and dev_best[r] (float32, optional) = that score, bit for bit the
+        value every other path reports for the row and the vector. A row without entries gets label 0 and +0.0. One pass over the
+        matrix per 16384 / column tier vectors (16 at up to 1024 columns, 4 up to 4096, 1 beyond); dev_best = 0 only with at most
+        that many vectors. No host sync, no engine state touched. The labels are what set_groups, enqueue_facets(dev_labels=...)
+        and the masks of enqueue_col_stats are made from."""
+        _lib.check(_lib.lib().tkspmv_enqueue_assign(self._h, ptr(dev_xs), int(count), ptr(dev_labels), ptr(dev_best), ptr(stream)))
+
+    def assign(self, vecs, install=False):
+        """enqueue_assign with host arrays: (labels uint32[rows], best float32[rows]) for vecs[count, cols] (or one vector of cols).
+        Waits. install: the labels become the engine's group labels, set_groups(labels, n_groups=count) -- run_grouped then returns
+        each cluster once, run_facets counts per cluster."""
+        xs = np.ascontiguousarray(vecs, dtype=np.float32)
+        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
+            raise ValueError(f"vectors must be [count >= 1, {self.num_cols}]")
+        labels = np.empty(max(self.num_rows, 1), dtype=np.uint32)
+        best = np.empty(max(self.num_rows, 1), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_assign(self._h, f32p(xs), int(xs.shape[0]), u32p(labels), f32p(best)))
+        labels, best = labels[:self.num_rows], best[:self.num_rows]
+        if install:
+            self.set_groups(labels, n_groups=int(xs.shape[0]))
+        return labels, best
+
     def enqueue_col_stats(self, kind, out, masks=None, mask_stride=0, out_stride=0, stream=None, count=1):
         """Column statistics: one 4-byte word per column and set of rows into device memory at `out` -- kind = _lib.COL_NNZ (uint32:
         the stored entries of the column; explicit zeros and a column repeated within a row count), COL_MAX / COL_MIN (float32: the
@@ -649,6 +674,14 @@ def cosine_spmv(m, vec, k, allow=None, **kw):
         e.set_cosine()
         idx, val, n, _, _ = e.run_boosted(allow=allow)
         return val[:n], idx[:n]
+
+
+def assign_spmv(m, vecs, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (labels, best) of SpMV.assign(vecs): for every row the index of
+    its best-scoring vector (ties to the smallest) and that score."""
+    kw.setdefault("k", 8)
+    with _one_shot(m, **kw) as e:
+        return e.assign(vecs)
 
 
 def knn_graph(m, k, rows=None, **kw):

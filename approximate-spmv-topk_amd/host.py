@@ -225,6 +225,23 @@ def inv_l2(l2sq):
     return np.where((s > 0) & np.isfinite(s), w, np.float32(0)).astype(np.float32)
 
 
+def nearest(scores):
+    """The contract of assignment (SpMV.assign, Packed.assign) restated in numpy, for CPU-side users and as the tests' expectation:
+    from float32 scores[count, rows] -- scores[q, r] what row r scores for vector q -- (labels uint32[rows], best float32[rows]):
+    vector 0 first, a later vector only where its score is strictly greater, so ties go to the smallest index and -0.0 never
+    replaces +0.0. NaN scores are outside the contract."""
+    y = np.ascontiguousarray(scores, dtype=np.float32)
+    if y.ndim != 2 or y.shape[0] < 1:
+        raise ValueError("scores must be [count >= 1, rows]")
+    best = y[0].copy()
+    labels = np.zeros(y.shape[1], dtype=np.uint32)
+    for q in range(1, y.shape[0]):
+        better = y[q] > best
+        best[better] = y[q][better]
+        labels[better] = q
+    return labels, best
+
+
 def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
     """The contract of facet counts (SpMV.enqueue_facets) restated in numpy, for CPU-side users and as the tests' expectation:
     from float32 scores[rows], present[rows] (the row has entries; allow[rows], if given, restricts further) and labels[rows], the
@@ -578,6 +595,21 @@ class Packed:
         out = np.empty(max(int(self.info()["rows"]), 1), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_packed_row_stats(self._h, int(kind), _lib.f32p(out)))
         return out[:int(self.info()["rows"])]
+
+    def assign(self, vecs):
+        """(labels uint32[rows], best float32[rows]): for every row the index of the best-scoring of vecs[count, cols] (ties to the
+        smallest) and that score, with the bits an engine created from this packed matrix reports (SpMV.assign): score_rows'
+        arithmetic per row and vector, on the host. A row without entries gets label 0 and +0.0. fp32 values only (TkspmvError
+        ERR_UNSUPPORTED otherwise)."""
+        rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
+        xs = np.ascontiguousarray(vecs, dtype=np.float32)
+        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != cols:
+            raise ValueError(f"vectors must be [count >= 1, {cols}]")
+        labels = np.empty(max(rows, 1), dtype=np.uint32)
+        best = np.empty(max(rows, 1), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_packed_assign(self._h, _lib.f32p(xs), int(xs.shape[0]), _lib.u32p(labels), _lib.f32p(best)))
+        return labels[:rows], best[:rows]
 
     def col_stats(self, kind, allow=None):
         """uint32[cols] (kind _lib.COL_NNZ) or float32[cols] (COL_MAX, COL_MIN): one statistic of every column over all rows, or over

@@ -534,6 +534,33 @@ int tkspmv_row_stats(tkspmv_t *e, int32_t kind, float *host_out /* [rows] */);
  * array on first use, and the boost counts as installed only once the launch has completed without error. Errors:
  * TKSPMV_ERR_INVALID for a NULL engine; TKSPMV_ERR_UNSUPPORTED where tkspmv_enqueue_row_stats reports it. */
 int tkspmv_set_boost_cosine(tkspmv_t *e);
+/* Assignment ("which of these vectors suits every row best?": nearest-centroid classification, the assignment step of spherical
+ * k-means, routing rows to shards or topics, labelling a collection against prototype vectors), the opposite question to every query
+ * form above. dev_xs holds count >= 1 dense vectors of desc.cols floats, back to back; every LOCAL row r (indexed like masks, group
+ * labels and row statistics) receives
+ *   best = s(r, 0); label = 0;  for q = 1 .. count-1: if (s(r, q) > best) { best = s(r, q); label = q; }
+ *   dev_labels[r] = label (uint32), dev_best[r] = best (float32, optional)
+ * with s(r, q) the fp32 score every other path reports for row r and vector q, bit for bit (tkspmv_scores, tkspmv_enqueue_score_rows,
+ * the top-k lists): the sums are formed in the streaming kernels' order, and tkspmv_packed_assign restates them on the host. Ties go to
+ * the smallest index. A row without entries scores +0.0f against every vector: label 0, best +0.0f. desc.min_score, the installed
+ * filter, the installed query and the boost play no part. The vectors must be finite and yield scores that are not NaN; otherwise
+ * the labels of the affected rows are unspecified. The labels are what tkspmv_set_groups, tkspmv_enqueue_facets (dev_labels) and
+ * the masks of tkspmv_enqueue_col_stats are made from.
+ * One pass over stream copy 0 of the matrix serves 16384 / T vectors held side by side in LDS, T the engine's column tier (1024,
+ * 4096 or 16384 for up to that many columns): 16, 4 or 1 (assign_kernel); more vectors run as consecutive launches that merge with
+ * the stored pair, behind a memset of both outputs on the same stream. dev_best = NULL is allowed only when count does not exceed the
+ * vectors of one pass: the later launches keep their running scores in dev_best, and the engine owns no scratch that a call on a
+ * caller's stream could use. Asynchronous, complete in stream order on any stream (NULL: the engine's); exactly desc.rows labels (and
+ * scores) are written; reads and writes no engine state, so it may be mixed freely with the other calls, as tkspmv_enqueue_row_stats
+ * may. With desc.rows = 0 the call succeeds and writes nothing.
+ * Errors: TKSPMV_ERR_INVALID (checked first, before any device call) for a NULL engine, NULL dev_xs, NULL dev_labels or count < 1;
+ * then TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_row_stats reports it (the approximate per-partition engines ARE served);
+ * then TKSPMV_ERR_INVALID for dev_best = NULL with more vectors than one pass. A rejected call writes nothing. */
+int tkspmv_enqueue_assign(tkspmv_t *e, const float *dev_xs, int32_t count, uint32_t *dev_labels /* [rows] */, float *dev_best /* [rows], may be NULL */,
+                          void *stream);
+/* The same with host arrays, any count with or without host_best: on engine-owned scratch (rows labels, rows scores, and the vectors
+ * in chunks of at most 64 MiB), allocated by the first call, on the engine's stream; waits for its own launches only. */
+int tkspmv_assign(tkspmv_t *e, const float *host_xs, int32_t count, uint32_t *host_labels /* [rows] */, float *host_best /* [rows], may be NULL */);
 /* Column statistics ("how many rows carry this term, how large do its values get?": what IDF / BM25 query weights, score upper
  * bounds -- the sum over c of max(0, x[c] * max[c], x[c] * min[c]) bounds every row's score -- and significant-terms counts are made
  * of), taken from the matrix the engine already holds: np.bincount(col) without a COO, and in ONE pass what tkspmv_enqueue_match
@@ -789,6 +816,12 @@ int tkspmv_packed_score_rows(const tkspmv_packed *p, const float *x, const uint3
  * tkspmv_packed_score_rows, with each product replaced by 1, |v| or v * v. No GPU needed. TKSPMV_ERR_INVALID for a NULL argument or
  * a kind outside 0 .. 3, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
 int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out /* [rows] */);
+/* Label and best score of EVERY row of a packed matrix against count vectors of cols floats (xs, back to back): labels[r] and best[r],
+ * rows of each, with the bits an engine created from this packed matrix reports (tkspmv_enqueue_assign): every row's
+ * tkspmv_packed_score_rows score against each vector in turn, the first kept and a later one only where it is strictly greater. A
+ * row without entries gets label 0 and +0.0f. No GPU needed. TKSPMV_ERR_INVALID for a NULL matrix, NULL xs, NULL labels or
+ * count < 1, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
+int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels /* [rows] */, float *best /* [rows], may be NULL */);
 /* One column statistic (TKSPMV_COL_NNZ .. TKSPMV_COL_MIN) of a packed matrix over all rows (mask = NULL) or the rows of an allow-mask
  * of ceil(rows / 32) words: out[c], cols words, with the bits an engine created from this packed matrix reports
  * (tkspmv_enqueue_col_stats): a plain walk over the packet stream, so it works on a loaded .tkspmv file with no COO. No GPU needed.
