@@ -13,6 +13,7 @@
 #include "host_utils.hpp"
 #include "options.hpp"
 #include "packed_host.hpp"
+#include "quantise.hpp"
 #include "wbscsr.hpp"
 #include "wsell.hpp"
 
@@ -187,6 +188,17 @@ int tkspmv_enqueue_assign(tkspmv_t *h, const float *dev_xs, int32_t count, uint3
 }
 int tkspmv_assign(tkspmv_t *h, const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best) {
     ENGINE_CALL(assign(host_xs, count, host_labels, host_best, err))
+}
+int tkspmv_enqueue_label_sums(tkspmv_t *h, const uint32_t *dev_labels, uint32_t n_bins, int32_t quantum_exp, uint32_t flags, int64_t *dev_sums, int32_t mode,
+                              float *dev_out, void *stream) {
+    ENGINE_CALL(enqueue_label_sums(dev_labels, n_bins, quantum_exp, flags, dev_sums, mode, dev_out, stream, err))
+}
+int tkspmv_enqueue_sums_close(tkspmv_t *h, const int64_t *dev_sums, uint32_t n_bins, int32_t quantum_exp, int32_t mode, float *dev_out, void *stream) {
+    ENGINE_CALL(enqueue_sums_close(dev_sums, n_bins, quantum_exp, mode, dev_out, stream, err))
+}
+int tkspmv_sums_exponent(tkspmv_t *h, int32_t *quantum_exp) { ENGINE_CALL(sums_exponent(quantum_exp, err)) }
+int tkspmv_label_sums(tkspmv_t *h, const uint32_t *host_labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *host_sums, float *host_out) {
+    ENGINE_CALL(label_sums(host_labels, n_bins, quantum_exp, mode, host_sums, host_out, err))
 }
 int tkspmv_enqueue_col_stats(tkspmv_t *h, int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
                              void *stream) {
@@ -463,6 +475,20 @@ int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
 int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels, float *best) {
     PACKED_CALL(p && xs && labels && count >= 1, "bad arguments (packed matrix, vectors and labels given, count >= 1)", packed_assign(p->pm, xs, count, labels, best, err))
 }
+int tkspmv_packed_label_sums(const tkspmv_packed *p, const uint32_t *labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *sums, float *out) {
+    PACKED_CALL(p && labels && n_bins >= 1u && n_bins <= (1u << 30) && mode >= TKSPMV_SUMS_RAW && mode <= TKSPMV_SUMS_UNIT && (mode == TKSPMV_SUMS_RAW || out),
+                "bad arguments (packed matrix and labels given, 1 <= n_bins <= 2^30, mode = TKSPMV_SUMS_RAW .. TKSPMV_SUMS_UNIT, out given unless RAW)",
+                packed_label_sums(p->pm, labels, n_bins, quantum_exp, mode, sums, out, err))
+}
+int tkspmv_packed_sums_exponent(const tkspmv_packed *p, int32_t *quantum_exp) {
+    PACKED_CALL(p && quantum_exp, "bad arguments (packed matrix and output given)", packed_sums_exponent(p->pm, quantum_exp, err))
+}
+int tkspmv_sums_close_host(const int64_t *sums, uint32_t n_bins, uint32_t cols, int32_t quantum_exp, int32_t mode, float *out) {
+    if (!sums || !out || (mode != TKSPMV_SUMS_FLOAT && mode != TKSPMV_SUMS_UNIT)) return fail(TKSPMV_ERR_INVALID, "bad arguments (sums and out given, mode = TKSPMV_SUMS_FLOAT or TKSPMV_SUMS_UNIT)");
+    sums_close_host(sums, n_bins, cols, quantum_exp, mode, out);
+    return TKSPMV_OK;
+}
+int64_t tkspmv_quantise(uint32_t value_bits, int32_t quantum_exp) { return quantise(value_bits, quantum_exp); }
 int tkspmv_packed_col_stats(const tkspmv_packed *p, int32_t kind, const uint32_t *mask, void *out) {
     PACKED_CALL(p && out && kind >= TKSPMV_COL_NNZ && kind <= TKSPMV_COL_MIN,
                 "bad arguments (packed matrix and output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)", packed_col_stats(p->pm, kind, mask, out, err))

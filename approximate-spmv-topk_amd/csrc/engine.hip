@@ -56,6 +56,7 @@
 #include "kernels/row_stats.hpp"
 #include "kernels/assign.hpp"
 #include "kernels/col_stats.hpp"
+#include "kernels/label_sums.hpp"
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
 #include "kernels/boost_cut.hpp"
@@ -115,6 +116,7 @@ typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*row_stats_fn)(const StreamParams, const RowStatsParams);
 typedef void (*col_stats_fn)(const StreamParams, const ColStatsParams);
 typedef void (*assign_fn)(const StreamParams, const AssignParams);
+typedef void (*label_sums_fn)(const StreamParams, const LabelSumsParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
 typedef void (*multi_fn)(const StreamParams, const SelectParams, const MultiParams);
@@ -129,6 +131,7 @@ struct Kernels {
     row_stats_fn row_stats[4] = {};      // [kind: TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2] (no x at all: likewise)
     col_stats_fn col_stats[2][2] = {};   // [EXT: TKSPMV_COL_MAX / _MIN][FILT]
     assign_fn assign = nullptr;          // (16384 / XCOLS vectors in LDS per pass)
+    label_sums_fn label_sums[2] = {};    // [LDS_SINK]; [1] NULL at the 16384-column tier (8192 / XCOLS bins in LDS per launch)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
     multi_fn multi = nullptr;  // multi-query engines only
@@ -167,6 +170,8 @@ static Kernels kernels_of(bool dbg) {
         K.col_stats[0][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, true>;
         K.col_stats[1][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, false>;
         K.col_stats[1][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, true>;
+        K.label_sums[0] = &label_sums_kernel<C, XCOLS, QM == QM_F32C12, false>;
+        if constexpr (label_sums_lds_bins(XCOLS) != 0u) K.label_sums[1] = &label_sums_kernel<C, XCOLS, QM == QM_F32C12, true>;
     }
     if constexpr (is_batchable(F)) {
         K.batch[0] = &batch_kernel<C, XCOLS, QM, false, false>;
@@ -520,6 +525,15 @@ struct EngineImpl {
         float *d_as_xs = nullptr;         // [as_cap][cols]
         uint32_t as_cap = 0;              // vectors the scratch holds
     } assign;
+
+    // Label sums (tkspmv_enqueue_label_sums, label_sums_kernel) likewise. The scratch of tkspmv_label_sums, which allocates it on its
+    // first call: rows labels, and n_bins * cols sums and floats, which grow to the largest n_bins asked for.
+    struct LabelSums {
+        uint32_t *d_ls_labels = nullptr;  // [rows]
+        int64_t *d_ls_sums = nullptr;     // [ls_cap][cols]
+        float *d_ls_out = nullptr;        // [ls_cap][cols]
+        uint32_t ls_cap = 0;              // bins the scratch holds
+    } lsums;
 
     // Column statistics (tkspmv_enqueue_col_stats, col_stats_kernel) likewise. The scratch of tkspmv_col_stats -- cols words --, which
     // allocates it on its first call.
@@ -1176,6 +1190,45 @@ struct EngineImpl {
             const uint32_t cgrid = (uint32_t)std::min<size_t>(((size_t)n * cols + 255u) / 256u, 16384u);
             hipLaunchKernelGGL(col_stats_close_kernel, dim3(cgrid), dim3(256), 0, s, out, (uint64_t)ostride, (uint32_t)cols, (uint32_t)n, negate);
         }
+    }
+    // Which sink a label-sums call takes when its flags force none: the LDS sink where the tier has one (1024 and 4096 columns) and
+    // the bins need at most LABEL_SUMS_LDS_MAX_WINDOWS launches, the direct sink otherwise. The crossover is measured, not reasoned:
+    // profiles/label_sums_probe.json (1M x 1024, 20 entries per row, B = 8 bins per launch) has the two sinks side by side. A launch
+    // of the LDS sink costs 42 .. 65 us whatever its window; the direct sink 0.93 .. 1.3 ms for 8 bins and more (2.7 ms for one bin:
+    // every atomic of a column meets in one word). The LDS sink wins at 128 bins (16 launches: 806 us against 983), the direct sink
+    // at 256 (32 launches: 1348 against 932): the rule changes sides between those two measured points. DESIGN.md section 3.23 has
+    // the table.
+    static constexpr uint32_t LABEL_SUMS_LDS_MAX_WINDOWS = 16;
+    bool label_sums_lds_sink(uint32_t n_bins) const {
+        const uint32_t B = label_sums_lds_bins(fmt.xcols);
+        return kern.label_sums[1] != nullptr && B != 0u && (n_bins + B - 1u) / B <= LABEL_SUMS_LDS_MAX_WINDOWS;
+    }
+    // The int64 sums of every bin and column (labels[r]: the bin of local row r, none when >= n_bins) into sums[n_bins][cols], complete
+    // in stream order when this returns: sums is zeroed in front unless the call accumulates, then one launch of the direct sink, or one
+    // launch of the LDS sink per window of 8192 / tier bins, over stream copy 0 with the scan kernels' geometry. No engine state is read
+    // or written besides the matrix.
+    void launch_label_sums(const uint32_t *labels, uint32_t n_bins, int32_t quantum_exp, bool accumulate, bool lds, int64_t *sums, hipStream_t s) const {
+        const size_t words = (size_t)n_bins * desc.cols;
+        if (words == 0u) return;
+        if (!accumulate) (void)hipMemsetAsync(sums, 0, words * 8, s);
+        if (desc.rows == 0u || pm.n_packets == 0u) return;
+        const StreamParams P = stream_params(nullptr);
+        LabelSumsParams R{mat.d_packets, labels, reinterpret_cast<unsigned long long *>(sums), desc.rows, n_bins, 0u, quantum_exp};
+        if (!lds) {
+            hipLaunchKernelGGL(kern.label_sums[0], dim3(grid), dim3(512), 0, s, P, R);
+            return;
+        }
+        for (uint32_t b0 = 0; b0 < n_bins; b0 += label_sums_lds_bins(fmt.xcols)) {
+            R.b0 = b0;
+            hipLaunchKernelGGL(kern.label_sums[1], dim3(grid), dim3(512), 0, s, P, R);
+        }
+    }
+    // sums[n_bins][cols] as floats into out (TKSPMV_SUMS_FLOAT) or as unit vectors (TKSPMV_SUMS_UNIT: a bin whose norm is 0 or
+    // overflows is not written), complete in stream order when this returns: one workgroup of 64 threads per bin.
+    void launch_sums_close(const int64_t *sums, uint32_t n_bins, int32_t quantum_exp, int mode, float *out, hipStream_t s) const {
+        if (n_bins == 0u || desc.cols == 0u) return;
+        hipLaunchKernelGGL(label_sums_close_kernel, dim3(n_bins), dim3(64), 0, s, reinterpret_cast<const long long *>(sums), out, (uint32_t)desc.cols, quantum_exp,
+                           mode == TKSPMV_SUMS_UNIT ? 1u : 0u);
     }
     // Why filtered queries are not served by this engine (nullptr: they are).
     const char *filter_unsupported() const {
@@ -3186,6 +3239,92 @@ int Engine::assign(const float *host_xs, int32_t count, uint32_t *host_labels, f
     }
     HIP_TRY(hipMemcpy(host_labels, A.d_as_labels, rows * 4, hipMemcpyDeviceToHost));
     if (host_best) HIP_TRY(hipMemcpy(host_best, A.d_as_best, rows * 4, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_label_sums(const uint32_t *dev_labels, uint32_t n_bins, int32_t quantum_exp, uint32_t flags, int64_t *dev_sums, int32_t mode, float *dev_out,
+                               void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    constexpr uint32_t SINKS = TKSPMV_SUMS_SINK_LDS | TKSPMV_SUMS_SINK_DIRECT;
+    if (!dev_sums || (reinterpret_cast<uintptr_t>(dev_sums) & 7u) != 0u || (dev_labels != nullptr) != (n_bins != 0u) || n_bins > (1u << 30) ||
+        mode < TKSPMV_SUMS_RAW || mode > TKSPMV_SUMS_UNIT || (mode != TKSPMV_SUMS_RAW && !dev_out) || (flags & ~(TKSPMV_SUMS_ACCUMULATE | SINKS)) != 0u ||
+        (flags & SINKS) == SINKS)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_label_sums (dev_sums given and 8-byte aligned, dev_labels with 1 <= n_bins <= 2^30 or dev_labels = "
+                                             "NULL with n_bins = 0, mode = TKSPMV_SUMS_RAW .. TKSPMV_SUMS_UNIT, dev_out given unless RAW, known flags, at most one sink)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    if (!dev_labels) {
+        if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_INVALID, "no labels given and none installed (call tkspmv_set_groups first)");
+        dev_labels = m.grouped.d_groups;
+        n_bins = m.grouped.n_groups;
+    }
+    if ((flags & TKSPMV_SUMS_SINK_LDS) && !m.kern.label_sums[1])
+        return fail(err, TKSPMV_ERR_INVALID, "TKSPMV_SUMS_SINK_LDS: the 16384-column tier has the direct sink only");
+    const bool lds = (flags & SINKS) ? (flags & TKSPMV_SUMS_SINK_LDS) != 0u : m.label_sums_lds_sink(n_bins);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_label_sums(dev_labels, n_bins, quantum_exp, (flags & TKSPMV_SUMS_ACCUMULATE) != 0u, lds, dev_sums, s);
+        if (mode != TKSPMV_SUMS_RAW) m.launch_sums_close(dev_sums, n_bins, quantum_exp, mode, dev_out, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::enqueue_sums_close(const int64_t *dev_sums, uint32_t n_bins, int32_t quantum_exp, int32_t mode, float *dev_out, void *stream, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_sums || (reinterpret_cast<uintptr_t>(dev_sums) & 7u) != 0u || !dev_out || n_bins < 1u || n_bins > (1u << 30) ||
+        (mode != TKSPMV_SUMS_FLOAT && mode != TKSPMV_SUMS_UNIT))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_sums_close (dev_sums given and 8-byte aligned, dev_out given, 1 <= n_bins <= 2^30, mode = "
+                                             "TKSPMV_SUMS_FLOAT or TKSPMV_SUMS_UNIT)");
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_sums_close(dev_sums, n_bins, quantum_exp, mode, dev_out, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::sums_exponent(int32_t *quantum_exp, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!quantum_exp) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to sums_exponent (output given)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    const size_t cols = m.desc.cols;
+    std::vector<uint32_t> nnz(cols), hi(cols), lo(cols);
+    if (const int st = col_stats(TKSPMV_COL_NNZ, 0, nnz.data(), err)) return st;
+    if (const int st = col_stats(TKSPMV_COL_MAX, 0, hi.data(), err)) return st;
+    if (const int st = col_stats(TKSPMV_COL_MIN, 0, lo.data(), err)) return st;
+    uint32_t max_nnz = 0u, max_abs = 0u;  // (|v| as bits: the order of the magnitudes of finite floats is the order of their bit patterns)
+    for (size_t c = 0; c < cols; ++c) {
+        if (nnz[c] == 0u) continue;  // (no counted entry: MAX / MIN hold -inf / +inf)
+        max_nnz = std::max(max_nnz, nnz[c]);
+        max_abs = std::max({max_abs, hi[c] & 0x7FFFFFFFu, lo[c] & 0x7FFFFFFFu});
+    }
+    *quantum_exp = sums_exponent_of(max_abs, max_nnz);
+    return TKSPMV_OK;
+}
+
+int Engine::label_sums(const uint32_t *host_labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *host_sums, float *host_out, std::string &err) {
+    EngineImpl &m = *impl_;
+    if ((host_labels != nullptr) != (n_bins != 0u) || n_bins > (1u << 30) || mode < TKSPMV_SUMS_RAW || mode > TKSPMV_SUMS_UNIT || (mode != TKSPMV_SUMS_RAW && !host_out))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to label_sums (host_labels with 1 <= n_bins <= 2^30 or host_labels = NULL with n_bins = 0, mode = "
+                                             "TKSPMV_SUMS_RAW .. TKSPMV_SUMS_UNIT, host_out given unless RAW)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    if (!host_labels) {
+        if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_INVALID, "no labels given and none installed (call tkspmv_set_groups first)");
+        n_bins = m.grouped.n_groups;
+    }
+    HIP_TRY(hipSetDevice(m.device));
+    EngineImpl::LabelSums &L = m.lsums;
+    const size_t rows = m.desc.rows, cols = std::max<size_t>(m.desc.cols, 1), words = (size_t)n_bins * m.desc.cols;
+    if (host_labels && !L.d_ls_labels) HIP_TRY(m.alloc(L.d_ls_labels, std::max<size_t>(rows, 1) * 4));
+    if (n_bins > L.ls_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's launches are long complete: label_sums waits itself)
+        HIP_TRY(m.grow_scratch(L.ls_cap, n_bins, {{(void **)&L.d_ls_sums, (size_t)n_bins * cols * 8}, {(void **)&L.d_ls_out, (size_t)n_bins * cols * 4}}));
+    }
+    if (host_labels && rows) HIP_TRY(hipMemcpy(L.d_ls_labels, host_labels, rows * 4, hipMemcpyHostToDevice));
+    // (UNIT leaves a bin without a norm unwritten: such a bin keeps what the caller's array holds)
+    if (mode == TKSPMV_SUMS_UNIT && words) HIP_TRY(hipMemcpy(L.d_ls_out, host_out, words * 4, hipMemcpyHostToDevice));
+    // No result is read and no result buffer written, so the engine need not be settled: the wait is for this call's own launches.
+    if (const int st = enqueue_label_sums(host_labels ? L.d_ls_labels : nullptr, host_labels ? n_bins : 0u, quantum_exp, 0u, L.d_ls_sums, mode, L.d_ls_out, nullptr, err))
+        return st;
+    HIP_TRY(hipStreamSynchronize(m.stream));
+    if (host_sums && words) HIP_TRY(hipMemcpy(host_sums, L.d_ls_sums, words * 8, hipMemcpyDeviceToHost));
+    if (mode != TKSPMV_SUMS_RAW && words) HIP_TRY(hipMemcpy(host_out, L.d_ls_out, words * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 

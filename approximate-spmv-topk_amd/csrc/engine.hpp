@@ -96,6 +96,15 @@ class Engine {
     // one pass only. assign is the host-side counterpart (engine-owned scratch, chunks of vectors, waits for its own launches).
     int enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream, std::string &err);
     int assign(const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best, std::string &err);
+    // Label sums (label_sums_kernel): per label the column sums of the local rows, as int64 multiples of 2^quantum_exp (quantise.hpp),
+    // exact and bit-identical whatever the geometry or the order of the atomics; mode FLOAT / UNIT adds the closing launch
+    // (label_sums_close_kernel), which enqueue_sums_close runs alone, e.g. over merged shard sums. sums_exponent is the default
+    // exponent, from three col_stats passes (waits); label_sums is the host-side counterpart (engine-owned scratch, waits).
+    int enqueue_label_sums(const uint32_t *dev_labels, uint32_t n_bins, int32_t quantum_exp, uint32_t flags, int64_t *dev_sums, int32_t mode, float *dev_out,
+                           void *stream, std::string &err);
+    int enqueue_sums_close(const int64_t *dev_sums, uint32_t n_bins, int32_t quantum_exp, int32_t mode, float *dev_out, void *stream, std::string &err);
+    int sums_exponent(int32_t *quantum_exp, std::string &err);
+    int label_sums(const uint32_t *host_labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *host_sums, float *host_out, std::string &err);
     // Column statistics (col_stats_kernel): one word per column and set of rows -- the number of stored entries (uint32) or the largest /
     // smallest stored value (float32) --, a set being all rows or the rows of an allow-mask; exact whatever the order of the atomics.
     // col_stats is the host-side counterpart (engine-owned scratch, waits; use_filter: among the rows of the installed mask).

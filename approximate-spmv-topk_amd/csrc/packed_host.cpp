@@ -1,4 +1,4 @@
-// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel, col_stats_kernel and assign_kernel (packed_host.hpp).
+// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel, col_stats_kernel, assign_kernel and label_sums_kernel (packed_host.hpp).
 #include "packed_host.hpp"
 
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/tkspmv.h"
+#include "quantise.hpp"
 
 namespace tkspmv {
 
@@ -227,6 +228,71 @@ int packed_col_stats(const PackedMatrix &pm, int32_t kind, const uint32_t *mask,
     uint32_t *const o = static_cast<uint32_t *>(out);
     for (uint32_t c = 0; c < pm.cols; ++c)  // key 0: -inf; then the negation of MIN undone
         o[c] = kind == TKSPMV_COL_NNZ ? acc[c] : ((acc[c] == 0u ? 0xFF800000u : key_to_float(acc[c])) ^ negate);
+    return TKSPMV_OK;
+}
+
+// label_sums_close_kernel (kernels/label_sums.hpp) restated: FLOAT's value is ldexp of the int64 rounded to fp32 (nearest even); UNIT
+// forms the 64 partials of the squares in double -- partial l: the columns l, l + 64, ... ascending --, adds them in the order 0 .. 63,
+// and scales by inv_l2_of; a bin whose weight is 0 is not written.
+void sums_close_host(const int64_t *sums, uint32_t n_bins, uint32_t cols, int32_t quantum_exp, int32_t mode, float *out) {
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        const int64_t *const s = sums + (size_t)b * cols;
+        float *const o = out + (size_t)b * cols;
+        if (mode != TKSPMV_SUMS_UNIT) {
+            for (uint32_t c = 0; c < cols; ++c) o[c] = std::ldexp((float)s[c], quantum_exp);
+            continue;
+        }
+        double part[64] = {};
+        for (uint32_t c = 0; c < cols; ++c) {
+            const double f = (double)std::ldexp((float)s[c], quantum_exp);
+            part[c & 63u] += f * f;
+        }
+        double n2 = 0.0;
+        for (int l = 0; l < 64; ++l) n2 += part[l];
+        const float w = inv_l2_of((float)n2);
+        if (w == 0.0f) continue;
+        for (uint32_t c = 0; c < cols; ++c) o[c] = std::ldexp((float)s[c], quantum_exp) * w;
+    }
+}
+
+// label_sums_kernel (kernels/label_sums.hpp) restated row by row: every row located in the stream (locate_row), the entries of its
+// run -- a placeholder has none, and padding belongs to no row -- quantised and added to the word of the row's label and their column.
+int packed_label_sums(const PackedMatrix &pm, const uint32_t *labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *sums, float *out, std::string &err) {
+    HostRowView V;
+    if (const int st = open_f32_stream(pm, "label sums are taken from", V, err); st != TKSPMV_OK) return st;
+    std::vector<uint64_t> acc((size_t)n_bins * pm.cols, 0ull);  // (unsigned: the additions wrap like the device's)
+    for (uint32_t r = 0; r < pm.rows; ++r) {
+        RowRun run{0u, 0u, 0u, 0u};
+        if (labels[r] >= n_bins || locate_entries(pm, V, r, run) == 0u) continue;
+        uint64_t *const a = acc.data() + (size_t)labels[r] * pm.cols;
+        for (uint32_t pk = run.first_pkt; pk <= run.last_pkt; ++pk) {
+            const uint32_t s0 = pk == run.first_pkt ? run.first_slot : 0u, s1 = pk == run.last_pkt ? run.last_slot : V.PE - 1u;
+            for (uint32_t ss = s0; ss <= s1; ++ss) {
+                const uint32_t c = (uint32_t)(V.word(pk, ss) >> COLW_COL_SHIFT);
+                const float v = V.value(pk, ss);
+                uint32_t bits;
+                std::memcpy(&bits, &v, 4);
+                if (c < pm.cols) a[c] += (uint64_t)quantise(bits, quantum_exp);
+            }
+        }
+    }
+    if (sums) std::memcpy(sums, acc.data(), acc.size() * 8);
+    if (mode != TKSPMV_SUMS_RAW) sums_close_host(reinterpret_cast<const int64_t *>(acc.data()), n_bins, pm.cols, quantum_exp, mode, out);
+    return TKSPMV_OK;
+}
+
+int packed_sums_exponent(const PackedMatrix &pm, int32_t *quantum_exp, std::string &err) {
+    std::vector<uint32_t> nnz(pm.cols), hi(pm.cols), lo(pm.cols);
+    if (const int st = packed_col_stats(pm, TKSPMV_COL_NNZ, nullptr, nnz.data(), err); st != TKSPMV_OK) return st;
+    if (const int st = packed_col_stats(pm, TKSPMV_COL_MAX, nullptr, hi.data(), err); st != TKSPMV_OK) return st;
+    if (const int st = packed_col_stats(pm, TKSPMV_COL_MIN, nullptr, lo.data(), err); st != TKSPMV_OK) return st;
+    uint32_t max_nnz = 0u, max_abs = 0u;  // (|v| as bits: the magnitudes of finite floats order like their bit patterns)
+    for (uint32_t c = 0; c < pm.cols; ++c) {
+        if (nnz[c] == 0u) continue;  // (no counted entry: MAX / MIN hold -inf / +inf)
+        max_nnz = std::max(max_nnz, nnz[c]);
+        max_abs = std::max({max_abs, hi[c] & 0x7FFFFFFFu, lo[c] & 0x7FFFFFFFu});
+    }
+    *quantum_exp = sums_exponent_of(max_abs, max_nnz);
     return TKSPMV_OK;
 }
 

@@ -488,6 +488,75 @@ class SpMV:
             self.set_groups(labels, n_groups=int(xs.shape[0]))
         return labels, best
 
+    def enqueue_label_sums(self, dev_labels, n_bins, exp, dev_sums, mode=_lib.SUMS_RAW, dev_out=0, flags=0, stream=0):
+        """Label sums: dev_sums[b][c] (int64, [n_bins][cols]) = the sum of quantise(v, exp) over the stored entries (r, c, v) of the
+        LOCAL rows with dev_labels[r] == b (uint32 labels; one >= n_bins has no bin; dev_labels = 0 with n_bins = 0: the labels
+        set_groups installed). Integers added with integer atomics: exact with respect to host.quantise and bit-identical whatever
+        the geometry or sharding, so the sums of shards taken with one common exp simply add up. mode _lib.SUMS_FLOAT / SUMS_UNIT
+        adds the closing launch into dev_out (float32 [n_bins][cols]): the sums as floats, or scaled to unit length -- a bin without
+        a norm is then NOT written, so dev_out holding the previous centroids keeps them: enqueue_assign followed by
+        enqueue_label_sums(SUMS_UNIT, dev_out = the vectors of the next assign) is one k-means iteration in stream order. flags:
+        _lib.SUMS_ACCUMULATE adds to what dev_sums holds; SUMS_SINK_LDS / SUMS_SINK_DIRECT force one of the kernel's sinks. No host
+        sync, no engine state touched."""
+        _lib.check(_lib.lib().tkspmv_enqueue_label_sums(self._h, ptr(dev_labels), int(n_bins), int(exp), int(flags), ptr(dev_sums), int(mode), ptr(dev_out),
+                                                        ptr(stream)))
+
+    def enqueue_sums_close(self, dev_sums, n_bins, exp, mode, dev_out, stream=0):
+        """The closing launch of enqueue_label_sums alone (mode SUMS_FLOAT or SUMS_UNIT) over int64 sums the caller holds, e.g. the
+        integer sum of the shards' sums. No host sync."""
+        _lib.check(_lib.lib().tkspmv_enqueue_sums_close(self._h, ptr(dev_sums), int(n_bins), int(exp), int(mode), ptr(dev_out), ptr(stream)))
+
+    def sums_exponent(self):
+        """The default exponent of label sums: no sum can reach 2^63 with it, and the largest values are summed exactly (from three
+        col_stats passes; waits). Shards whose sums are merged must share one exponent: the maximum of theirs."""
+        e = C.c_int32()
+        _lib.check(_lib.lib().tkspmv_sums_exponent(self._h, C.byref(e)))
+        return int(e.value)
+
+    def label_sums(self, labels=None, n_bins=None, mode=_lib.SUMS_RAW, exp=None, out=None):
+        """enqueue_label_sums with host arrays: (sums int64[n_bins, cols], floats float32[n_bins, cols] or None with SUMS_RAW).
+        labels = None: the labels and bin count set_groups (or assign(install=True)) installed; exp = None: sums_exponent(). out:
+        with SUMS_UNIT the rows that bins without a norm keep (zeros without it). Waits."""
+        if labels is None:
+            lab, n_bins = None, int(getattr(self, "_n_groups", 0) if n_bins is None else n_bins)
+        else:
+            lab = np.ascontiguousarray(labels, dtype=np.uint32).ravel()
+            if lab.shape != (self.num_rows,):
+                raise ValueError(f"labels must have shape ({self.num_rows},)")
+            n_bins = int(lab.max()) + 1 if n_bins is None and lab.size else int(n_bins or 1)
+            lab = lab if lab.size else np.zeros(1, dtype=np.uint32)
+        exp = self.sums_exponent() if exp is None else int(exp)
+        cols = self.num_cols
+        sums = np.zeros((max(n_bins, 1), max(cols, 1)), dtype=np.int64)
+        res = None
+        if int(mode) != _lib.SUMS_RAW:
+            res = np.zeros((n_bins, cols), dtype=np.float32) if out is None else np.array(out, dtype=np.float32).reshape(n_bins, cols)
+        _lib.check(_lib.lib().tkspmv_label_sums(self._h, u32p(lab), 0 if lab is None else n_bins, exp, int(mode), _lib.i64p(sums), f32p(res)))
+        return sums.reshape(-1)[:n_bins * cols].reshape(n_bins, cols), res
+
+    def kmeans(self, cent, iters):
+        """Spherical k-means on the device: `iters` times enqueue_assign against the centroids, then enqueue_label_sums(SUMS_UNIT)
+        into the centroid buffer itself -- a cluster that ends empty keeps its vector --, then one final assignment; the centroids
+        never visit the host in between. cent: float32[count, cols] start vectors. Returns (cent float32[count, cols], labels
+        uint32[rows], best float32[rows]): the final centroids and every row's assignment to them. Waits."""
+        import torch
+        xs = np.ascontiguousarray(cent, dtype=np.float32)
+        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
+            raise ValueError(f"centroids must be [count >= 1, {self.num_cols}]")
+        count, exp = int(xs.shape[0]), self.sums_exponent()
+        dev = torch.device("cuda", int(self.info()["device"]))
+        d_xs = torch.from_numpy(xs).to(dev)
+        d_lab = torch.zeros(max(self.num_rows, 1), dtype=torch.int32, device=dev)
+        d_best = torch.zeros(max(self.num_rows, 1), dtype=torch.float32, device=dev)
+        d_sums = torch.zeros(count * max(self.num_cols, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        for it in range(int(iters) + 1):
+            self.enqueue_assign(d_xs.data_ptr(), count, d_lab.data_ptr(), d_best.data_ptr())
+            if it < int(iters):
+                self.enqueue_label_sums(d_lab.data_ptr(), count, exp, d_sums.data_ptr(), _lib.SUMS_UNIT, d_xs.data_ptr())
+        self.synchronize()
+        return d_xs.cpu().numpy(), d_lab.cpu().numpy().view(np.uint32)[:self.num_rows], d_best.cpu().numpy()[:self.num_rows]
+
     def enqueue_col_stats(self, kind, out, masks=None, mask_stride=0, out_stride=0, stream=None, count=1):
         """Column statistics: one 4-byte word per column and set of rows into device memory at `out` -- kind = _lib.COL_NNZ (uint32:
         the stored entries of the column; explicit zeros and a column repeated within a row count), COL_MAX / COL_MIN (float32: the
@@ -682,6 +751,14 @@ def assign_spmv(m, vecs, **kw):
     kw.setdefault("k", 8)
     with _one_shot(m, **kw) as e:
         return e.assign(vecs)
+
+
+def kmeans_spmv(m, cent, iters, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (cent, labels, best) of SpMV.kmeans(cent, iters): spherical
+    k-means whose assignment and centroid update both run on the device."""
+    kw.setdefault("k", 8)
+    with _one_shot(m, **kw) as e:
+        return e.kmeans(cent, iters)
 
 
 def knn_graph(m, k, rows=None, **kw):

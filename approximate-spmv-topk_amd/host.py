@@ -384,6 +384,81 @@ def col_stats(m, kind, allow=None):
     return bits.astype(np.uint32).view(np.float32)
 
 
+def quantise(values, exp):
+    """quantise(v, E) of label sums (SpMV.enqueue_label_sums) restated in numpy integers: float32 values as int64 multiples of
+    2^exp. |v| = m * 2^x with m the 24-bit significand (a subnormal: no hidden bit, x = -149); s = x - exp; s >= 0: m << s;
+    s < 0: m >> -s rounded to nearest, ties to even on the magnitude (a shift of 64 or more gives 0); the sign of v. Defined
+    for finite values with s <= 38."""
+    bits = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    e = (bits >> np.uint64(23)) & np.uint64(0xFF)
+    m = (bits & np.uint64(0x7FFFFF)) | np.where(e != 0, np.uint64(0x800000), np.uint64(0))
+    s = np.where(e != 0, e.astype(np.int64) - 150, np.int64(-149)) - np.int64(int(exp))
+    left = m << np.clip(s, 0, 39).astype(np.uint64)
+    t = np.clip(-s, 1, 63).astype(np.uint64)
+    q = m >> t
+    rem, half = m & ((np.uint64(1) << t) - np.uint64(1)), np.uint64(1) << (t - np.uint64(1))
+    q = q + ((rem > half) | ((rem == half) & ((q & np.uint64(1)) != 0))).astype(np.uint64)
+    mag = np.where(s >= 0, left, q).astype(np.int64)
+    return np.where((bits >> np.uint64(31)) != 0, -mag, mag)
+
+
+def sums_exponent(m):
+    """The default exponent of label sums for CooMatrix m (SpMV.sums_exponent): xmax + 1 + ceil_log2(max(1, the fullest column's
+    entries)) - 62 with xmax the unbiased exponent of the largest |value| (-126 for a subnormal or zero); 0 without entries. No
+    sum can reach 2^63 with it."""
+    v = np.ascontiguousarray(m.val, dtype=np.float32).ravel()
+    if v.size == 0:
+        return 0
+    e = int(np.max(v.view(np.uint32) & np.uint32(0x7FFFFFFF))) >> 23
+    n = int(np.max(np.bincount(np.asarray(m.col).astype(np.int64).ravel())))
+    return (e - 127 if e else -126) + 1 + (n - 1).bit_length() - 62
+
+
+def label_sums(m, labels, n_bins, exp):
+    """The contract of label sums (SpMV.enqueue_label_sums) restated in numpy from the COO alone, for CPU-side users and as the
+    tests' expectation: int64 sums[n_bins, cols], sums[b, c] = the sum of quantise(v, exp) over the entries (r, c, v) of CooMatrix
+    m with labels[r] == b. Every stored entry counts (explicit zeros, a column repeated within a row); a label >= n_bins has no
+    bin."""
+    n_bins, cols = int(n_bins), int(m.cols)
+    lab = np.asarray(labels).astype(np.int64).ravel()
+    if lab.shape != (int(m.rows),):
+        raise ValueError(f"labels must have shape ({int(m.rows)},)")
+    r = np.asarray(m.row).astype(np.int64).ravel()
+    c = np.asarray(m.col).astype(np.int64).ravel()
+    q = quantise(np.ascontiguousarray(m.val, dtype=np.float32).ravel(), exp)
+    keep = lab[r] < n_bins
+    sums = np.zeros(n_bins * cols, dtype=np.int64)
+    np.add.at(sums, lab[r][keep] * cols + c[keep], q[keep])
+    return sums.reshape(n_bins, cols)
+
+
+def close_sums(sums, exp, mode, out=None):
+    """The closing rules of label sums (SpMV.enqueue_sums_close) restated in numpy: from int64 sums[n_bins, cols] float32
+    [n_bins, cols]. mode _lib.SUMS_FLOAT: ldexp(float32(sums), exp), the conversion rounding to nearest even. SUMS_UNIT: those
+    values times inv_l2(float32(n2)), n2 the float64 sum of their squares taken as 64 partials (partial l: the columns l, l + 64,
+    ... ascending) added in the order 0 .. 63; a bin whose weight is 0 keeps its row of `out` (zeros without one)."""
+    s = np.ascontiguousarray(sums, dtype=np.int64)
+    if s.ndim != 2 or int(mode) not in (_lib.SUMS_FLOAT, _lib.SUMS_UNIT):
+        raise ValueError("sums must be [n_bins, cols] and mode SUMS_FLOAT or SUMS_UNIT")
+    with np.errstate(over="ignore", under="ignore"):
+        f = np.ldexp(s.astype(np.float32), np.int32(int(exp))).astype(np.float32)
+    if int(mode) == _lib.SUMS_FLOAT:
+        return f
+    res = np.zeros_like(f) if out is None else np.array(out, dtype=np.float32).reshape(f.shape)
+    sq = np.zeros((s.shape[0], (s.shape[1] + 63) // 64 * 64), dtype=np.float64)
+    sq[:, :s.shape[1]] = f.astype(np.float64) ** 2
+    part = np.zeros((s.shape[0], 64), dtype=np.float64)
+    for k in range(sq.shape[1] // 64):
+        part += sq[:, 64 * k:64 * k + 64]
+    n2 = np.zeros(s.shape[0], dtype=np.float64)
+    for lane in range(64):
+        n2 += part[:, lane]
+    with np.errstate(over="ignore"):
+        w = inv_l2(n2.astype(np.float32))
+    res[w != 0] = (f * w[:, None])[w != 0]
+    return res
+
+
 def idf_weights(df, n_rows, scheme="bm25"):
     """Inverse document frequency weights from document frequencies df[cols] (col_stats(COL_NNZ) of a matrix without repeated
     columns) and the number of rows n: scheme "bm25" is log(1 + (n - df + 0.5) / (df + 0.5)), "smooth" is log((1 + n) / (1 + df)) + 1;
@@ -610,6 +685,30 @@ class Packed:
         best = np.empty(max(rows, 1), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_packed_assign(self._h, _lib.f32p(xs), int(xs.shape[0]), _lib.u32p(labels), _lib.f32p(best)))
         return labels[:rows], best[:rows]
+
+    def label_sums(self, labels, n_bins, exp, mode=_lib.SUMS_RAW, out=None):
+        """(sums int64[n_bins, cols], floats float32[n_bins, cols] or None): the label sums of the packed matrix with the bits an
+        engine created from it reports (SpMV.label_sums): every row located in the stream, quantise(v, exp) of its entries added
+        to the word of labels[row] and their column; mode SUMS_FLOAT / SUMS_UNIT adds the closing rule (UNIT: a bin whose norm is
+        0 or overflows keeps its row of `out`, zeros without one). fp32 values only (TkspmvError ERR_UNSUPPORTED otherwise)."""
+        rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).ravel()
+        if lab.shape != (rows,):
+            raise ValueError(f"labels must have shape ({rows},)")
+        lab = lab if rows else np.zeros(1, dtype=np.uint32)
+        n_bins = int(n_bins)
+        sums = np.zeros((max(n_bins, 1), max(cols, 1)), dtype=np.int64)
+        res = None
+        if int(mode) != _lib.SUMS_RAW:
+            res = np.zeros((n_bins, cols), dtype=np.float32) if out is None else np.array(out, dtype=np.float32).reshape(n_bins, cols)
+        _lib.check(_lib.lib().tkspmv_packed_label_sums(self._h, _lib.u32p(lab), n_bins, int(exp), int(mode), _lib.i64p(sums), _lib.f32p(res)))
+        return sums.reshape(-1)[:n_bins * cols].reshape(n_bins, cols), res
+
+    def sums_exponent(self):
+        """The default exponent of label sums (SpMV.sums_exponent) from the packed matrix's own column statistics."""
+        e = C.c_int32()
+        _lib.check(_lib.lib().tkspmv_packed_sums_exponent(self._h, C.byref(e)))
+        return int(e.value)
 
     def col_stats(self, kind, allow=None):
         """uint32[cols] (kind _lib.COL_NNZ) or float32[cols] (COL_MAX, COL_MIN): one statistic of every column over all rows, or over

@@ -561,6 +561,72 @@ int tkspmv_enqueue_assign(tkspmv_t *e, const float *dev_xs, int32_t count, uint3
 /* The same with host arrays, any count with or without host_best: on engine-owned scratch (rows labels, rows scores, and the vectors
  * in chunks of at most 64 MiB), allocated by the first call, on the engine's stream; waits for its own launches only. */
 int tkspmv_assign(tkspmv_t *e, const float *host_xs, int32_t count, uint32_t *host_labels /* [rows] */, float *host_best /* [rows], may be NULL */);
+/* Label sums ("what does every cluster, class or topic look like?": the centroid update of (spherical) k-means -- the second half of
+ * an iteration whose first half is tkspmv_enqueue_assign --, class prototypes for nearest-centroid classification, topic or shard
+ * profiles; with one label the column sums of the matrix, or of a tkspmv_enqueue_match result turned into labels): np.add.at over the
+ * COO keyed by (labels[row], col), without a COO and without leaving the device.
+ * labels[r] (uint32, by LOCAL row, indexed like masks and group labels) names the bin of row r; a label >= n_bins has no bin, as in
+ * tkspmv_enqueue_facets. dev_labels = NULL with n_bins = 0 takes the labels and the bin count installed by tkspmv_set_groups.
+ *   sums[b][c] (int64, [n_bins][cols]) = the sum of quantise(v, E) over the COUNTED entries (r, c, v) with labels[r] == b
+ * "Counted" is tkspmv_enqueue_col_stats' rule: every stored entry except the placeholder of an empty row and the padding behind a
+ * partition's last row end; explicit zeros and a column repeated within a row each contribute.
+ * quantise(v, E), E = quantum_exp, is integer arithmetic on the fp32 bit pattern (one function compiled for host and device):
+ *   |v| = m * 2^x, m the 24-bit significand (a subnormal: no hidden bit, x = -149);  s = x - E;
+ *   s >= 0: q = m << s;   s < 0: q = m >> -s, rounded to nearest with ties to even on the magnitude (a shift of 64 or more gives 0);
+ *   the result takes the sign of v, so quantise(-v) = -quantise(v).
+ * No floating-point instruction takes part. Defined for finite values with s <= 38; Inf, NaN and larger shifts leave the affected
+ * words unspecified. The sums are integers added with integer atomics, so they are exact with respect to this rule and bit-identical
+ * whatever the launch geometry, the partition cuts, the order of the atomics or the sharding: the int64 sums of the shards of a split
+ * matrix, taken with ONE common E (the largest of the shards' tkspmv_sums_exponent), add up to the sums of the whole matrix -- an
+ * integer all-reduce -- and tkspmv_enqueue_sums_close finishes the merged words. |ldexp(sums[b][c], E) - the exact sum| is at most
+ * half a quantum per counted entry of the word.
+ * mode: TKSPMV_SUMS_RAW writes dev_sums only; TKSPMV_SUMS_FLOAT and _UNIT add the closing launch into dev_out (float32,
+ * [n_bins][cols], required):
+ *   FLOAT  out[b][c] = ldexpf((float)sums[b][c], E), the int64 -> fp32 conversion rounding to nearest even; exactly n_bins * cols
+ *          floats are written.
+ *   UNIT   f_c = FLOAT's value; n2 = the sum over c of (double)f_c * (double)f_c, formed as 64 partials -- partial l takes the columns
+ *          l, l + 64, ... ascending -- added in the order 0 .. 63; w = 1 / sqrt((float)n2) in two rounded fp32 operations, 0 where
+ *          (float)n2 is 0 or not finite (tkspmv_enqueue_row_stats' TKSPMV_ROW_INV_L2 rule); out[b][c] = f_c * w. A bin with w == 0 --
+ *          an empty cluster, a zero sum, an overflowed norm -- is NOT written: dev_out holding the previous centroids keeps them.
+ * So tkspmv_enqueue_assign followed by tkspmv_enqueue_label_sums(UNIT, dev_out = the vectors of the next assign) is one iteration of
+ * spherical k-means in stream order, with no host round trip.
+ * flags: TKSPMV_SUMS_ACCUMULATE adds to what dev_sums holds instead of zeroing it in front (on the same stream): the shards of a
+ * matrix, or its row blocks, into one buffer. TKSPMV_SUMS_SINK_LDS / _DIRECT force one of the kernel's two sinks -- bins in LDS
+ * flushed per workgroup, 8192 / T bins per launch (T the column tier: 8 at 1024 columns, 2 at 4096, none at 16384), or one global
+ * atomic per entry in one launch for any n_bins --, which the engine otherwise chooses by n_bins; the sums are the same bits
+ * (label_sums_kernel). For tests and measurements.
+ * Asynchronous, complete in stream order on any stream (NULL: the engine's); reads and writes no engine state, so it may be mixed
+ * freely with the other calls. desc.min_score, the installed filter, the installed query and the boost play no part. With desc.rows =
+ * 0 the call succeeds and leaves zeros. fp32 packet streams only.
+ * Errors: TKSPMV_ERR_INVALID (checked first, before any device call) for a NULL engine, NULL or misaligned dev_sums, dev_labels
+ * without n_bins or n_bins without dev_labels, n_bins > 2^30, an unknown mode or flag, both sink flags, or dev_out = NULL unless
+ * RAW; then TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_row_stats reports it (the approximate per-partition engines and
+ * engines made from a .tkspmv file ARE served); then TKSPMV_ERR_INVALID for dev_labels = NULL with no labels installed, or
+ * TKSPMV_SUMS_SINK_LDS at the 16384-column tier. A rejected call writes nothing. */
+#define TKSPMV_SUMS_RAW 0
+#define TKSPMV_SUMS_FLOAT 1
+#define TKSPMV_SUMS_UNIT 2
+#define TKSPMV_SUMS_ACCUMULATE 1u
+#define TKSPMV_SUMS_SINK_LDS 2u
+#define TKSPMV_SUMS_SINK_DIRECT 4u
+int tkspmv_enqueue_label_sums(tkspmv_t *e, const uint32_t *dev_labels /* [rows], may be NULL */, uint32_t n_bins, int32_t quantum_exp, uint32_t flags,
+                              int64_t *dev_sums /* [n_bins][cols] */, int32_t mode, float *dev_out /* [n_bins][cols], may be NULL with RAW */, void *stream);
+/* The closing launch alone (mode TKSPMV_SUMS_FLOAT or _UNIT, as above) over int64 sums the caller holds: merged shard sums, or sums
+ * kept from a RAW call. Asynchronous, any stream, no engine state. TKSPMV_ERR_INVALID for a NULL engine, NULL or misaligned dev_sums,
+ * NULL dev_out, n_bins outside 1 .. 2^30 or another mode. */
+int tkspmv_enqueue_sums_close(tkspmv_t *e, const int64_t *dev_sums /* [n_bins][cols] */, uint32_t n_bins, int32_t quantum_exp, int32_t mode,
+                              float *dev_out /* [n_bins][cols] */, void *stream);
+/* The default exponent: E = xmax + 1 + ceil_log2(max(1, the fullest column's counted entries)) - 62, xmax the unbiased exponent of
+ * the largest stored |v| (-126 for a subnormal or zero), from three tkspmv_col_stats passes (TKSPMV_COL_NNZ, _MAX, _MIN): with it no
+ * sum can reach 2^63 whatever the labels, and at 1M x 1024 with 20 entries per row every value within 2^-13 of the largest is summed
+ * exactly. A matrix without entries gives 0. A host form: waits. Shards whose sums are to be merged must use ONE common E: take the
+ * maximum of theirs. Errors: TKSPMV_ERR_INVALID for a NULL argument; TKSPMV_ERR_UNSUPPORTED where tkspmv_col_stats reports it. */
+int tkspmv_sums_exponent(tkspmv_t *e, int32_t *quantum_exp);
+/* tkspmv_enqueue_label_sums with host arrays (host_labels = NULL with n_bins = 0: the installed labels): on engine-owned scratch
+ * (rows labels, n_bins * cols sums and floats), allocated by the first call, on the engine's stream; waits for its own launches only.
+ * Either output may be NULL (host_out only with RAW). With UNIT host_out is read first: a bin that is not written keeps its values. */
+int tkspmv_label_sums(tkspmv_t *e, const uint32_t *host_labels /* [rows], may be NULL */, uint32_t n_bins, int32_t quantum_exp, int32_t mode,
+                      int64_t *host_sums /* [n_bins][cols], may be NULL */, float *host_out /* [n_bins][cols], may be NULL with RAW */);
 /* Column statistics ("how many rows carry this term, how large do its values get?": what IDF / BM25 query weights, score upper
  * bounds -- the sum over c of max(0, x[c] * max[c], x[c] * min[c]) bounds every row's score -- and significant-terms counts are made
  * of), taken from the matrix the engine already holds: np.bincount(col) without a COO, and in ONE pass what tkspmv_enqueue_match
@@ -822,6 +888,19 @@ int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out /* 
  * row without entries gets label 0 and +0.0f. No GPU needed. TKSPMV_ERR_INVALID for a NULL matrix, NULL xs, NULL labels or
  * count < 1, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
 int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels /* [rows] */, float *best /* [rows], may be NULL */);
+/* The label sums of a packed matrix (tkspmv_enqueue_label_sums' contract, with the bits an engine created from this packed matrix
+ * reports): every row located in the stream and its entries' quantise(v, E) added to sums[labels[r]][c], then the closing rule of
+ * `mode` into out (UNIT: a bin whose w is 0 is not written and keeps what out holds). sums may be NULL; out only with
+ * TKSPMV_SUMS_RAW. No GPU needed. TKSPMV_ERR_INVALID for a NULL matrix, NULL labels, n_bins outside 1 .. 2^30, an unknown mode or
+ * out = NULL unless RAW; TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
+int tkspmv_packed_label_sums(const tkspmv_packed *p, const uint32_t *labels /* [rows] */, uint32_t n_bins, int32_t quantum_exp, int32_t mode,
+                             int64_t *sums /* [n_bins][cols], may be NULL */, float *out /* [n_bins][cols], may be NULL with RAW */);
+/* tkspmv_sums_exponent of a packed matrix, from tkspmv_packed_col_stats' three statistics. The closing rule alone over int64 sums
+ * (tkspmv_enqueue_sums_close on the host; UNIT: see above) is tkspmv_packed_label_sums' second half and needs no matrix: cols is given. */
+int tkspmv_packed_sums_exponent(const tkspmv_packed *p, int32_t *quantum_exp);
+int tkspmv_sums_close_host(const int64_t *sums /* [n_bins][cols] */, uint32_t n_bins, uint32_t cols, int32_t quantum_exp, int32_t mode, float *out /* [n_bins][cols] */);
+/* quantise(v, E) of the value with the fp32 bit pattern value_bits: the function the kernel and the host twin share. */
+int64_t tkspmv_quantise(uint32_t value_bits, int32_t quantum_exp);
 /* One column statistic (TKSPMV_COL_NNZ .. TKSPMV_COL_MIN) of a packed matrix over all rows (mask = NULL) or the rows of an allow-mask
  * of ceil(rows / 32) words: out[c], cols words, with the bits an engine created from this packed matrix reports
  * (tkspmv_enqueue_col_stats): a plain walk over the packet stream, so it works on a loaded .tkspmv file with no COO. No GPU needed.
