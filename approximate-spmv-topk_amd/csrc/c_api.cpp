@@ -200,6 +200,12 @@ int tkspmv_sums_exponent(tkspmv_t *h, int32_t *quantum_exp) { ENGINE_CALL(sums_e
 int tkspmv_label_sums(tkspmv_t *h, const uint32_t *host_labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *host_sums, float *host_out) {
     ENGINE_CALL(label_sums(host_labels, n_bins, quantum_exp, mode, host_sums, host_out, err))
 }
+int tkspmv_enqueue_nearest(tkspmv_t *h, const float *dev_xs, int32_t count, int32_t n, const uint32_t *dev_mask, uint32_t *dev_labels, float *dev_scores, void *stream) {
+    ENGINE_CALL(enqueue_nearest(dev_xs, count, n, dev_mask, dev_labels, dev_scores, stream, err))
+}
+int tkspmv_nearest(tkspmv_t *h, const float *host_xs, int32_t count, int32_t n, int32_t use_filter, uint32_t *host_labels, float *host_scores) {
+    ENGINE_CALL(nearest(host_xs, count, n, use_filter, host_labels, host_scores, err))
+}
 int tkspmv_enqueue_col_stats(tkspmv_t *h, int32_t kind, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, void *dev_out, int64_t out_stride_words,
                              void *stream) {
     ENGINE_CALL(enqueue_col_stats(kind, count, dev_mask, mask_stride_words, dev_out, out_stride_words, stream, err))
@@ -474,6 +480,11 @@ int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out) {
 }
 int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels, float *best) {
     PACKED_CALL(p && xs && labels && count >= 1, "bad arguments (packed matrix, vectors and labels given, count >= 1)", packed_assign(p->pm, xs, count, labels, best, err))
+}
+int tkspmv_packed_nearest(const tkspmv_packed *p, const float *xs, int32_t count, int32_t n, const uint32_t *mask, uint32_t *labels, float *scores) {
+    PACKED_CALL(p && xs && labels && scores && count >= 1 && n >= 1 && n <= TKSPMV_NEAREST_MAX_N,
+                "bad arguments (packed matrix, vectors, labels and scores given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N)",
+                packed_nearest(p->pm, xs, count, n, mask, labels, scores, err))
 }
 int tkspmv_packed_label_sums(const tkspmv_packed *p, const uint32_t *labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *sums, float *out) {
     PACKED_CALL(p && labels && n_bins >= 1u && n_bins <= (1u << 30) && mode >= TKSPMV_SUMS_RAW && mode <= TKSPMV_SUMS_UNIT && (mode == TKSPMV_SUMS_RAW || out),

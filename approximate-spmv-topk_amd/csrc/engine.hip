@@ -55,6 +55,7 @@
 #include "kernels/score_rows.hpp"
 #include "kernels/row_stats.hpp"
 #include "kernels/assign.hpp"
+#include "kernels/nearest.hpp"
 #include "kernels/col_stats.hpp"
 #include "kernels/label_sums.hpp"
 #include "kernels/group_select.hpp"
@@ -116,6 +117,7 @@ typedef void (*score_rows_fn)(const ScoreRowsParams);
 typedef void (*row_stats_fn)(const StreamParams, const RowStatsParams);
 typedef void (*col_stats_fn)(const StreamParams, const ColStatsParams);
 typedef void (*assign_fn)(const StreamParams, const AssignParams);
+typedef void (*nearest_fn)(const StreamParams, const NearestParams);
 typedef void (*label_sums_fn)(const StreamParams, const LabelSumsParams);
 typedef void (*batch_fn)(const BatchArgs);
 typedef void (*single_fn)(const StreamParams, const SelectParams, const LocalParams);
@@ -131,6 +133,7 @@ struct Kernels {
     row_stats_fn row_stats[4] = {};      // [kind: TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2] (no x at all: likewise)
     col_stats_fn col_stats[2][2] = {};   // [EXT: TKSPMV_COL_MAX / _MIN][FILT]
     assign_fn assign = nullptr;          // (16384 / XCOLS vectors in LDS per pass)
+    nearest_fn nearest[3] = {};          // [lists of 1, 2, 4 entries] (the same vectors per pass)
     label_sums_fn label_sums[2] = {};    // [LDS_SINK]; [1] NULL at the 16384-column tier (8192 / XCOLS bins in LDS per launch)
     batch_fn batch[2] = {};    // [LOCAL: the kernel of the checked local thresholds]; the tracing twins likewise
     single_fn single = nullptr;
@@ -166,6 +169,9 @@ static Kernels kernels_of(bool dbg) {
         K.row_stats[TKSPMV_ROW_L2SQ] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_L2SQ>;
         K.row_stats[TKSPMV_ROW_INV_L2] = &row_stats_kernel<C, QM == QM_F32C12, ROW_STAT_INV_L2>;
         K.assign = &assign_kernel<C, XCOLS, QM>;
+        K.nearest[0] = &nearest_kernel<C, XCOLS, QM, 1>;
+        K.nearest[1] = &nearest_kernel<C, XCOLS, QM, 2>;
+        K.nearest[2] = &nearest_kernel<C, XCOLS, QM, 4>;
         K.col_stats[0][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, false>;
         K.col_stats[0][1] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, false, true>;
         K.col_stats[1][0] = &col_stats_kernel<C, XCOLS, QM == QM_F32C12, true, false>;
@@ -525,6 +531,15 @@ struct EngineImpl {
         float *d_as_xs = nullptr;         // [as_cap][cols]
         uint32_t as_cap = 0;              // vectors the scratch holds
     } assign;
+
+    // Nearest-n assignment (tkspmv_enqueue_nearest; nearest_fill_kernel, nearest_kernel) likewise. The scratch of tkspmv_nearest, which
+    // allocates it on its first call: rows * TKSPMV_NEAREST_MAX_N labels and scores, and a chunk of vectors like tkspmv_assign's.
+    struct Nearest {
+        uint32_t *d_nn_labels = nullptr;  // [rows][n], n <= TKSPMV_NEAREST_MAX_N
+        float *d_nn_scores = nullptr;     // [rows][n]
+        float *d_nn_xs = nullptr;         // [nn_cap][cols]
+        uint32_t nn_cap = 0;              // vectors the scratch holds
+    } nearest;
 
     // Label sums (tkspmv_enqueue_label_sums, label_sums_kernel) likewise. The scratch of tkspmv_label_sums, which allocates it on its
     // first call: rows labels, and n_bins * cols sums and floats, which grow to the largest n_bins asked for.
@@ -1156,6 +1171,29 @@ struct EngineImpl {
         for (int i = 0; i < n; i += qp) {
             const AssignParams R{mat.d_packets, xs + (size_t)i * desc.cols, labels, best, desc.rows, (uint32_t)std::min(qp, n - i), q_base + (uint32_t)i};
             hipLaunchKernelGGL(kern.assign, dim3(grid), dim3(512), 0, s, P, R);
+        }
+    }
+    // The n best of the call's `total` vectors for every local row, in order, for the vectors xs[0 .. cnt), which are the vectors
+    // q_base .. q_base + cnt of their call, complete in stream order when this returns. q_base = 0: nearest_fill_kernel writes every
+    // row's default list in front (what the two memsets are to launch_assign: rows without entries and rows outside the mask are never
+    // written by the streaming kernel) and the first launch stores its lists as they are; every later launch -- of this call or,
+    // q_base != 0, of the call's later chunks -- merges with the stored list. One pass over stream copy 0 per assign_pass() vectors,
+    // with the scan kernels' geometry. A loop of its own beside launch_assign's, and no launch_scan call for the same reason. No
+    // engine state is read or written besides the matrix.
+    void launch_nearest(const float *xs, int cnt, uint32_t q_base, uint32_t total, uint32_t n, const uint32_t *mask, uint32_t *labels, float *scores,
+                        hipStream_t s) const {
+        if (desc.rows == 0u) return;
+        if (q_base == 0u) {
+            const uint64_t words = (uint64_t)desc.rows * n;
+            const uint32_t fill_grid = (uint32_t)std::min<uint64_t>((words + 255u) / 256u, (uint64_t)std::max(1u, info.num_cus) * 32u);
+            hipLaunchKernelGGL(nearest_fill_kernel, dim3(fill_grid), dim3(256), 0, s, mask, labels, scores, desc.rows, n, total);
+        }
+        if (pm.n_packets == 0u) return;
+        const StreamParams P = stream_params(nullptr);
+        const int qp = assign_pass();
+        for (int i = 0; i < cnt; i += qp) {
+            const NearestParams R{mat.d_packets, xs + (size_t)i * desc.cols, mask, labels, scores, desc.rows, n, (uint32_t)std::min(qp, cnt - i), q_base + (uint32_t)i};
+            hipLaunchKernelGGL(kern.nearest[(n > 1u) + (n > 2u)], dim3(grid), dim3(512), 0, s, P, R);
         }
     }
     // Why column statistics are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask). Served where
@@ -3239,6 +3277,50 @@ int Engine::assign(const float *host_xs, int32_t count, uint32_t *host_labels, f
     }
     HIP_TRY(hipMemcpy(host_labels, A.d_as_labels, rows * 4, hipMemcpyDeviceToHost));
     if (host_best) HIP_TRY(hipMemcpy(host_best, A.d_as_best, rows * 4, hipMemcpyDeviceToHost));
+    return TKSPMV_OK;
+}
+
+int Engine::enqueue_nearest(const float *dev_xs, int32_t count, int32_t n, const uint32_t *dev_mask, uint32_t *dev_labels, float *dev_scores, void *stream,
+                            std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!dev_xs || !dev_labels || !dev_scores || count < 1 || n < 1 || n > TKSPMV_NEAREST_MAX_N)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_nearest (vectors, labels and scores given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
+    if (const char *why = m.col_stats_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment under an allow-mask: ") + why);
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
+        m.launch_nearest(dev_xs, count, 0u, (uint32_t)count, (uint32_t)n, dev_mask, dev_labels, dev_scores, s);
+        return TKSPMV_OK;
+    });
+}
+
+int Engine::nearest(const float *host_xs, int32_t count, int32_t n, int32_t use_filter, uint32_t *host_labels, float *host_scores, std::string &err) {
+    EngineImpl &m = *impl_;
+    if (!host_xs || !host_labels || count < 1 || n < 1 || n > TKSPMV_NEAREST_MAX_N)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to nearest (vectors and labels given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N)");
+    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
+    if (const char *why = m.col_stats_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment under an allow-mask: ") + why);
+    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_STATE, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    if (m.desc.rows == 0u) return TKSPMV_OK;
+    HIP_TRY(hipSetDevice(m.device));
+    EngineImpl::Nearest &A = m.nearest;
+    const size_t cols = m.desc.cols, rows = m.desc.rows;
+    if (!A.d_nn_labels) HIP_TRY(m.alloc(A.d_nn_labels, rows * TKSPMV_NEAREST_MAX_N * 4));
+    if (!A.d_nn_scores) HIP_TRY(m.alloc(A.d_nn_scores, rows * TKSPMV_NEAREST_MAX_N * 4));
+    const uint32_t want = (uint32_t)std::min<size_t>((size_t)count, std::max<size_t>(1, EngineImpl::Assign::ASSIGN_MAX_BYTES / (std::max<size_t>(cols, 1) * 4)));
+    if (want > A.nn_cap) {
+        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: nearest waits itself)
+        HIP_TRY(m.grow_scratch(A.nn_cap, want, {{(void **)&A.d_nn_xs, (size_t)want * std::max<size_t>(cols, 1) * 4}}));
+    }
+    // chunks of vectors as in assign: up, the chunk's launches, wait. The waits are for this call's own launches.
+    for (int32_t q0 = 0; q0 < count; q0 += (int32_t)A.nn_cap) {
+        const int32_t qc = std::min<int32_t>((int32_t)A.nn_cap, count - q0);
+        HIP_TRY(hipMemcpy(A.d_nn_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
+        m.launch_nearest(A.d_nn_xs, qc, (uint32_t)q0, (uint32_t)count, (uint32_t)n, use_filter ? m.filter.d_filter : nullptr, A.d_nn_labels, A.d_nn_scores, m.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m.stream));
+    }
+    HIP_TRY(hipMemcpy(host_labels, A.d_nn_labels, rows * (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (host_scores) HIP_TRY(hipMemcpy(host_scores, A.d_nn_scores, rows * (size_t)n * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 

@@ -96,6 +96,12 @@ class Engine {
     // one pass only. assign is the host-side counterpart (engine-owned scratch, chunks of vectors, waits for its own launches).
     int enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream, std::string &err);
     int assign(const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best, std::string &err);
+    // Nearest-n assignment (nearest_fill_kernel, nearest_kernel): for every local row its n best-scoring of `count` vectors in order
+    // (score descending, ties by index ascending), labels[rows][n] and scores[rows][n]; dev_mask, if given, restricts the rows
+    // (one bit per local row; the others get TKSPMV_NEAREST_NONE and -inf throughout). nearest is the host-side counterpart
+    // (engine-owned scratch, chunks of vectors, waits for its own launches; use_filter: among the rows of the installed mask).
+    int enqueue_nearest(const float *dev_xs, int32_t count, int32_t n, const uint32_t *dev_mask, uint32_t *dev_labels, float *dev_scores, void *stream, std::string &err);
+    int nearest(const float *host_xs, int32_t count, int32_t n, int32_t use_filter, uint32_t *host_labels, float *host_scores, std::string &err);
     // Label sums (label_sums_kernel): per label the column sums of the local rows, as int64 multiples of 2^quantum_exp (quantise.hpp),
     // exact and bit-identical whatever the geometry or the order of the atomics; mode FLOAT / UNIT adds the closing launch
     // (label_sums_close_kernel), which enqueue_sums_close runs alone, e.g. over merged shard sums. sums_exponent is the default

@@ -1,4 +1,4 @@
-// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel, col_stats_kernel, assign_kernel and label_sums_kernel (packed_host.hpp).
+// packed_host.cpp -- the host twins of row_vectors_kernel, score_rows_kernel, row_stats_kernel, col_stats_kernel, assign_kernel, nearest_kernel and label_sums_kernel (packed_host.hpp).
 #include "packed_host.hpp"
 
 #include <algorithm>
@@ -183,6 +183,41 @@ int packed_assign(const PackedMatrix &pm, const float *xs, int32_t count, uint32
         }
         labels[r] = label;
         if (best) best[r] = b;
+    }
+    return TKSPMV_OK;
+}
+
+// nearest_kernel (kernels/nearest.hpp) restated row by row: the row's score against every vector in turn -- packed_score_rows' value --,
+// each placed behind every kept entry that scores at least as much (ties go to the smaller index), the first n kept. Entries beyond
+// count: (TKSPMV_NEAREST_NONE, -inf). A row without entries scores +0.0f throughout; a row outside the mask is padding throughout.
+int packed_nearest(const PackedMatrix &pm, const float *xs, int32_t count, int32_t n, const uint32_t *mask, uint32_t *labels, float *scores, std::string &err) {
+    HostRowView V;
+    if (const int st = open_f32_stream(pm, "rows are assigned in", V, err); st != TKSPMV_OK) return st;
+    const float none = -std::numeric_limits<float>::infinity();
+    for (uint32_t r = 0; r < pm.rows; ++r) {
+        uint32_t *const lb = labels + (size_t)r * (size_t)n;
+        float *const sc = scores + (size_t)r * (size_t)n;
+        for (int32_t j = 0; j < n; ++j) {
+            lb[j] = TKSPMV_NEAREST_NONE;
+            sc[j] = none;
+        }
+        if (mask && ((mask[r >> 5] >> (r & 31u)) & 1u) == 0u) continue;
+        RowRun run{0u, 0u, 0u, 0u};
+        const bool stored = locate_entries(pm, V, r, run) != 0u;
+        int32_t len = 0;  // entries kept so far
+        for (int32_t q = 0; q < count; ++q) {
+            const float s = stored ? score_located_row(V, run, xs + (size_t)q * pm.cols) : 0.0f;
+            int32_t at = len;  // behind every entry with a score >= s
+            while (at > 0 && s > sc[at - 1]) --at;
+            if (at >= n) continue;
+            for (int32_t j = std::min(len, n - 1); j > at; --j) {
+                sc[j] = sc[j - 1];
+                lb[j] = lb[j - 1];
+            }
+            sc[at] = s;
+            lb[at] = (uint32_t)q;
+            if (len < n) ++len;
+        }
     }
     return TKSPMV_OK;
 }

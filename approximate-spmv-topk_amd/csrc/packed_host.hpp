@@ -1,5 +1,5 @@
 // packed_host.hpp -- the host twins of six kernels over a packed fp32 stream (wbscsr.hpp), behind tkspmv_packed_get_row,
-// tkspmv_packed_score_rows, tkspmv_packed_row_stats, tkspmv_packed_col_stats, tkspmv_packed_assign and tkspmv_packed_label_sums (c_api.cpp). Plain C++ over a PackedMatrix, no GPU:
+// tkspmv_packed_score_rows, tkspmv_packed_row_stats, tkspmv_packed_col_stats, tkspmv_packed_assign, tkspmv_packed_nearest and tkspmv_packed_label_sums (c_api.cpp). Plain C++ over a PackedMatrix, no GPU:
 // what they return agrees with the device bit for bit, and the host tests compare them with models that share nothing with them.
 #pragma once
 #include <cstdint>
@@ -46,6 +46,8 @@ int packed_score_rows(const PackedMatrix &pm, const float *x, const uint32_t *ro
 int packed_row_stats(const PackedMatrix &pm, int32_t kind, float *out, std::string &err);
 int packed_col_stats(const PackedMatrix &pm, int32_t kind, const uint32_t *mask, void *out, std::string &err);
 int packed_assign(const PackedMatrix &pm, const float *xs, int32_t count, uint32_t *labels, float *best, std::string &err);
+// nearest_fill_kernel and nearest_kernel (kernels/nearest.hpp): every row's n best vectors in order, under an optional allow-mask.
+int packed_nearest(const PackedMatrix &pm, const float *xs, int32_t count, int32_t n, const uint32_t *mask, uint32_t *labels, float *scores, std::string &err);
 // label_sums_kernel and label_sums_close_kernel (kernels/label_sums.hpp): the int64 sums of every label and column, the default
 // exponent, and the closing rule alone (mode TKSPMV_SUMS_FLOAT / _UNIT; UNIT leaves a bin without a norm unwritten).
 int packed_label_sums(const PackedMatrix &pm, const uint32_t *labels, uint32_t n_bins, int32_t quantum_exp, int32_t mode, int64_t *sums, float *out, std::string &err);

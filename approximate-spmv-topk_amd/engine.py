@@ -557,6 +557,32 @@ class SpMV:
         self.synchronize()
         return d_xs.cpu().numpy(), d_lab.cpu().numpy().view(np.uint32)[:self.num_rows], d_best.cpu().numpy()[:self.num_rows]
 
+    def enqueue_nearest(self, dev_xs, count, n, dev_labels, dev_scores, dev_mask=0, stream=0):
+        """Nearest-n assignment: for every LOCAL row r its n best-scoring of the `count` vectors at dev_xs (float32, cols each, back to
+        back), in order -- score descending, ties to the smaller index --: dev_labels[r, j] (uint32) and dev_scores[r, j] (float32),
+        rows x n each, row-major, the scores bit for bit what every other path reports. 1 <= n <= _lib.NEAREST_MAX_N. Entries beyond
+        count are (_lib.NEAREST_NONE, -inf). dev_mask (row_mask() words on the device, 0: every row) restricts the rows: a row outside
+        it is (NEAREST_NONE, -inf) throughout, so its label falls into no bin of enqueue_label_sums or enqueue_facets. A row without
+        entries gets labels 0, 1, .. with +0.0. n = 1 without a mask is enqueue_assign. One pass over the matrix per 16384 / column
+        tier vectors. No host sync, no engine state touched."""
+        _lib.check(_lib.lib().tkspmv_enqueue_nearest(self._h, ptr(dev_xs), int(count), int(n), ptr(dev_mask), ptr(dev_labels), ptr(dev_scores), ptr(stream)))
+
+    def nearest(self, vecs, n, mask=None):
+        """enqueue_nearest with host arrays: (labels uint32[rows, n], scores float32[rows, n]) for vecs[count, cols] (or one vector of
+        cols). mask None: every row; True: the rows of the mask set_filter() installed; a bool array of length rows or row_mask()
+        words: installed with set_filter() first, as run_filtered does. host.margin(scores) is each row's s1 - s2. Waits."""
+        xs = np.ascontiguousarray(vecs, dtype=np.float32)
+        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
+            raise ValueError(f"vectors must be [count >= 1, {self.num_cols}]")
+        n = int(n)
+        if mask is not None and mask is not True:
+            self._install(allow=mask)
+        labels = np.empty((max(self.num_rows, 1), max(n, 1)), dtype=np.uint32)
+        scores = np.empty((max(self.num_rows, 1), max(n, 1)), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_nearest(self._h, f32p(xs), int(xs.shape[0]), n, int(mask is not None), u32p(labels), f32p(scores)))
+        return labels[:self.num_rows], scores[:self.num_rows]
+
     def enqueue_col_stats(self, kind, out, masks=None, mask_stride=0, out_stride=0, stream=None, count=1):
         """Column statistics: one 4-byte word per column and set of rows into device memory at `out` -- kind = _lib.COL_NNZ (uint32:
         the stored entries of the column; explicit zeros and a column repeated within a row count), COL_MAX / COL_MIN (float32: the
@@ -751,6 +777,14 @@ def assign_spmv(m, vecs, **kw):
     kw.setdefault("k", 8)
     with _one_shot(m, **kw) as e:
         return e.assign(vecs)
+
+
+def nearest_spmv(m, vecs, n, mask=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (labels[rows, n], scores[rows, n]) of SpMV.nearest(vecs, n, mask):
+    for every row (of the mask) its n best-scoring vectors in order and their scores."""
+    kw.setdefault("k", 8)
+    with _one_shot(m, **kw) as e:
+        return e.nearest(vecs, n, mask)
 
 
 def kmeans_spmv(m, cent, iters, **kw):

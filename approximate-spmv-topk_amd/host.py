@@ -242,6 +242,46 @@ def nearest(scores):
     return labels, best
 
 
+def nearest_n(scores, n, mask=None):
+    """The contract of nearest-n assignment (SpMV.nearest, Packed.nearest) restated in numpy, for CPU-side users and as the tests'
+    expectation: from float32 scores[count, rows] -- scores[q, r] what row r scores for vector q -- (labels uint32[rows, n], scores
+    float32[rows, n]): a stable sort of the vectors by descending score, so ties (-0.0 and +0.0 among them) go to the smaller
+    index; entries j >= count are (NEAREST_NONE, -inf). mask: bool[rows]; a row it excludes is (NEAREST_NONE, -inf) throughout.
+    NaN scores are outside the contract."""
+    y = np.ascontiguousarray(scores, dtype=np.float32)
+    n = int(n)
+    if y.ndim != 2 or y.shape[0] < 1:
+        raise ValueError("scores must be [count >= 1, rows]")
+    if not 1 <= n <= _lib.NEAREST_MAX_N:
+        raise ValueError(f"n must be 1 .. {_lib.NEAREST_MAX_N}")
+    count, rows = y.shape
+    labels = np.full((rows, n), _lib.NEAREST_NONE, dtype=np.uint32)
+    out = np.full((rows, n), -np.inf, dtype=np.float32)
+    m = min(n, count)
+    order = np.argsort(-(y + np.float32(0)).T, axis=1, kind="stable")[:, :m]  # (+ 0: -0.0 becomes +0.0, so the two tie as keys too)
+    labels[:, :m] = order
+    out[:, :m] = np.take_along_axis(y.T, order, axis=1)
+    if mask is not None:
+        a = np.asarray(mask)
+        if a.dtype != np.bool_ or a.shape != (rows,):
+            raise ValueError(f"mask must be a bool array of shape ({rows},)")
+        labels[~a] = _lib.NEAREST_NONE
+        out[~a] = -np.inf
+    return labels, out
+
+
+def margin(scores_n):
+    """s1 - s2 of every row of nearest-n scores[rows, n] (float32[rows]): how sure the row's first assignment is. +inf where there is
+    no second entry (n = 1, or a single vector); NaN for a row outside the mask, which has no first either."""
+    s = np.ascontiguousarray(scores_n, dtype=np.float32)
+    if s.ndim != 2 or s.shape[1] < 1:
+        raise ValueError("scores must be [rows, n >= 1]")
+    if s.shape[1] < 2:
+        return np.where(np.isneginf(s[:, 0]), np.float32(np.nan), np.float32(np.inf)).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return (s[:, 0] - s[:, 1]).astype(np.float32)
+
+
 def facet_counts(scores, present, labels, n_bins, threshold, first_row=0, allow=None):
     """The contract of facet counts (SpMV.enqueue_facets) restated in numpy, for CPU-side users and as the tests' expectation:
     from float32 scores[rows], present[rows] (the row has entries; allow[rows], if given, restricts further) and labels[rows], the
@@ -709,6 +749,28 @@ class Packed:
         e = C.c_int32()
         _lib.check(_lib.lib().tkspmv_packed_sums_exponent(self._h, C.byref(e)))
         return int(e.value)
+
+    def nearest(self, vecs, n, mask=None):
+        """(labels uint32[rows, n], scores float32[rows, n]): for every row its n best-scoring of vecs[count, cols] in order -- score
+        descending, ties to the smaller index --, with the bits an engine created from this packed matrix reports (SpMV.nearest):
+        score_rows' arithmetic per row and vector, on the host. Entries beyond count are (NEAREST_NONE, -inf); so is every entry of
+        a row outside mask (a bool array of length rows, or row_mask() words; None: every row). 1 <= n <= NEAREST_MAX_N. fp32 values
+        only (TkspmvError ERR_UNSUPPORTED otherwise)."""
+        rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
+        xs = np.ascontiguousarray(vecs, dtype=np.float32)
+        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != cols:
+            raise ValueError(f"vectors must be [count >= 1, {cols}]")
+        n = int(n)
+        words = None
+        if mask is not None:
+            words = _allow_words(rows, mask)
+            if words.shape != (max(1, (rows + 31) // 32),):
+                raise ValueError("mask must be bool[rows] or ceil(rows / 32) mask words")
+        labels = np.empty((max(rows, 1), max(n, 1)), dtype=np.uint32)
+        scores = np.empty((max(rows, 1), max(n, 1)), dtype=np.float32)
+        _lib.check(_lib.lib().tkspmv_packed_nearest(self._h, _lib.f32p(xs), int(xs.shape[0]), n, _lib.u32p(words), _lib.u32p(labels), _lib.f32p(scores)))
+        return labels[:rows], scores[:rows]
 
     def col_stats(self, kind, allow=None):
         """uint32[cols] (kind _lib.COL_NNZ) or float32[cols] (COL_MAX, COL_MIN): one statistic of every column over all rows, or over

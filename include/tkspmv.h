@@ -561,6 +561,40 @@ int tkspmv_enqueue_assign(tkspmv_t *e, const float *dev_xs, int32_t count, uint3
 /* The same with host arrays, any count with or without host_best: on engine-owned scratch (rows labels, rows scores, and the vectors
  * in chunks of at most 64 MiB), allocated by the first call, on the engine's stream; waits for its own launches only. */
 int tkspmv_assign(tkspmv_t *e, const float *host_xs, int32_t count, uint32_t *host_labels /* [rows] */, float *host_best /* [rows], may be NULL */);
+/* Nearest-n assignment ("which n of these vectors suit every row best, and by how much?": multi-assignment when an inverted-file
+ * index is built, soft clustering, multi-label classification, the margin s1 - s2 of an assignment), optionally among the rows of an
+ * allow-mask only (k-means on a subset, re-assigning one cluster's rows, classifying the rows a predicate lets through).
+ * Inputs: count >= 1 dense vectors of desc.cols floats at dev_xs, back to back; 1 <= n <= TKSPMV_NEAREST_MAX_N; dev_mask, or NULL for
+ * all rows: one bit per LOCAL row, LSB first, ceil(rows / 32) words, as in tkspmv_enqueue_filtered.
+ * Outputs: dev_labels[rows][n] (uint32) and dev_scores[rows][n] (float32), row-major: a row's list is contiguous.
+ *  - A row is eligible if it is in the mask, or if there is no mask. Entry j of an eligible row r is the j-th of the vectors
+ *    0 .. count-1 ordered by s(r, q) descending, then by index q ascending on a tie; scores compare as floats (-0.0 and +0.0 tie).
+ *    s(r, q) is the fp32 score every other path reports for that row and vector, bit for bit (tkspmv_scores,
+ *    tkspmv_enqueue_score_rows, the top-k lists, tkspmv_enqueue_assign); tkspmv_packed_nearest restates the lists on the host.
+ *  - Entries j >= count are (TKSPMV_NEAREST_NONE, -inf).
+ *  - An eligible row without entries scores +0.0f against every vector: labels 0, 1, .., scores +0.0f, then the padding.
+ *  - A row outside the mask gets (TKSPMV_NEAREST_NONE, -inf) in every entry, so its labels fall into no bin of
+ *    tkspmv_enqueue_label_sums or tkspmv_enqueue_facets.
+ *  - n = 1 without a mask gives exactly the labels and bits of tkspmv_enqueue_assign.
+ *  - desc.min_score, the installed query and filter and the boost play no part. NaN scores are outside the contract, as in assign.
+ * One launch of nearest_fill_kernel writes every row's default list; then one pass over stream copy 0 of the matrix serves 16384 / T
+ * vectors held in LDS (T the column tier: 16, 4 or 1 vectors, nearest_kernel), and more vectors run as consecutive launches that
+ * merge with the stored list -- the running lists live in the outputs, so both are required. Asynchronous, complete in stream order
+ * on any stream (NULL: the engine's); exactly rows * n words of each output are written; no engine state is read or written, so the
+ * call may be mixed freely with the others. With desc.rows = 0 the call succeeds and writes nothing.
+ * Errors: TKSPMV_ERR_INVALID (checked first, before any device call) for a NULL engine, dev_xs, dev_labels or dev_scores, count < 1
+ * or n outside 1 .. TKSPMV_NEAREST_MAX_N; then TKSPMV_ERR_UNSUPPORTED exactly where tkspmv_enqueue_assign reports it and, with a
+ * mask, where tkspmv_enqueue_col_stats with a mask does. A rejected call writes nothing. */
+#define TKSPMV_NEAREST_MAX_N 4
+#define TKSPMV_NEAREST_NONE 0xFFFFFFFFu
+int tkspmv_enqueue_nearest(tkspmv_t *e, const float *dev_xs, int32_t count, int32_t n, const uint32_t *dev_mask /* NULL: all rows */,
+                           uint32_t *dev_labels /* [rows][n] */, float *dev_scores /* [rows][n] */, void *stream);
+/* The same with host arrays: on engine-owned scratch (rows * TKSPMV_NEAREST_MAX_N labels and scores, and the vectors in chunks of at
+ * most 64 MiB, the vector index continuing across the chunks), allocated by the first call, on the engine's stream; waits for its
+ * own launches only. use_filter != 0: among the rows of the installed allow-mask (tkspmv_set_filter); TKSPMV_ERR_STATE without one,
+ * behind the checks above. */
+int tkspmv_nearest(tkspmv_t *e, const float *host_xs, int32_t count, int32_t n, int32_t use_filter, uint32_t *host_labels /* [rows][n] */,
+                   float *host_scores /* [rows][n], may be NULL */);
 /* Label sums ("what does every cluster, class or topic look like?": the centroid update of (spherical) k-means -- the second half of
  * an iteration whose first half is tkspmv_enqueue_assign --, class prototypes for nearest-centroid classification, topic or shard
  * profiles; with one label the column sums of the matrix, or of a tkspmv_enqueue_match result turned into labels): np.add.at over the
@@ -888,6 +922,14 @@ int tkspmv_packed_row_stats(const tkspmv_packed *p, int32_t kind, float *out /* 
  * row without entries gets label 0 and +0.0f. No GPU needed. TKSPMV_ERR_INVALID for a NULL matrix, NULL xs, NULL labels or
  * count < 1, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call writes nothing. */
 int tkspmv_packed_assign(const tkspmv_packed *p, const float *xs, int32_t count, uint32_t *labels /* [rows] */, float *best /* [rows], may be NULL */);
+/* The n best of count vectors for EVERY row of a packed matrix, in order: labels[rows][n] and scores[rows][n] with the bits an engine
+ * created from this packed matrix reports (tkspmv_enqueue_nearest, whose contract this restates): every eligible row's
+ * tkspmv_packed_score_rows score against each vector in turn, each placed behind the entries that score at least as much. mask: one
+ * bit per row, ceil(rows / 32) words, or NULL for all rows. No GPU needed. TKSPMV_ERR_INVALID for a NULL matrix, xs, labels or scores,
+ * count < 1 or n outside 1 .. TKSPMV_NEAREST_MAX_N, TKSPMV_ERR_UNSUPPORTED for value types other than TKSPMV_F32; a rejected call
+ * writes nothing. */
+int tkspmv_packed_nearest(const tkspmv_packed *p, const float *xs, int32_t count, int32_t n, const uint32_t *mask /* may be NULL */,
+                          uint32_t *labels /* [rows][n] */, float *scores /* [rows][n] */);
 /* The label sums of a packed matrix (tkspmv_enqueue_label_sums' contract, with the bits an engine created from this packed matrix
  * reports): every row located in the stream and its entries' quantise(v, E) added to sums[labels[r]][c], then the closing rule of
  * `mode` into out (UNIT: a bin whose w is 0 is not written and keeps what out holds). sums may be NULL; out only with
