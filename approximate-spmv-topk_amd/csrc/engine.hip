@@ -522,24 +522,19 @@ struct EngineImpl {
         float *d_rs_out = nullptr;  // [rows]
     } stats;
 
-    // Assignment (tkspmv_enqueue_assign, assign_kernel) likewise. The scratch of tkspmv_assign, which allocates it on its first call:
-    // rows labels and rows scores, and a chunk of vectors that grows to the largest chunk asked for (at most ASSIGN_MAX_BYTES).
+    // Assignment (tkspmv_enqueue_assign, assign_kernel) and nearest-n assignment (tkspmv_enqueue_nearest; nearest_fill_kernel,
+    // nearest_kernel) likewise. The scratch of tkspmv_assign and tkspmv_nearest, ONE set for both: each host form waits for its own
+    // launches before it returns, so a call never finds the other's launches in flight on it. as_n labels and scores per row, grown to
+    // the longest list asked for (tkspmv_assign: 1), and a chunk of vectors that grows to the largest chunk asked for (at most
+    // ASSIGN_MAX_BYTES).
     struct Assign {
         static constexpr size_t ASSIGN_MAX_BYTES = (size_t)64 << 20;
-        uint32_t *d_as_labels = nullptr;  // [rows]
-        float *d_as_best = nullptr;       // [rows]
+        uint32_t *d_as_labels = nullptr;  // [rows][n], n <= as_n
+        float *d_as_scores = nullptr;     // [rows][n]
+        uint32_t as_n = 0;                // entries per row the two hold, <= TKSPMV_NEAREST_MAX_N
         float *d_as_xs = nullptr;         // [as_cap][cols]
-        uint32_t as_cap = 0;              // vectors the scratch holds
+        uint32_t as_cap = 0;              // vectors the chunk holds
     } assign;
-
-    // Nearest-n assignment (tkspmv_enqueue_nearest; nearest_fill_kernel, nearest_kernel) likewise. The scratch of tkspmv_nearest, which
-    // allocates it on its first call: rows * TKSPMV_NEAREST_MAX_N labels and scores, and a chunk of vectors like tkspmv_assign's.
-    struct Nearest {
-        uint32_t *d_nn_labels = nullptr;  // [rows][n], n <= TKSPMV_NEAREST_MAX_N
-        float *d_nn_scores = nullptr;     // [rows][n]
-        float *d_nn_xs = nullptr;         // [nn_cap][cols]
-        uint32_t nn_cap = 0;              // vectors the scratch holds
-    } nearest;
 
     // Label sums (tkspmv_enqueue_label_sums, label_sums_kernel) likewise. The scratch of tkspmv_label_sums, which allocates it on its
     // first call: rows labels, and n_bins * cols sums and floats, which grow to the largest n_bins asked for.
@@ -1156,30 +1151,20 @@ struct EngineImpl {
     // Labels and best scores of every local row for the vectors xs[0 .. n), which are the vectors q_base .. q_base + n of their call,
     // complete in stream order when this returns. q_base = 0: both outputs are zeroed in front (rows without entries are never written
     // by the kernel) and the first launch stores unconditionally; every later launch -- of this call or, q_base != 0, of the call's
-    // later chunks -- merges with the stored pair and needs best. One pass over stream copy 0 per assign_pass() vectors, with the
-    // scan kernels' geometry. Not a launch_scan call: AssignParams has no stream-copy table and no mask geometry to fill. No engine
-    // state is read or written besides the matrix.
+    // later chunks -- merges with the stored pair and needs best. No engine state is read or written besides the matrix.
     void launch_assign(const float *xs, int n, uint32_t q_base, uint32_t *labels, float *best, hipStream_t s) const {
         if (desc.rows == 0u) return;
         if (q_base == 0u) {
             (void)hipMemsetAsync(labels, 0, (size_t)desc.rows * 4, s);
             if (best) (void)hipMemsetAsync(best, 0, (size_t)desc.rows * 4, s);
         }
-        if (pm.n_packets == 0u) return;
-        const StreamParams P = stream_params(nullptr);
-        const int qp = assign_pass();
-        for (int i = 0; i < n; i += qp) {
-            const AssignParams R{mat.d_packets, xs + (size_t)i * desc.cols, labels, best, desc.rows, (uint32_t)std::min(qp, n - i), q_base + (uint32_t)i};
-            hipLaunchKernelGGL(kern.assign, dim3(grid), dim3(512), 0, s, P, R);
-        }
+        launch_assign_passes(kern.assign, xs, n, q_base, s, [&](const float *x, uint32_t n_q, uint32_t q0) { return AssignParams{mat.d_packets, x, labels, best, desc.rows, n_q, q0}; });
     }
     // The n best of the call's `total` vectors for every local row, in order, for the vectors xs[0 .. cnt), which are the vectors
     // q_base .. q_base + cnt of their call, complete in stream order when this returns. q_base = 0: nearest_fill_kernel writes every
     // row's default list in front (what the two memsets are to launch_assign: rows without entries and rows outside the mask are never
     // written by the streaming kernel) and the first launch stores its lists as they are; every later launch -- of this call or,
-    // q_base != 0, of the call's later chunks -- merges with the stored list. One pass over stream copy 0 per assign_pass() vectors,
-    // with the scan kernels' geometry. A loop of its own beside launch_assign's, and no launch_scan call for the same reason. No
-    // engine state is read or written besides the matrix.
+    // q_base != 0, of the call's later chunks -- merges with the stored list. No engine state is read or written besides the matrix.
     void launch_nearest(const float *xs, int cnt, uint32_t q_base, uint32_t total, uint32_t n, const uint32_t *mask, uint32_t *labels, float *scores,
                         hipStream_t s) const {
         if (desc.rows == 0u) return;
@@ -1188,13 +1173,20 @@ struct EngineImpl {
             const uint32_t fill_grid = (uint32_t)std::min<uint64_t>((words + 255u) / 256u, (uint64_t)std::max(1u, info.num_cus) * 32u);
             hipLaunchKernelGGL(nearest_fill_kernel, dim3(fill_grid), dim3(256), 0, s, mask, labels, scores, desc.rows, n, total);
         }
+        launch_assign_passes(kern.nearest[(n > 1u) + (n > 2u)], xs, cnt, q_base, s,
+                             [&](const float *x, uint32_t n_q, uint32_t q0) { return NearestParams{mat.d_packets, x, mask, labels, scores, desc.rows, n, n_q, q0}; });
+    }
+    // The passes of launch_assign and launch_nearest behind their zeroing: one launch of fn over stream copy 0 per assign_pass() vectors,
+    // with the scan kernels' geometry; params(x, n_q, q0) are the AssignParams / NearestParams of the pass of n_q vectors at x, which are
+    // the call's vectors q0 .. q0 + n_q. Not a launch_scan call: neither struct has a stream-copy table or mask geometry to fill, the
+    // chunk size is the format's, and q0 continues across the host forms' chunks (q_base), which launch_scan restarts at 0 per call.
+    template <class Fn, class MakeParams>
+    void launch_assign_passes(Fn fn, const float *xs, int n, uint32_t q_base, hipStream_t s, MakeParams params) const {
         if (pm.n_packets == 0u) return;
         const StreamParams P = stream_params(nullptr);
         const int qp = assign_pass();
-        for (int i = 0; i < cnt; i += qp) {
-            const NearestParams R{mat.d_packets, xs + (size_t)i * desc.cols, mask, labels, scores, desc.rows, n, (uint32_t)std::min(qp, cnt - i), q_base + (uint32_t)i};
-            hipLaunchKernelGGL(kern.nearest[(n > 1u) + (n > 2u)], dim3(grid), dim3(512), 0, s, P, R);
-        }
+        for (int i = 0; i < n; i += qp)
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(512), 0, s, P, params(xs + (size_t)i * desc.cols, (uint32_t)std::min(qp, n - i), q_base + (uint32_t)i));
     }
     // Why column statistics are not served by this engine (nullptr: they are; with_mask: the call carries an allow-mask). Served where
     // row statistics are; among the rows of a mask, where filtered queries are (match_unsupported's rule).
@@ -1571,10 +1563,49 @@ struct EngineImpl {
         dev_xs = host.d_x_cur;
         return TKSPMV_OK;
     }
-    // use_filter of the tkspmv_run_* host forms names the mask tkspmv_set_filter installed: that mask, or NULL without use_filter.
-    int installed_mask(int32_t use_filter, const uint32_t *&mask_out, std::string &err) const {
-        if (use_filter && !filter.have_filter) return fail(err, TKSPMV_ERR_INVALID, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    // use_filter of the host forms names the mask tkspmv_set_filter installed: that mask, or NULL without use_filter. A missing mask
+    // is answered with `status`: INVALID by the tkspmv_run_* forms, STATE by tkspmv_nearest and tkspmv_col_stats.
+    int installed_mask(int32_t use_filter, const uint32_t *&mask_out, std::string &err, int status = TKSPMV_ERR_INVALID) const {
+        if (use_filter && !filter.have_filter) return fail(err, status, "use_filter without an installed allow-mask (tkspmv_set_filter)");
         mask_out = use_filter ? filter.d_filter : nullptr;
+        return TKSPMV_OK;
+    }
+    // The scope test of the whole-matrix calls, which all share the row vectors' scope: UNSUPPORTED, the call's prefix in front of the reason.
+    static constexpr const char *STATS_SCOPE = "row statistics share the row vectors' scope: ", *ASSIGN_SCOPE = "assignment shares the row vectors' scope: ",
+                                *SUMS_SCOPE = "label sums share the row vectors' scope: ";
+    int row_scope(std::string &err, const char *prefix = "") const {
+        const char *why = row_vectors_unsupported();
+        return why ? fail(err, TKSPMV_ERR_UNSUPPORTED, std::string(prefix) + why) : TKSPMV_OK;
+    }
+    // A host form's own launches on the engine's stream, and the wait for them. No result is read and no result buffer written, so the
+    // engine need not be settled (wait_idle, which tkspmv_row_vectors and tkspmv_run_similar call, settles it).
+    template <class Launch>
+    hipError_t launch_and_wait(Launch launch) const {
+        launch();
+        const hipError_t e = hipGetLastError();
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    }
+    // tkspmv_assign (n = 1) and tkspmv_nearest: n labels and scores per row for `count` host vectors. Chunks of vectors: up, the chunk's
+    // launches -- launch(xs, qc, q0, labels, scores): the chunk's qc vectors are the call's vectors q0 .. --, wait (the next chunk
+    // overwrites the vectors); then the results down. The scratch grows behind a wait for the stream (an earlier call's chunks are long
+    // complete: the host forms wait themselves).
+    template <class Launch>
+    int assign_host(const float *host_xs, int32_t count, uint32_t n, uint32_t *host_labels, float *host_scores, std::string &err, Launch launch) {
+        if (desc.rows == 0u) return TKSPMV_OK;
+        HIP_TRY(hipSetDevice(device));
+        Assign &A = assign;
+        const size_t cols = desc.cols, rows = desc.rows, x_bytes = std::max<size_t>(cols, 1) * 4;
+        const uint32_t want = (uint32_t)std::min<size_t>((size_t)count, std::max<size_t>(1, Assign::ASSIGN_MAX_BYTES / x_bytes));
+        if (n > A.as_n || want > A.as_cap) HIP_TRY(hipStreamSynchronize(stream));
+        if (n > A.as_n) HIP_TRY(grow_scratch(A.as_n, n, {{(void **)&A.d_as_labels, rows * n * 4}, {(void **)&A.d_as_scores, rows * n * 4}}));
+        if (want > A.as_cap) HIP_TRY(grow_scratch(A.as_cap, want, {{(void **)&A.d_as_xs, (size_t)want * x_bytes}}));
+        for (int32_t q0 = 0; q0 < count; q0 += (int32_t)A.as_cap) {
+            const int32_t qc = std::min<int32_t>((int32_t)A.as_cap, count - q0);
+            HIP_TRY(hipMemcpy(A.d_as_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
+            HIP_TRY(launch_and_wait([&] { launch(A.d_as_xs, qc, (uint32_t)q0, A.d_as_labels, A.d_as_scores); }));
+        }
+        HIP_TRY(hipMemcpy(host_labels, A.d_as_labels, rows * n * 4, hipMemcpyDeviceToHost));
+        if (host_scores) HIP_TRY(hipMemcpy(host_scores, A.d_as_scores, rows * n * 4, hipMemcpyDeviceToHost));
         return TKSPMV_OK;
     }
     // A call's own masks are mask_stride_words apart; the installed mask, or none, serves every query of the call.
@@ -3072,10 +3103,45 @@ int Engine::run_match(const uint32_t *host_clauses, const tkspmv_match *pred, in
     return TKSPMV_OK;
 }
 
+// What both entries of a whole-matrix operation -- tkspmv_enqueue_X on device pointers, tkspmv_X on host pointers -- test first, one
+// function per operation: the arguments (INVALID; the message carries the entry's name), then the stored rows' scope (UNSUPPORTED).
+// (Label sums and column statistics keep two argument checks each: the enqueue forms test alignment and flags, sets and strides,
+// which the host forms do not have, and each message lists its own rules.)
+static int bad_arguments(std::string &err, const char *entry, const std::string &rules) {
+    return fail(err, TKSPMV_ERR_INVALID, std::string("bad arguments to ") + entry + " (" + rules + ")");
+}
+static int check_row_vectors(const EngineImpl &m, const char *entry, const void *rows, const void *xs, int32_t count, std::string &err) {
+    return rows && xs && count >= 1 ? m.row_scope(err) : bad_arguments(err, entry, "row ids and vectors given, count >= 1");
+}
+// (xs_name: "dev_xs" / "host_xs", as the entry's prototype calls the vectors)
+static int check_score_rows(const EngineImpl &m, const char *entry, const char *xs_name, const void *xs, int32_t count, const void *rows, int32_t n_rows,
+                            int64_t rows_stride, const void *scores, std::string &err) {
+    if (!rows || !scores || count < 1 || n_rows < 1 || rows_stride < 0 || (rows_stride != 0 && rows_stride < n_rows))
+        return bad_arguments(err, entry, "row ids and scores given, count >= 1, n_rows >= 1, rows_stride = 0 or >= n_rows");
+    if (!xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, std::string(xs_name) + " = NULL takes the installed query vector: count must be 1");
+    return m.row_scope(err);
+}
+static int check_row_stats(const EngineImpl &m, const char *entry, const void *out, int32_t kind, std::string &err) {
+    if (!out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2) return bad_arguments(err, entry, "output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2");
+    return m.row_scope(err, EngineImpl::STATS_SCOPE);
+}
+static int check_assign(const EngineImpl &m, const char *entry, const void *xs, const void *labels, int32_t count, std::string &err) {
+    return xs && labels && count >= 1 ? m.row_scope(err, EngineImpl::ASSIGN_SCOPE) : bad_arguments(err, entry, "vectors and labels given, count >= 1");
+}
+// (the one real difference of a pair: tkspmv_enqueue_nearest needs the scores -- later passes merge with them --, tkspmv_nearest keeps
+//  them in its scratch and takes host_scores = NULL. with_mask: the call names a mask, whose scope is the filtered queries'.)
+static int check_nearest(const EngineImpl &m, const char *entry, const void *xs, const void *labels, const void *scores, bool scores_optional, int32_t count,
+                         int32_t n, bool with_mask, std::string &err) {
+    if (!xs || !labels || !(scores || scores_optional) || count < 1 || n < 1 || n > TKSPMV_NEAREST_MAX_N)
+        return bad_arguments(err, entry, std::string(scores_optional ? "vectors and labels" : "vectors, labels and scores") + " given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N");
+    if (const int st = m.row_scope(err, EngineImpl::ASSIGN_SCOPE)) return st;
+    const char *why = m.col_stats_unsupported(with_mask);
+    return why ? fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment under an allow-mask: ") + why) : TKSPMV_OK;
+}
+
 int Engine::enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *dev_xs, uint32_t *dev_len, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_rows || !dev_xs || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_row_vectors (row ids and vectors given, count >= 1)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = check_row_vectors(m, "enqueue_row_vectors", dev_rows, dev_xs, count, err)) return st;
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
         m.launch_row_vectors(dev_rows, count, dev_xs, dev_len, s);
         return TKSPMV_OK;
@@ -3084,8 +3150,7 @@ int Engine::enqueue_row_vectors(const uint32_t *dev_rows, int32_t count, float *
 
 int Engine::row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs, uint32_t *host_len, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_rows || !host_xs || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to row_vectors (row ids and vectors given, count >= 1)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = check_row_vectors(m, "row_vectors", host_rows, host_xs, count, err)) return st;
     HIP_TRY(hipSetDevice(m.device));
     // (buffers of this call alone: the caller asks for `count` whole vectors at once, whatever their size)
     ScratchBuffer<uint32_t> d_rows, d_len;
@@ -3106,7 +3171,7 @@ int Engine::row_vectors(const uint32_t *host_rows, int32_t count, float *host_xs
 int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclude_self, uint32_t *idx, float *val, std::string &err) {
     EngineImpl &m = *impl_;
     if (!host_rows || !idx || !val || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_similar (row ids and [count][k] outputs given, count >= 1)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = m.row_scope(err)) return st;
     HIP_TRY(hipSetDevice(m.device));
     const size_t k = (size_t)m.desc.k, cols = m.desc.cols;
     const uint32_t chunk_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(EngineImpl::Similar::SIMILAR_MAX_ROWS, EngineImpl::Similar::SIMILAR_MAX_BYTES / (cols * 4)));
@@ -3150,10 +3215,7 @@ int Engine::run_similar(const uint32_t *host_rows, int32_t count, int32_t exclud
 int Engine::enqueue_score_rows(const float *dev_xs, int32_t count, const uint32_t *dev_rows, int32_t n_rows, int64_t rows_stride, float *dev_scores,
                                void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_rows || !dev_scores || count < 1 || n_rows < 1 || rows_stride < 0 || (rows_stride != 0 && rows_stride < n_rows))
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_score_rows (row ids and scores given, count >= 1, n_rows >= 1, rows_stride = 0 or >= n_rows)");
-    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = check_score_rows(m, "enqueue_score_rows", "dev_xs", dev_xs, count, dev_rows, n_rows, rows_stride, dev_scores, err)) return st;
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
         HIP_TRY(m.order_x(dev_xs, s));
@@ -3165,10 +3227,7 @@ int Engine::enqueue_score_rows(const float *dev_xs, int32_t count, const uint32_
 int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host_rows, int32_t n_rows, int64_t rows_stride, float *host_scores,
                        std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_rows || !host_scores || count < 1 || n_rows < 1 || rows_stride < 0 || (rows_stride != 0 && rows_stride < n_rows))
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to score_rows (row ids and scores given, count >= 1, n_rows >= 1, rows_stride = 0 or >= n_rows)");
-    if (!host_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "host_xs = NULL takes the installed query vector: count must be 1");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    if (const int st = check_score_rows(m, "score_rows", "host_xs", host_xs, count, host_rows, n_rows, rows_stride, host_scores, err)) return st;
     const float *installed = nullptr;
     if (!host_xs) {
         if (const int st = m.resolve_query(installed, 1, err)) return st;
@@ -3188,8 +3247,7 @@ int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host
         m.score.sr_q_cap = q_cap;
         m.score.sr_row_cap = r_cap;
     }
-    // chunks of queries, and of list entries inside them: vectors and ids up, the launch, wait, scores down. No result is read and no
-    // result buffer written, so the engine need not be settled: the wait is for this call's own launch.
+    // chunks of queries, and of list entries inside them: vectors and ids up, the launch, wait, scores down.
     for (int32_t q0 = 0; q0 < count; q0 += (int32_t)m.score.sr_q_cap) {
         const int32_t qc = std::min<int32_t>((int32_t)m.score.sr_q_cap, count - q0);
         if (host_xs) HIP_TRY(hipMemcpy(m.score.d_sr_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
@@ -3200,9 +3258,9 @@ int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host
             else
                 HIP_TRY(hipMemcpy2D(m.score.d_sr_rows, (size_t)rc * 4, host_rows + (size_t)q0 * (size_t)rows_stride + r0, (size_t)rows_stride * 4, (size_t)rc * 4,
                                     (size_t)qc, hipMemcpyHostToDevice));
-            m.launch_score_rows(host_xs ? m.score.d_sr_xs : installed, qc, m.score.d_sr_rows, rc, rows_stride == 0 ? 0u : (size_t)rc, m.score.d_sr_scores, m.stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(m.stream));
+            HIP_TRY(m.launch_and_wait([&] {
+                m.launch_score_rows(host_xs ? m.score.d_sr_xs : installed, qc, m.score.d_sr_rows, rc, rows_stride == 0 ? 0u : (size_t)rc, m.score.d_sr_scores, m.stream);
+            }));
             HIP_TRY(hipMemcpy2D(host_scores + (size_t)q0 * n_rows + r0, (size_t)n_rows * 4, m.score.d_sr_scores, (size_t)rc * 4, (size_t)rc * 4, (size_t)qc,
                                 hipMemcpyDeviceToHost));
         }
@@ -3212,9 +3270,7 @@ int Engine::score_rows(const float *host_xs, int32_t count, const uint32_t *host
 
 int Engine::enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_row_stats (output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    if (const int st = check_row_stats(m, "enqueue_row_stats", dev_out, kind, err)) return st;
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
         m.launch_row_stats(kind, dev_out, s);
         return TKSPMV_OK;
@@ -3223,24 +3279,18 @@ int Engine::enqueue_row_stats(int32_t kind, float *dev_out, void *stream, std::s
 
 int Engine::row_stats(int32_t kind, float *host_out, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_out || kind < TKSPMV_ROW_NNZ || kind > TKSPMV_ROW_INV_L2)
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to row_stats (output given, kind = TKSPMV_ROW_NNZ .. TKSPMV_ROW_INV_L2)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    if (const int st = check_row_stats(m, "row_stats", host_out, kind, err)) return st;
     if (m.desc.rows == 0u) return TKSPMV_OK;
     HIP_TRY(hipSetDevice(m.device));
     if (!m.stats.d_rs_out) HIP_TRY(m.alloc(m.stats.d_rs_out, (size_t)m.desc.rows * 4));
-    // No result is read and no result buffer written, so the engine need not be settled: the wait is for this call's own launch.
-    m.launch_row_stats(kind, m.stats.d_rs_out, m.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(m.launch_and_wait([&] { m.launch_row_stats(kind, m.stats.d_rs_out, m.stream); }));
     HIP_TRY(hipMemcpy(host_out, m.stats.d_rs_out, (size_t)m.desc.rows * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
 
 int Engine::enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_labels, float *dev_best, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || !dev_labels || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_assign (vectors and labels given, count >= 1)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
+    if (const int st = check_assign(m, "enqueue_assign", dev_xs, dev_labels, count, err)) return st;
     // (the launches behind the first merge with the scores of the ones before: without dev_best there is nowhere to keep them -- the
     //  engine owns no scratch that a call on a caller's stream could use without a wait)
     if (!dev_best && count > m.assign_pass())
@@ -3253,40 +3303,16 @@ int Engine::enqueue_assign(const float *dev_xs, int32_t count, uint32_t *dev_lab
 
 int Engine::assign(const float *host_xs, int32_t count, uint32_t *host_labels, float *host_best, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_xs || !host_labels || count < 1) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to assign (vectors and labels given, count >= 1)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
-    if (m.desc.rows == 0u) return TKSPMV_OK;
-    HIP_TRY(hipSetDevice(m.device));
-    EngineImpl::Assign &A = m.assign;
-    const size_t cols = m.desc.cols, rows = m.desc.rows;
-    if (!A.d_as_labels) HIP_TRY(m.alloc(A.d_as_labels, rows * 4));
-    if (!A.d_as_best) HIP_TRY(m.alloc(A.d_as_best, rows * 4));
-    const uint32_t want = (uint32_t)std::min<size_t>((size_t)count, std::max<size_t>(1, EngineImpl::Assign::ASSIGN_MAX_BYTES / (std::max<size_t>(cols, 1) * 4)));
-    if (want > A.as_cap) {
-        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: assign waits itself)
-        HIP_TRY(m.grow_scratch(A.as_cap, want, {{(void **)&A.d_as_xs, (size_t)want * std::max<size_t>(cols, 1) * 4}}));
-    }
-    // chunks of vectors: up, the chunk's launches, wait (the next chunk overwrites the vectors). No result is read and no result buffer
-    // written, so the engine need not be settled: the waits are for this call's own launches.
-    for (int32_t q0 = 0; q0 < count; q0 += (int32_t)A.as_cap) {
-        const int32_t qc = std::min<int32_t>((int32_t)A.as_cap, count - q0);
-        HIP_TRY(hipMemcpy(A.d_as_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
-        m.launch_assign(A.d_as_xs, qc, (uint32_t)q0, A.d_as_labels, A.d_as_best, m.stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m.stream));
-    }
-    HIP_TRY(hipMemcpy(host_labels, A.d_as_labels, rows * 4, hipMemcpyDeviceToHost));
-    if (host_best) HIP_TRY(hipMemcpy(host_best, A.d_as_best, rows * 4, hipMemcpyDeviceToHost));
-    return TKSPMV_OK;
+    if (const int st = check_assign(m, "assign", host_xs, host_labels, count, err)) return st;
+    return m.assign_host(host_xs, count, 1u, host_labels, host_best, err, [&](const float *xs, int qc, uint32_t q0, uint32_t *labels, float *best) {
+        m.launch_assign(xs, qc, q0, labels, best, m.stream);
+    });
 }
 
 int Engine::enqueue_nearest(const float *dev_xs, int32_t count, int32_t n, const uint32_t *dev_mask, uint32_t *dev_labels, float *dev_scores, void *stream,
                             std::string &err) {
     EngineImpl &m = *impl_;
-    if (!dev_xs || !dev_labels || !dev_scores || count < 1 || n < 1 || n > TKSPMV_NEAREST_MAX_N)
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_nearest (vectors, labels and scores given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
-    if (const char *why = m.col_stats_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment under an allow-mask: ") + why);
+    if (const int st = check_nearest(m, "enqueue_nearest", dev_xs, dev_labels, dev_scores, false, count, n, dev_mask != nullptr, err)) return st;
     return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written)
         m.launch_nearest(dev_xs, count, 0u, (uint32_t)count, (uint32_t)n, dev_mask, dev_labels, dev_scores, s);
         return TKSPMV_OK;
@@ -3295,33 +3321,12 @@ int Engine::enqueue_nearest(const float *dev_xs, int32_t count, int32_t n, const
 
 int Engine::nearest(const float *host_xs, int32_t count, int32_t n, int32_t use_filter, uint32_t *host_labels, float *host_scores, std::string &err) {
     EngineImpl &m = *impl_;
-    if (!host_xs || !host_labels || count < 1 || n < 1 || n > TKSPMV_NEAREST_MAX_N)
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to nearest (vectors and labels given, count >= 1, n = 1 .. TKSPMV_NEAREST_MAX_N)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment shares the row vectors' scope: ") + why);
-    if (const char *why = m.col_stats_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("assignment under an allow-mask: ") + why);
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_STATE, "use_filter without an installed allow-mask (tkspmv_set_filter)");
-    if (m.desc.rows == 0u) return TKSPMV_OK;
-    HIP_TRY(hipSetDevice(m.device));
-    EngineImpl::Nearest &A = m.nearest;
-    const size_t cols = m.desc.cols, rows = m.desc.rows;
-    if (!A.d_nn_labels) HIP_TRY(m.alloc(A.d_nn_labels, rows * TKSPMV_NEAREST_MAX_N * 4));
-    if (!A.d_nn_scores) HIP_TRY(m.alloc(A.d_nn_scores, rows * TKSPMV_NEAREST_MAX_N * 4));
-    const uint32_t want = (uint32_t)std::min<size_t>((size_t)count, std::max<size_t>(1, EngineImpl::Assign::ASSIGN_MAX_BYTES / (std::max<size_t>(cols, 1) * 4)));
-    if (want > A.nn_cap) {
-        HIP_TRY(hipStreamSynchronize(m.stream));  // (an earlier call's chunks are long complete: nearest waits itself)
-        HIP_TRY(m.grow_scratch(A.nn_cap, want, {{(void **)&A.d_nn_xs, (size_t)want * std::max<size_t>(cols, 1) * 4}}));
-    }
-    // chunks of vectors as in assign: up, the chunk's launches, wait. The waits are for this call's own launches.
-    for (int32_t q0 = 0; q0 < count; q0 += (int32_t)A.nn_cap) {
-        const int32_t qc = std::min<int32_t>((int32_t)A.nn_cap, count - q0);
-        HIP_TRY(hipMemcpy(A.d_nn_xs, host_xs + (size_t)q0 * cols, (size_t)qc * cols * 4, hipMemcpyHostToDevice));
-        m.launch_nearest(A.d_nn_xs, qc, (uint32_t)q0, (uint32_t)count, (uint32_t)n, use_filter ? m.filter.d_filter : nullptr, A.d_nn_labels, A.d_nn_scores, m.stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m.stream));
-    }
-    HIP_TRY(hipMemcpy(host_labels, A.d_nn_labels, rows * (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (host_scores) HIP_TRY(hipMemcpy(host_scores, A.d_nn_scores, rows * (size_t)n * 4, hipMemcpyDeviceToHost));
-    return TKSPMV_OK;
+    if (const int st = check_nearest(m, "nearest", host_xs, host_labels, host_scores, true, count, n, use_filter != 0, err)) return st;
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err, TKSPMV_ERR_STATE)) return st;
+    return m.assign_host(host_xs, count, (uint32_t)n, host_labels, host_scores, err, [&](const float *xs, int qc, uint32_t q0, uint32_t *labels, float *scores) {
+        m.launch_nearest(xs, qc, q0, (uint32_t)count, (uint32_t)n, mask, labels, scores, m.stream);
+    });
 }
 
 int Engine::enqueue_label_sums(const uint32_t *dev_labels, uint32_t n_bins, int32_t quantum_exp, uint32_t flags, int64_t *dev_sums, int32_t mode, float *dev_out,
@@ -3333,7 +3338,7 @@ int Engine::enqueue_label_sums(const uint32_t *dev_labels, uint32_t n_bins, int3
         (flags & SINKS) == SINKS)
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_label_sums (dev_sums given and 8-byte aligned, dev_labels with 1 <= n_bins <= 2^30 or dev_labels = "
                                              "NULL with n_bins = 0, mode = TKSPMV_SUMS_RAW .. TKSPMV_SUMS_UNIT, dev_out given unless RAW, known flags, at most one sink)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    if (const int st = m.row_scope(err, EngineImpl::SUMS_SCOPE)) return st;
     if (!dev_labels) {
         if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_INVALID, "no labels given and none installed (call tkspmv_set_groups first)");
         dev_labels = m.grouped.d_groups;
@@ -3364,19 +3369,13 @@ int Engine::enqueue_sums_close(const int64_t *dev_sums, uint32_t n_bins, int32_t
 int Engine::sums_exponent(int32_t *quantum_exp, std::string &err) {
     EngineImpl &m = *impl_;
     if (!quantum_exp) return fail(err, TKSPMV_ERR_INVALID, "bad arguments to sums_exponent (output given)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    if (const int st = m.row_scope(err, EngineImpl::SUMS_SCOPE)) return st;
     const size_t cols = m.desc.cols;
     std::vector<uint32_t> nnz(cols), hi(cols), lo(cols);
     if (const int st = col_stats(TKSPMV_COL_NNZ, 0, nnz.data(), err)) return st;
     if (const int st = col_stats(TKSPMV_COL_MAX, 0, hi.data(), err)) return st;
     if (const int st = col_stats(TKSPMV_COL_MIN, 0, lo.data(), err)) return st;
-    uint32_t max_nnz = 0u, max_abs = 0u;  // (|v| as bits: the order of the magnitudes of finite floats is the order of their bit patterns)
-    for (size_t c = 0; c < cols; ++c) {
-        if (nnz[c] == 0u) continue;  // (no counted entry: MAX / MIN hold -inf / +inf)
-        max_nnz = std::max(max_nnz, nnz[c]);
-        max_abs = std::max({max_abs, hi[c] & 0x7FFFFFFFu, lo[c] & 0x7FFFFFFFu});
-    }
-    *quantum_exp = sums_exponent_of(max_abs, max_nnz);
+    *quantum_exp = sums_exponent_of_columns(nnz.data(), hi.data(), lo.data(), cols);
     return TKSPMV_OK;
 }
 
@@ -3385,7 +3384,7 @@ int Engine::label_sums(const uint32_t *host_labels, uint32_t n_bins, int32_t qua
     if ((host_labels != nullptr) != (n_bins != 0u) || n_bins > (1u << 30) || mode < TKSPMV_SUMS_RAW || mode > TKSPMV_SUMS_UNIT || (mode != TKSPMV_SUMS_RAW && !host_out))
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to label_sums (host_labels with 1 <= n_bins <= 2^30 or host_labels = NULL with n_bins = 0, mode = "
                                              "TKSPMV_SUMS_RAW .. TKSPMV_SUMS_UNIT, host_out given unless RAW)");
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("label sums share the row vectors' scope: ") + why);
+    if (const int st = m.row_scope(err, EngineImpl::SUMS_SCOPE)) return st;
     if (!host_labels) {
         if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_INVALID, "no labels given and none installed (call tkspmv_set_groups first)");
         n_bins = m.grouped.n_groups;
@@ -3429,14 +3428,12 @@ int Engine::col_stats(int32_t kind, int32_t use_filter, void *host_out, std::str
     if (!host_out || kind < TKSPMV_COL_NNZ || kind > TKSPMV_COL_MIN)
         return fail(err, TKSPMV_ERR_INVALID, "bad arguments to col_stats (output given, kind = TKSPMV_COL_NNZ .. TKSPMV_COL_MIN)");
     if (const char *why = m.col_stats_unsupported(use_filter != 0)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("column statistics: ") + why);
-    if (use_filter && !m.filter.have_filter) return fail(err, TKSPMV_ERR_STATE, "use_filter without an installed allow-mask (tkspmv_set_filter)");
+    const uint32_t *mask = nullptr;
+    if (const int st = m.installed_mask(use_filter, mask, err, TKSPMV_ERR_STATE)) return st;
     if (m.desc.cols == 0u) return TKSPMV_OK;
     HIP_TRY(hipSetDevice(m.device));
     if (!m.cstats.d_cs_out) HIP_TRY(m.alloc(m.cstats.d_cs_out, (size_t)m.desc.cols * 4));
-    // No result is read and no result buffer written, so the engine need not be settled: the wait is for this call's own launch.
-    m.launch_col_stats(kind, 1, use_filter ? m.filter.d_filter : nullptr, 0u, m.cstats.d_cs_out, 0u, m.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m.stream));
+    HIP_TRY(m.launch_and_wait([&] { m.launch_col_stats(kind, 1, mask, 0u, m.cstats.d_cs_out, 0u, m.stream); }));
     HIP_TRY(hipMemcpy(host_out, m.cstats.d_cs_out, (size_t)m.desc.cols * 4, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
 }
@@ -3444,14 +3441,13 @@ int Engine::col_stats(int32_t kind, int32_t use_filter, void *host_out, std::str
 int Engine::set_boost_cosine(std::string &err) {
     EngineImpl &m = *impl_;
     EngineImpl::Boost &Q = m.boost;
-    if (const char *why = m.row_vectors_unsupported()) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("row statistics share the row vectors' scope: ") + why);
+    if (const int st = m.row_scope(err, EngineImpl::STATS_SCOPE)) return st;
     HIP_TRY(hipSetDevice(m.device));
     HIP_TRY(hipStreamSynchronize(m.stream));  // (a boosted query enqueued earlier may still read the installed arrays)
     Q.have_weight = Q.have_bias = false;  // (until the launch below has completed; the state aimed at is set_boost(w, NULL)'s)
     if (!Q.d_weight) HIP_TRY(m.alloc(Q.d_weight, std::max<size_t>(m.desc.rows, 1) * 4));
-    m.launch_row_stats(TKSPMV_ROW_INV_L2, Q.d_weight, m.stream);  // (the weights never visit the host; finite by construction)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m.stream));
+    // (the weights never visit the host; finite by construction)
+    HIP_TRY(m.launch_and_wait([&] { m.launch_row_stats(TKSPMV_ROW_INV_L2, Q.d_weight, m.stream); }));
     Q.have_weight = true;
     return TKSPMV_OK;
 }

@@ -162,29 +162,11 @@ int packed_row_stats(const PackedMatrix &pm, int32_t kind, float *out, std::stri
     return TKSPMV_OK;
 }
 
-// assign_kernel (kernels/assign.hpp) restated row by row: the row's score against every vector in turn -- packed_score_rows' value --,
-// the first kept, a later one only where it is strictly greater (ties go to the smallest index). A row without entries: label 0, +0.0f.
+// assign_kernel (kernels/assign.hpp) restated: packed_nearest's lists of one entry without a mask -- the first vector kept, a later one
+// only where it scores strictly more; a row without entries: label 0, +0.0f. best = NULL: the scores go to an array of this call.
 int packed_assign(const PackedMatrix &pm, const float *xs, int32_t count, uint32_t *labels, float *best, std::string &err) {
-    HostRowView V;
-    if (const int st = open_f32_stream(pm, "rows are assigned in", V, err); st != TKSPMV_OK) return st;
-    for (uint32_t r = 0; r < pm.rows; ++r) {
-        RowRun run{0u, 0u, 0u, 0u};
-        uint32_t label = 0u;
-        float b = 0.0f;
-        if (locate_entries(pm, V, r, run) != 0u) {
-            b = score_located_row(V, run, xs);
-            for (int32_t q = 1; q < count; ++q) {
-                const float s = score_located_row(V, run, xs + (size_t)q * pm.cols);
-                if (s > b) {
-                    b = s;
-                    label = (uint32_t)q;
-                }
-            }
-        }
-        labels[r] = label;
-        if (best) best[r] = b;
-    }
-    return TKSPMV_OK;
+    std::vector<float> scores(best ? 0u : pm.rows);
+    return packed_nearest(pm, xs, count, 1, nullptr, labels, best ? best : scores.data(), err);
 }
 
 // nearest_kernel (kernels/nearest.hpp) restated row by row: the row's score against every vector in turn -- packed_score_rows' value --,
@@ -321,13 +303,7 @@ int packed_sums_exponent(const PackedMatrix &pm, int32_t *quantum_exp, std::stri
     if (const int st = packed_col_stats(pm, TKSPMV_COL_NNZ, nullptr, nnz.data(), err); st != TKSPMV_OK) return st;
     if (const int st = packed_col_stats(pm, TKSPMV_COL_MAX, nullptr, hi.data(), err); st != TKSPMV_OK) return st;
     if (const int st = packed_col_stats(pm, TKSPMV_COL_MIN, nullptr, lo.data(), err); st != TKSPMV_OK) return st;
-    uint32_t max_nnz = 0u, max_abs = 0u;  // (|v| as bits: the magnitudes of finite floats order like their bit patterns)
-    for (uint32_t c = 0; c < pm.cols; ++c) {
-        if (nnz[c] == 0u) continue;  // (no counted entry: MAX / MIN hold -inf / +inf)
-        max_nnz = std::max(max_nnz, nnz[c]);
-        max_abs = std::max({max_abs, hi[c] & 0x7FFFFFFFu, lo[c] & 0x7FFFFFFFu});
-    }
-    *quantum_exp = sums_exponent_of(max_abs, max_nnz);
+    *quantum_exp = sums_exponent_of_columns(nnz.data(), hi.data(), lo.data(), pm.cols);
     return TKSPMV_OK;
 }
 

@@ -1,6 +1,8 @@
 // quantise.hpp -- the fixed-point grid of the label sums (tkspmv_enqueue_label_sums): one function, compiled for the device
 // (kernels/label_sums.hpp) and for the host (packed_host.cpp), so that both sides add the same integers.
 #pragma once
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -47,6 +49,19 @@ TKSPMV_HOST_DEVICE inline int32_t sums_exponent_of(uint32_t max_abs_bits, uint32
     int32_t lg = 0;
     while ((1ull << lg) < (uint64_t)max_col_nnz) ++lg;
     return xmax + 1 + lg - 62;
+}
+
+// ... from the three column statistics of the matrix (TKSPMV_COL_NNZ, _MAX, _MIN as words, cols of each): what tkspmv_sums_exponent
+// and tkspmv_packed_sums_exponent answer. |v| as bits: the magnitudes of finite floats order like their bit patterns. A column
+// without a counted entry holds -inf / +inf and is left out.
+inline int32_t sums_exponent_of_columns(const uint32_t *nnz, const uint32_t *hi, const uint32_t *lo, size_t cols) {
+    uint32_t max_nnz = 0u, max_abs = 0u;
+    for (size_t c = 0; c < cols; ++c) {
+        if (nnz[c] == 0u) continue;
+        max_nnz = std::max(max_nnz, nnz[c]);
+        max_abs = std::max({max_abs, hi[c] & 0x7FFFFFFFu, lo[c] & 0x7FFFFFFFu});
+    }
+    return sums_exponent_of(max_abs, max_nnz);
 }
 
 }  // namespace tkspmv

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import f32p, ptr, u32p
-from .host import _allow_words
+from .host import _allow_words, _vectors
 
 MAX_PAGE = 1000  # ranked_spmv's default page: every page takes the scores + radix-select route whatever k is, so a large page is cheapest
 
@@ -476,10 +476,7 @@ class SpMV:
         """enqueue_assign with host arrays: (labels uint32[rows], best float32[rows]) for vecs[count, cols] (or one vector of cols).
         Waits. install: the labels become the engine's group labels, set_groups(labels, n_groups=count) -- run_grouped then returns
         each cluster once, run_facets counts per cluster."""
-        xs = np.ascontiguousarray(vecs, dtype=np.float32)
-        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
-        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
-            raise ValueError(f"vectors must be [count >= 1, {self.num_cols}]")
+        xs = _vectors(vecs, self.num_cols)
         labels = np.empty(max(self.num_rows, 1), dtype=np.uint32)
         best = np.empty(max(self.num_rows, 1), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_assign(self._h, f32p(xs), int(xs.shape[0]), u32p(labels), f32p(best)))
@@ -540,9 +537,7 @@ class SpMV:
         never visit the host in between. cent: float32[count, cols] start vectors. Returns (cent float32[count, cols], labels
         uint32[rows], best float32[rows]): the final centroids and every row's assignment to them. Waits."""
         import torch
-        xs = np.ascontiguousarray(cent, dtype=np.float32)
-        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
-            raise ValueError(f"centroids must be [count >= 1, {self.num_cols}]")
+        xs = _vectors(cent, self.num_cols, what="centroids")
         count, exp = int(xs.shape[0]), self.sums_exponent()
         dev = torch.device("cuda", int(self.info()["device"]))
         d_xs = torch.from_numpy(xs).to(dev)
@@ -571,11 +566,7 @@ class SpMV:
         """enqueue_nearest with host arrays: (labels uint32[rows, n], scores float32[rows, n]) for vecs[count, cols] (or one vector of
         cols). mask None: every row; True: the rows of the mask set_filter() installed; a bool array of length rows or row_mask()
         words: installed with set_filter() first, as run_filtered does. host.margin(scores) is each row's s1 - s2. Waits."""
-        xs = np.ascontiguousarray(vecs, dtype=np.float32)
-        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
-        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != self.num_cols:
-            raise ValueError(f"vectors must be [count >= 1, {self.num_cols}]")
-        n = int(n)
+        xs, n = _vectors(vecs, self.num_cols), int(n)
         if mask is not None and mask is not True:
             self._install(allow=mask)
         labels = np.empty((max(self.num_rows, 1), max(n, 1)), dtype=np.uint32)

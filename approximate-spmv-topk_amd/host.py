@@ -103,6 +103,26 @@ def _allow_words(rows, allow):
     return np.ascontiguousarray(row_mask(rows, a) if a.dtype == np.bool_ else a, dtype=np.uint32)
 
 
+def _mask_words(rows, mask, what):
+    """The mask of Packed.nearest / Packed.col_stats as the words the C call takes: None stays None (every row); else _allow_words,
+    ceil(rows / 32) of them (at least one)."""
+    if mask is None:
+        return None
+    words = _allow_words(rows, mask)
+    if words.shape != (max(1, (rows + 31) // 32),):
+        raise ValueError(f"{what} must be bool[rows] or ceil(rows / 32) mask words")
+    return words
+
+
+def _vectors(vecs, cols, what="vectors"):
+    """The vectors of the assignment calls as contiguous float32 [count >= 1, cols]; one vector of cols is a set of one."""
+    xs = np.ascontiguousarray(vecs, dtype=np.float32)
+    xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+    if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != cols:
+        raise ValueError(f"{what} must be [count >= 1, {cols}]")
+    return xs
+
+
 def _order_key(f):
     """Monotone float32 -> uint32, the engine's order_key."""
     u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
@@ -230,16 +250,8 @@ def nearest(scores):
     from float32 scores[count, rows] -- scores[q, r] what row r scores for vector q -- (labels uint32[rows], best float32[rows]):
     vector 0 first, a later vector only where its score is strictly greater, so ties go to the smallest index and -0.0 never
     replaces +0.0. NaN scores are outside the contract."""
-    y = np.ascontiguousarray(scores, dtype=np.float32)
-    if y.ndim != 2 or y.shape[0] < 1:
-        raise ValueError("scores must be [count >= 1, rows]")
-    best = y[0].copy()
-    labels = np.zeros(y.shape[1], dtype=np.uint32)
-    for q in range(1, y.shape[0]):
-        better = y[q] > best
-        best[better] = y[q][better]
-        labels[better] = q
-    return labels, best
+    labels, best = nearest_n(scores, 1)  # (a stable sort's first entry: the first of the largest scores, -0.0 and +0.0 tying)
+    return np.ascontiguousarray(labels[:, 0]), np.ascontiguousarray(best[:, 0])
 
 
 def nearest_n(scores, n, mask=None):
@@ -717,10 +729,7 @@ class Packed:
         arithmetic per row and vector, on the host. A row without entries gets label 0 and +0.0. fp32 values only (TkspmvError
         ERR_UNSUPPORTED otherwise)."""
         rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
-        xs = np.ascontiguousarray(vecs, dtype=np.float32)
-        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
-        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != cols:
-            raise ValueError(f"vectors must be [count >= 1, {cols}]")
+        xs = _vectors(vecs, cols)
         labels = np.empty(max(rows, 1), dtype=np.uint32)
         best = np.empty(max(rows, 1), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_packed_assign(self._h, _lib.f32p(xs), int(xs.shape[0]), _lib.u32p(labels), _lib.f32p(best)))
@@ -757,16 +766,7 @@ class Packed:
         a row outside mask (a bool array of length rows, or row_mask() words; None: every row). 1 <= n <= NEAREST_MAX_N. fp32 values
         only (TkspmvError ERR_UNSUPPORTED otherwise)."""
         rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
-        xs = np.ascontiguousarray(vecs, dtype=np.float32)
-        xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
-        if xs.ndim != 2 or xs.shape[0] < 1 or xs.shape[1] != cols:
-            raise ValueError(f"vectors must be [count >= 1, {cols}]")
-        n = int(n)
-        words = None
-        if mask is not None:
-            words = _allow_words(rows, mask)
-            if words.shape != (max(1, (rows + 31) // 32),):
-                raise ValueError("mask must be bool[rows] or ceil(rows / 32) mask words")
+        xs, n, words = _vectors(vecs, cols), int(n), _mask_words(rows, mask, "mask")
         labels = np.empty((max(rows, 1), max(n, 1)), dtype=np.uint32)
         scores = np.empty((max(rows, 1), max(n, 1)), dtype=np.float32)
         _lib.check(_lib.lib().tkspmv_packed_nearest(self._h, _lib.f32p(xs), int(xs.shape[0]), n, _lib.u32p(words), _lib.u32p(labels), _lib.f32p(scores)))
@@ -778,11 +778,7 @@ class Packed:
         matrix reports (SpMV.col_stats): a walk over the packet stream, placeholders and padding dropped. fp32 values only
         (TkspmvError ERR_UNSUPPORTED otherwise); ERR_INVALID for a kind outside 0..2."""
         rows, cols = int(self.info()["rows"]), int(self.info()["cols"])
-        words = None
-        if allow is not None:
-            words = _allow_words(rows, allow)
-            if words.shape != (max(1, (rows + 31) // 32),):
-                raise ValueError("allow must be bool[rows] or ceil(rows / 32) mask words")
+        words = _mask_words(rows, allow, "allow")
         out = np.empty(max(cols, 1), dtype=np.uint32)
         _lib.check(_lib.lib().tkspmv_packed_col_stats(self._h, int(kind), _lib.u32p(words), _lib.ptr(out.ctypes.data)))
         out = out[:cols]

@@ -411,3 +411,62 @@ def test_one_shot_helper(pkg):
     eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=8, device=0)
     _same((labels, scores), eng.nearest(xs, 2, mask), "nearest_spmv")
     eng.close()
+
+
+def test_host_forms_interleaved_on_one_engine(pkg):
+    """nearest and assign in turn on ONE engine, each call with another list length and another number of vectors -- the smallest
+    sequence in which result arrays sized for one n, or a vector chunk sized for one count, are used again for another. Rows without
+    entries, rows on which every vector ties and rows outside the mask are among the 300."""
+    rng = np.random.default_rng(81)
+    rows, cols, per = 300, 1024, 6
+    keep = np.ones(rows, dtype=bool)
+    keep[[0, 7, 150, 299]] = False  # rows without entries: the first, the last, two in between
+    tied = np.arange(10, 15)  # one entry each, in column 0, where every vector holds 1.0
+    keep[tied] = False
+    r = np.repeat(np.flatnonzero(keep), per)
+    r, c, v = np.concatenate([r, tied]), np.concatenate([rng.integers(1, cols, r.size), np.zeros(tied.size)]), np.concatenate([rng.standard_normal(r.size), np.full(tied.size, 0.5)])
+    by_row = np.argsort(r, kind="stable")
+    m = coo(pkg, rows, cols, r[by_row], c[by_row], v[by_row])
+    xs = _xs(40, cols, 82)
+    xs[:, 0] = 1.0
+    xs[35] = xs[1]  # a tie across passes
+    mask = np.ones(rows, dtype=bool)
+    mask[[7, 12, 20]] = False  # an empty row, a tied row and an ordinary one
+    eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=4, device=0)
+    packed = _packed_like(pkg, eng, m)
+
+    def assign(count, label):
+        (gl, gb), (wl, wb) = eng.assign(xs[:count]), packed.assign(xs[:count])
+        _same((gl[:, None], gb[:, None]), (wl[:, None], wb[:, None]), label)
+        return gl
+
+    labels, _ = _check_engine(pkg, eng, m, xs[:3], 4, "nearest(n=4), 3 vectors", packed)
+    assert np.all(labels[tied] == np.array([0, 1, 2, NONE], dtype=np.uint32)) and np.all(labels[0] == labels[tied[0]])
+    a40 = assign(40, "assign, 40 vectors: three passes")
+    assert np.all(a40[tied] == 0) and not np.any(a40 == 35) and np.any(a40 == 1) and np.any(a40 > 31)
+    labels, _ = _check_engine(pkg, eng, m, xs[:17], 2, "nearest(n=2, mask), 17 vectors", packed, mask)
+    assert np.all(labels[~mask] == NONE) and np.all(labels[11] == np.array([0, 1], dtype=np.uint32))
+    assert np.all(assign(1, "assign, 1 vector") == 0)
+    labels, _ = _check_engine(pkg, eng, m, xs, 1, "nearest(n=1), 40 vectors", packed)
+    assert np.array_equal(labels[:, 0], a40)
+    eng.close()
+
+
+def test_host_forms_across_the_vector_chunk(pkg):
+    """One vector more than the host forms upload at once (64 MiB: 1024 vectors of 16384 columns): the second chunk holds vector 1024
+    alone, which merges with the first chunk's results as vector 1024. It is a copy of vector 3, so a tie crosses the chunk
+    boundary and goes to 3."""
+    rng = np.random.default_rng(91)
+    rows, cols, per, count = 96, 16384, 5, 1025
+    m = coo(pkg, rows, cols, np.repeat(np.arange(rows), per), rng.integers(0, cols, rows * per), rng.standard_normal(rows * per))
+    xs = rng.standard_normal((count, cols), dtype=np.float32)
+    xs[3] *= 8.0  # the best vector of many rows ...
+    xs[1024] = xs[3]  # ... and its copy behind the boundary
+    eng = pkg.SpMV(m.row, m.col, m.val, m.rows, m.cols, k=4, device=0)
+    packed = _packed_like(pkg, eng, m)
+    (gl, gb), (wl, wb) = eng.assign(xs), packed.assign(xs)
+    _same((gl[:, None], gb[:, None]), (wl[:, None], wb[:, None]), "assign, 1025 vectors")
+    assert np.count_nonzero(gl == 3) >= 8 and not np.any(gl == 1024)
+    labels, _ = _check_engine(pkg, eng, m, xs, 2, "nearest(n=2), 1025 vectors", packed)
+    assert np.array_equal(labels[:, 0], gl) and np.all(labels[gl == 3, 1] == 1024) and np.all(labels[labels[:, 1] == 1024, 0] == 3)
+    eng.close()

@@ -1,6 +1,6 @@
 // nearest_sanitize.cpp -- a stand-alone host program for the sanitizers: the host twin of nearest_kernel (packed_nearest;
 // csrc/packed_host.cpp) on generated matrices, with and without an allow-mask, for every list length and for counts around it, checked
-// against a stable sort of packed_score_rows' scores. No GPU, no Python. Build and run once on the CPU (from the repository's root):
+// against a stable sort of packed_score_rows' scores; and packed_assign, which calls it, with and without `best`. No GPU, no Python. Build and run once on the CPU (from the repository's root):
 //   g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -o /tmp/nearest_sanitize \
 //       tools/nearest_sanitize.cpp approximate-spmv-topk_amd/csrc/{packed_host,wbscsr,host_utils,options}.cpp -pthread && /tmp/nearest_sanitize
 // Exit status 0 and "nearest_sanitize: ok" when the twin equals the sorted scores and no sanitizer spoke.
@@ -82,6 +82,23 @@ static int one_matrix(uint32_t rows, uint32_t cols, uint32_t C, uint32_t hint, u
                     }
                 }
             }
+    // packed_assign is packed_nearest's lists of one entry: with best given and with best = NULL (the scores then go to an array of
+    // the call), exactly rows words each, equal to the first of the sorted scores
+    for (const int32_t count : {1, 5, 20})
+        for (const bool with_best : {true, false}) {
+            std::vector<uint32_t> labels((size_t)rows + 1u, 0xAAAAAAAAu);
+            std::vector<float> best((size_t)rows + 1u, -7.0f);
+            if (packed_assign(pm, xs.data(), count, labels.data(), with_best ? best.data() : nullptr, err) != TKSPMV_OK) return fail(err.c_str());
+            if (labels.back() != 0xAAAAAAAAu || best.back() != -7.0f) return fail("packed_assign wrote behind its outputs");
+            for (uint32_t r = 0; r < rows; ++r) {
+                int32_t first = 0;
+                for (int32_t q = 1; q < count; ++q)
+                    if (y[(size_t)q * rows + r] > y[(size_t)first * rows + r]) first = q;
+                const float want_s = with_best ? y[(size_t)first * rows + r] : -7.0f;
+                if (labels[r] != (uint32_t)first || std::memcmp(&best[r], &want_s, 4) != 0) return fail("packed_assign differs from the first of packed_score_rows' scores");
+                mix += labels[r];
+            }
+        }
     return 0;
 }
 
