@@ -104,7 +104,7 @@ class Match(C.Structure):
 # Every symbol include/tkspmv.h declares; tests check the library exports all of them.
 EXPORTED_SYMBOLS = [
     "tkspmv_create", "tkspmv_destroy", "tkspmv_get_info", "tkspmv_set_query", "tkspmv_set_query_device",
-    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_set_boost", "tkspmv_enqueue_boosted", "tkspmv_run_boosted", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_match", "tkspmv_run_match", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_enqueue_row_stats", "tkspmv_row_stats", "tkspmv_set_boost_cosine", "tkspmv_enqueue_assign", "tkspmv_assign", "tkspmv_enqueue_nearest", "tkspmv_nearest", "tkspmv_enqueue_label_sums", "tkspmv_enqueue_sums_close", "tkspmv_sums_exponent", "tkspmv_label_sums", "tkspmv_enqueue_col_stats", "tkspmv_col_stats", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
+    "tkspmv_run", "tkspmv_enqueue", "tkspmv_enqueue_many", "tkspmv_enqueue_batch", "tkspmv_enqueue_filtered", "tkspmv_set_filter", "tkspmv_set_groups", "tkspmv_enqueue_grouped", "tkspmv_run_grouped", "tkspmv_enqueue_after", "tkspmv_run_after", "tkspmv_set_boost", "tkspmv_enqueue_boosted", "tkspmv_run_boosted", "tkspmv_enqueue_boosted_range", "tkspmv_run_boosted_range", "tkspmv_enqueue_boosted_facets", "tkspmv_run_boosted_facets", "tkspmv_enqueue_boosted_grouped", "tkspmv_run_boosted_grouped", "tkspmv_enqueue_range", "tkspmv_enqueue_facets", "tkspmv_run_facets", "tkspmv_run_range", "tkspmv_enqueue_match", "tkspmv_run_match", "tkspmv_enqueue_row_vectors", "tkspmv_row_vectors", "tkspmv_run_similar", "tkspmv_enqueue_score_rows", "tkspmv_score_rows", "tkspmv_enqueue_row_stats", "tkspmv_row_stats", "tkspmv_set_boost_cosine", "tkspmv_enqueue_assign", "tkspmv_assign", "tkspmv_enqueue_nearest", "tkspmv_nearest", "tkspmv_enqueue_label_sums", "tkspmv_enqueue_sums_close", "tkspmv_sums_exponent", "tkspmv_label_sums", "tkspmv_enqueue_col_stats", "tkspmv_col_stats", "tkspmv_synchronize", "tkspmv_read", "tkspmv_result_device", "tkspmv_scores", "tkspmv_debug_trace", "tkspmv_debug_counters",
     "tkspmv_time_queries", "tkspmv_time_host_loop", "tkspmv_time_query_batches", "tkspmv_time_stream_read", "tkspmv_enqueue_multi", "tkspmv_time_multi", "tkspmv_profile", "tkspmv_last_error", "tkspmv_device_count", "tkspmv_mtx_read", "tkspmv_mtx_free",
     "tkspmv_mtx_write", "tkspmv_sample_vector", "tkspmv_generate", "tkspmv_generate_rows", "tkspmv_generate_degrees", "tkspmv_options_parse", "tkspmv_pack", "tkspmv_pack_device",
     "tkspmv_sell_roundtrip", "tkspmv_sell_pack_device_check", "tkspmv_packed_info", "tkspmv_packed_decode", "tkspmv_packed_raw", "tkspmv_packed_get_row", "tkspmv_packed_score_rows", "tkspmv_packed_row_stats", "tkspmv_packed_assign", "tkspmv_packed_nearest", "tkspmv_packed_label_sums", "tkspmv_packed_sums_exponent", "tkspmv_sums_close_host", "tkspmv_quantise", "tkspmv_packed_col_stats", "tkspmv_packed_free", "tkspmv_wave_partitions", "tkspmv_packed_save", "tkspmv_packed_load",
@@ -154,6 +154,12 @@ def lib():
     L.tkspmv_set_boost.argtypes = [vp, f32p, f32p]
     L.tkspmv_enqueue_boosted.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.tkspmv_run_boosted.argtypes = [vp, C.POINTER(Cursor), C.c_int32, u32p, f32p, C.POINTER(C.c_int32), u32p, C.POINTER(Cursor)]
+    L.tkspmv_enqueue_boosted_range.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_uint32, vp, vp]
+    L.tkspmv_run_boosted_range.argtypes = [vp, C.c_float, C.c_int32, u32p, f32p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.tkspmv_enqueue_boosted_facets.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, vp, vp]
+    L.tkspmv_run_boosted_facets.argtypes = [vp, C.c_float, C.c_int32, u32p, C.POINTER(FacetBest), C.POINTER(C.c_uint64)]
+    L.tkspmv_enqueue_boosted_grouped.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.tkspmv_run_boosted_grouped.argtypes = [vp, C.c_int32, u32p, f32p, u32p, C.POINTER(C.c_int32)]
     L.tkspmv_enqueue_range.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_uint32, vp, vp]
     L.tkspmv_run_range.argtypes = [vp, C.c_float, C.c_int32, u32p, f32p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.tkspmv_enqueue_facets.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, vp, vp]

@@ -140,6 +140,32 @@ int tkspmv_run_boosted(tkspmv_t *h, const tkspmv_cursor *cursor, int32_t use_fil
                        tkspmv_cursor *next) {
     ENGINE_CALL(run_boosted(cursor, use_filter, idx, val, n, total, next, err))
 }
+int tkspmv_enqueue_boosted_range(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                 const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                                 uint32_t capacity, uint32_t *dev_counts, void *stream) {
+    ENGINE_CALL(enqueue_boosted_range(dev_xs, count, dev_weight, dev_bias, boost_stride, dev_thresholds, dev_mask, mask_stride_words, dev_idx, dev_val, capacity,
+                                      dev_counts, stream, err))
+}
+int tkspmv_run_boosted_range(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count) {
+    ENGINE_CALL(run_boosted_range(threshold, use_filter, idx, val, capacity, count, err))
+}
+int tkspmv_enqueue_boosted_facets(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                  const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, const uint32_t *dev_labels, uint32_t n_bins,
+                                  uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream) {
+    ENGINE_CALL(enqueue_boosted_facets(dev_xs, count, dev_weight, dev_bias, boost_stride, dev_thresholds, dev_mask, mask_stride_words, dev_labels, n_bins, dev_counts,
+                                       dev_best, dev_totals, stream, err))
+}
+int tkspmv_run_boosted_facets(tkspmv_t *h, float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total) {
+    ENGINE_CALL(run_boosted_facets(threshold, use_filter, counts, best, total, err))
+}
+int tkspmv_enqueue_boosted_grouped(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                   const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp, uint32_t *dev_n,
+                                   void *stream) {
+    ENGINE_CALL(enqueue_boosted_grouped(dev_xs, count, dev_weight, dev_bias, boost_stride, dev_mask, mask_stride_words, dev_idx, dev_val, dev_grp, dev_n, stream, err))
+}
+int tkspmv_run_boosted_grouped(tkspmv_t *h, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n) {
+    ENGINE_CALL(run_boosted_grouped(use_filter, idx, val, grp, n, err))
+}
 int tkspmv_enqueue_range(tkspmv_t *h, const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask,
                          int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream) {
     ENGINE_CALL(enqueue_range(dev_xs, count, dev_thresholds, dev_mask, mask_stride_words, dev_idx, dev_val, capacity, dev_counts, stream, err))

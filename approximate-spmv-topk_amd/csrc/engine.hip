@@ -61,6 +61,7 @@
 #include "kernels/group_select.hpp"
 #include "kernels/after_select.hpp"
 #include "kernels/boost_cut.hpp"
+#include "kernels/boost_forms.hpp"
 
 namespace tkspmv {
 
@@ -573,6 +574,8 @@ struct EngineImpl {
         // SelectWords; word 1024 counts the non-empty groups (zeroed in front of every query, with the histogram)
         uint32_t *d_gwords = nullptr;
         static constexpr uint32_t W_NONEMPTY = 1024;
+        // boosted grouped queries: boost_cut_kernel's count goes here (it runs for its transform alone: nobody reads or zeroes the word)
+        static constexpr uint32_t W_BOOST_SINK = 1040;
         uint32_t *d_gout_grp = nullptr, *d_gout_n = nullptr;  // engine-owned [k] group ids and n ("the last query wins")
     } grouped;
 
@@ -602,7 +605,16 @@ struct EngineImpl {
     struct BoostSpec {
         const float *weight, *bias;
         size_t stride;
+        const float *weight_of(int i) const { return weight ? weight + (size_t)i * stride : nullptr; }
+        const float *bias_of(int i) const { return bias ? bias + (size_t)i * stride : nullptr; }
     };
+    // Both of a query's arrays (where given) start at a multiple of 16 bytes: the kernels load a lane's four rows at once (NULL counts as aligned).
+    static uint32_t boost_wide(const float *weight, const float *bias) {
+        return ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias)) & 15u) == 0u ? 1u : 0u;
+    }
+    // Boosted range, facet and grouped queries (tkspmv_enqueue_boosted_range / _facets / _grouped; boosted_hits_kernel,
+    // boosted_bins_kernel) own nothing: the first two score into the search-after path's array (ensure_after: d_ay) and read it with one
+    // array kernel, the third runs boost_cut_kernel over the grouped path's array in front of that path's own launches.
 
     // Diagnostics: the statistics block (d_stats: setup_host_boundary; every selection counts there), the options STATS / STAMPS /
     // TRACE / WG_TIMES (setup_diagnostics), which make the engine launch the instantiations that carry the tracing and ablation
@@ -1349,8 +1361,10 @@ struct EngineImpl {
     // select over the groups and the selection kernel ranking the groups' representatives. No exchange set, record, verdict, carried
     // threshold or deferred selection is read or written: the SpMV-only kernels touch none, and the selection kernel is given this
     // path's own words. Only mat.launch_counter moves.
+    // With a boost (tkspmv_enqueue_boosted_grouped) boost_cut_kernel runs behind the SpMV-only kernel, from the top (no cursor): it
+    // writes the transformed scores in place, and everything behind it reads them. Its count goes to a word of this path nobody reads.
     void launch_grouped(const float *xs, int n, const uint32_t *mask, size_t stride, uint32_t *out_idx, float *out_val, uint32_t *out_grp,
-                        size_t out_stride, uint32_t *out_n, size_t n_stride, hipStream_t s) {
+                        size_t out_stride, uint32_t *out_n, size_t n_stride, hipStream_t s, const BoostSpec *boost = nullptr) {
         using namespace grouped_kernels;
         const Grouped &Q = grouped;
         GroupParams G{};
@@ -1377,6 +1391,17 @@ struct EngineImpl {
         for (int i = 0; i < n; ++i) {
             const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
             launch_scores(xs + (size_t)i * desc.cols, s, Q.d_gy, mask ? &F : nullptr);
+            if (boost) {
+                using namespace boost_kernels;
+                AfterParams A{};
+                A.y = Q.d_gy;
+                A.total = Q.d_gwords + Grouped::W_BOOST_SINK;
+                A.rows = desc.rows;
+                A.first_row = desc.first_row;
+                A.kmin = G.kmin;
+                const BoostParams B{A, boost->weight_of(i), boost->bias_of(i), boost_wide(boost->weight_of(i), boost->bias_of(i))};
+                hipLaunchKernelGGL(boost_cut_kernel, dim3(rows_grid(desc.rows, BOOST_THREADS, BOOST_LANE_ROWS)), dim3(BOOST_THREADS), 0, s, B);
+            }
             (void)hipMemsetAsync(Q.d_gwords, 0, (Grouped::W_NONEMPTY + 1u) * 4, s);  // (the histogram and the non-empty-group counter)
             hipLaunchKernelGGL(group_best_kernel, dim3(best_grid), dim3(GROUP_THREADS), 0, s, G);
             hipLaunchKernelGGL(group_split_kernel, dim3(split_grid), dim3(GROUP_THREADS), 0, s, G);
@@ -1440,8 +1465,7 @@ struct EngineImpl {
             (void)hipMemsetAsync(Q.d_awords, 0, 4 * 256 * 4, s);  // (the histogram alone: after_finish_kernel zeroes W_TOTAL itself)
             A.cursor = cursors ? reinterpret_cast<const AfterCursor *>(cursors + i) : nullptr;
             if (boost) {
-                BoostParams B{A, boost->weight ? boost->weight + (size_t)i * boost->stride : nullptr, boost->bias ? boost->bias + (size_t)i * boost->stride : nullptr, 0u};
-                B.wide = ((reinterpret_cast<uintptr_t>(B.weight) | reinterpret_cast<uintptr_t>(B.bias)) & 15u) == 0u ? 1u : 0u;  // (NULL counts as aligned)
+                const BoostParams B{A, boost->weight_of(i), boost->bias_of(i), boost_wide(boost->weight_of(i), boost->bias_of(i))};
                 hipLaunchKernelGGL(boost_cut_kernel, dim3(cut_grid), dim3(BOOST_THREADS), 0, s, B);
             } else {
                 hipLaunchKernelGGL(after_cut_kernel, dim3(cut_grid), dim3(AFTER_THREADS), 0, s, A);
@@ -1456,6 +1480,71 @@ struct EngineImpl {
             Z.total_out = out_total ? out_total + i : nullptr;
             Z.next = out_next ? reinterpret_cast<AfterCursor *>(out_next + i) : nullptr;
             hipLaunchKernelGGL(after_finish_kernel, dim3(1), dim3(AFTER_FINISH_THREADS), 0, s, Z);
+        }
+    }
+    // What the two boosted threshold forms share per query: the SpMV-only kernel into the search-after path's array, and the array
+    // kernel's view of it (the query's boost and threshold).
+    boost_forms::ScanParams boosted_scan(const float *xs, int i, const float *thresholds, const BoostSpec &boost, const uint32_t *mask, size_t stride,
+                                         hipStream_t s) {
+        const FilterParams F{mask ? mask + (size_t)i * stride : nullptr, mask_words()};
+        launch_scores(xs + (size_t)i * desc.cols, s, after.d_ay, mask ? &F : nullptr);
+        boost_forms::ScanParams S{};
+        S.y = after.d_ay;
+        S.weight = boost.weight_of(i);
+        S.bias = boost.bias_of(i);
+        S.threshold = thresholds + i;
+        S.wide = boost_wide(S.weight, S.bias);
+        S.rows = desc.rows;
+        S.first_row = desc.first_row;
+        return S;
+    }
+    // n boosted range queries (launch_range's queries and outputs, read on the boosted score of launch_after's boost), complete in stream
+    // order when this returns: the counters are zeroed in front, then per query the SpMV-only kernel and boosted_hits_kernel over its
+    // scores. No exchange set, record, verdict, carried threshold or deferred selection is read or written: only mat.launch_counter moves.
+    void launch_boosted_range(const float *xs, int n, const float *thresholds, const BoostSpec &boost, const uint32_t *mask, size_t stride, uint32_t *idx,
+                              float *val, uint32_t capacity, uint32_t *counts, hipStream_t s) {
+        using namespace boost_forms;
+        (void)hipMemsetAsync(counts, 0, (size_t)n * 4, s);
+        const uint32_t grid_rows = rows_grid(desc.rows, BOOST_THREADS, BOOST_LANE_ROWS);
+        for (int i = 0; i < n; ++i) {
+            HitsParams H{};
+            H.S = boosted_scan(xs, i, thresholds, boost, mask, stride, s);
+            H.idx = idx ? idx + (size_t)i * capacity : nullptr;
+            H.val = val ? val + (size_t)i * capacity : nullptr;
+            H.capacity = capacity;
+            H.count = counts + i;
+            hipLaunchKernelGGL(boosted_hits_kernel, dim3(grid_rows), dim3(BOOST_THREADS), 0, s, H);
+        }
+    }
+    // n boosted facet queries (launch_facets' queries and outputs, read on the boosted score), complete in stream order when this
+    // returns: counts, best and totals are zeroed in front, then per query the SpMV-only kernel and boosted_bins_kernel, then
+    // launch_facets' closing launch. The regime: calls of at most min(FACET_LDS_BINS, BINS_LDS_CAP) bins deposit in LDS -- on a grid of
+    // two workgroups per CU where every workgroup sweeps more than 256 bins --, calls of more bins with global atomics.
+    void launch_boosted_facets(const float *xs, int n, const float *thresholds, const BoostSpec &boost, const uint32_t *mask, size_t stride,
+                               const uint32_t *labels, uint32_t n_bins, uint32_t *counts, tkspmv_facet_best *best, uint32_t *totals, hipStream_t s) {
+        using namespace boost_forms;
+        const size_t n_out = (size_t)n * n_bins;
+        if (n_out) (void)hipMemsetAsync(counts, 0, n_out * 4, s);
+        if (best && n_out) (void)hipMemsetAsync(best, 0, n_out * 8, s);
+        if (totals) (void)hipMemsetAsync(totals, 0, (size_t)n * 4, s);
+        const bool in_lds = n_bins <= std::min(range.facet_lds_bins, BINS_LDS_CAP);
+        uint32_t grid_rows = rows_grid(desc.rows, BOOST_THREADS, BOOST_LANE_ROWS);
+        if (in_lds && n_bins > 256u) grid_rows = std::min(grid_rows, std::max(1u, info.num_cus) * 2u);
+        for (int i = 0; i < n; ++i) {
+            BinsParams B{};
+            B.S = boosted_scan(xs, i, thresholds, boost, mask, stride, s);
+            B.labels = labels;
+            B.wide_labels = (reinterpret_cast<uintptr_t>(labels) & 15u) == 0u ? 1u : 0u;
+            B.n_bins = n_bins;
+            B.in_lds = in_lds ? 1u : 0u;
+            B.counts = counts + (size_t)i * n_bins;
+            B.best = best ? reinterpret_cast<unsigned long long *>(best) + (size_t)i * n_bins : nullptr;
+            B.total = totals ? totals + i : nullptr;
+            hipLaunchKernelGGL(boosted_bins_kernel, dim3(grid_rows), dim3(BOOST_THREADS), in_lds ? (size_t)n_bins * 12u : 0u, s, B);
+        }
+        if (best && n_out) {
+            const uint32_t cgrid = (uint32_t)std::min<size_t>((n_out + 255u) / 256u, 16384u);
+            hipLaunchKernelGGL(facet_close_kernel, dim3(cgrid), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(best), (unsigned long long)n_out);
         }
     }
     // The fused launch hands its result to the host itself: the pinned block, a new epoch, the start stamp (tkspmv_run).
@@ -2824,12 +2913,26 @@ int Engine::set_groups(const uint32_t *host_groups, uint32_t n_groups, std::stri
     return TKSPMV_OK;
 }
 
-int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
-                            float *dev_val, uint32_t *dev_grp, uint32_t *dev_n, void *stream, std::string &err) {
-    EngineImpl &m = *impl_;
-    if (count < 1 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) || (dev_idx == nullptr) != (dev_grp == nullptr))
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_grouped (count >= 1, mask_stride_words >= 0, dev_idx, dev_val and dev_grp all given or all NULL)");
+// The boost of a boosted call: the caller's arrays, or -- both NULL -- the installed pair, one for every query (STATE if none is).
+static int resolve_boost(const EngineImpl &m, const float *dev_weight, const float *dev_bias, int64_t boost_stride, EngineImpl::BoostSpec &spec, std::string &err) {
+    spec = EngineImpl::BoostSpec{dev_weight, dev_bias, (size_t)boost_stride};
+    if (dev_weight || dev_bias) return TKSPMV_OK;
+    if (!m.boost.have_weight && !m.boost.have_bias) return fail(err, TKSPMV_ERR_STATE, "no boost installed (call tkspmv_set_boost first, or give dev_weight / dev_bias)");
+    spec = EngineImpl::BoostSpec{m.boost.have_weight ? m.boost.d_weight : nullptr, m.boost.have_bias ? m.boost.d_bias : nullptr, 0u};
+    return TKSPMV_OK;
+}
+
+// Grouped queries, plain or boosted: the argument checks, the error order and the launch are one.
+static int enqueue_groups(EngineImpl &m, const char *what, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                          bool boosted, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp,
+                          uint32_t *dev_n, void *stream, std::string &err) {
+    if (count < 1 || boost_stride < 0 || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) || (dev_idx == nullptr) != (dev_grp == nullptr))
+        return fail(err, TKSPMV_ERR_INVALID, std::string("bad arguments to ") + what + " (count >= 1, strides >= 0, dev_idx, dev_val and dev_grp all given or all NULL)");
+    if (boosted && !dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
     if (const char *why = m.grouped_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, why);
+    EngineImpl::BoostSpec spec{};
+    if (boosted)
+        if (const int st = resolve_boost(m, dev_weight, dev_bias, boost_stride, spec, err)) return st;
     if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no group labels installed (call tkspmv_set_groups first)");
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     const bool own = dev_idx == nullptr;  // the engine-owned result pair, group ids and n: the last query wins
@@ -2838,16 +2941,30 @@ int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *
         HIP_TRY(m.order_x(dev_xs, s));
         const size_t k = own ? 0u : (size_t)m.desc.k;
         m.launch_grouped(dev_xs, count, dev_mask, m.stride_of(dev_mask, mask_stride_words), own ? m.host.d_out_idx : dev_idx, own ? m.host.d_out_val : dev_val,
-                         own ? m.grouped.d_gout_grp : dev_grp, k, dev_n ? dev_n : m.grouped.d_gout_n, dev_n ? 1u : 0u, s);
+                         own ? m.grouped.d_gout_grp : dev_grp, k, dev_n ? dev_n : m.grouped.d_gout_n, dev_n ? 1u : 0u, s, boosted ? &spec : nullptr);
         return TKSPMV_OK;
     });
 }
 
-int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
-    EngineImpl &m = *impl_;
+int Engine::enqueue_grouped(const float *dev_xs, int32_t count, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
+                            float *dev_val, uint32_t *dev_grp, uint32_t *dev_n, void *stream, std::string &err) {
+    return enqueue_groups(*impl_, "enqueue_grouped", dev_xs, count, nullptr, nullptr, 0, false, dev_mask, mask_stride_words, dev_idx, dev_val, dev_grp, dev_n, stream, err);
+}
+
+int Engine::enqueue_boosted_grouped(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                    const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp, uint32_t *dev_n,
+                                    void *stream, std::string &err) {
+    return enqueue_groups(*impl_, "enqueue_boosted_grouped", dev_xs, count, dev_weight, dev_bias, boost_stride, true, dev_mask, mask_stride_words, dev_idx, dev_val,
+                          dev_grp, dev_n, stream, err);
+}
+
+// The host forms of the two: the installed vector, mask and labels (and boost); waits.
+static int run_groups(EngineImpl &m, bool boosted, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
     const uint32_t *mask = nullptr;
     if (const int st = m.installed_mask(use_filter, mask, err)) return st;
-    if (const int st = enqueue_grouped(nullptr, 1, mask, 0, nullptr, nullptr, nullptr, nullptr, nullptr, err)) return st;
+    if (const int st = enqueue_groups(m, boosted ? "run_boosted_grouped" : "run_grouped", nullptr, 1, nullptr, nullptr, 0, boosted, mask, 0, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr, err))
+        return st;
     if (const int st = m.finish_host_form(err)) return st;
     const size_t k = (size_t)m.desc.k;
     uint32_t found = 0u;
@@ -2859,6 +2976,14 @@ int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t 
     return TKSPMV_OK;
 }
 
+int Engine::run_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
+    return run_groups(*impl_, false, use_filter, idx, val, grp, n, err);
+}
+
+int Engine::run_boosted_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err) {
+    return run_groups(*impl_, true, use_filter, idx, val, grp, n, err);
+}
+
 // Search-after pages, plain (boost NULL, both arrays NULL) or boosted: the argument checks, the error order and the launch are one.
 static int enqueue_pages(EngineImpl &m, const char *what, const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
                          bool boosted, const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx,
@@ -2867,11 +2992,9 @@ static int enqueue_pages(EngineImpl &m, const char *what, const float *dev_xs, i
         return fail(err, TKSPMV_ERR_INVALID, std::string("bad arguments to ") + what + " (count >= 1, strides >= 0, dev_idx and dev_val both given or both NULL)");
     if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
     if (const char *why = m.grouped_unsupported(dev_mask != nullptr)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("search-after queries take the grouped queries' route: ") + why);
-    EngineImpl::BoostSpec spec{dev_weight, dev_bias, (size_t)boost_stride};
-    if (boosted && !dev_weight && !dev_bias) {  // both NULL: the installed boost, one pair for every query
-        if (!m.boost.have_weight && !m.boost.have_bias) return fail(err, TKSPMV_ERR_STATE, "no boost installed (call tkspmv_set_boost first, or give dev_weight / dev_bias)");
-        spec = EngineImpl::BoostSpec{m.boost.have_weight ? m.boost.d_weight : nullptr, m.boost.have_bias ? m.boost.d_bias : nullptr, 0u};
-    }
+    EngineImpl::BoostSpec spec{};
+    if (boosted)
+        if (const int st = resolve_boost(m, dev_weight, dev_bias, boost_stride, spec, err)) return st;
     if (const int st = m.resolve_query(dev_xs, count, err)) return st;
     const bool own = dev_idx == nullptr;  // the engine-owned result pair: the last query wins
     return enqueue_on(m, stream, own, err, [&](hipStream_t s) -> int {
@@ -2973,13 +3096,46 @@ int Engine::enqueue_range(const float *dev_xs, int32_t count, const float *dev_t
     });
 }
 
-int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err) {
+// A boosted threshold form's own checks, in tkspmv_enqueue_boosted's order: UNSUPPORTED by the grouped queries' rule, then STATE for
+// a missing boost.
+static int boosted_form_scope(const EngineImpl &m, bool with_mask, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                              EngineImpl::BoostSpec &spec, std::string &err) {
+    if (const char *why = m.grouped_unsupported(with_mask)) return fail(err, TKSPMV_ERR_UNSUPPORTED, std::string("boosted thresholds take the grouped queries' route: ") + why);
+    return resolve_boost(m, dev_weight, dev_bias, boost_stride, spec, err);
+}
+
+int Engine::enqueue_boosted_range(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                  const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                                  uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
+    if (count < 1 || boost_stride < 0 || !dev_thresholds || !dev_counts || mask_stride_words < 0 || (dev_idx == nullptr) != (dev_val == nullptr) ||
+        (capacity > 0u && !dev_idx) || (capacity == 0u && dev_idx))
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_boosted_range (count >= 1, thresholds and counts given, strides >= 0, dev_idx and "
+                                             "dev_val both given with capacity > 0 or both NULL with capacity = 0)");
+    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+    EngineImpl::BoostSpec spec{};
+    if (const int st = boosted_form_scope(m, dev_mask != nullptr, dev_weight, dev_bias, boost_stride, spec, err)) return st;
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
+        HIP_TRY(m.ensure_after());
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_boosted_range(dev_xs, count, dev_thresholds, spec, dev_mask, m.stride_of(dev_mask, mask_stride_words), dev_idx, dev_val, capacity, dev_counts, s);
+        return TKSPMV_OK;
+    });
+}
+
+// The host forms of the two range calls: the installed vector (and boost), a host threshold, the installed mask; waits and sorts.
+static int run_range_form(Engine &e, EngineImpl &m, bool boosted, float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count,
+                          std::string &err) {
+    if (!boosted && m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
     if (!count || (idx == nullptr) != (val == nullptr) || (capacity > 0u && !idx) || (capacity == 0u && idx))
-        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to run_range (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)");
+        return fail(err, TKSPMV_ERR_INVALID, std::string("bad arguments to ") + (boosted ? "run_boosted_range" : "run_range") +
+                                                 " (count given, idx and val both given with capacity > 0 or both NULL with capacity = 0)");
     const uint32_t *mask = nullptr;
     if (const int st = m.installed_mask(use_filter, mask, err)) return st;
+    EngineImpl::BoostSpec spec{};
+    if (boosted)
+        if (const int st = boosted_form_scope(m, use_filter != 0, nullptr, nullptr, 0, spec, err)) return st;
     const float *installed = nullptr;
     if (const int st = m.resolve_query(installed, 1, err)) return st;
     HIP_TRY(hipSetDevice(m.device));
@@ -2989,8 +3145,11 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
         HIP_TRY(m.grow_scratch(m.range.range_cap, capacity, {{(void **)&m.range.d_range_idx, (size_t)capacity * 4}, {(void **)&m.range.d_range_val, (size_t)capacity * 4}}));
     }
     HIP_TRY(hipMemcpy(m.range.d_range_word, &threshold, 4, hipMemcpyHostToDevice));
-    if (const int st = enqueue_range(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word), mask, 0, capacity ? m.range.d_range_idx : nullptr,
-                                     capacity ? m.range.d_range_val : nullptr, capacity, m.range.d_range_word + 1, nullptr, err))
+    const float *const tau = reinterpret_cast<const float *>(m.range.d_range_word);
+    uint32_t *const d_idx = capacity ? m.range.d_range_idx : nullptr;
+    float *const d_val = capacity ? m.range.d_range_val : nullptr;
+    if (const int st = boosted ? e.enqueue_boosted_range(nullptr, 1, nullptr, nullptr, 0, tau, mask, 0, d_idx, d_val, capacity, m.range.d_range_word + 1, nullptr, err)
+                               : e.enqueue_range(nullptr, 1, tau, mask, 0, d_idx, d_val, capacity, m.range.d_range_word + 1, nullptr, err))
         return st;
     if (const int st = m.finish_host_form(err)) return st;
     uint32_t found = 0u;
@@ -3003,6 +3162,14 @@ int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float 
         sort_tuples(kept, idx, val);
     }
     return TKSPMV_OK;
+}
+
+int Engine::run_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err) {
+    return run_range_form(*this, *impl_, false, threshold, use_filter, idx, val, capacity, count, err);
+}
+
+int Engine::run_boosted_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err) {
+    return run_range_form(*this, *impl_, true, threshold, use_filter, idx, val, capacity, count, err);
 }
 
 int Engine::enqueue_facets(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
@@ -3028,11 +3195,41 @@ int Engine::enqueue_facets(const float *dev_xs, int32_t count, const float *dev_
     });
 }
 
-int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err) {
+int Engine::enqueue_boosted_facets(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                   const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, const uint32_t *dev_labels, uint32_t n_bins,
+                                   uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream, std::string &err) {
     EngineImpl &m = *impl_;
-    if (m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
+    if (count < 1 || boost_stride < 0 || !dev_thresholds || !dev_counts || mask_stride_words < 0 || (dev_labels != nullptr) != (n_bins != 0u) || n_bins > (1u << 30) ||
+        (reinterpret_cast<uintptr_t>(dev_best) & 7u) != 0u)
+        return fail(err, TKSPMV_ERR_INVALID, "bad arguments to enqueue_boosted_facets (count >= 1, thresholds and counts given, strides >= 0, dev_labels with "
+                                             "1 <= n_bins <= 2^30 or dev_labels = NULL with n_bins = 0, dev_best 8-byte aligned)");
+    if (!dev_xs && count != 1) return fail(err, TKSPMV_ERR_INVALID, "dev_xs = NULL takes the installed query vector: count must be 1");
+    EngineImpl::BoostSpec spec{};
+    if (const int st = boosted_form_scope(m, dev_mask != nullptr, dev_weight, dev_bias, boost_stride, spec, err)) return st;
+    if (const int st = m.resolve_query(dev_xs, count, err)) return st;
+    if (!dev_labels) {
+        if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no labels given and none installed (call tkspmv_set_groups first)");
+        dev_labels = m.grouped.d_groups;
+        n_bins = m.grouped.n_groups;
+    }
+    return enqueue_on(m, stream, false, err, [&](hipStream_t s) -> int {  // (no result pair is written: tkspmv_read's view stays)
+        HIP_TRY(m.ensure_after());
+        HIP_TRY(m.order_x(dev_xs, s));
+        m.launch_boosted_facets(dev_xs, count, dev_thresholds, spec, dev_mask, m.stride_of(dev_mask, mask_stride_words), dev_labels, n_bins, dev_counts, dev_best,
+                                dev_totals, s);
+        return TKSPMV_OK;
+    });
+}
+
+// The host forms of the two facet calls: the installed vector and labels (and boost), a host threshold, the installed mask; waits.
+static int run_facets_form(Engine &e, EngineImpl &m, bool boosted, float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total,
+                           std::string &err) {
+    if (!boosted && m.range_unsupported(err)) return TKSPMV_ERR_UNSUPPORTED;
     const uint32_t *mask = nullptr;
     if (const int st = m.installed_mask(use_filter, mask, err)) return st;
+    EngineImpl::BoostSpec spec{};
+    if (boosted)
+        if (const int st = boosted_form_scope(m, use_filter != 0, nullptr, nullptr, 0, spec, err)) return st;
     const float *installed = nullptr;
     if (const int st = m.resolve_query(installed, 1, err)) return st;
     if (!m.grouped.have_groups) return fail(err, TKSPMV_ERR_STATE, "no labels installed (call tkspmv_set_groups first)");
@@ -3044,8 +3241,11 @@ int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tk
         HIP_TRY(m.grow_scratch(m.range.facet_cap, n_bins, {{(void **)&m.range.d_facet_counts, (size_t)n_bins * 4}, {(void **)&m.range.d_facet_best, (size_t)n_bins * 8}}));
     }
     HIP_TRY(hipMemcpy(m.range.d_range_word + 2, &threshold, 4, hipMemcpyHostToDevice));
-    if (const int st = enqueue_facets(nullptr, 1, reinterpret_cast<const float *>(m.range.d_range_word + 2), mask, 0, nullptr, 0u, m.range.d_facet_counts,
-                                      best ? m.range.d_facet_best : nullptr, m.range.d_range_word + 3, nullptr, err))
+    const float *const tau = reinterpret_cast<const float *>(m.range.d_range_word + 2);
+    tkspmv_facet_best *const d_best = best ? m.range.d_facet_best : nullptr;
+    if (const int st = boosted ? e.enqueue_boosted_facets(nullptr, 1, nullptr, nullptr, 0, tau, mask, 0, nullptr, 0u, m.range.d_facet_counts, d_best,
+                                                          m.range.d_range_word + 3, nullptr, err)
+                               : e.enqueue_facets(nullptr, 1, tau, mask, 0, nullptr, 0u, m.range.d_facet_counts, d_best, m.range.d_range_word + 3, nullptr, err))
         return st;
     if (const int st = m.finish_host_form(err)) return st;
     uint32_t found = 0u;
@@ -3054,6 +3254,14 @@ int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tk
     if (counts) HIP_TRY(hipMemcpy(counts, m.range.d_facet_counts, (size_t)n_bins * 4, hipMemcpyDeviceToHost));
     if (best) HIP_TRY(hipMemcpy(best, m.range.d_facet_best, (size_t)n_bins * 8, hipMemcpyDeviceToHost));
     return TKSPMV_OK;
+}
+
+int Engine::run_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err) {
+    return run_facets_form(*this, *impl_, false, threshold, use_filter, counts, best, total, err);
+}
+
+int Engine::run_boosted_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err) {
+    return run_facets_form(*this, *impl_, true, threshold, use_filter, counts, best, total, err);
 }
 
 int Engine::enqueue_match(const uint32_t *dev_clauses, int64_t clause_stride_words, const tkspmv_match *dev_preds, int32_t count, const uint32_t *dev_mask,

@@ -55,6 +55,22 @@ class Engine {
                         uint32_t *dev_n, uint32_t *dev_total, tkspmv_cursor *dev_next, void *stream, std::string &err);
     int run_boosted(const tkspmv_cursor *cursor, int32_t use_filter, uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next,
                     std::string &err);
+    // Boosted range, facet and grouped queries (boosted_hits_kernel, boosted_bins_kernel; boost_cut_kernel in front of the grouped path):
+    // enqueue_range's, enqueue_facets' and enqueue_grouped's contracts read on enqueue_boosted's s', with its weight / bias / stride
+    // behind `count`. The first two run on the search-after path's scratch, the third on the grouped path's. The run_* forms are the
+    // host-side counterparts (installed vector, boost, mask and labels; wait).
+    int enqueue_boosted_range(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                              const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val,
+                              uint32_t capacity, uint32_t *dev_counts, void *stream, std::string &err);
+    int run_boosted_range(float threshold, int32_t use_filter, uint32_t *idx, float *val, uint32_t capacity, uint64_t *count, std::string &err);
+    int enqueue_boosted_facets(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                               const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words, const uint32_t *dev_labels, uint32_t n_bins,
+                               uint32_t *dev_counts, tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream, std::string &err);
+    int run_boosted_facets(float threshold, int32_t use_filter, uint32_t *counts, tkspmv_facet_best *best, uint64_t *total, std::string &err);
+    int enqueue_boosted_grouped(const float *dev_xs, int32_t count, const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                const uint32_t *dev_mask, int64_t mask_stride_words, uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp, uint32_t *dev_n,
+                                void *stream, std::string &err);
+    int run_boosted_grouped(int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n, std::string &err);
     // Range queries (range_kernel): every allowed row with entries that scores >= the query's threshold, unordered; run_range is
     // the host-side counterpart (installed vector, host threshold, waits, sorts).
     int enqueue_range(const float *dev_xs, int32_t count, const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,

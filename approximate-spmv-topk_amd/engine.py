@@ -209,11 +209,15 @@ class SpMV:
         row_mask() words; the query is then restricted to it), set_groups(groups) if given. Returns (values, indices, groups) of
         the groups that exist for the query, at most k, ordered like read_result."""
         self._install(vec, allow, groups)
+        return self._run_grouped(allow is not None)
+
+    def _run_grouped(self, use_filter, boosted=False):
         idx = np.zeros(self.k, dtype=np.uint32)
         val = np.zeros(self.k, dtype=np.float32)
         grp = np.zeros(self.k, dtype=np.uint32)
         n = C.c_int32(0)
-        _lib.check(_lib.lib().tkspmv_run_grouped(self._h, int(allow is not None), u32p(idx), f32p(val), u32p(grp), C.byref(n)))
+        run = _lib.lib().tkspmv_run_boosted_grouped if boosted else _lib.lib().tkspmv_run_grouped
+        _lib.check(run(self._h, int(use_filter), u32p(idx), f32p(val), u32p(grp), C.byref(n)))
         return val[:n.value], idx[:n.value], grp[:n.value]
 
     def enqueue_after(self, dev_xs, count, dev_cursors=0, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0, dev_n=0, dev_total=0, dev_next=0,
@@ -319,12 +323,13 @@ class SpMV:
         _lib.check(_lib.lib().tkspmv_enqueue_range(self._h, ptr(dev_xs), int(count), ptr(dev_thresholds), ptr(dev_mask), int(mask_stride),
                                                    ptr(dev_idx), ptr(dev_val), int(capacity), ptr(dev_counts), ptr(stream)))
 
-    def _run_range(self, threshold, use_filter, capacity):
+    def _run_range(self, threshold, use_filter, capacity, boosted=False):
         idx = np.zeros(max(capacity, 1), dtype=np.uint32)
         val = np.zeros(max(capacity, 1), dtype=np.float32)
         count = C.c_uint64(0)
-        _lib.check(_lib.lib().tkspmv_run_range(self._h, float(threshold), int(use_filter), u32p(idx) if capacity else None,
-                                               f32p(val) if capacity else None, int(capacity), C.byref(count)))
+        run = _lib.lib().tkspmv_run_boosted_range if boosted else _lib.lib().tkspmv_run_range
+        _lib.check(run(self._h, float(threshold), int(use_filter), u32p(idx) if capacity else None, f32p(val) if capacity else None, int(capacity),
+                       C.byref(count)))
         n = min(int(count.value), capacity)
         return val[:n], idx[:n], int(count.value)
 
@@ -338,6 +343,37 @@ class SpMV:
         if capacity is None:
             _, _, capacity = self._run_range(threshold, use_filter, 0)
         val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity))
+        return val, idx
+
+    def _install_boost(self, vec, allow, groups, weight, bias):
+        """The prologue of the boosted host-array forms: _install, then set_boost(weight, bias) if either is given (else the boost
+        installed before stays)."""
+        self._install(vec, allow, groups)
+        if weight is not None or bias is not None:
+            self.set_boost(weight, bias)
+
+    def enqueue_boosted_range(self, dev_xs, count, dev_thresholds, dev_counts, dev_weight=0, dev_bias=0, boost_stride=0, dev_idx=0, dev_val=0,
+                              capacity=0, dev_mask=0, mask_stride=0, stream=0):
+        """enqueue_range over boosted scores: query i reads dev_weight / dev_bias + i*boost_stride as in enqueue_boosted (either may
+        be 0; both 0: the boost installed by set_boost), and a row matches when its boosted score s' is above -inf and >=
+        dev_thresholds[i] (min_score plays no part). dev_counts[i] receives the number of matches; dev_idx / dev_val + i*capacity
+        the first min(count, capacity) of them as (row id, s'), in no particular order. Per query the scores kernel and one pass
+        over its scores. No host sync; one enqueue_after / enqueue_boosted / enqueue_boosted_range / enqueue_boosted_facets call in
+        flight at a time (they share their scratch)."""
+        _lib.check(_lib.lib().tkspmv_enqueue_boosted_range(self._h, ptr(dev_xs), int(count), ptr(dev_weight), ptr(dev_bias), int(boost_stride),
+                                                           ptr(dev_thresholds), ptr(dev_mask), int(mask_stride), ptr(dev_idx), ptr(dev_val),
+                                                           int(capacity), ptr(dev_counts), ptr(stream)))
+
+    def run_boosted_range(self, threshold, vec=None, allow=None, weight=None, bias=None, capacity=None):
+        """run_range over boosted scores: reset(vec) / set_filter(allow) if given, set_boost(weight, bias) if either is given (else
+        the boost installed before, e.g. by set_cosine()), then every row whose boosted score is >= threshold. Returns (values,
+        indices) sorted like read_result; values are boosted scores. capacity as in run_range (last_range_count holds the true
+        number). host.boosted_matches restates the contract."""
+        self._install_boost(vec, allow, None, weight, bias)
+        use_filter = allow is not None
+        if capacity is None:
+            _, _, capacity = self._run_range(threshold, use_filter, 0, True)
+        val, idx, self.last_range_count = self._run_range(threshold, use_filter, int(capacity), True)
         return val, idx
 
     def enqueue_match(self, dev_clauses, dev_preds, count, dev_out, out_stride=0, dev_counts=0, clause_stride=0, dev_mask=0, mask_stride=0, stream=0):
@@ -381,14 +417,52 @@ class SpMV:
         counted per installed label. Returns (counts, best_idx, best_val, total): per group its matches and the row id and score
         of its best match ((0, 0.0) for a group without one), and the number of all matches."""
         self._install(vec, allow, groups)
+        return self._run_facets(threshold, allow is not None)
+
+    def _run_facets(self, threshold, use_filter, boosted=False):
         n = max(1, self._n_groups)  # (none installed: the library says so and writes nothing)
         counts = np.zeros(n, dtype=np.uint32)
         records = (_lib.FacetBest * n)()
         total = C.c_uint64(0)
-        _lib.check(_lib.lib().tkspmv_run_facets(self._h, float(threshold), int(allow is not None), u32p(counts), records, C.byref(total)))
+        run = _lib.lib().tkspmv_run_boosted_facets if boosted else _lib.lib().tkspmv_run_facets
+        _lib.check(run(self._h, float(threshold), int(use_filter), u32p(counts), records, C.byref(total)))
         best = np.frombuffer(records, dtype=np.uint32).reshape(n, 2)
         n = self._n_groups
         return counts[:n], best[:n, 0].copy(), best[:n, 1].copy().view(np.float32), int(total.value)
+
+    def enqueue_boosted_facets(self, dev_xs, count, dev_thresholds, dev_counts, dev_weight=0, dev_bias=0, boost_stride=0, n_bins=0, dev_labels=0,
+                               dev_best=0, dev_totals=0, dev_mask=0, mask_stride=0, stream=0):
+        """enqueue_facets over boosted scores: the match rule of enqueue_boosted_range, the outputs of enqueue_facets (dev_best
+        holds boosted scores). The expectation is host.facet_counts(sb, ok, ...) with sb = host.boost_scores(y, w, b) and ok =
+        present & allow & (sb > -inf). No host sync; shares the scratch of enqueue_boosted_range."""
+        _lib.check(_lib.lib().tkspmv_enqueue_boosted_facets(self._h, ptr(dev_xs), int(count), ptr(dev_weight), ptr(dev_bias), int(boost_stride),
+                                                            ptr(dev_thresholds), ptr(dev_mask), int(mask_stride), ptr(dev_labels), int(n_bins),
+                                                            ptr(dev_counts), ptr(dev_best), ptr(dev_totals), ptr(stream)))
+
+    def run_boosted_facets(self, threshold, vec=None, allow=None, groups=None, weight=None, bias=None):
+        """run_facets over boosted scores: the prologue of run_facets, set_boost(weight, bias) if either is given (else the boost
+        installed before), then the rows whose boosted score is >= threshold counted per installed label. Returns run_facets'
+        tuple; best_val holds boosted scores. The expectation is host.facet_counts(sb, ok, ...) with sb = host.boost_scores(y, w,
+        b) and ok = present & allow & (sb > -inf)."""
+        self._install_boost(vec, allow, groups, weight, bias)
+        return self._run_facets(threshold, allow is not None, True)
+
+    def enqueue_boosted_grouped(self, dev_xs, count, dev_weight=0, dev_bias=0, boost_stride=0, dev_mask=0, mask_stride=0, dev_idx=0, dev_val=0,
+                                dev_grp=0, dev_n=0, stream=0):
+        """enqueue_grouped over boosted scores (dev_weight / dev_bias / boost_stride as in enqueue_boosted): eligibility (min_score),
+        each group's representative, the order and the returned values all go by the boosted score. The expectation is
+        host.collapse_topk(sb, ok, ...) with sb = host.boost_scores(y, w, b) and ok = present & allow & (sb > -inf). No host sync;
+        one enqueue_grouped or enqueue_boosted_grouped call in flight at a time."""
+        _lib.check(_lib.lib().tkspmv_enqueue_boosted_grouped(self._h, ptr(dev_xs), int(count), ptr(dev_weight), ptr(dev_bias), int(boost_stride),
+                                                             ptr(dev_mask), int(mask_stride), ptr(dev_idx), ptr(dev_val), ptr(dev_grp), ptr(dev_n),
+                                                             ptr(stream)))
+
+    def run_boosted_grouped(self, vec=None, allow=None, groups=None, weight=None, bias=None):
+        """run_grouped over boosted scores: the prologue of run_grouped, set_boost(weight, bias) if either is given (else the boost
+        installed before). Returns (values, indices, groups) like run_grouped; values are boosted scores. The expectation is
+        host.collapse_topk(sb, ok, ...) with sb = host.boost_scores(y, w, b) and ok = present & allow & (sb > -inf)."""
+        self._install_boost(vec, allow, groups, weight, bias)
+        return self._run_grouped(allow is not None, True)
 
     def enqueue_row_vectors(self, dev_rows, count, dev_xs, dev_len=0, stream=0):
         """Stored rows as dense query vectors: dev_rows[i] (uint32, a GLOBAL row id as queries return them) is expanded into
@@ -760,6 +834,42 @@ def cosine_spmv(m, vec, k, allow=None, **kw):
         e.set_cosine()
         idx, val, n, _, _ = e.run_boosted(allow=allow)
         return val[:n], idx[:n]
+
+
+def boosted_range_spmv(m, vec, threshold, weight=None, bias=None, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices) of every row (among the rows of `allow`, if
+    given) whose boosted score weight[r] * score + bias[r] is >= threshold (either array may be None, not both), sorted like
+    topk_spmv's result; values are boosted scores."""
+    kw.setdefault("k", 8)
+    with _one_shot(m, vec=vec, **kw) as e:
+        return e.run_boosted_range(threshold, allow=allow, weight=weight, bias=bias)
+
+
+def boosted_facet_spmv(m, vec, threshold, groups, n_groups=None, weight=None, bias=None, allow=None, **kw):
+    """One-shot helper: facet_spmv over boosted scores weight[r] * score + bias[r] (either array may be None, not both)."""
+    kw.setdefault("k", 8)
+    with _one_shot(m, vec=vec, **kw) as e:
+        e.set_groups(groups, n_groups)
+        return e.run_boosted_facets(threshold, allow=allow, weight=weight, bias=bias)
+
+
+def boosted_grouped_spmv(m, vec, groups, k=100, weight=None, bias=None, allow=None, **kw):
+    """One-shot helper: grouped_spmv over boosted scores weight[r] * score + bias[r] (either array may be None, not both)."""
+    with _one_shot(m, vec=vec, k=k, **kw) as e:
+        return e.run_boosted_grouped(allow=allow, groups=groups, weight=weight, bias=bias)
+
+
+def cosine_range_spmv(m, vec, threshold, allow=None, **kw):
+    """One-shot helper: build the engine for CooMatrix m, return (values, indices) of every row (among the rows of `allow`, if
+    given) whose cosine to vec is >= threshold, sorted like topk_spmv's result; values are cosines. vec is scaled to norm 1 as in
+    cosine_spmv and the rows' weights come from set_cosine()."""
+    v = np.asarray(vec, dtype=np.float64)
+    norm = float(np.sqrt(np.sum(v * v)))
+    x = (v / norm if norm > 0 else v).astype(np.float32)
+    kw.setdefault("k", 8)
+    with _one_shot(m, vec=x, **kw) as e:
+        e.set_cosine()
+        return e.run_boosted_range(threshold, allow=allow)
 
 
 def assign_spmv(m, vecs, **kw):

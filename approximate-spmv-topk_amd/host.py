@@ -223,6 +223,29 @@ def boost_scores(y, weight=None, bias=None):
     return np.where((y == ninf) | ~np.isfinite(t), ninf, t).astype(np.float32)
 
 
+def boosted_matches(y, present, threshold, weight=None, bias=None, allow=None, first_row=0):
+    """The contract of boosted range queries (SpMV.enqueue_boosted_range) restated in numpy, for CPU-side users and as the tests'
+    expectation: from float32 y[rows] and present[rows] (the row has entries; allow[rows], if given, restricts further) the rows
+    whose boosted score s' = boost_scores(y, weight, bias) is above -inf and >= threshold, compared as float32 (-inf matches every
+    such row, NaN none; min_score plays no part). Returns (idx uint32 = row + first_row, val float32 = s', count), sorted like
+    run_range's result: score descending (compared as floats: -0.0 and +0.0 tie), then row id descending."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    ok = np.asarray(present).astype(bool)
+    if y.ndim != 1 or ok.shape != y.shape:
+        raise ValueError("y and present must be 1-D arrays of one length")
+    if allow is not None:
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.shape != y.shape:
+            raise ValueError("allow must be a bool array of y's length")
+        ok = ok & a
+    sb = boost_scores(np.where(ok, y, np.float32(-np.inf)), weight, bias)
+    with np.errstate(invalid="ignore"):
+        ok = ok & (sb > -np.inf) & (sb >= np.float32(threshold))
+    rows = np.flatnonzero(ok)
+    rows = rows[np.lexsort((rows, sb[rows]))[::-1]]
+    return (rows + int(first_row)).astype(np.uint32), sb[rows], int(rows.size)
+
+
 def cosine_weights(m):
     """Weights that turn the engine's dot products into cosines by row (SpMV.set_boost(weight=...) with a query of norm 1):
     1 / ||row r||_2 of CooMatrix m, the squares summed in float64 and the result rounded once to float32; 0.0 for a row without

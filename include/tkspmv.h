@@ -440,7 +440,8 @@ int tkspmv_set_boost(tkspmv_t *e, const float *host_weight, const float *host_bi
  * Errors, in this order: TKSPMV_ERR_INVALID, before any device call, for a NULL engine, count < 1, a negative boost_stride or
  * mask_stride_words, dev_idx / dev_val partly given, dev_xs = NULL with count != 1; TKSPMV_ERR_UNSUPPORTED where
  * tkspmv_enqueue_after reports it; TKSPMV_ERR_STATE for both arrays NULL with no boost installed, or dev_xs = NULL with no vector
- * installed. Every value type is served without a mask. Not available in range, facet and grouped queries. */
+ * installed. Every value type is served without a mask. Range, facet and grouped queries over s': tkspmv_enqueue_boosted_range,
+ * tkspmv_enqueue_boosted_facets, tkspmv_enqueue_boosted_grouped below. */
 int tkspmv_enqueue_boosted(tkspmv_t *e, const float *dev_xs, int32_t count,
                            const float *dev_weight, const float *dev_bias, int64_t boost_stride,
                            const tkspmv_cursor *dev_cursors, const uint32_t *dev_mask, int64_t mask_stride_words,
@@ -449,6 +450,58 @@ int tkspmv_enqueue_boosted(tkspmv_t *e, const float *dev_xs, int32_t count,
 /* tkspmv_run_after with the installed boost (TKSPMV_ERR_STATE if none is installed). */
 int tkspmv_run_boosted(tkspmv_t *e, const tkspmv_cursor *cursor /* host, NULL = START */, int32_t use_filter,
                        uint32_t *idx, float *val, int32_t *n, uint32_t *total, tkspmv_cursor *next);
+/* Boosted range, facet and grouped queries: thresholds, counts and groups on the boosted score. The match rule is one for all three.
+ * With s' = tkspmv_enqueue_boosted's boosted score of LOCAL row r (above: two separately rounded operations; a row that holds -inf
+ * stays -inf; an s' that is not finite becomes -inf), a row whose s' is -inf takes part in nothing: it is no match, is not counted,
+ * is not eligible and never a representative. dev_weight, dev_bias and boost_stride are tkspmv_enqueue_boosted's: device arrays by
+ * local row, either may be NULL, BOTH NULL names the installed boost, the stride in floats (0 = one pair for every query), no
+ * alignment required. They stand behind `count`; every other argument is the base call's.
+ * Why not inside range_kernel / facet_kernel: their per-packet trigger bounds RAW row sums, so a boosted threshold has to score every
+ * row. Per query, on the caller's stream: the SpMV-only kernel into an engine-owned score array (through the filtered kernel when
+ * there is a mask), then ONE pass over that array which transforms, compares and delivers (boosted_hits_kernel, boosted_bins_kernel);
+ * the array is read only. The grouped form runs boost_cut_kernel (no cursor) over the grouped path's array, then that path unchanged.
+ * Stream contract: the scratch is the engine's. tkspmv_enqueue_after, tkspmv_enqueue_boosted, tkspmv_enqueue_boosted_range and
+ * tkspmv_enqueue_boosted_facets share the search-after path's scratch (the first call of any of them allocates it, about 12 bytes per
+ * row): only ONE call of these four kinds may be in flight at a time, TOGETHER. tkspmv_enqueue_boosted_grouped counts together with
+ * tkspmv_enqueue_grouped in the same way. No exchange set, record, verdict, carried threshold or deferred selection is read or
+ * written.
+ * Errors, in tkspmv_enqueue_boosted's order: TKSPMV_ERR_INVALID, before any device call, for what the base call rejects, a negative
+ * boost_stride, or dev_xs = NULL with count != 1; TKSPMV_ERR_UNSUPPORTED where tkspmv_enqueue_grouped reports it (so every value
+ * type is served without a mask, fp32 with one, and the approximate per-partition engines are refused); TKSPMV_ERR_STATE for both
+ * arrays NULL with no boost installed, dev_xs = NULL with no vector installed, or no labels.
+ *
+ * tkspmv_enqueue_boosted_range extends tkspmv_enqueue_range: row r matches query i when s' > -inf and s' >= dev_thresholds[i],
+ * compared as floats (a threshold of -inf returns every row with a finite s', NaN nothing; desc.min_score plays no part).
+ * dev_counts[i] is the number of matches, also beyond capacity; the first min(count, capacity) distinct matches are written as
+ * (first_row + r, s') in no particular order, nothing beyond them. */
+int tkspmv_enqueue_boosted_range(tkspmv_t *e, const float *dev_xs, int32_t count,
+                                 const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                 const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                                 uint32_t *dev_idx, float *dev_val, uint32_t capacity, uint32_t *dev_counts, void *stream);
+/* tkspmv_run_range with the installed boost (TKSPMV_ERR_STATE if none is installed): the matches sorted like tkspmv_run_range's. */
+int tkspmv_run_boosted_range(tkspmv_t *e, float threshold, int32_t use_filter, uint32_t *idx, float *val,
+                             uint32_t capacity, uint64_t *count);
+/* tkspmv_enqueue_boosted_facets extends tkspmv_enqueue_facets: the same match rule; dev_counts, dev_best and dev_totals are exactly
+ * tkspmv_enqueue_facets' (dev_best: the maximum of order key of s' << 32 | global row, as {row, bits of s'}; labels >= n_bins count
+ * in the total only; {0, 0} for an empty bin). Calls of at most min(option FACET_LDS_BINS, 4096) bins are counted in a
+ * workgroup-private histogram in LDS, calls of more bins with global atomics. */
+int tkspmv_enqueue_boosted_facets(tkspmv_t *e, const float *dev_xs, int32_t count,
+                                  const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                  const float *dev_thresholds, const uint32_t *dev_mask, int64_t mask_stride_words,
+                                  const uint32_t *dev_labels, uint32_t n_bins, uint32_t *dev_counts,
+                                  tkspmv_facet_best *dev_best, uint32_t *dev_totals, void *stream);
+/* tkspmv_run_facets with the installed boost (TKSPMV_ERR_STATE if none is installed). */
+int tkspmv_run_boosted_facets(tkspmv_t *e, float threshold, int32_t use_filter,
+                              uint32_t *counts, tkspmv_facet_best *best, uint64_t *total);
+/* tkspmv_enqueue_boosted_grouped extends tkspmv_enqueue_grouped: a row is eligible when the order key of s' is at least that of
+ * desc.min_score and s' > -inf; the representative, the order and the returned value are all on s'. Pads, dev_grp and dev_n are
+ * unchanged, and so are the engine-owned outputs for dev_idx = dev_val = dev_grp = NULL. */
+int tkspmv_enqueue_boosted_grouped(tkspmv_t *e, const float *dev_xs, int32_t count,
+                                   const float *dev_weight, const float *dev_bias, int64_t boost_stride,
+                                   const uint32_t *dev_mask, int64_t mask_stride_words,
+                                   uint32_t *dev_idx, float *dev_val, uint32_t *dev_grp, uint32_t *dev_n, void *stream);
+/* tkspmv_run_grouped with the installed boost (TKSPMV_ERR_STATE if none is installed). */
+int tkspmv_run_boosted_grouped(tkspmv_t *e, int32_t use_filter, uint32_t *idx, float *val, uint32_t *grp, int32_t *n);
 /* Queries by stored row ("which rows are closest to row r?": more-like-this, de-duplication, the k-NN self-join A.A^T top-n --
  * the product the reference's CPU comparator sparse_dot_topn exists for). dev_rows[i] is a GLOBAL row id (desc.first_row + local
  * row): exactly what queries return, so results can be fed back. dev_xs + i * cols receives row i as the dense vector of cols
