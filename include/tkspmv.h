@@ -618,7 +618,8 @@ int tkspmv_assign(tkspmv_t *e, const float *host_xs, int32_t count, uint32_t *ho
  * index is built, soft clustering, multi-label classification, the margin s1 - s2 of an assignment), optionally among the rows of an
  * allow-mask only (k-means on a subset, re-assigning one cluster's rows, classifying the rows a predicate lets through).
  * Inputs: count >= 1 dense vectors of desc.cols floats at dev_xs, back to back; 1 <= n <= TKSPMV_NEAREST_MAX_N; dev_mask, or NULL for
- * all rows: one bit per LOCAL row, LSB first, ceil(rows / 32) words, as in tkspmv_enqueue_filtered.
+ * all rows: one bit per LOCAL row, LSB first, ceil(rows / 32) words, as in tkspmv_enqueue_filtered; bits at and beyond rows are
+ * ignored.
  * Outputs: dev_labels[rows][n] (uint32) and dev_scores[rows][n] (float32), row-major: a row's list is contiguous.
  *  - A row is eligible if it is in the mask, or if there is no mask. Entry j of an eligible row r is the j-th of the vectors
  *    0 .. count-1 ordered by s(r, q) descending, then by index q ascending on a tie; scores compare as floats (-0.0 and +0.0 tie).
@@ -719,7 +720,8 @@ int tkspmv_label_sums(tkspmv_t *e, const uint32_t *host_labels /* [rows], may be
  * of), taken from the matrix the engine already holds: np.bincount(col) without a COO, and in ONE pass what tkspmv_enqueue_match
  * answers with one pass per single-column predicate. One 4-byte word per column, desc.cols of them per SET; a set is all rows
  * (dev_mask = NULL, count must be 1) or the rows of one allow-mask (set i: dev_mask + i * mask_stride_words, indexed by LOCAL row like
- * every mask; stride 0: one mask for all sets). Set i's words are written at dev_out + i * out_stride_words words (out_stride_words
+ * every mask, ceil(rows / 32) words, bits at and beyond rows are ignored; stride 0: one mask for all sets). Set i's words are
+ * written at dev_out + i * out_stride_words words (out_stride_words
  * >= cols when count > 1; the words between the sets are not touched):
  *   TKSPMV_COL_NNZ  uint32   the number of counted entries stored in column c; 0 for a column without one
  *   TKSPMV_COL_MAX  float32  the largest counted value; -inf for a column without a counted entry
